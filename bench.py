@@ -7,6 +7,14 @@ resident in HBM when the timed region starts.  One process per GPU; for N > 1 th
 launches this file under torch.distributed.run and the read set is sharded over the ranks
 (humid_amd.sharded).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times --steps passes and prints the line.  Everything else it can
+measure or check -- the per-kernel and per-stage event times, the roofline of the dominant kernel,
+the CPU oracle baseline with its bit-for-bit comparison, the end-to-end leg of the command line and,
+with several ranks, the comparison with one single-GPU pass -- runs only with --full.
+
+--dump-outputs DIR writes what the last timed pass computed (rank 0's shard with several ranks) as
+float .npy files, so that two builds can be compared output for output on the same seeded reads.
+
 The oracle (oracle/) is used here ONLY for the cpu_baseline leg; it is never the thing timed
 as `value`.
 """
@@ -37,27 +45,63 @@ def parse():
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads per GPU")
     ap.add_argument("--word-nt", type=int, default=24)
     ap.add_argument("--distance", type=int, default=1)
-    ap.add_argument("--cpu-sample", type=int, default=-1,
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-kernel and per-stage times, "
+                         "roofline, CPU baseline and oracle parity, end-to-end leg, multi-rank verification")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed pass's per-read results and summary to DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None,
                     help="reads of the same workload the CPU oracle is run on, outside the timed region "
                          "(-1 = the whole workload: the GPU result is then compared with it bit for bit "
-                         "-> verified_vs_oracle; 0 = skip).  One rank only.")
+                         "-> verified_vs_oracle; 0 = skip; default: -1 with --full, else 0).  One rank only.")
     ap.add_argument("--verify", action="store_true", default=None,
                     help="several ranks: after the timed passes gather every shard's results on rank 0 and "
                          "compare them, bit for bit, with one single-GPU pass over the whole read set "
-                         "(default: on)")
+                         "(default: on with --full)")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--shard-mode", default=None, choices=["exchange", "allgather", "both"],
                     help="multi-GPU orchestration to time (default: HUMID_SHARD_MODE or exchange; 'both' "
                          "times the second one as well and reports it under other_mode)")
-    ap.add_argument("--e2e-reads", type=int, default=10_000_000,
+    ap.add_argument("--e2e-reads", type=int, default=None,
                     help="one rank only: read PAIRS of the end-to-end leg -- the `humid` command line timed on "
                          "synthetic PE150 FastQ files with the UMI in the header (FastQ in -> _dedup FastQ out), "
-                         "reported as t_e2e_s / e2e_reads_per_s next to the core value (0 = skip)")
+                         "reported as t_e2e_s / e2e_reads_per_s next to the core value (0 = skip; default: "
+                         "10000000 with --full, else 0)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU code path even with one rank (overhead measurement)")
     ap.add_argument("--traffic-json", default=None,
-                    help="optional JSON with PMC-derived HBM bytes per launch of the dominant kernel")
-    return ap.parse_args()
+                    help="optional JSON with PMC-derived HBM bytes per launch of the dominant kernel (--full)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.cpu_sample is None:
+        a.cpu_sample = -1 if a.full else 0
+    if a.e2e_reads is None:
+        a.e2e_reads = 10_000_000 if a.full else 0
+    if a.verify is None:
+        a.verify = a.full
+    return a
+
+
+DUMP_SAMPLE = 2_000_000      # reads per dumped array: 2 M x (8 B index + 8 B cluster id + 4 B flag) = 40 MB
+DUMP_SEED = 20251016
+SUMMARY_KEYS = ("total", "usable", "unique", "clusters", "edges")
+
+
+def dump_outputs(out_dir, cid, keep, summary):
+    """What a caller of the timed pass receives: the per-read cluster id (uint32, exact in float64) and duplicate
+    flag, at the reads of a fixed seeded sample when there are more than DUMP_SAMPLE of them (read_index.npy says
+    which), and the pass's counts (summary.npy, in the order of SUMMARY_KEYS)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(cid)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "cluster_id.npy"), cid[idx].astype(np.float64))
+    np.save(os.path.join(out_dir, "keep.npy"), keep[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "summary.npy"), np.array([summary[k] for k in SUMMARY_KEYS], dtype=np.float64))
 
 
 def e2e_leg(n_reads, word_nt, distance):
@@ -268,7 +312,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         for k in ks:
-            ks[k] /= max(a.steps, 1)
+            ks[k] /= a.steps
+        if a.dump_outputs and rank == 0:       # before any later pass overwrites d_cid / d_keep
+            dump_outputs(a.dump_outputs, d_cid.cpu().numpy().view(np.uint32), d_keep.cpu().numpy(), last)
         return dt, ks, last
 
     DETAIL = ("ms_k_pairs", "ms_k_cluster", "ms_k_map", "ms_k_part", "ms_k_unperm", "ms_count", "ms_neighbours", "ms_cluster",
@@ -301,7 +347,8 @@ def main():
             return dd.run_device(d_w.data_ptr(), d_f.data_ptr(), d_cid.data_ptr(), d_keep.data_ptr(),
                                  n_local, a.word_nt, a.distance, humid_amd.DIRECTIONAL)
         dt, ks, last = timed(step)
-        ks = detail_times(step, dd.set_option, ks)
+        if a.full:
+            ks = detail_times(step, dd.set_option, ks)
     else:
         from humid_amd.sharded import ShardedDedup
         first = a.shard_mode if a.shard_mode in ("exchange", "allgather") else None
@@ -315,7 +362,8 @@ def main():
                     s.update(m.ops.kernel_ms())
                 return s
             r = timed(step, getattr(m, "trace", None))
-            r = (r[0], detail_times(step, m.ops.set_option, r[1]), r[2])      # (every rank runs the extra passes: they contain collectives)
+            if a.full:
+                r = (r[0], detail_times(step, m.ops.set_option, r[1]), r[2])      # (every rank runs the extra passes: they contain collectives)
             if rank == 0 and getattr(m, "trace", None):
                 print("shard trace %s (ms per timed pass): %s" %
                       (m.mode_used, {k: round(v / a.steps, 3) for k, v in sorted(m.trace.items())}), file=sys.stderr)
@@ -339,7 +387,7 @@ def main():
                 "pci_bus": getattr(pr, "pci_bus_id", None), "pid": os.getpid()}
         ranks_seen = [None] * dist.get_world_size()
         dist.all_gather_object(ranks_seen, mine)
-    if world_sharded and (a.verify is None or a.verify):
+    if world_sharded and a.verify:
         t_verify = time.perf_counter()
         # every shard's results, gathered on rank 0, against ONE single-GPU pass over the whole set
         from humid_amd.sharded import _all_gather_flat
@@ -367,36 +415,39 @@ def main():
     value = total_reads * a.steps / dt
 
     # ---- roofline of the dominant kernel (HIP events around its single launch, live) ----
-    # candidates: the N-proportional single-launch kernels (13 B/read x N is their unit)
-    mode_used = int(last.get("count_mode_used", 0))
-    lds = mode_used in (0, 2) and (not world_sharded or getattr(sd, "mode_used", "") == "exchange")
-    # (names: the word-ordered count runs on 8-byte records since round 3 -- k_dedup_rec, k_p8_scatter2,
-    # k_unperm_bins8; hashed buckets and the fall-backs keep k_dedup_lds / k_pt_scatter<2> / k_unperm_bins)
-    rec8 = bool(last.get("records8", False))
-    kern = {(("k_dedup_rec" if rec8 else "k_dedup_lds") if lds else "k_hash_insert"): ks["ms_k_insert"],
-            (("k_unperm_bins8" if rec8 else "k_unperm_bins") if ks["ms_k_unperm"] > 0 else ("k_read_map_bucket" if lds else "k_read_map")): ks["ms_k_map"]}
-    if ks["ms_k_part"] > 0:
-        kern["k_p8_scatter2" if rec8 else "k_pt_scatter<2>"] = ks["ms_k_part"]
-    if ks["ms_k_unperm"] > 0:
-        kern["k_unperm_window"] = ks["ms_k_unperm"]
-    dom = max(kern, key=lambda k: kern[k])
-    dom_ms = kern[dom]
-    achieved = (BYTES_PER_READ * n_local / (dom_ms * 1e-3)) / 1e9 if dom_ms > 0 else 0.0
-    traffic = None
-    tj = a.traffic_json or os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tj):
-        tr = json.load(open(tj))
-        traffic = tr.get(dom)
-        if traffic is None:                       # template instantiations: k_dedup_lds<true>
-            traffic = next((v for k, v in tr.items() if k.split("<")[0] == dom.split("<")[0]), None)
-    roofline = {"bound": "hbm", "kernel": dom, "kernel_ms": round(dom_ms, 4),
-                "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                "traffic_source": "profiles/traffic.json (separate rocprofv3 --pmc passes of this command; 2*FETCH_SIZE+WRITE_SIZE)" if traffic else None,
-                "alg_bytes_per_read": BYTES_PER_READ, "reads_per_launch": n_local,
-                "other_kernels_ms": {k: round(v, 4) for k, v in kern.items() if k != dom},
-                "whole_path": {"achieved": round(BYTES_PER_READ * n_local / (ms_per_step * 1e-3) / 1e9, 2),
-                               "frac": round(BYTES_PER_READ * n_local / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}}
+    # (--full only: the other candidates' times come from the detail passes)
+    roofline = None
+    if a.full:
+        # candidates: the N-proportional single-launch kernels (13 B/read x N is their unit)
+        mode_used = int(last.get("count_mode_used", 0))
+        lds = mode_used in (0, 2) and (not world_sharded or getattr(sd, "mode_used", "") == "exchange")
+        # (names: the word-ordered count runs on 8-byte records since round 3 -- k_dedup_rec, k_p8_scatter2,
+        # k_unperm_bins8; hashed buckets and the fall-backs keep k_dedup_lds / k_pt_scatter<2> / k_unperm_bins)
+        rec8 = bool(last.get("records8", False))
+        kern = {(("k_dedup_rec" if rec8 else "k_dedup_lds") if lds else "k_hash_insert"): ks["ms_k_insert"],
+                (("k_unperm_bins8" if rec8 else "k_unperm_bins") if ks["ms_k_unperm"] > 0 else ("k_read_map_bucket" if lds else "k_read_map")): ks["ms_k_map"]}
+        if ks["ms_k_part"] > 0:
+            kern["k_p8_scatter2" if rec8 else "k_pt_scatter<2>"] = ks["ms_k_part"]
+        if ks["ms_k_unperm"] > 0:
+            kern["k_unperm_window"] = ks["ms_k_unperm"]
+        dom = max(kern, key=lambda k: kern[k])
+        dom_ms = kern[dom]
+        achieved = (BYTES_PER_READ * n_local / (dom_ms * 1e-3)) / 1e9 if dom_ms > 0 else 0.0
+        traffic = None
+        tj = a.traffic_json or os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tj):
+            tr = json.load(open(tj))
+            traffic = tr.get(dom)
+            if traffic is None:                       # template instantiations: k_dedup_lds<true>
+                traffic = next((v for k, v in tr.items() if k.split("<")[0] == dom.split("<")[0]), None)
+        roofline = {"bound": "hbm", "kernel": dom, "kernel_ms": round(dom_ms, 4),
+                    "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                    "traffic_source": "profiles/traffic.json (separate rocprofv3 --pmc passes of this command; 2*FETCH_SIZE+WRITE_SIZE)" if traffic else None,
+                    "alg_bytes_per_read": BYTES_PER_READ, "reads_per_launch": n_local,
+                    "other_kernels_ms": {k: round(v, 4) for k, v in kern.items() if k != dom},
+                    "whole_path": {"achieved": round(BYTES_PER_READ * n_local / (ms_per_step * 1e-3) / 1e9, 2),
+                                   "frac": round(BYTES_PER_READ * n_local / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}}
 
     # ---- CPU baseline + parity: the oracle (1 thread) on the SAME reads, outside the timed region ----
     cpu = None
@@ -452,7 +503,8 @@ def main():
                        if sd.mode_used == "exchange" else
                        "reads sharded by input order; RCCL all-gather of the packed words")},
         "summary": {k: int(last[k]) for k in ("total", "usable", "unique", "clusters", "edges") if k in last},
-        "device_ms": {k: round(v, 4) for k, v in ks.items()},
+        # without --full only the columns the timed passes themselves measured (the detail passes fill the rest)
+        "device_ms": {k: round(v, 4) for k, v in ks.items() if a.full or v > 0},
         "roofline": roofline,
         "cpu_baseline": cpu,
     }
