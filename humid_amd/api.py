@@ -125,6 +125,48 @@ class Dedup(Context):
         self._wide = word_nt > 32
         return self.summary
 
+    def run_grouped(self, words, groups, filtered, word_nt=24, n_groups=None, distance=1, method=DIRECTIONAL,
+                    edit=False):
+        """Deduplicate within groups (include/humid_hip.h, humid_dedup_run_grouped): the results are those of
+        run() on every group's reads on their own, ids of group g raised by the clusters of the groups below it.
+        groups: u32[N] (None: all reads in group 0); n_groups None: groups[filtered == 0].max() + 1.
+        Returns (cluster_id, keep, summary) like run(); leaves() then also gives every leaf's "group"."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        want = (len(f), 2) if word_nt > 32 else (len(f),)
+        if f.ndim != 1 or w.shape != want:
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % (want, word_nt, f.shape))
+        g = None
+        if groups is not None:
+            g = np.ascontiguousarray(groups, dtype=np.uint32)
+            if g.shape != f.shape:
+                raise ValueError("groups must have shape %r" % (f.shape,))
+        if n_groups is None:
+            usable = g[f == 0] if g is not None else np.zeros(0, np.uint32)
+            n_groups = int(usable.max()) + 1 if len(usable) else 1
+        n = len(f)
+        self._wide = word_nt > 32
+        self.set_option("edit_distance", int(bool(edit)))
+        cid = np.zeros(n, dtype=np.uint32)
+        keep = np.zeros(n, dtype=np.uint8)
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_grouped(self._h, _vp(w), _vp(g), _vp(f), n, word_nt, n_groups,
+                                                      distance, method, _vp(cid), _vp(keep), C.byref(s)))
+        self.summary = self._grouped_summary = s.asdict()
+        return cid, keep, self.summary
+
+    def run_grouped_device(self, d_words, d_groups, d_filtered, d_cluster_id, d_keep, n_reads, n_groups,
+                           word_nt=24, distance=1, method=DIRECTIONAL):
+        """run_grouped on device pointers (ints, e.g. tensor.data_ptr(); d_groups u32, 0 for none); results stay
+        in HBM.  n_groups is required here."""
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_grouped_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_groups) if d_groups else None, C.c_void_p(d_filtered),
+            n_reads, word_nt, n_groups, distance, method, C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = self._grouped_summary = s.asdict()
+        self._wide = word_nt > 32
+        return self.summary
+
     def leaves(self):
         u = int(self.summary["unique"])
         wshape = (u, 2) if getattr(self, "_wide", False) else u
@@ -134,6 +176,9 @@ class Dedup(Context):
         self._check(self._lib.humid_get_leaves(self._h, _vp(out["word"]), _vp(out["count"]),
                                                _vp(out["first_read"]), _vp(out["degree"]),
                                                _vp(out["cluster_id"]), _vp(out["is_max_leaf"])))
+        if getattr(self, "_grouped_summary", None) is self.summary:      # the last run was a grouped one
+            out["group"] = np.zeros(u, np.uint32)
+            self._check(self._lib.humid_get_leaf_groups(self._h, _vp(out["group"])))
         return out
 
     def adjacency(self):

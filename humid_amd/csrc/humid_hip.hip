@@ -99,7 +99,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -235,14 +235,34 @@ int humid_dedup_run_device(humid_ctx *c, const uint64_t *d_words, const uint8_t 
   return run_device<u64>(c, d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
 }
 
-// host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device
+int humid_dedup_run_grouped_device(humid_ctx *c, const uint64_t *d_words, const uint32_t *d_group,
+                                   const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt, uint32_t n_groups,
+                                   uint32_t distance, uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                   humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (word_nt > 32)
+    return run_grouped_device<W2>(c, (const W2 *)d_words, d_group, d_filtered, n_reads, word_nt, n_groups, distance, method,
+                                  d_cluster_id, d_keep, summary);
+  return run_grouped_device<u64>(c, d_words, d_group, d_filtered, n_reads, word_nt, n_groups, distance, method,
+                                 d_cluster_id, d_keep, summary);
+}
+
+// host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
+// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1)
 static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
                     uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
-                    uint8_t *keep, humid_summary *summary) {
+                    uint8_t *keep, humid_summary *summary, bool grouped = false, const uint32_t *group = nullptr,
+                    uint32_t n_groups = 1) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (n_reads && (!(bases || (words && filtered)) || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
   if (bases) TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (grouped) {                                             // (before any copy: a refused shape moves nothing)
+    c->have_run = c->have_graph = c->gk_leaves = false;
+    TRY(check_run_args(c, n_reads, word_nt, method, 64));
+    TRY(check_grouped_args(c, word_nt, n_groups));
+    if (!group && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
+  }
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   humid_summary s;
@@ -271,8 +291,17 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
     HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
   }
+  if (n && grouped && group) {
+    ENSURE(c->gk_group_in, n * 4 + 8);
+    HIPCHK(hipMemcpyAsync(c->gk_group_in.p, group, n * 4, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipEventRecord(e1, st));
-  int rc = word_nt > 32
+  int rc = grouped ? (word_nt > 32
+               ? run_grouped_device<W2>(c, c->in_words.as<W2>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
+                                        n_reads, word_nt, n_groups, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
+               : run_grouped_device<u64>(c, c->in_words.as<u64>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
+                                         n_reads, word_nt, n_groups, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
+           : word_nt > 32
                ? run_device<W2>(c, c->in_words.as<W2>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
                                 c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
                : run_device<u64>(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
@@ -298,6 +327,13 @@ int humid_dedup_run(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
   return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary);
 }
 
+int humid_dedup_run_grouped(humid_ctx *c, const uint64_t *words, const uint32_t *group, const uint8_t *filtered,
+                            uint64_t n_reads, uint32_t word_nt, uint32_t n_groups, uint32_t distance, uint32_t method,
+                            uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, true, group,
+                  n_groups);
+}
+
 int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
                           uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   if (n_reads && !bases) return fail(c, HUMID_E_INVALID, "null buffer");
@@ -318,6 +354,22 @@ int humid_get_packed_words(humid_ctx *c, uint64_t *words, uint8_t *filtered) {
   return HUMID_OK;
 }
 
+// the internal words of a grouped run's leaves (host copy, g_wpr u64 each) -> the caller's words (layout of
+// gk_word_nt) and / or the groups
+static void gkey_split(const humid_ctx *c, const std::vector<u64> &iw, size_t U, uint64_t *word, uint32_t *group) {
+  const u32 wb = 2 * c->gk_word_nt, wpr = c->g_wpr, out_wpr = c->gk_word_nt > 32 ? 2 : 1;
+  const unsigned __int128 wmask = wb >= 128 ? ~(unsigned __int128)0 : ((unsigned __int128)1 << wb) - 1;
+  for (size_t i = 0; i < U; i++) {
+    const unsigned __int128 v = wpr == 2 ? ((unsigned __int128)iw[2 * i] << 64) | iw[2 * i + 1] : (unsigned __int128)iw[i];
+    if (word) {
+      const unsigned __int128 w = v & wmask;
+      if (out_wpr == 2) { word[2 * i] = (u64)(w >> 64); word[2 * i + 1] = (u64)w; }
+      else word[i] = (u64)w;
+    }
+    if (group) group[i] = wb >= 128 ? 0u : (u32)(v >> wb);
+  }
+}
+
 #define NEED_RUN()                                                                            \
   do {                                                                                        \
     if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");                             \
@@ -336,13 +388,47 @@ int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *fi
   if (U == 0) return HUMID_OK;
   if (first_read && !c->have_run)
     return fail(c, HUMID_E_STATE, "first_read is only available after a single-GPU humid_dedup_run*");
-  D2H(word, c->g_word, U * 8 * c->g_wpr);
+  if (word && c->gk_leaves && (c->gk_leaf_nt || c->g_wpr != (c->gk_word_nt > 32 ? 2u : 1u))) {
+    // grouped internal words -> the caller's words (the group goes to humid_get_leaf_groups)
+    std::vector<u64> iw(U * c->g_wpr);
+    HIPCHK(hipMemcpyAsync(iw.data(), c->g_word, U * 8 * c->g_wpr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    gkey_split(c, iw, U, word, nullptr);
+  } else
+    D2H(word, c->g_word, U * 8 * c->g_wpr);
   D2H(count, c->g_cnt, U * 4);
   D2H(first_read, c->s_first.p, U * 4);
   D2H(degree, c->deg.p, U * 4);
   D2H(cluster_id, c->cid.p, U * 4);
   D2H(is_max_leaf, c->ismax.p, U);
   HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
+  NEED_RUN();
+  if (!c->gk_leaves) return fail(c, HUMID_E_STATE, "the last run was not a grouped run");
+  size_t U = (size_t)c->gU;
+  if (U == 0 || !group) return HUMID_OK;
+  if (!c->gk_leaf_nt) { memset(group, 0, U * 4); return HUMID_OK; }
+  std::vector<u64> iw(U * c->g_wpr);
+  HIPCHK(hipMemcpyAsync(iw.data(), c->g_word, U * 8 * c->g_wpr, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  gkey_split(c, iw, U, nullptr, group);
+  return HUMID_OK;
+}
+
+int humid_grouped_plan_info(humid_ctx *c, uint32_t word_nt, uint32_t n_groups, uint32_t distance, uint64_t n_unique,
+                            uint32_t *n_combos, uint32_t *key_bits, uint32_t *group_nt) {
+  // pure host arithmetic: ctx may be NULL (no GPU needed; the automatic plan is reported)
+  TRY(check_run_args(c, 0, word_nt, 0, 64));
+  TRY(check_grouped_args(c, word_nt, n_groups));
+  const u32 gnt = gkey_nt_for(n_groups);
+  const ComboPlan plan = make_plan(word_nt, distance, n_unique, c ? c->force_segments : 0u, true, gnt);
+  if (plan.ncombo == 0 || plan.ncombo > MAX_COMBOS) return fail(c, HUMID_E_INVALID, "internal: bad pigeonhole plan");
+  if (n_combos) *n_combos = plan.ncombo;
+  if (key_bits) *key_bits = plan.key_bits;
+  if (group_nt) *group_nt = gnt;
   return HUMID_OK;
 }
 

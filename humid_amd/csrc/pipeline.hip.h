@@ -26,6 +26,7 @@
 #include "kernels_map.hip.h"
 #include "kernels_xchg.hip.h"
 #include "kernels_wide.hip.h"
+#include "kernels_gkey.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -151,6 +152,15 @@ struct humid_ctx {
   bool last_count_lds = false;
   bool last_count_ordered = false;
   int count_order = -1;      // LDS buckets by word prefix: -1 automatic (uniform prefix), 0 never, 1 always
+  // grouped runs (humid_dedup_run_grouped*): the pass runs over internal words that carry the group ("gkey")
+  // in gk_nt nucleotides above the caller's word; the count sorts them into (group, word) walk order and every
+  // combination of the plan starts with the whole group field (make_plan), so buckets never mix groups
+  bool gk_on = false;        // a grouped pass is running (reset on every exit: stage entry points never see it)
+  u32 gk_nt = 0;             // its group field (nucleotides); 0 unless gk_on
+  u32 gk_epoch = 0;          // value k_gkey_words stores into h_ctr[CTR_N + 1] when a usable read's group is out of range
+  bool gk_leaves = false;    // the leaf arrays of the last graph stage hold grouped internal words ...
+  u32 gk_word_nt = 0, gk_leaf_nt = 0;   // ... of this caller word length and group field
+  DBuf gk_words, gk_group_in, gk_bad;   // internal words; host entry point staging of the groups; device flag (no mapped memory)
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -304,19 +314,32 @@ static u64 n_choose_k(u32 n, u32 k) {
 // apart, and at <= 24 bits the order comes from the two-level grouping instead of a library sort over
 // every key bit (48 bits for two halves of a 48-nt word).  Only the one-GPU Hamming search asks for it:
 // the shifted joins of the edit search and the exchange pass's routing keep whole segments.
-static ComboPlan make_plan(u32 n, u32 d, u64 U, u32 force_segments, bool short_later = false) {
+// gnt > 0 (grouped runs): the words carry a group field of gnt nucleotides ABOVE their n nucleotides.  The segments
+// are cut over the n word nucleotides only, and every combination starts with the whole group field, never cut
+// (field 0; later word fields are cut to fit 64 key bits): buckets never mix groups, and the first combination is
+// still a prefix of the (group, word)-sorted words.  The "all pairs" plan becomes all pairs within a group.
+static ComboPlan make_plan(u32 n, u32 d, u64 U, u32 force_segments, bool short_later = false, u32 gnt = 0) {
   ComboPlan p;
   memset(&p, 0, sizeof p);
+  const u32 gw = 2 * gnt, gsh = 2 * n;           // the group field: bits [gsh, gsh + gw)
+  const unsigned __int128 gmask = gnt ? (((unsigned __int128)1 << gw) - 1) << gsh : 0;
+  if (gnt && (d >= n || n_choose_k(d + 1, 1) > MAX_COMBOS)) {
+    p.ncombo = 1; p.key_bits = gw; p.mask[0] = W2{(u64)(gmask >> 64), (u64)gmask};
+    p.nfield[0] = 1; p.shift[0][0] = (u8)gsh; p.width[0][0] = (u8)gw;
+    return p;
+  }
   // d >= n: every pair is a neighbour pair.  d >= MAX_COMBOS: even the smallest plan, s = d + 1,
   // has d + 1 > MAX_COMBOS combinations (of ONE segment of at most n / (d + 1) <= 3 nucleotides at
   // n <= 64: buckets of a quarter of all words and more), so the search degenerates to the same
   // single combination with an empty mask: one bucket, every pair compared.
   if (d >= n || n_choose_k(d + 1, 1) > MAX_COMBOS) { p.ncombo = 1; p.key_bits = 0; p.mask[0] = W2{0, 0}; p.nfield[0] = 0; return p; }
   u32 want = 1;                                  // nucleotides of key wanted: 4^want >= U
-  while (want < n && ((u64)1 << (2 * want)) < U) want++;
+  while (want < n + gnt && ((u64)1 << (2 * want)) < U) want++;
+  const u32 want_all = want;                     // (the group field stands for gnt of them)
+  if (gnt) want = std::min<u32>(n, want > gnt ? want - gnt : 1u);
   u32 best_s = d + 1, best_len = 0;
   u64 best_c = ~0ull;
-  for (u32 sgm = d + 1; sgm <= n && sgm <= d + MAX_FIELDS; sgm++) {
+  for (u32 sgm = d + 1; sgm <= n && sgm <= d + MAX_FIELDS - (gnt ? 1u : 0u); sgm++) {
     const u64 combos = n_choose_k(sgm, sgm - d);
     if (combos > MAX_COMBOS) break;
     if (force_segments) {                         // test hook: take exactly this s if it is legal
@@ -347,9 +370,10 @@ static ComboPlan make_plan(u32 n, u32 d, u64 U, u32 force_segments, bool short_l
     // A combo key holds at most 64 bits (only wide words can exceed that): the last field is cut
     // to its top bits and later fields are dropped.  Two words within distance d still agree on the
     // shortened mask of some combo, so the search stays complete; it only compares a few more pairs.
-    unsigned __int128 m = 0;
-    u32 bits = 0, nf = 0;
-    const u32 limit = (short_later && c > 0 && !force_segments) ? std::min<u32>(64u, std::max<u32>(24u, 2 * want)) : 64u;
+    unsigned __int128 m = gmask;
+    u32 bits = gw, nf = 0;
+    const u32 limit = (short_later && c > 0 && !force_segments) ? std::min<u32>(64u, std::max<u32>(std::max<u32>(24u, 2 * want_all), gw + 2)) : 64u;
+    if (gnt) { p.shift[c][0] = (u8)gsh; p.width[c][0] = (u8)gw; nf = 1; }
     for (u32 t = 0; t < k && bits < limit; t++) {
       const u32 sg = idx[t];
       u32 wd = seg_width[sg], sh = seg_shift[sg];
@@ -1276,6 +1300,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   c->g_wpr = (u32)(sizeof(WT) / 8);
   c->g_cnt = g_cnt;
   c->gU = U;
+  c->gk_leaves = c->gk_on;
   c->cg_valid = false;
   // ---------------- 3. neighbours -----------------
   // deg has U+1 entries (last stays 0) so that one exclusive scan yields nbr_off[U] = 2E
@@ -1290,7 +1315,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
                      c->deg.as<u32>(), c->csize.as<u32>(), c->cur.as<u32>(), U);
   u64 E = 0, M = 0, Mbig = 0;
   u32 n_pair_segs = 0;
-  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments, true);
+  const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
   EarlierMasksT<WT> d_masks;                         // masks of all combos, for the first-combo rule
   for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = w_from<WT>(plan.mask[t]);
   auto fields_of = [&](u32 cb) {
@@ -1612,9 +1637,10 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->g_wpr = (u32)(sizeof(WT) / 8);
   c->g_cnt = g_cnt;
   c->gU = U;
+  c->gk_leaves = c->gk_on;
   c->cg_valid = false;
   c->cg_expanded = false;
-  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments, true);
+  const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
   EarlierMasksT<WT> d_masks;
   for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = w_from<WT>(plan.mask[t]);
   const bool given = ext_edges != nullptr;
@@ -1858,7 +1884,11 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
   hipStream_t st = c->stream;
   *n_edges_out = 0;
   if (U < 2) return HUMID_OK;
-  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments);
+  // grouped runs: field 0 of every combination is the group field, joined at offset 0 only (a common prefix does
+  // not change the Levenshtein distance, so verifying the whole internal word stays exact); word fields never
+  // shift into it
+  const u32 gnt = c->gk_nt, wn = word_nt - gnt;
+  const ComboPlan plan = make_plan(wn, distance, U, c->force_segments, false, gnt);
   const u32 kb = plan.key_bits ? plan.key_bits : 1;
   const bool k32 = kb <= 32;
   ENSURE(c->e_kx, (size_t)U * 8);
@@ -1900,6 +1930,7 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
         }
         for (int v = -D; v <= D; v++) {
           if (!signed_yet && v < 0) continue;                 // canonical sign
+          if (gnt && t == 0 && v != 0) continue;              // the group field stays in place
           const int prev = t ? o[t - 1] : 0;
           const int step = v > prev ? v - prev : prev - v;
           if (cost + step > 2 * D) continue;
@@ -1916,7 +1947,7 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
         for (u32 t = 0; t < k; t++) {
           // offset +1 = one nucleotide towards the end of the word = a field shift lower by 2 bits
           const int sh = (int)cfy.shift[t] - 2 * o[t];
-          if (sh < 0 || sh + (int)cfy.width[t] > (int)(2 * word_nt)) { valid = false; break; }   // off the word
+          if (sh < 0 || sh + (int)cfy.width[t] > (int)(2 * ((gnt && t == 0) ? word_nt : wn))) { valid = false; break; }   // off the word
           cfy.shift[t] = (u8)sh;
           shifted = shifted || o[t] != 0;
         }
@@ -2297,6 +2328,14 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
   return HUMID_OK;
 }
 
+// grouped runs: did k_gkey_words see a usable read with group >= n_groups?  Read after a host wait that followed it.
+static int gkey_check(humid_ctx *c) {
+  if (!c->gk_on) return HUMID_OK;
+  const u32 seen = *(volatile u32 *)&c->h_ctr[CTR_N + 1];
+  if (seen == c->gk_epoch) return fail(c, HUMID_E_INVALID, "a usable read has a group >= n_groups");
+  return HUMID_OK;
+}
+
 static int check_run_args(humid_ctx *c, u64 n_reads, u32 word_nt, u32 method, u32 max_nt = 32) {
   if (word_nt == 0) return fail(c, HUMID_E_INVALID, "word_nt must be >= 1");
   if (word_nt > max_nt) return fail(c, HUMID_E_UNSUPPORTED, "word_nt %u > %u is not supported by this entry point", word_nt, max_nt);
@@ -2316,6 +2355,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->graph_mode = false;
   c->have_graph = false;
   c->dense_mode = false;
+  c->gk_leaves = c->gk_on;
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (WIDE != (word_nt > 32)) return fail(c, HUMID_E_INVALID, "word layout does not match word_nt");
   if (WIDE && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
@@ -2337,6 +2377,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->lean_events = !c->kev_on && getenv("HUMID_ALL_EVENTS") == nullptr;
   if constexpr (WIDE) TRY(stage_count_wide(c, d_words, d_filt, N, word_nt, s));
   else TRY(stage_count(c, d_words, d_filt, N, word_nt, 0ull, ~0ull, 0, s));
+  TRY(gkey_check(c));                                        // (the count stage's host wait has seen k_gkey_words)
   const u32 U = (u32)c->U;
   if (U == 0) {   // everything filtered
     HIPCHK(hipMemsetAsync(d_cid, 0, (size_t)N * 4, st));
@@ -2379,6 +2420,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     HIPCHK(hipEventElapsedTime(&s.ms_map, c->ev[3], c->ev[4]));
   }
   HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
+  TRY(gkey_check(c));
   HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));
   if (!c->kev_on) s.ms_k_map = s.ms_map;
   else if (c->last_count_lds) HIPCHK(hipEventElapsedTime(&s.ms_k_map, c->ev[3], c->kev[36]));   // first map kernel alone
@@ -2399,6 +2441,73 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   if (sum) *sum = s;
   c->have_run = true;
   c->have_graph = true;
+  return HUMID_OK;
+}
+
+// ---- grouped runs (humid_dedup_run_grouped*): one pass over many groups ------------------------------------
+// group nucleotides of n_groups groups: ceil(ceil(log2(n_groups)) / 2), 0 for one group
+static inline u32 gkey_nt_for(u32 n_groups) { return n_groups <= 1 ? 0u : (bits_for(n_groups) + 1) / 2; }
+
+static int check_grouped_args(humid_ctx *c, u32 word_nt, u32 n_groups) {
+  if (n_groups == 0) return fail(c, HUMID_E_INVALID, "n_groups must be >= 1");
+  if (word_nt >= 1 && word_nt <= 64 && word_nt + gkey_nt_for(n_groups) > 64)
+    return fail(c, HUMID_E_UNSUPPORTED, "word_nt %u + %u group nucleotides (%u groups) > 64 is not supported", word_nt,
+                gkey_nt_for(n_groups), n_groups);
+  return HUMID_OK;
+}
+
+// The whole grouped pass: k_gkey_words writes the internal words (and checks the groups), run_device runs the
+// pass over them with the group field in every combination of the plan.  group == null: all reads in group 0
+// (n_groups must be 1), the plain pass itself.  WI: the caller's word type (word_nt <= 32: u64).
+template <class WI>
+static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_group, const u8 *d_filt, u64 n_reads,
+                              u32 word_nt, u32 n_groups, u32 distance, u32 method, u32 *d_cid, u8 *d_keep,
+                              humid_summary *sum) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  c->have_run = c->have_graph = c->gk_leaves = false;
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  TRY(check_grouped_args(c, word_nt, n_groups));
+  if (!d_group && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
+  if (n_reads && (!d_words || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (sizeof(WI) == 16 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  HIPCHK(hipSetDevice(c->device));
+  const u32 gnt = gkey_nt_for(n_groups), n_int = word_nt + gnt, N = (u32)n_reads;
+  struct GkGuard { humid_ctx *c; ~GkGuard() { c->gk_on = false; c->gk_nt = 0; } } gk_guard{c};
+  c->gk_on = true;
+  c->gk_nt = gnt;
+  c->gk_word_nt = word_nt;
+  c->gk_leaf_nt = gnt;
+  c->gk_epoch = c->gk_epoch + 1 ? c->gk_epoch + 1 : 1;     // (a value a store of an earlier pass cannot match)
+  int rc;
+  if (!d_group || N == 0) {
+    rc = run_device<WI>(c, d_words, d_filt, n_reads, word_nt, distance, method, d_cid, d_keep, sum);
+  } else {
+    hipStream_t st = c->stream;
+    const bool wide = n_int > 32, copy = gnt > 0;             // (one group: the caller's words are the internal ones)
+    if (copy) ENSURE(c->gk_words, (size_t)N * (wide ? 16 : 8) + 16);
+    u32 *bad = (c->h_ctr_dev && !c->no_poll) ? (u32 *)&c->h_ctr_dev[CTR_N + 1] : nullptr;
+    if (!bad) {                                              // no mapped mirror: a device word, copied at the host wait
+      if (!c->gk_bad.p) {
+        ENSURE(c->gk_bad, 16);
+        HIPCHK(hipMemsetAsync(c->gk_bad.p, 0, 16, st));
+      }
+      bad = c->gk_bad.as<u32>();
+    }
+    if (wide)
+      hipLaunchKernelGGL((k_gkey_words<WI, W2>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_group, d_filt, N,
+                         word_nt, gnt, n_groups, copy ? c->gk_words.as<W2>() : nullptr, bad, c->gk_epoch);
+    else
+      hipLaunchKernelGGL((k_gkey_words<WI, u64>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_group, d_filt, N,
+                         word_nt, gnt, n_groups, copy ? c->gk_words.as<u64>() : nullptr, bad, c->gk_epoch);
+    HIPCHK(hipGetLastError());
+    if (bad == c->gk_bad.as<u32>())
+      HIPCHK(hipMemcpyAsync(&c->h_ctr[CTR_N + 1], bad, 4, hipMemcpyDeviceToHost, st));
+    if (!copy) rc = run_device<WI>(c, d_words, d_filt, n_reads, word_nt, distance, method, d_cid, d_keep, sum);
+    else if (wide) rc = run_device<W2>(c, c->gk_words.as<W2>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
+    else rc = run_device<u64>(c, c->gk_words.as<u64>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
+  }
+  if (rc != HUMID_OK) { c->have_run = c->have_graph = c->gk_leaves = false; return rc; }
+  c->word_nt = word_nt;
   return HUMID_OK;
 }
 

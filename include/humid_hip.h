@@ -168,6 +168,40 @@ int humid_dedup_run_bases(humid_ctx *ctx, const uint8_t *bases, uint64_t n_reads
                           humid_summary *summary);
 int humid_get_packed_words(humid_ctx *ctx, uint64_t *words, uint8_t *filtered);
 
+/* ---- grouped deduplication: words are clustered only within caller-given groups ----------------
+ * (per cell barcode, per alignment position, per sample: UMI-tools --per-cell / dedup, fgbio
+ * GroupReadsByUmi).  group[n_reads] (u32) beside words and filtered; 1 <= n_groups.  The results are
+ * DEFINED as: for each group g in ascending order, humid_dedup_run on the reads with group == g (input
+ * order), its cluster_id / keep scattered back to the reads' positions, every non-zero cluster id
+ * raised by the clusters of all groups below g.  So words in different groups are never neighbours;
+ * the walk order (leaf i of humid_get_leaves / _adjacency / _clusters, the cluster ids) is (group,
+ * word) ascending; first_read is a global read index; summary counts and the three histograms are
+ * over all groups.  Filtered reads get cluster id 0 and keep 0 and their group is not read.
+ * n_groups == 1 (group may then be NULL) is the plain pass, bit for bit.  The option "edit_distance"
+ * applies (Levenshtein between the words only), and no tuning option changes results.
+ * Let group_nt = ceil(ceil(log2(n_groups)) / 2) (0 for one group): word_nt + group_nt > 64 returns
+ * HUMID_E_UNSUPPORTED.  A usable read with group >= n_groups returns HUMID_E_INVALID (the context stays
+ * usable).  words keep the caller's layout (one uint64 per read up to 32 nt, two beyond).  Not for the
+ * multi-GPU pass.
+ *   humid_dedup_run_grouped_device: the same with DEVICE pointers, like humid_dedup_run_device.
+ *   humid_get_leaf_groups: after a grouped run, the group of every leaf (u32[unique]); humid_get_leaves
+ *     returns the words without it.  HUMID_E_STATE after any other run.
+ *   humid_grouped_plan_info: the pigeonhole plan of a grouped run over n_unique unique words in total
+ *     (combinations, bits of the longest combination key, which always starts with the whole group
+ *     field) and group_nt.  Host arithmetic only: ctx may be NULL. */
+int humid_dedup_run_grouped(humid_ctx *ctx, const uint64_t *words, const uint32_t *group,
+                            const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                            uint32_t n_groups, uint32_t distance, uint32_t method,
+                            uint32_t *cluster_id, uint8_t *keep, humid_summary *summary);
+int humid_dedup_run_grouped_device(humid_ctx *ctx, const uint64_t *d_words, const uint32_t *d_group,
+                                   const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt,
+                                   uint32_t n_groups, uint32_t distance, uint32_t method,
+                                   uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary);
+int humid_get_leaf_groups(humid_ctx *ctx, uint32_t *group);
+int humid_grouped_plan_info(humid_ctx *ctx, uint32_t word_nt, uint32_t n_groups, uint32_t distance,
+                            uint64_t n_unique, uint32_t *n_combos, uint32_t *key_bits,
+                            uint32_t *group_nt);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
