@@ -182,6 +182,13 @@ void orc_graph_link(orc_graph *g, size_t a, size_t b) {
   leaf_push(&g->leaf[a], &g->leaf[b]);
   leaf_push(&g->leaf[b], &g->leaf[a]);
 }
+void orc_graph_set_counts(orc_graph *g, const uint64_t *counts) {
+  for (size_t i = 0; i < g->n; i++) g->leaf[i].count = counts[i];
+}
+void orc_graph_append_csr(orc_graph *g, const uint64_t *off, const uint32_t *idx) {
+  for (size_t i = 0; i < g->n; i++)
+    for (uint64_t j = off[i]; j < off[i + 1]; j++) leaf_push(&g->leaf[i], &g->leaf[idx[j]]);
+}
 static OCluster *graph_cluster(orc_graph *g, size_t id) {
   if (id >= g->cl_cap) {
     size_t nc = g->cl_cap ? g->cl_cap : 8;

@@ -73,6 +73,11 @@ orc_graph *orc_graph_create(size_t n_leaves);
 void   orc_graph_destroy(orc_graph *g);
 void   orc_graph_set_count(orc_graph *g, size_t leaf, size_t count);
 void   orc_graph_link(orc_graph *g, size_t a, size_t b);        /* link()  */
+/* batch import for large graphs: every leaf's count from one array, then leaf i's
+ * neighbours idx[off[i] .. off[i+1]) appended to its own list in row order (one side
+ * only: a symmetric graph lists every pair in both rows) */
+void   orc_graph_set_counts(orc_graph *g, const uint64_t *counts);
+void   orc_graph_append_csr(orc_graph *g, const uint64_t *off, const uint32_t *idx);
 void   orc_graph_preassign(orc_graph *g, size_t leaf, size_t cluster_id);
 size_t orc_graph_max_neighbour(orc_graph *g, size_t leaf);
 /* one explicit call of assign{Directional,Max}Cluster(leaf, new Cluster{id}) */

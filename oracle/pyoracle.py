@@ -42,6 +42,8 @@ def lib():
         L.orc_graph_destroy.argtypes = [C.c_void_p]
         L.orc_graph_set_count.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
         L.orc_graph_link.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
+        L.orc_graph_set_counts.argtypes = [C.c_void_p, u64p]
+        L.orc_graph_append_csr.argtypes = [C.c_void_p, u64p, u32p]
         L.orc_graph_preassign.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
         L.orc_graph_max_neighbour.argtypes = [C.c_void_p, C.c_size_t]
         L.orc_graph_max_neighbour.restype = C.c_size_t
@@ -161,8 +163,8 @@ class Graph:
     def __init__(self, counts):
         self.n = len(counts)
         self.h = lib().orc_graph_create(self.n)
-        for i, c in enumerate(counts):
-            lib().orc_graph_set_count(self.h, i, int(c))
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        lib().orc_graph_set_counts(self.h, _p(c, u64p))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -171,6 +173,14 @@ class Graph:
 
     def link(self, a, b):
         lib().orc_graph_link(self.h, a, b)
+
+    def append_csr(self, off, idx):
+        """leaf i's neighbours idx[off[i]:off[i + 1]] appended to its list in row order (one side only: a
+        symmetric graph lists every pair in both rows) -- a whole graph in one call"""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        x = np.ascontiguousarray(idx, dtype=np.uint32)
+        assert len(o) == self.n + 1 and int(o[-1]) == len(x) and (len(x) == 0 or int(x.max()) < self.n)
+        lib().orc_graph_append_csr(self.h, _p(o, u64p), _p(x, u32p))
 
     def preassign(self, leaf, cluster_id):
         lib().orc_graph_preassign(self.h, leaf, cluster_id)
