@@ -167,6 +167,59 @@ class Dedup(Context):
         self._wide = word_nt > 32
         return self.summary
 
+    def run_keyed(self, words, keys, filtered, word_nt=24, distance=1, method=DIRECTIONAL, edit=False):
+        """Deduplicate within groups given by arbitrary 64-bit keys (include/humid_hip.h, humid_dedup_run_keyed):
+        run_grouped with every usable read's group = the rank of its key among the distinct keys of the usable
+        reads, ranked on the device.  keys: u64[N]; keys of filtered reads are not read.
+        Returns (cluster_id, keep, summary) like run(); leaves() then also gives every leaf's "group" (the rank)
+        and "key", and group_keys() the sorted distinct keys."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        want = (len(f), 2) if word_nt > 32 else (len(f),)
+        if f.ndim != 1 or w.shape != want:
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % (want, word_nt, f.shape))
+        k = np.asarray(keys)
+        if k.dtype.kind not in "ui" or k.dtype.itemsize > 8 or k.shape != f.shape:
+            raise ValueError("keys must be integers of at most 64 bits with shape %r" % (f.shape,))
+        if k.dtype.kind == "i" and len(k) and int(k.min()) < 0:
+            raise ValueError("keys must not be negative")
+        k = np.ascontiguousarray(k, dtype=np.uint64)
+        n = len(f)
+        self._wide = word_nt > 32
+        self.set_option("edit_distance", int(bool(edit)))
+        cid = np.zeros(n, dtype=np.uint32)
+        keep = np.zeros(n, dtype=np.uint8)
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_keyed(self._h, _vp(w), _vp(k), _vp(f), n, word_nt, distance, method,
+                                                    _vp(cid), _vp(keep), C.byref(s)))
+        self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
+        return cid, keep, self.summary
+
+    def run_keyed_device(self, d_words, d_keys, d_filtered, d_cluster_id, d_keep, n_reads, word_nt=24, distance=1,
+                         method=DIRECTIONAL):
+        """run_keyed on device pointers (ints, e.g. tensor.data_ptr(); d_keys u64); results stay in HBM."""
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_keyed_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_keys), C.c_void_p(d_filtered), n_reads, word_nt, distance,
+            method, C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
+        self._wide = word_nt > 32
+        return self.summary
+
+    def group_keys(self):
+        """after a keyed run: the distinct keys of the usable reads, ascending (u64[G]); group g is key [g]"""
+        n = C.c_uint64()
+        self._check(self._lib.humid_get_group_keys(self._h, None, 0, C.byref(n)))
+        k = np.zeros(n.value, np.uint64)
+        self._check(self._lib.humid_get_group_keys(self._h, _vp(k), n.value, C.byref(n)))
+        return k
+
+    def keyed_rank_info(self):
+        """after a keyed run: dict(n_keys, table_log2, n_redo) of its key ranking (humid_keyed_rank_info)"""
+        g, t, r = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.humid_keyed_rank_info(self._h, C.byref(g), C.byref(t), C.byref(r)))
+        return dict(n_keys=g.value, table_log2=t.value, n_redo=r.value)
+
     def leaves(self):
         u = int(self.summary["unique"])
         wshape = (u, 2) if getattr(self, "_wide", False) else u
@@ -179,6 +232,8 @@ class Dedup(Context):
         if getattr(self, "_grouped_summary", None) is self.summary:      # the last run was a grouped one
             out["group"] = np.zeros(u, np.uint32)
             self._check(self._lib.humid_get_leaf_groups(self._h, _vp(out["group"])))
+        if getattr(self, "_keyed_summary", None) is self.summary:        # ... a keyed one
+            out["key"] = self.group_keys()[out["group"]] if u else np.zeros(0, np.uint64)
         return out
 
     def adjacency(self):

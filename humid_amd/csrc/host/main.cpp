@@ -53,17 +53,21 @@ struct Args {
   std::vector<std::string> files;
   std::string dump_words;      // --dump-words (development: stop after pass 1, no GPU)
   unsigned gpus = 1;           // -g (not in the reference): ranks the read set is sharded over, one GPU each
+  bool keyed = false;          // -b given (not in the reference): the first `barcode` nucleotides of the word are matched exactly
+  size_t barcode = 0;          // -b
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
                "  -a  write annotated FastQ files\n  -e  use edit distance (Levenshtein neighbours)\n"
                "  -x  use maximum clustering method\n"
-               "  -g  GPUs to shard the read set over (1..16; default 1 or $HUMID_GPUS; no -e beyond -m 1)\n",
+               "  -g  GPUs to shard the read set over (1..16; default 1 or $HUMID_GPUS)\n"
+               "  -b  barcode length K (1..32, K < n): the first K nucleotides of the word are matched exactly,\n"
+               "      -m / -e / -x apply to the remaining n - K (reads are deduplicated per barcode; one GPU)\n",
                argv0);
 }
 
@@ -80,6 +84,7 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-l") { const char *v = need("-l"); if (!v) return false; a.log_name = v; }
     else if (t == "-d") { const char *v = need("-d"); if (!v) return false; a.dir_name = v; }
     else if (t == "-g") { const char *v = need("-g"); if (!v) return false; a.gpus = (unsigned)std::strtoul(v, nullptr, 10); }
+    else if (t == "-b") { const char *v = need("-b"); if (!v) return false; a.keyed = true; a.barcode = std::strtoull(v, nullptr, 10); }
     else if (t == "--dump-words") { const char *v = need("--dump-words"); if (!v) return false; a.dump_words = v; }
     else if (t == "-s") a.stats = !a.stats;
     else if (t == "-q") a.filter = !a.filter;
@@ -235,6 +240,14 @@ int main(int argc, char **argv) {
   }
   // HUMID_FORCE_SHARDED=1: the rank orchestration also for -g 1 (one rank; exercises the transport)
   const bool sharded = a.gpus > 1 || getenv("HUMID_FORCE_SHARDED") != nullptr;
+  if (a.keyed && (a.barcode < 1 || a.barcode > 32 || a.barcode >= a.word_length)) {
+    std::fprintf(stderr, "humid: -b takes a barcode length of 1 .. 32 nucleotides below the word length (-n %zu)\n", a.word_length);
+    return 2;
+  }
+  if (a.keyed && sharded) {
+    std::fprintf(stderr, "humid: -b runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
+    return 2;
+  }
   std::ofstream log(a.log_name.c_str(), std::ios::out | std::ios::binary);
 
   // The HIP runtime and the context come up (a few hundred ms) while pass 1 parses the files.
@@ -269,7 +282,7 @@ int main(int argc, char **argv) {
         const uint64_t wb = (uint64_t)n * (a.word_length > 32 ? 16 : 8);
         pin_bytes = wb + (uint64_t)n + (uint64_t)n * 4 + (uint64_t)n + 64;
         std::thread pin_thread;                            // the two take ~30 ms and ~40 ms: side by side
-        if (getenv("HUMID_NO_PINNED") == nullptr)
+        if (getenv("HUMID_NO_PINNED") == nullptr && !a.keyed)   // (-b: keys and shorter words, from ordinary memory)
           pin_thread = std::thread([&] { pinned = (uint8_t *)humid_host_alloc(pin_bytes); t_pin = since(); });
         if (getenv("HUMID_NO_SLAB") == nullptr)
           humid_ctx_reserve(ctx, (uint64_t)n, (uint32_t)a.word_length);   // one slab + the code object loaded
@@ -334,7 +347,7 @@ int main(int argc, char **argv) {
   // HUMID_DEVICE_PACK=1: the host only gathers the raw symbols and the GPU packs them
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
-  const bool device_pack = fast && a.dump_words.empty() && !sharded && getenv("HUMID_DEVICE_PACK") != nullptr;
+  const bool device_pack = fast && a.dump_words.empty() && !sharded && !a.keyed && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
   if (fast) {
     size_t n = maps[0].records();
@@ -398,6 +411,27 @@ int main(int argc, char **argv) {
     return 0;
   }
 
+  // -b K: the packed n-nucleotide word splits into the key (its first K nucleotides, one uint64) and the word the
+  // run clusters (the remaining n - K, one uint64 up to 32 nucleotides, two beyond): a shift per read
+  std::vector<uint64_t> keys;
+  const size_t run_nt = a.keyed ? a.word_length - a.barcode : a.word_length;
+  if (a.keyed) {
+    const size_t out_wpr = run_nt > 32 ? 2 : 1;
+    const unsigned rb = 2 * (unsigned)run_nt;              // bits of the remaining word, 2 .. 126
+    keys.resize(N);
+    std::vector<uint64_t> rest(N * out_wpr);
+    parallel_ranges(N, threads, [&](size_t b, size_t e, unsigned) {
+      for (size_t i = b; i < e; i++) {
+        const unsigned __int128 v = wpr == 2 ? ((unsigned __int128)words[2 * i] << 64) | words[2 * i + 1] : (unsigned __int128)words[i];
+        const unsigned __int128 w = v & ((((unsigned __int128)1) << rb) - 1);
+        keys[i] = (uint64_t)(v >> rb);
+        if (out_wpr == 2) { rest[2 * i] = (uint64_t)(w >> 64); rest[2 * i + 1] = (uint64_t)w; }
+        else rest[i] = (uint64_t)w;
+      }
+    });
+    words.swap(rest);
+  }
+
   // ---- the hot path on the GPU ----
   phase("pass 1 done");
   if (ctx_init.th.joinable()) ctx_init.th.join();
@@ -413,7 +447,7 @@ int main(int argc, char **argv) {
   uint8_t *keep = nullptr;
   const uint64_t *run_words = words.data();
   const uint8_t *run_filt = filtered.data();
-  const bool staged = pinned != nullptr && N > 0 && !device_pack && (uint64_t)n_known.load() == N;
+  const bool staged = pinned != nullptr && N > 0 && !device_pack && !a.keyed && (uint64_t)n_known.load() == N;
   if (staged) {
     const uint64_t wb = N * 8 * wpr;
     uint8_t *p_words = pinned, *p_filt = pinned + wb;
@@ -448,7 +482,10 @@ int main(int argc, char **argv) {
     if (rc == HUMID_OK && getenv("HUMID_TIMING"))
       std::fprintf(stderr, "[humid]   %u ranks, bulk data by %s: set-up %.1f ms, ranks %.1f ms\n", a.gpus,
                    shr.comm.c_str(), shr.ms_init, shr.ms_run);
-  } else
+  } else if (a.keyed)
+    rc = humid_dedup_run_keyed(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance, method,
+                               cluster_id, keep, &sum);
+  else
   rc = device_pack
                ? humid_dedup_run_bases(ctx, bases.data(), N, (uint32_t)a.word_length, (uint32_t)a.distance, method,
                                        cluster_id, keep, &sum)
@@ -468,6 +505,7 @@ int main(int argc, char **argv) {
   t = start_message(log, a.maximum ? "Calculating maximum clusters" : "Calculating directional clusters");
   end_message(log, t);
   std::vector<uint64_t>().swap(words);
+  std::vector<uint64_t>().swap(keys);
   std::vector<uint8_t>().swap(bases);
 
   make_dirs(a.dir_name);

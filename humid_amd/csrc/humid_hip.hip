@@ -99,7 +99,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -177,6 +177,11 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->edit = value != 0;
     return HUMID_OK;
   }
+  if (strcmp(key, "keyrank_table_log2") == 0) {
+    if (value != 0 && (value < 4 || value > 32)) return fail(c, HUMID_E_INVALID, "keyrank_table_log2 must be 0 (automatic) or 4 .. 32");
+    c->kr_force_log2 = (u32)value;
+    return HUMID_OK;
+  }
   if (strcmp(key, "tile_partition") == 0) {
     c->use_tile_partition = value != 0;
     return HUMID_OK;
@@ -248,11 +253,11 @@ int humid_dedup_run_grouped_device(humid_ctx *c, const uint64_t *d_words, const 
 }
 
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
-// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1)
+// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1); key != null: humid_dedup_run_keyed
 static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
                     uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                     uint8_t *keep, humid_summary *summary, bool grouped = false, const uint32_t *group = nullptr,
-                    uint32_t n_groups = 1) {
+                    uint32_t n_groups = 1, const uint64_t *key = nullptr) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (n_reads && (!(bases || (words && filtered)) || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
@@ -295,8 +300,17 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
     ENSURE(c->gk_group_in, n * 4 + 8);
     HIPCHK(hipMemcpyAsync(c->gk_group_in.p, group, n * 4, hipMemcpyHostToDevice, st));
   }
+  if (n && key) {
+    ENSURE(c->kr_key_in, n * 8 + 8);
+    HIPCHK(hipMemcpyAsync(c->kr_key_in.p, key, n * 8, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipEventRecord(e1, st));
-  int rc = grouped ? (word_nt > 32
+  int rc = key ? (word_nt > 32
+               ? run_keyed_device<W2>(c, c->in_words.as<W2>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
+                                      distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
+               : run_keyed_device<u64>(c, c->in_words.as<u64>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
+                                       distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
+           : grouped ? (word_nt > 32
                ? run_grouped_device<W2>(c, c->in_words.as<W2>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
                                         n_reads, word_nt, n_groups, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
                : run_grouped_device<u64>(c, c->in_words.as<u64>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
@@ -332,6 +346,29 @@ int humid_dedup_run_grouped(humid_ctx *c, const uint64_t *words, const uint32_t 
                             uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, true, group,
                   n_groups);
+}
+
+int humid_dedup_run_keyed_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
+                                 uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (word_nt > 32)
+    return run_keyed_device<W2>(c, (const W2 *)d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id,
+                                d_keep, summary);
+  return run_keyed_device<u64>(c, d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+}
+
+int humid_dedup_run_keyed(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
+                          uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
+                          uint8_t *keep, humid_summary *summary) {
+  if (c) {                                                   // (before any copy: a refused shape moves nothing)
+    c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
+    TRY(check_run_args(c, n_reads, word_nt, method, 64));
+    if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
+  }
+  static const uint64_t no_key = 0;                          // (n_reads == 0: nothing is read)
+  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, false, nullptr, 1,
+                  key ? key : &no_key);
 }
 
 int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
@@ -415,6 +452,28 @@ int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
   HIPCHK(hipMemcpyAsync(iw.data(), c->g_word, U * 8 * c->g_wpr, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   gkey_split(c, iw, U, nullptr, group);
+  return HUMID_OK;
+}
+
+int humid_get_group_keys(humid_ctx *c, uint64_t *keys, uint64_t cap, uint64_t *n_out) {
+  NEED_RUN();
+  if (!c->kr_leaves) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
+  if (!n_out) return fail(c, HUMID_E_INVALID, "null argument");
+  *n_out = c->kr_n;
+  const u64 take = c->kr_n < cap ? c->kr_n : cap;
+  if (take && keys) {
+    D2H(keys, c->kr_keys.p, take * 8);
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return HUMID_OK;
+}
+
+int humid_keyed_rank_info(humid_ctx *c, uint64_t *n_keys, uint32_t *table_log2, uint32_t *n_redo) {
+  NEED_RUN();
+  if (!c->kr_leaves) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
+  if (n_keys) *n_keys = c->kr_n;
+  if (table_log2) *table_log2 = c->kr_last_log2;
+  if (n_redo) *n_redo = c->kr_redo;
   return HUMID_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "kernels_xchg.hip.h"
 #include "kernels_wide.hip.h"
 #include "kernels_gkey.hip.h"
+#include "kernels_keyrank.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -161,6 +162,14 @@ struct humid_ctx {
   bool gk_leaves = false;    // the leaf arrays of the last graph stage hold grouped internal words ...
   u32 gk_word_nt = 0, gk_leaf_nt = 0;   // ... of this caller word length and group field
   DBuf gk_words, gk_group_in, gk_bad;   // internal words; host entry point staging of the groups; device flag (no mapped memory)
+  // keyed runs (humid_dedup_run_keyed*): grouped runs whose groups are the ranks of 64-bit keys (kernels_keyrank.hip.h)
+  bool kr_on = false;        // a keyed pass is running (reset on every exit, like gk_on)
+  bool kr_leaves = false;    // the last run was a keyed run: kr_keys holds its kr_n sorted distinct keys
+  u32 kr_n = 0;
+  u32 kr_cap_log2 = 0;       // log2 of the table size of the next ranking (0: 16); remembered from pass to pass, grown on demand
+  u32 kr_force_log2 = 0;     // option "keyrank_table_log2": every ranking starts with this table size (test hook)
+  u32 kr_last_log2 = 0, kr_redo = 0;    // the last ranking: its final table size and how often it was repeated
+  DBuf kr_table, kr_raw, kr_rawslot, kr_keys, kr_slot, kr_key_in;   // table; compacted and sorted (key, slot); host entry point staging
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -1301,6 +1310,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   c->g_cnt = g_cnt;
   c->gU = U;
   c->gk_leaves = c->gk_on;
+  c->kr_leaves = c->kr_on;
   c->cg_valid = false;
   // ---------------- 3. neighbours -----------------
   // deg has U+1 entries (last stays 0) so that one exclusive scan yields nbr_off[U] = 2E
@@ -1638,6 +1648,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->g_cnt = g_cnt;
   c->gU = U;
   c->gk_leaves = c->gk_on;
+  c->kr_leaves = c->kr_on;
   c->cg_valid = false;
   c->cg_expanded = false;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
@@ -2332,6 +2343,7 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
 static int gkey_check(humid_ctx *c) {
   if (!c->gk_on) return HUMID_OK;
   const u32 seen = *(volatile u32 *)&c->h_ctr[CTR_N + 1];
+  if (seen == c->gk_epoch && c->kr_on) return fail(c, HUMID_E_INVALID, "internal: a usable read's key was not ranked");
   if (seen == c->gk_epoch) return fail(c, HUMID_E_INVALID, "a usable read has a group >= n_groups");
   return HUMID_OK;
 }
@@ -2356,6 +2368,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->have_graph = false;
   c->dense_mode = false;
   c->gk_leaves = c->gk_on;
+  c->kr_leaves = c->kr_on;
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (WIDE != (word_nt > 32)) return fail(c, HUMID_E_INVALID, "word layout does not match word_nt");
   if (WIDE && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
@@ -2459,15 +2472,17 @@ static int check_grouped_args(humid_ctx *c, u32 word_nt, u32 n_groups) {
 // The whole grouped pass: k_gkey_words writes the internal words (and checks the groups), run_device runs the
 // pass over them with the group field in every combination of the plan.  group == null: all reads in group 0
 // (n_groups must be 1), the plain pass itself.  WI: the caller's word type (word_nt <= 32: u64).
+// d_key != null (run_keyed_device, which has ranked the keys into c->kr_table; d_group is null): the group of a read
+// is the rank of its key, n_groups the number of distinct keys, and k_kr_words writes the internal words.
 template <class WI>
 static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_group, const u8 *d_filt, u64 n_reads,
                               u32 word_nt, u32 n_groups, u32 distance, u32 method, u32 *d_cid, u8 *d_keep,
-                              humid_summary *sum) {
+                              humid_summary *sum, const u64 *d_key = nullptr) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = c->gk_leaves = false;
+  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   TRY(check_grouped_args(c, word_nt, n_groups));
-  if (!d_group && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
+  if (!d_group && !d_key && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
   if (n_reads && (!d_words || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (sizeof(WI) == 16 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
   HIPCHK(hipSetDevice(c->device));
@@ -2479,7 +2494,7 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
   c->gk_leaf_nt = gnt;
   c->gk_epoch = c->gk_epoch + 1 ? c->gk_epoch + 1 : 1;     // (a value a store of an earlier pass cannot match)
   int rc;
-  if (!d_group || N == 0) {
+  if ((!d_group && !d_key) || N == 0 || (d_key && gnt == 0)) {
     rc = run_device<WI>(c, d_words, d_filt, n_reads, word_nt, distance, method, d_cid, d_keep, sum);
   } else {
     hipStream_t st = c->stream;
@@ -2493,7 +2508,13 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
       }
       bad = c->gk_bad.as<u32>();
     }
-    if (wide)
+    if (d_key && wide)
+      hipLaunchKernelGGL((k_kr_words<WI, W2>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_key, d_filt, N,
+                         (const KrSlot *)c->kr_table.p, c->kr_last_log2, n_groups, word_nt, gnt, c->gk_words.as<W2>(), bad, c->gk_epoch);
+    else if (d_key)
+      hipLaunchKernelGGL((k_kr_words<WI, u64>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_key, d_filt, N,
+                         (const KrSlot *)c->kr_table.p, c->kr_last_log2, n_groups, word_nt, gnt, c->gk_words.as<u64>(), bad, c->gk_epoch);
+    else if (wide)
       hipLaunchKernelGGL((k_gkey_words<WI, W2>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_group, d_filt, N,
                          word_nt, gnt, n_groups, copy ? c->gk_words.as<W2>() : nullptr, bad, c->gk_epoch);
     else
@@ -2509,6 +2530,76 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
   if (rc != HUMID_OK) { c->have_run = c->have_graph = c->gk_leaves = false; return rc; }
   c->word_nt = word_nt;
   return HUMID_OK;
+}
+
+// ---- keyed runs (humid_dedup_run_keyed*): grouped runs whose groups are the ranks of 64-bit keys ---------------
+// Ranks the distinct keys of the usable reads on the device (kernels_keyrank.hip.h): table insert, compaction, ONE
+// host wait (the number of distinct keys G chooses group_nt and the plan; the same wait reports a table that was
+// too small, and the ranking is then repeated with a larger one), a G-proportional sort, the ranks written back
+// into the table.  Leaves c->kr_keys (G sorted keys), c->kr_n = G and c->kr_table / kr_last_log2 for k_kr_words.
+static int rank_keys(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N) {
+  hipStream_t st = c->stream;
+  u32 full_log2 = 4;                                          // the size that cannot be too small: cap >= 2 N
+  while (full_log2 < 32 && ((u64)1 << full_log2) < 2 * (u64)N) full_log2++;
+  u32 cap_log2 = c->kr_force_log2 ? c->kr_force_log2 : (c->kr_cap_log2 ? c->kr_cap_log2 : 16u);
+  cap_log2 = std::min(std::max(cap_log2, 4u), full_log2);
+  c->kr_redo = 0;
+  u32 G = 0;
+  u64 bits = 0;
+  while (true) {
+    const u32 cap = 1u << cap_log2;
+    const u32 out_cap = std::min<u64>((u64)cap + 1, N);         // (every distinct key is some read's key)
+    ENSURE(c->kr_table, ((size_t)cap + 1) * sizeof(KrSlot));
+    ENSURE(c->kr_raw, (size_t)out_cap * 8 + 16);
+    ENSURE(c->kr_rawslot, (size_t)out_cap * 4 + 16);
+    HIPCHK(hipMemsetAsync(c->kr_table.p, 0xff, ((size_t)cap + 1) * sizeof(KrSlot), st));
+    HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
+    hipLaunchKernelGGL(k_kr_insert, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_key, d_filt, N, c->kr_table.as<KrSlot>(),
+                       cap_log2, cap_log2 == full_log2 ? cap : 128u, c->d_ctr);
+    hipLaunchKernelGGL(k_kr_compact, dim3(std::min<u32>(COMPACT_BLOCKS, blocks_for((u64)cap + 1))), dim3(256), 0, st,
+                       (const KrSlot *)c->kr_table.p, cap, c->kr_raw.as<u64>(), c->kr_rawslot.as<u32>(), out_cap, c->d_ctr);
+    HIPCHK(hipGetLastError());
+    TRY(read_counters(c));                                     // the host wait of the ranking
+    const bool overfull = c->h_ctr[CTR_OVERFULL] != 0 || c->h_ctr[CTR_UNIQUE] > out_cap;
+    if (!overfull) { G = (u32)c->h_ctr[CTR_UNIQUE]; bits = c->h_ctr[CTR_KEYBITS]; break; }
+    if (cap_log2 >= full_log2) return fail(c, HUMID_E_INVALID, "internal: the key table of 2^%u slots overflowed", cap_log2);
+    cap_log2 = std::min(cap_log2 + 4, full_log2);
+    c->kr_redo++;
+  }
+  c->kr_last_log2 = cap_log2;
+  c->kr_n = G;
+  // the next ranking starts with a table at most a third full for as many keys as this one saw
+  u32 next = 12;
+  while (next < full_log2 && ((u64)1 << next) < 3 * (u64)G) next++;
+  c->kr_cap_log2 = next;
+  if (G == 0) return HUMID_OK;
+  ENSURE(c->kr_keys, (size_t)G * 8 + 16);
+  ENSURE(c->kr_slot, (size_t)G * 4 + 16);
+  TRY((sort_pairs<u64, u32>(c, c->kr_raw.as<u64>(), c->kr_keys.as<u64>(), c->kr_rawslot.as<u32>(), c->kr_slot.as<u32>(), G, 0,
+                            bits ? 64u - (u32)__builtin_clzll(bits) : 1u)));          // (key bits above the highest one set: all 0)
+  hipLaunchKernelGGL(k_kr_ranks, dim3(blocks_for(G)), dim3(256), 0, st, (const u32 *)c->kr_slot.p, G, c->kr_table.as<KrSlot>(),
+                     1u << cap_log2);
+  HIPCHK(hipGetLastError());
+  return HUMID_OK;
+}
+
+// The whole keyed pass.  WI: the caller's word type (word_nt <= 32: u64).
+template <class WI>
+static int run_keyed_device(humid_ctx *c, const WI *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads, u32 word_nt,
+                            u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (n_reads && (!d_words || !d_key || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  struct KrGuard { humid_ctx *c; ~KrGuard() { c->kr_on = false; } } kr_guard{c};
+  c->kr_on = true;
+  c->kr_n = 0;
+  if (n_reads) TRY(rank_keys(c, d_key, d_filt, (u32)n_reads));
+  const int rc = run_grouped_device<WI>(c, d_words, nullptr, d_filt, n_reads, word_nt, std::max(c->kr_n, 1u), distance, method,
+                                        d_cid, d_keep, sum, n_reads ? d_key : nullptr);
+  if (rc != HUMID_OK) c->kr_leaves = false;
+  return rc;
 }
 
 #endif  // HUMID_PIPELINE_HIP_H

@@ -202,6 +202,44 @@ int humid_grouped_plan_info(humid_ctx *ctx, uint32_t word_nt, uint32_t n_groups,
                             uint64_t n_unique, uint32_t *n_combos, uint32_t *key_bits,
                             uint32_t *group_nt);
 
+/* ---- keyed deduplication: grouped runs whose groups are arbitrary 64-bit keys -------------------
+ * (a 16-nt cell barcode as a 32-bit value, barcode + gene or (contig, position, strand) as a 64-bit
+ * value).  key[n_reads] (u64) beside words and filtered.  Let K be the ascending (unsigned) list of
+ * the distinct key[r] over the usable reads (filtered[r] == 0) and G = len(K).  The results --
+ * cluster_id / keep, summary, humid_get_leaves, humid_get_leaf_groups, _adjacency, _clusters, the
+ * three histograms -- are DEFINED as those of humid_dedup_run_grouped with group[r] = index of key[r]
+ * in K and n_groups = max(G, 1).  Every 64-bit value is a legal key.  Keys of filtered reads are
+ * never read: they may be anything and never become a group.  With group_nt as above for G groups,
+ * word_nt + group_nt > 64 returns HUMID_E_UNSUPPORTED and leaves the context usable; G <= n_reads <
+ * 2^31 gives group_nt <= 16, so every word_nt <= 48 is accepted whatever the keys are.  The option
+ * "edit_distance" applies as in grouped runs; no tuning option changes results.  Not for the
+ * multi-GPU pass.
+ * The keys are ranked on the device (no host-side sort or hash): the distinct keys go into an
+ * open-address table, are compacted and sorted (work proportional to G), and a second pass over the
+ * reads writes every rank straight into the internal word of the grouped pass.  G chooses group_nt
+ * and the pigeonhole plan, so the ranking has ONE host wait of its own (about 10 us of idle device,
+ * in front of the three waits of the pass).  A table that turns out too small is seen at that wait
+ * and the ranking is repeated with a larger one (16 times the slots, at most 2 n_reads rounded up
+ * to a power of two, which cannot be too small); the size that fitted is remembered for the next
+ * run of the context.  Option "keyrank_table_log2" (4 .. 32, 0 = automatic): every ranking starts
+ * with a table of that many slots instead; results do not depend on it.
+ *   humid_dedup_run_keyed_device: the same with DEVICE pointers, like humid_dedup_run_grouped_device.
+ *   humid_get_group_keys: K of the last run, up to cap keys; *n_out = G (call with cap = 0 to size
+ *     the buffer).  The key of a leaf is K[leaf group].  HUMID_E_STATE unless the last run was a
+ *     keyed run.
+ *   humid_keyed_rank_info: the ranking of the last keyed run: G, log2 of the table size it ended
+ *     with, and how often it was repeated with a larger table.  Any pointer may be NULL. */
+int humid_dedup_run_keyed(humid_ctx *ctx, const uint64_t *words, const uint64_t *key,
+                          const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                          uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep,
+                          humid_summary *summary);
+int humid_dedup_run_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const uint64_t *d_key,
+                                 const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt,
+                                 uint32_t distance, uint32_t method, uint32_t *d_cluster_id,
+                                 uint8_t *d_keep, humid_summary *summary);
+int humid_get_group_keys(humid_ctx *ctx, uint64_t *keys, uint64_t cap, uint64_t *n_out);
+int humid_keyed_rank_info(humid_ctx *ctx, uint64_t *n_keys, uint32_t *table_log2, uint32_t *n_redo);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
