@@ -84,6 +84,9 @@ SYMBOLS = {
                                                C.POINTER(HumidSummary)]),
     "humid_get_group_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "humid_keyed_rank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, u32p]),
+    "humid_get_group_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "humid_group_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 4),
     "humid_get_leaves": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "humid_get_adjacency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_get_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

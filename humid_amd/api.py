@@ -220,6 +220,37 @@ class Dedup(Context):
         self._check(self._lib.humid_keyed_rank_info(self._h, C.byref(g), C.byref(t), C.byref(r)))
         return dict(n_keys=g.value, table_log2=t.value, n_redo=r.value)
 
+    def group_stats(self):
+        """Per-group statistics of the last run (include/humid_hip.h, humid_get_group_stats), reduced on the device:
+        dict(reads u64[G], unique u32[G], clusters u32[G], edges u32[G], leaf_off u32[G+1], cluster_off u32[G+1]).
+        G = n_groups after a grouped run, the number of distinct keys after a keyed run, 1 after a plain run.
+        Group g owns the leaves [leaf_off[g], leaf_off[g+1]) and the cluster ids cluster_off[g]+1 .. cluster_off[g+1];
+        clusters[g] is its number of molecules.  After a keyed run "key" (u64[G]) is group_keys(), so
+        (key, clusters) is the count table in coordinate form."""
+        n = C.c_uint64()
+        self._check(self._lib.humid_get_group_stats(self._h, 0, C.byref(n), None, None, None, None))
+        g = n.value
+        reads, edges = np.zeros(g, np.uint64), np.zeros(g, np.uint32)
+        leaf_off, cluster_off = np.zeros(g + 1, np.uint32), np.zeros(g + 1, np.uint32)
+        self._check(self._lib.humid_get_group_stats(self._h, g, C.byref(n), _vp(reads), _vp(leaf_off),
+                                                    _vp(cluster_off), _vp(edges)))
+        out = dict(reads=reads, unique=np.diff(leaf_off), clusters=np.diff(cluster_off), edges=edges,
+                   leaf_off=leaf_off, cluster_off=cluster_off)
+        if getattr(self, "_keyed_summary", None) is self.summary:        # the last run was a keyed one
+            out["key"] = self.group_keys()
+        return out
+
+    def group_stats_device(self):
+        """The arrays of group_stats() left in HBM: dict(n, reads, leaf_off, cluster_off, edges) with n = G and
+        integer device pointers (reads u64[G], leaf_off u32[G+1], cluster_off u32[G+1], edges u32[G]), e.g. for
+        a torch tensor over them without a download.  The memory belongs to this object: it is valid until its
+        next run or close(), and complete when the call returns."""
+        n = C.c_uint64()
+        p = [C.c_void_p() for _ in range(4)]
+        self._check(self._lib.humid_group_stats_device(self._h, C.byref(n), *[C.byref(x) for x in p]))
+        return dict(n=n.value, reads=p[0].value or 0, leaf_off=p[1].value or 0, cluster_off=p[2].value or 0,
+                    edges=p[3].value or 0)
+
     def leaves(self):
         u = int(self.summary["unique"])
         wshape = (u, 2) if getattr(self, "_wide", False) else u

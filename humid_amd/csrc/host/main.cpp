@@ -67,7 +67,8 @@ void usage(const char *argv0) {
                "  -x  use maximum clustering method\n"
                "  -g  GPUs to shard the read set over (1..16; default 1 or $HUMID_GPUS)\n"
                "  -b  barcode length K (1..32, K < n): the first K nucleotides of the word are matched exactly,\n"
-               "      -m / -e / -x apply to the remaining n - K (reads are deduplicated per barcode; one GPU)\n",
+               "      -m / -e / -x apply to the remaining n - K (reads are deduplicated per barcode; one GPU);\n"
+               "      with -s also groups.dat: one line \"<barcode> <reads> <unique> <clusters>\" per barcode\n",
                argv0);
 }
 
@@ -128,6 +129,27 @@ int write_hist(humid_ctx *ctx, uint32_t which, const std::string &path) {
   if (n && humid_get_histogram(ctx, which, k.data(), v.data(), n, &n) != HUMID_OK) return 0;
   std::ofstream out(path, std::ios::out | std::ios::binary);
   for (uint64_t i = 0; i < n; i++) out << k[i] << ' ' << v[i] << '\n';   // src/humid.cc:333-349
+  out.close();
+  return out.fail() ? -1 : 1;
+}
+
+// -b K with -s: groups.dat, one line per distinct barcode in ascending order: "<barcode> <reads> <unique> <clusters>",
+// the barcode as its K letters (first nucleotide first); the table comes reduced from the device
+// (humid_get_group_stats).  Returns like write_hist.
+int write_groups(humid_ctx *ctx, size_t barcode_nt, const std::string &path) {
+  uint64_t n = 0, nk = 0;
+  if (humid_get_group_stats(ctx, 0, &n, nullptr, nullptr, nullptr, nullptr) != HUMID_OK) return 0;
+  std::vector<uint64_t> key(n ? n : 1), reads(n ? n : 1);
+  std::vector<uint32_t> leaf_off(n + 1), cluster_off(n + 1);
+  if (humid_get_group_stats(ctx, n, &n, reads.data(), leaf_off.data(), cluster_off.data(), nullptr) != HUMID_OK) return 0;
+  if (humid_get_group_keys(ctx, key.data(), n, &nk) != HUMID_OK) return 0;
+  if (nk != n) return -1;
+  std::ofstream out(path, std::ios::out | std::ios::binary);
+  std::string letters(barcode_nt, 'A');
+  for (uint64_t g = 0; g < n; g++) {
+    for (size_t i = 0; i < barcode_nt; i++) letters[i] = "ACGT"[(key[g] >> (2 * (barcode_nt - 1 - i))) & 3];
+    out << letters << ' ' << reads[g] << ' ' << leaf_off[g + 1] - leaf_off[g] << ' ' << cluster_off[g + 1] - cluster_off[g] << '\n';
+  }
   out.close();
   return out.fail() ? -1 : 1;
 }
@@ -689,6 +711,7 @@ int main(int argc, char **argv) {
       out.close();
       if (out.fail()) ok = -1;
     }
+    if (ok == 1 && a.keyed) ok = write_groups(ctx, a.barcode, a.dir_name + "/groups.dat");   // (-b is never sharded)
     end_message(log, t);
     if (ok == 0) { std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx)); humid_ctx_destroy(ctx); return 1; }
     std::ofstream out(a.dir_name + "/stats.dat", std::ios::out | std::ios::binary);

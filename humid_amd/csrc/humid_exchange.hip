@@ -1111,6 +1111,7 @@ int humid_stage_graph(humid_ctx *c, const uint64_t *d_g_word, const uint32_t *d_
                       const uint32_t **d_cluster_id, const uint8_t **d_is_max, humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   c->have_graph = false;
+  c->gs_run = false;
   c->graph_mode = false;
   TRY(check_run_args(c, n_unique, word_nt, method, 64));
   HIPCHK(hipSetDevice(c->device));
@@ -1176,6 +1177,7 @@ int humid_stage_graph_edges(humid_ctx *c, const uint64_t *d_g_word, const uint32
                             humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   c->have_graph = false;
+  c->gs_run = false;
   c->graph_mode = false;
   TRY(check_run_args(c, n_unique, word_nt, method, 64));
   if (n_edges >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "2*edges exceeds 32 bits");

@@ -99,7 +99,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -566,6 +566,73 @@ int humid_get_histogram(humid_ctx *c, uint32_t which, uint64_t *keys, uint64_t *
   return HUMID_OK;
 }
 
+// Per-group statistics of the last single-GPU run, left in c->gs_* (kernels_gstats.hip.h): one exclusive scan over
+// the leaves, one lower-bound search per group boundary, one difference per group.  Runs on the first call after a
+// run; every later call finds gs_valid.  Nothing of g_word is copied to the host.
+static int group_stats(humid_ctx *c) {
+  if (!c->have_run || !c->gs_run) return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
+  if (c->gs_valid) return HUMID_OK;
+  hipStream_t st = c->stream;
+  const u32 U = c->gU;
+  const u32 G = c->kr_leaves ? c->kr_n : c->gk_leaves ? c->gk_groups : 1u;
+  const size_t off_bytes = ((size_t)G + 1) * 4;
+  ENSURE(c->gs_loff, off_bytes);
+  ENSURE(c->gs_coff, off_bytes);
+  ENSURE(c->gs_reads, (size_t)G * 8 + 8);
+  ENSURE(c->gs_edges, (size_t)G * 4 + 4);
+  if (U == 0 || G == 0) {                                    // no leaf: every range is empty, nothing indexes the leaf arrays
+    HIPCHK(hipMemsetAsync(c->gs_loff.p, 0, off_bytes, st));
+    HIPCHK(hipMemsetAsync(c->gs_coff.p, 0, off_bytes, st));
+    HIPCHK(hipMemsetAsync(c->gs_reads.p, 0, (size_t)G * 8 + 8, st));
+    HIPCHK(hipMemsetAsync(c->gs_edges.p, 0, (size_t)G * 4 + 4, st));
+  } else {
+    ENSURE(c->gs_ps, (size_t)U * 8);
+    TRY(exscan_in<u64>(c, GsPairIn{c->g_cnt, c->deg.as<u32>()}, c->gs_ps.as<u64>(), U));
+    const u32 gnt = c->gk_leaves ? c->gk_leaf_nt : 0u, wb = 2 * c->gk_word_nt;
+    const u32 nb = grid_stride_blocks((u64)G + 1);
+    if (c->g_wpr == 2)
+      hipLaunchKernelGGL(k_gs_offsets<W2>, dim3(nb), dim3(256), 0, st, (const W2 *)c->g_word, c->pos.as<u32>(), U, (u32)c->C, wb,
+                         gnt, G, c->gs_loff.as<u32>(), c->gs_coff.as<u32>());
+    else
+      hipLaunchKernelGGL(k_gs_offsets<u64>, dim3(nb), dim3(256), 0, st, (const u64 *)c->g_word, c->pos.as<u32>(), U, (u32)c->C, wb,
+                         gnt, G, c->gs_loff.as<u32>(), c->gs_coff.as<u32>());
+    hipLaunchKernelGGL(k_gs_sums, dim3(grid_stride_blocks(G)), dim3(256), 0, st, (const u32 *)c->gs_loff.p,
+                       (const u64 *)c->gs_ps.p, U, (u64)c->usable | ((u64)(2 * c->E) << 32), G, c->gs_reads.as<u64>(),
+                       c->gs_edges.as<u32>());
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  c->gs_G = G;
+  c->gs_valid = true;
+  return HUMID_OK;
+}
+
+int humid_get_group_stats(humid_ctx *c, uint64_t cap, uint64_t *n_out, uint64_t *reads, uint32_t *leaf_off,
+                          uint32_t *cluster_off, uint32_t *edges) {
+  NEED_RUN();
+  TRY(group_stats(c));
+  if (n_out) *n_out = c->gs_G;
+  const size_t take = (size_t)(c->gs_G < cap ? c->gs_G : cap);
+  D2H(reads, c->gs_reads.p, take * 8);
+  D2H(leaf_off, c->gs_loff.p, (take + 1) * 4);
+  D2H(cluster_off, c->gs_coff.p, (take + 1) * 4);
+  D2H(edges, c->gs_edges.p, take * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_group_stats_device(humid_ctx *c, uint64_t *n_out, const uint64_t **d_reads, const uint32_t **d_leaf_off,
+                             const uint32_t **d_cluster_off, const uint32_t **d_edges) {
+  NEED_RUN();
+  TRY(group_stats(c));
+  if (n_out) *n_out = c->gs_G;
+  if (d_reads) *d_reads = c->gs_reads.as<u64>();
+  if (d_leaf_off) *d_leaf_off = c->gs_loff.as<u32>();
+  if (d_cluster_off) *d_cluster_off = c->gs_coff.as<u32>();
+  if (d_edges) *d_edges = c->gs_edges.as<u32>();
+  return HUMID_OK;
+}
+
 int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr_off,
                         const uint32_t *nbr_idx, uint32_t n_leaves, uint32_t method,
                         uint32_t *leaf_cluster, uint64_t *cl_size, uint32_t *cl_max_count,
@@ -586,6 +653,7 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
   hipStream_t st = c->stream;
   c->have_run = false;
   c->have_graph = false;
+  c->gs_run = false;
   c->graph_mode = true;
   c->cg_valid = false;
   ENSURE(c->s_cnt, (size_t)U * 4);

@@ -28,6 +28,7 @@
 #include "kernels_wide.hip.h"
 #include "kernels_gkey.hip.h"
 #include "kernels_keyrank.hip.h"
+#include "kernels_gstats.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -170,6 +171,13 @@ struct humid_ctx {
   u32 kr_force_log2 = 0;     // option "keyrank_table_log2": every ranking starts with this table size (test hook)
   u32 kr_last_log2 = 0, kr_redo = 0;    // the last ranking: its final table size and how often it was repeated
   DBuf kr_table, kr_raw, kr_rawslot, kr_keys, kr_slot, kr_key_in;   // table; compacted and sorted (key, slot); host entry point staging
+  // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
+  // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
+  u32 gk_groups = 1;         // n_groups of the last grouped run
+  bool gs_run = false;       // the leaf arrays are those of a completed humid_dedup_run* (no stage or graph call since)
+  bool gs_valid = false;     // gs_* hold that run's statistics for gs_G groups
+  u32 gs_G = 0;
+  DBuf gs_reads, gs_loff, gs_coff, gs_edges, gs_ps;   // reads u64[G], leaf / cluster offsets u32[G + 1], pairs u32[G]; scan of (count | degree << 32)
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -2366,6 +2374,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->have_run = false;
   c->graph_mode = false;
   c->have_graph = false;
+  c->gs_run = c->gs_valid = false;
   c->dense_mode = false;
   c->gk_leaves = c->gk_on;
   c->kr_leaves = c->kr_on;
@@ -2383,7 +2392,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
   c->word_nt = word_nt; c->distance = distance; c->method = method;
   c->gU = 0;
-  if (N == 0) { if (sum) *sum = s; c->have_run = c->have_graph = true; return HUMID_OK; }
+  if (N == 0) { if (sum) *sum = s; c->have_run = c->have_graph = c->gs_run = true; return HUMID_OK; }
   // the stages' own events only with the per-kernel timing (ms_count .. ms_map are 0 without it; ms_total and the
   // count kernel's time are always measured)
   struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = false; } } lean_guard{c};
@@ -2397,7 +2406,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)N, st));
     HIPCHK(hipStreamSynchronize(st));
     if (sum) *sum = s;
-    c->have_run = c->have_graph = true;
+    c->have_run = c->have_graph = c->gs_run = true;
     return HUMID_OK;
   }
   u32 n_pair_segs = 0;
@@ -2454,6 +2463,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   if (sum) *sum = s;
   c->have_run = true;
   c->have_graph = true;
+  c->gs_run = true;
   return HUMID_OK;
 }
 
@@ -2492,6 +2502,7 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
   c->gk_nt = gnt;
   c->gk_word_nt = word_nt;
   c->gk_leaf_nt = gnt;
+  c->gk_groups = n_groups;
   c->gk_epoch = c->gk_epoch + 1 ? c->gk_epoch + 1 : 1;     // (a value a store of an earlier pass cannot match)
   int rc;
   if ((!d_group && !d_key) || N == 0 || (d_key && gnt == 0)) {

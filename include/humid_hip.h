@@ -240,6 +240,41 @@ int humid_dedup_run_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const 
 int humid_get_group_keys(humid_ctx *ctx, uint64_t *keys, uint64_t cap, uint64_t *n_out);
 int humid_keyed_rank_info(humid_ctx *ctx, uint64_t *n_keys, uint32_t *table_log2, uint32_t *n_redo);
 
+/* ---- per-group statistics: how many molecules every group holds ---------------------------------
+ * (the UMI count per cell, or per (cell, gene): the count matrix.)  After a successful single-GPU run let G be
+ * its number of groups: n_groups as passed to humid_dedup_run_grouped*; after humid_dedup_run_keyed* the number
+ * of distinct keys, what humid_get_group_keys reports (G may be 0); a plain run (humid_dedup_run, _device,
+ * _bases) counts as ONE group, G = 1.  The leaves are in (group, word) walk order and the cluster ids are
+ * numbered on across the groups in group order, so both are one contiguous range per group.  For 0 <= g < G:
+ *   leaf_off[g]     walk index of the first leaf whose group is >= g; leaf_off[G] = summary.unique.  The leaves
+ *                   of g are [leaf_off[g], leaf_off[g + 1]): an absent group is an empty range, and
+ *                   unique[g] = leaf_off[g + 1] - leaf_off[g].
+ *   cluster_off[g]  the cluster ids of g are cluster_off[g] + 1 .. cluster_off[g + 1]; cluster_off[0] = 0,
+ *                   cluster_off[G] = summary.clusters.  clusters[g] = cluster_off[g + 1] - cluster_off[g], the
+ *                   molecules of g, is also the number of reads of g with keep == 1.
+ *   reads[g]        (u64) usable reads of g = the sum of count over its leaves.
+ *   edges[g]        (u32) neighbour pairs inside g = half the sum of degree over its leaves.
+ * The sums over g are summary.usable, .unique, .clusters and .edges.  After a keyed run group g is key
+ * humid_get_group_keys()[g], so (key, clusters) is the count table in coordinate form.
+ * The statistics are computed on the device by the first of these two calls after a run (an exclusive scan
+ * over the leaves, a lower-bound search per group, read from the internal words where the run left them:
+ * work proportional to unique + G log unique, whatever the sizes of the groups and the gaps between them)
+ * and kept until the next run; the runs themselves do nothing for them.
+ *   humid_get_group_stats: host copies.  *n_out = G (call with cap = 0 to size the buffers); writes
+ *     min(cap, G) entries of reads / edges and min(cap, G) + 1 entries of leaf_off / cluster_off.  Any pointer
+ *     may be NULL.
+ *   humid_group_stats_device: the same arrays left in HBM (reads u64[G], leaf_off u32[G + 1],
+ *     cluster_off u32[G + 1], edges u32[G]), owned by the context and valid until its next run or
+ *     humid_ctx_destroy; complete when the call returns.  Any pointer may be NULL.
+ * Both return HUMID_E_STATE before any run and after a multi-GPU pass, a humid_stage_* call or
+ * humid_cluster_graph, HUMID_E_INVALID for a NULL context, and HUMID_E_NOMEM when an allocation fails (the
+ * context stays usable). */
+int humid_get_group_stats(humid_ctx *ctx, uint64_t cap, uint64_t *n_out, uint64_t *reads,
+                          uint32_t *leaf_off, uint32_t *cluster_off, uint32_t *edges);
+int humid_group_stats_device(humid_ctx *ctx, uint64_t *n_out, const uint64_t **d_reads,
+                             const uint32_t **d_leaf_off, const uint32_t **d_cluster_off,
+                             const uint32_t **d_edges);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
