@@ -84,6 +84,19 @@ SYMBOLS = {
                                                C.POINTER(HumidSummary)]),
     "humid_get_group_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "humid_keyed_rank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, u32p]),
+    "humid_whitelist_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "humid_whitelist_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, u32p]),
+    "humid_whitelist_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "humid_whitelist_correct_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    "humid_dedup_run_keyed_corrected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(HumidSummary)]),
+    "humid_dedup_run_keyed_corrected_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                         C.POINTER(HumidSummary)]),
+    "humid_get_barcode_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "humid_get_group_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "humid_group_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 4),

@@ -19,6 +19,9 @@ from . import _lib
 DIRECTIONAL = 0
 MAXIMUM = 1
 
+# per-read status of the barcode correction (include/humid_hip.h, HUMID_BC_*); also the index into its five counts
+BC_FILTERED, BC_EXACT, BC_CORRECTED, BC_AMBIGUOUS, BC_UNMATCHED = range(5)
+
 
 class HumidError(RuntimeError):
     def __init__(self, code, msg):
@@ -30,6 +33,16 @@ def _vp(a):
     if a is None:
         return None
     return C.c_void_p(a.ctypes.data)
+
+
+def _keys_u64(keys, shape, what="keys"):
+    """integers of at most 64 bits, not negative, of the given shape (None: any one-dimensional) -> contiguous u64"""
+    k = np.asarray(keys)
+    if k.dtype.kind not in "ui" or k.dtype.itemsize > 8 or (k.shape != shape if shape is not None else k.ndim != 1):
+        raise ValueError("%s must be integers of at most 64 bits with shape %r" % (what, shape if shape is not None else "(n,)"))
+    if k.dtype.kind == "i" and len(k) and int(k.min()) < 0:
+        raise ValueError("%s must not be negative" % what)
+    return np.ascontiguousarray(k, dtype=np.uint64)
 
 
 class Context:
@@ -167,12 +180,15 @@ class Dedup(Context):
         self._wide = word_nt > 32
         return self.summary
 
-    def run_keyed(self, words, keys, filtered, word_nt=24, distance=1, method=DIRECTIONAL, edit=False):
+    def run_keyed(self, words, keys, filtered, word_nt=24, distance=1, method=DIRECTIONAL, edit=False, correct=False):
         """Deduplicate within groups given by arbitrary 64-bit keys (include/humid_hip.h, humid_dedup_run_keyed):
         run_grouped with every usable read's group = the rank of its key among the distinct keys of the usable
         reads, ranked on the device.  keys: u64[N]; keys of filtered reads are not read.
         Returns (cluster_id, keep, summary) like run(); leaves() then also gives every leaf's "group" (the rank)
-        and "key", and group_keys() the sorted distinct keys."""
+        and "key", and group_keys() the sorted distinct keys.
+        correct=True: the keys are corrected against the whitelist of set_whitelist() first and reads whose key is
+        ambiguous or unmatched count as filtered (humid_dedup_run_keyed_corrected); barcode_status() then gives
+        every read's status."""
         w = np.ascontiguousarray(words, dtype=np.uint64)
         f = np.ascontiguousarray(filtered, dtype=np.uint8)
         want = (len(f), 2) if word_nt > 32 else (len(f),)
@@ -190,8 +206,8 @@ class Dedup(Context):
         cid = np.zeros(n, dtype=np.uint32)
         keep = np.zeros(n, dtype=np.uint8)
         s = _lib.HumidSummary()
-        self._check(self._lib.humid_dedup_run_keyed(self._h, _vp(w), _vp(k), _vp(f), n, word_nt, distance, method,
-                                                    _vp(cid), _vp(keep), C.byref(s)))
+        fn = self._lib.humid_dedup_run_keyed_corrected if correct else self._lib.humid_dedup_run_keyed
+        self._check(fn(self._h, _vp(w), _vp(k), _vp(f), n, word_nt, distance, method, _vp(cid), _vp(keep), C.byref(s)))
         self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
         return cid, keep, self.summary
 
@@ -205,6 +221,67 @@ class Dedup(Context):
         self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
         self._wide = word_nt > 32
         return self.summary
+
+    def run_keyed_corrected_device(self, d_words, d_keys, d_filtered, d_cluster_id, d_keep, n_reads, word_nt=24,
+                                   distance=1, method=DIRECTIONAL):
+        """run_keyed(correct=True) on device pointers (ints, e.g. tensor.data_ptr(); d_keys u64); results stay in
+        HBM."""
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_keyed_corrected_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_keys), C.c_void_p(d_filtered), n_reads, word_nt, distance,
+            method, C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
+        self._wide = word_nt > 32
+        return self.summary
+
+    def set_whitelist(self, barcodes, barcode_nt=16):
+        """The known barcodes (include/humid_hip.h, humid_whitelist_set): integers of at most 64 bits, each a
+        barcode_nt-nucleotide word (< 4 ** barcode_nt); duplicates collapse.  None or an empty array clears the
+        whitelist.  It stays with this object through any number of runs until it is replaced or cleared."""
+        if barcodes is None:
+            b = np.zeros(0, np.uint64)
+        else:
+            b = _keys_u64(barcodes, None, "barcodes")
+        if len(b):
+            if not 1 <= int(barcode_nt) <= 32:
+                raise ValueError("barcode_nt must be 1 .. 32")
+            if barcode_nt < 32 and int(b.max()) >= 4 ** int(barcode_nt):
+                raise ValueError("a barcode is not a %d-nucleotide word" % barcode_nt)
+        self._check(self._lib.humid_whitelist_set(self._h, _vp(b) if len(b) else None, len(b), int(barcode_nt)))
+
+    def whitelist_info(self):
+        """dict(n_distinct, barcode_nt, table_log2) of the whitelist (n_distinct = 0: none is set)"""
+        n, k, t = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.humid_whitelist_info(self._h, C.byref(n), C.byref(k), C.byref(t)))
+        return dict(n_distinct=n.value, barcode_nt=k.value, table_log2=t.value)
+
+    def correct_keys(self, keys, filtered):
+        """Correct keys against the whitelist without running anything else (humid_whitelist_correct): returns
+        (keys_out u64[N], status u8[N] of BC_FILTERED .. BC_UNMATCHED, counts u64[5] indexed by status).  The
+        results of the last run stay untouched."""
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("filtered must be one-dimensional")
+        k = _keys_u64(keys, f.shape)
+        n = len(f)
+        out, status, counts = np.zeros(n, np.uint64), np.zeros(n, np.uint8), np.zeros(5, np.uint64)
+        self._check(self._lib.humid_whitelist_correct(self._h, _vp(k), _vp(f), n, _vp(out), _vp(status), _vp(counts)))
+        return out, status, counts
+
+    def correct_keys_device(self, d_keys, d_filtered, d_keys_out, d_status, n_reads):
+        """correct_keys on device pointers (ints; d_keys_out u64[N] and d_status u8[N] may be 0); returns counts"""
+        counts = np.zeros(5, np.uint64)
+        self._check(self._lib.humid_whitelist_correct_device(
+            self._h, C.c_void_p(d_keys), C.c_void_p(d_filtered), n_reads, C.c_void_p(d_keys_out) if d_keys_out else None,
+            C.c_void_p(d_status) if d_status else None, _vp(counts)))
+        return counts
+
+    def barcode_status(self):
+        """after run_keyed(correct=True): (status u8[N], counts u64[5]) of that run (humid_get_barcode_status)"""
+        n = int(self.summary["total"])
+        status, counts = np.zeros(n, np.uint8), np.zeros(5, np.uint64)
+        self._check(self._lib.humid_get_barcode_status(self._h, _vp(status), n, _vp(counts)))
+        return status, counts
 
     def group_keys(self):
         """after a keyed run: the distinct keys of the usable reads, ascending (u64[G]); group g is key [g]"""

@@ -55,11 +55,12 @@ struct Args {
   unsigned gpus = 1;           // -g (not in the reference): ranks the read set is sharded over, one GPU each
   bool keyed = false;          // -b given (not in the reference): the first `barcode` nucleotides of the word are matched exactly
   size_t barcode = 0;          // -b
+  std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -68,7 +69,11 @@ void usage(const char *argv0) {
                "  -g  GPUs to shard the read set over (1..16; default 1 or $HUMID_GPUS)\n"
                "  -b  barcode length K (1..32, K < n): the first K nucleotides of the word are matched exactly,\n"
                "      -m / -e / -x apply to the remaining n - K (reads are deduplicated per barcode; one GPU);\n"
-               "      with -s also groups.dat: one line \"<barcode> <reads> <unique> <clusters>\" per barcode\n",
+               "      with -s also groups.dat: one line \"<barcode> <reads> <unique> <clusters>\" per barcode\n"
+               "  -w  whitelist FILE for -b: plain text, one barcode of K letters per line (a trailing -1 is dropped, lines\n"
+               "      starting with # are skipped).  A barcode that is not listed but has exactly one listed barcode one\n"
+               "      substitution away becomes that barcode; reads whose barcode has several or none are left out like\n"
+               "      reads with an N; with -s also barcodes.dat: exact / corrected / ambiguous / unmatched reads\n",
                argv0);
 }
 
@@ -86,6 +91,7 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-d") { const char *v = need("-d"); if (!v) return false; a.dir_name = v; }
     else if (t == "-g") { const char *v = need("-g"); if (!v) return false; a.gpus = (unsigned)std::strtoul(v, nullptr, 10); }
     else if (t == "-b") { const char *v = need("-b"); if (!v) return false; a.keyed = true; a.barcode = std::strtoull(v, nullptr, 10); }
+    else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelist = v; }
     else if (t == "--dump-words") { const char *v = need("--dump-words"); if (!v) return false; a.dump_words = v; }
     else if (t == "-s") a.stats = !a.stats;
     else if (t == "-q") a.filter = !a.filter;
@@ -152,6 +158,49 @@ int write_groups(humid_ctx *ctx, size_t barcode_nt, const std::string &path) {
   }
   out.close();
   return out.fail() ? -1 : 1;
+}
+
+// -w FILE: one barcode of barcode_nt letters per line -> packed like the words (first letter most significant).
+// Trailing whitespace and CR are dropped, then a trailing "-1" (10x style); empty lines and lines starting with '#'
+// are skipped; letters in either case.  false + a one-line message in err when the file cannot serve.
+bool read_whitelist(const std::string &path, size_t barcode_nt, std::vector<uint64_t> &out, std::string &err) {
+  if (path.size() >= 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+    err = "-w takes a plain text file, not " + path + " (decompress it first)";
+    return false;
+  }
+  std::ifstream in(path, std::ios::in | std::ios::binary);
+  if (!in) { err = "-w: cannot open " + path; return false; }
+  std::string line;
+  size_t ln = 0;
+  while (std::getline(in, line)) {
+    ln++;
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    if (line.size() >= 2 && line.compare(line.size() - 2, 2, "-1") == 0) line.resize(line.size() - 2);
+    if (line.size() != barcode_nt) {
+      err = "-w: " + path + " line " + std::to_string(ln) + " has " + std::to_string(line.size()) + " letters, -b says " +
+            std::to_string(barcode_nt);
+      return false;
+    }
+    uint64_t v = 0;
+    for (char ch : line) {
+      uint64_t x;
+      switch (ch) {
+        case 'A': case 'a': x = 0; break;
+        case 'C': case 'c': x = 1; break;
+        case 'G': case 'g': x = 2; break;
+        case 'T': case 't': x = 3; break;
+        default:
+          err = "-w: " + path + " line " + std::to_string(ln) + " has a letter outside ACGT";
+          return false;
+      }
+      v = (v << 2) | x;
+    }
+    out.push_back(v);
+  }
+  if (in.bad()) { err = "-w: reading " + path + " failed"; return false; }
+  if (out.empty()) { err = "-w: " + path + " holds no barcode"; return false; }
+  return true;
 }
 
 // Plain (uncompressed) output of the fast path, written through a shared mapping of the output file:
@@ -270,6 +319,19 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -b runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
     return 2;
   }
+  std::vector<uint64_t> whitelist;
+  if (!a.whitelist.empty()) {
+    if (!a.keyed) {
+      std::fprintf(stderr, "humid: -w needs -b K (the whitelist holds barcodes of K letters)\n");
+      return 2;
+    }
+    std::string err;
+    if (!read_whitelist(a.whitelist, a.barcode, whitelist, err)) {
+      std::fprintf(stderr, "humid: %s\n", err.c_str());
+      return 2;
+    }
+  }
+  const bool corrected = !whitelist.empty();
   std::ofstream log(a.log_name.c_str(), std::ios::out | std::ios::binary);
 
   // The HIP runtime and the context come up (a few hundred ms) while pass 1 parses the files.
@@ -491,6 +553,11 @@ int main(int argc, char **argv) {
   humid_summary sum;
   std::memset(&sum, 0, sizeof sum);
   if (a.edit) humid_ctx_set_option(ctx, "edit_distance", 1);
+  if (corrected && humid_whitelist_set(ctx, whitelist.data(), whitelist.size(), (uint32_t)a.barcode) != HUMID_OK) {
+    std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+    humid_ctx_destroy(ctx);
+    return 1;
+  }
   t = start_message(log, a.edit ? "Calculating neighbours using Levenshtein distance"     // src/humid.cc:142
                                 : "Calculating neighbours using Hamming distance");
   const uint32_t method = a.maximum ? HUMID_METHOD_MAXIMUM : HUMID_METHOD_DIRECTIONAL;
@@ -504,7 +571,10 @@ int main(int argc, char **argv) {
     if (rc == HUMID_OK && getenv("HUMID_TIMING"))
       std::fprintf(stderr, "[humid]   %u ranks, bulk data by %s: set-up %.1f ms, ranks %.1f ms\n", a.gpus,
                    shr.comm.c_str(), shr.ms_init, shr.ms_run);
-  } else if (a.keyed)
+  } else if (corrected)
+    rc = humid_dedup_run_keyed_corrected(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
+                                         method, cluster_id, keep, &sum);
+  else if (a.keyed)
     rc = humid_dedup_run_keyed(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance, method,
                                cluster_id, keep, &sum);
   else
@@ -519,7 +589,18 @@ int main(int argc, char **argv) {
     humid_ctx_destroy(ctx);
     return 1;
   }
+  uint64_t bc_counts[5] = {0, 0, 0, 0, 0};
+  if (rc == HUMID_OK && corrected) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
+  if (rc != HUMID_OK) {
+    log << "failed.\n";
+    std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+    humid_ctx_destroy(ctx);
+    return 1;
+  }
   end_message(log, t);
+  if (corrected)
+    log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
+        << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
   phase("device path done");
   if (getenv("HUMID_TIMING"))
     std::fprintf(stderr, "[humid]   of which on the device: upload%s %.1f ms, hot path %.2f ms, download %.1f ms\n",
@@ -712,6 +793,15 @@ int main(int argc, char **argv) {
       if (out.fail()) ok = -1;
     }
     if (ok == 1 && a.keyed) ok = write_groups(ctx, a.barcode, a.dir_name + "/groups.dat");   // (-b is never sharded)
+    if (ok == 1 && corrected) {
+      std::ofstream out(a.dir_name + "/barcodes.dat", std::ios::out | std::ios::binary);
+      out << "exact: " << bc_counts[HUMID_BC_EXACT] << '\n';
+      out << "corrected: " << bc_counts[HUMID_BC_CORRECTED] << '\n';
+      out << "ambiguous: " << bc_counts[HUMID_BC_AMBIGUOUS] << '\n';
+      out << "unmatched: " << bc_counts[HUMID_BC_UNMATCHED] << '\n';
+      out.close();
+      if (out.fail()) ok = -1;
+    }
     end_message(log, t);
     if (ok == 0) { std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx)); humid_ctx_destroy(ctx); return 1; }
     std::ofstream out(a.dir_name + "/stats.dat", std::ios::out | std::ios::binary);

@@ -99,7 +99,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -182,6 +182,10 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->kr_force_log2 = (u32)value;
     return HUMID_OK;
   }
+  if (strcmp(key, "whitelist_coop") == 0) {
+    c->wl_coop = value != 0;
+    return HUMID_OK;
+  }
   if (strcmp(key, "tile_partition") == 0) {
     c->use_tile_partition = value != 0;
     return HUMID_OK;
@@ -253,11 +257,12 @@ int humid_dedup_run_grouped_device(humid_ctx *c, const uint64_t *d_words, const 
 }
 
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
-// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1); key != null: humid_dedup_run_keyed
+// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1); key != null: humid_dedup_run_keyed, or
+// (corrected) humid_dedup_run_keyed_corrected
 static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
                     uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                     uint8_t *keep, humid_summary *summary, bool grouped = false, const uint32_t *group = nullptr,
-                    uint32_t n_groups = 1, const uint64_t *key = nullptr) {
+                    uint32_t n_groups = 1, const uint64_t *key = nullptr, bool corrected = false) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (n_reads && (!(bases || (words && filtered)) || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
@@ -305,7 +310,12 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
     HIPCHK(hipMemcpyAsync(c->kr_key_in.p, key, n * 8, hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipEventRecord(e1, st));
-  int rc = key ? (word_nt > 32
+  int rc = key && corrected ? (word_nt > 32
+               ? run_keyed_corrected_device<W2>(c, c->in_words.as<W2>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads,
+                                                word_nt, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
+               : run_keyed_corrected_device<u64>(c, c->in_words.as<u64>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads,
+                                                 word_nt, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
+           : key ? (word_nt > 32
                ? run_keyed_device<W2>(c, c->in_words.as<W2>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
                                       distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
                : run_keyed_device<u64>(c, c->in_words.as<u64>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
@@ -474,6 +484,141 @@ int humid_keyed_rank_info(humid_ctx *c, uint64_t *n_keys, uint32_t *table_log2, 
   if (n_keys) *n_keys = c->kr_n;
   if (table_log2) *table_log2 = c->kr_last_log2;
   if (n_redo) *n_redo = c->kr_redo;
+  return HUMID_OK;
+}
+
+// ---- barcode whitelist ---------------------------------------------------------------------------------------
+int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint32_t barcode_nt) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  if (n == 0) {                                              // clear
+    HIPCHK(hipStreamSynchronize(st));
+    c->wl_table.release();
+    c->wl_n = 0; c->wl_nt = 0; c->wl_log2 = 0;
+    return HUMID_OK;
+  }
+  if (barcode_nt < 1 || barcode_nt > 32) return fail(c, HUMID_E_INVALID, "barcode_nt must be 1 .. 32");
+  if (!barcodes) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n > ((u64)1 << 30)) return fail(c, HUMID_E_OVERFLOW, "a whitelist of %llu barcodes exceeds 2^30", (ull)n);
+  if (barcode_nt < 32) {
+    const u64 lim = (u64)1 << (2 * barcode_nt);
+    for (u64 i = 0; i < n; i++)
+      if (barcodes[i] >= lim)
+        return fail(c, HUMID_E_INVALID, "barcode %llu = 0x%llx is not a %u-nucleotide word", (ull)i, (ull)barcodes[i], barcode_nt);
+  }
+  u32 log2 = 1;
+  while (((u64)1 << log2) < 2 * n) log2++;
+  const size_t cap = (size_t)1 << log2;
+  // the new table is built beside the old one, which stays in place until the new one is complete
+  DBuf fresh, stage;
+  hipError_t e = fresh.ensure((cap + 2) * 8);
+  if (e == hipSuccess) e = stage.ensure((size_t)n * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(fresh.p, 0xff, (cap + 1) * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(fresh.as<u64>() + cap + 1, 0, 8, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage.p, barcodes, (size_t)n * 8, hipMemcpyHostToDevice, st);
+  u64 distinct = 0;
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_wl_insert, dim3(grid_stride_blocks(n)), dim3(256), 0, st, (const u64 *)stage.p, (u32)n, fresh.as<u64>(), log2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&distinct, fresh.as<u64>() + cap + 1, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  stage.release();
+  if (e != hipSuccess) {
+    fresh.release();
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? HUMID_E_NOMEM : HUMID_E_HIP, "humid_whitelist_set: %s", hipGetErrorString(e));
+  }
+  c->wl_table.release();
+  c->wl_table = fresh;
+  c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
+  return HUMID_OK;
+}
+
+int humid_whitelist_info(humid_ctx *c, uint64_t *n_distinct, uint32_t *barcode_nt, uint32_t *table_log2) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (n_distinct) *n_distinct = c->wl_n;
+  if (barcode_nt) *barcode_nt = c->wl_nt;
+  if (table_log2) *table_log2 = c->wl_log2;
+  return HUMID_OK;
+}
+
+static int whitelist_correct_args(humid_ctx *c, const void *key, const void *filtered, uint64_t n_reads) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
+  if (n_reads && (!key || !filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
+  return HUMID_OK;
+}
+
+int humid_whitelist_correct_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads,
+                                   uint64_t *d_key_out, uint8_t *d_status, uint64_t counts[5]) {
+  TRY(whitelist_correct_args(c, d_key, d_filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  ENSURE(c->wc_counts, 5 * sizeof(ull));
+  TRY(wl_correct_launch(c, d_key, d_filtered, (u32)n_reads, d_key_out, d_status, nullptr, c->wc_counts.as<ull>()));
+  D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_whitelist_correct(humid_ctx *c, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads,
+                            uint64_t *key_out, uint8_t *status, uint64_t counts[5]) {
+  TRY(whitelist_correct_args(c, key, filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads;
+  ENSURE(c->wc_key, n * 8 + 16);
+  ENSURE(c->wc_filt, n + 16);
+  ENSURE(c->wc_out, n * 8 + 16);
+  ENSURE(c->wc_status, n + 16);
+  ENSURE(c->wc_counts, 5 * sizeof(ull));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->wc_key.p, key, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->wc_filt.p, filtered, n, hipMemcpyHostToDevice, st));
+  }
+  TRY(wl_correct_launch(c, c->wc_key.as<u64>(), c->wc_filt.as<u8>(), (u32)n, c->wc_out.as<u64>(), c->wc_status.as<u8>(), nullptr,
+                        c->wc_counts.as<ull>()));
+  D2H(key_out, c->wc_out.p, n * 8);
+  D2H(status, c->wc_status.p, n);
+  D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
+  HIPCHK(hipStreamSynchronize(st));
+  return HUMID_OK;
+}
+
+int humid_dedup_run_keyed_corrected_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key,
+                                           const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
+                                           uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (word_nt > 32)
+    return run_keyed_corrected_device<W2>(c, (const W2 *)d_words, d_key, d_filtered, n_reads, word_nt, distance, method,
+                                          d_cluster_id, d_keep, summary);
+  return run_keyed_corrected_device<u64>(c, d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep,
+                                         summary);
+}
+
+int humid_dedup_run_keyed_corrected(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
+                                    uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
+                                    uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  if (c) {                                                   // (before any copy: a refused shape moves nothing)
+    c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = c->bc_leaves = false;
+    if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+    TRY(check_run_args(c, n_reads, word_nt, method, 64));
+    if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
+  }
+  static const uint64_t no_key = 0;                          // (n_reads == 0: nothing is read)
+  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, false, nullptr, 1,
+                  key ? key : &no_key, true);
+}
+
+int humid_get_barcode_status(humid_ctx *c, uint8_t *status, uint64_t cap, uint64_t counts[5]) {
+  NEED_RUN();
+  if (!c->have_run || !c->bc_leaves) return fail(c, HUMID_E_STATE, "the last run was not a corrected keyed run");
+  const size_t take = (size_t)(c->bc_N < cap ? c->bc_N : cap);
+  D2H(status, c->bc_status.p, take);
+  D2H(counts, c->bc_counts.p, 5 * sizeof(ull));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 

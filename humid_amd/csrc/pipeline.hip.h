@@ -29,6 +29,7 @@
 #include "kernels_gkey.hip.h"
 #include "kernels_keyrank.hip.h"
 #include "kernels_gstats.hip.h"
+#include "kernels_whitelist.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -171,6 +172,17 @@ struct humid_ctx {
   u32 kr_force_log2 = 0;     // option "keyrank_table_log2": every ranking starts with this table size (test hook)
   u32 kr_last_log2 = 0, kr_redo = 0;    // the last ranking: its final table size and how often it was repeated
   DBuf kr_table, kr_raw, kr_rawslot, kr_keys, kr_slot, kr_key_in;   // table; compacted and sorted (key, slot); host entry point staging
+  // barcode whitelist (humid_whitelist_*, kernels_whitelist.hip.h): the table belongs to the context, in memory of its
+  // own (never the slab, never a buffer a run carves), until it is replaced, cleared or the context destroyed
+  DBuf wl_table;             // u64[cap + 2]: keys, the reserved slot of the key EMPTY_KEY, the number of distinct barcodes
+  u64 wl_n = 0;              // distinct barcodes (0: no whitelist)
+  u32 wl_nt = 0, wl_log2 = 0;   // nucleotides of a barcode; log2 of the table's slots
+  bool wl_coop = true;       // option "whitelist_coop": 0 = the lane-serial correction kernel (measurement / cross-check)
+  bool bc_on = false;        // a corrected keyed pass is running (reset on every exit, like kr_on)
+  bool bc_leaves = false;    // the last run was a corrected keyed run: bc_status / bc_counts are those of its bc_N reads
+  u64 bc_N = 0;
+  DBuf bc_key, bc_filt, bc_status, bc_counts;            // corrected run: key_out, filtered', status, u64[5]
+  DBuf wc_key, wc_filt, wc_out, wc_status, wc_counts;    // humid_whitelist_correct*: staging and counts of its own
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
@@ -1319,6 +1331,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   c->gU = U;
   c->gk_leaves = c->gk_on;
   c->kr_leaves = c->kr_on;
+  c->bc_leaves = c->bc_on;
   c->cg_valid = false;
   // ---------------- 3. neighbours -----------------
   // deg has U+1 entries (last stays 0) so that one exclusive scan yields nbr_off[U] = 2E
@@ -1657,6 +1670,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->gU = U;
   c->gk_leaves = c->gk_on;
   c->kr_leaves = c->kr_on;
+  c->bc_leaves = c->bc_on;
   c->cg_valid = false;
   c->cg_expanded = false;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
@@ -2378,6 +2392,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->dense_mode = false;
   c->gk_leaves = c->gk_on;
   c->kr_leaves = c->kr_on;
+  c->bc_leaves = c->bc_on;
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (WIDE != (word_nt > 32)) return fail(c, HUMID_E_INVALID, "word layout does not match word_nt");
   if (WIDE && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
@@ -2610,6 +2625,50 @@ static int run_keyed_device(humid_ctx *c, const WI *d_words, const u64 *d_key, c
   const int rc = run_grouped_device<WI>(c, d_words, nullptr, d_filt, n_reads, word_nt, std::max(c->kr_n, 1u), distance, method,
                                         d_cid, d_keep, sum, n_reads ? d_key : nullptr);
   if (rc != HUMID_OK) c->kr_leaves = false;
+  return rc;
+}
+
+// ---- barcode whitelist (humid_whitelist_*, humid_dedup_run_keyed_corrected*; kernels_whitelist.hip.h) -----------
+// The correction pass over device arrays: zeroes d_counts (u64[5]) and launches the kernel; nothing waits here.
+static int wl_correct_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N, u64 *d_key_out, u8 *d_status,
+                             u8 *d_filt_out, ull *d_counts) {
+  hipStream_t st = c->stream;
+  HIPCHK(hipMemsetAsync(d_counts, 0, 5 * sizeof(ull), st));
+  if (N == 0) return HUMID_OK;
+  if (c->wl_coop)
+    hipLaunchKernelGGL(k_wl_correct<true>, dim3(blocks_for(N)), dim3(256), 0, st, d_key, d_filt, N, (const u64 *)c->wl_table.p,
+                       c->wl_log2, 3 * c->wl_nt, d_key_out, d_status, d_filt_out, d_counts);
+  else
+    hipLaunchKernelGGL(k_wl_correct<false>, dim3(blocks_for(N)), dim3(256), 0, st, d_key, d_filt, N, (const u64 *)c->wl_table.p,
+                       c->wl_log2, 3 * c->wl_nt, d_key_out, d_status, d_filt_out, d_counts);
+  HIPCHK(hipGetLastError());
+  return HUMID_OK;
+}
+
+// The corrected keyed pass: key_out and filtered' (filtered, ambiguous or unmatched) into context buffers, then the
+// keyed pass over them, unchanged.  The status counts are not waited for: humid_get_barcode_status reads them.
+template <class WI>
+static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads,
+                                      u32 word_nt, u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = c->bc_leaves = false;
+  if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (n_reads && (!d_words || !d_key || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  const u32 N = (u32)n_reads;
+  ENSURE(c->bc_key, (size_t)N * 8 + 16);
+  ENSURE(c->bc_filt, (size_t)N + 16);
+  ENSURE(c->bc_status, (size_t)N + 16);
+  ENSURE(c->bc_counts, 5 * sizeof(ull));
+  TRY(wl_correct_launch(c, d_key, d_filt, N, c->bc_key.as<u64>(), c->bc_status.as<u8>(), c->bc_filt.as<u8>(),
+                        c->bc_counts.as<ull>()));
+  struct BcGuard { humid_ctx *c; ~BcGuard() { c->bc_on = false; } } bc_guard{c};
+  c->bc_on = true;
+  c->bc_N = n_reads;
+  const int rc = run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method,
+                                      d_cid, d_keep, sum);
+  if (rc != HUMID_OK) c->bc_leaves = false;
   return rc;
 }
 

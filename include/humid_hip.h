@@ -240,6 +240,77 @@ int humid_dedup_run_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const 
 int humid_get_group_keys(humid_ctx *ctx, uint64_t *keys, uint64_t cap, uint64_t *n_out);
 int humid_keyed_rank_info(humid_ctx *ctx, uint64_t *n_keys, uint32_t *table_log2, uint32_t *n_redo);
 
+/* ---- barcode whitelist: keys one substitution away from a known barcode are corrected ------------
+ * (UMI-tools --per-cell with a whitelist, Cell Ranger, STARsolo 1MM.)  Let K = barcode_nt, 1 <= K <= 32.
+ * A barcode is a K-nucleotide word packed like every word here (first nucleotide most significant,
+ * value < 4^K); W is the set of distinct barcodes of the whitelist.  For a read r with k = key[r]:
+ *   status               value  condition                                               key_out[r]
+ *   HUMID_BC_FILTERED      0    filtered[r] != 0; the key is not read                   0
+ *   HUMID_BC_EXACT         1    k in W                                                  k
+ *   HUMID_BC_CORRECTED     2    k not in W, exactly one w in W at Hamming distance 1    that w
+ *                               from k over the K nucleotides
+ *   HUMID_BC_AMBIGUOUS     3    k not in W, two or more such w                          k
+ *   HUMID_BC_UNMATCHED     4    k not in W, no such w                                   k
+ * So a key with bits set above 2K is unmatched, and a key that IS a whitelist barcode is exact even
+ * when another barcode lies one nucleotide away.  Distance 2, insertions / deletions, base qualities
+ * and barcodes with N (the caller marks such a read filtered) are not handled.
+ * A CORRECTED KEYED RUN is humid_dedup_run_keyed on key_out with
+ *   filtered'[r] = filtered[r] || status[r] is AMBIGUOUS or UNMATCHED;
+ * cluster_id / keep, the summary (usable counts filtered' == 0), humid_get_group_keys (now a subset
+ * of W), leaves, adjacency, clusters, histograms and humid_get_group_stats follow from the contracts
+ * above.
+ * On the device: the whitelist is an open-address table of keys in HBM, 2^ceil(log2(2 n)) slots for
+ * the n barcodes passed (load <= 0.5: every probe ends at a free slot), built once by
+ * humid_whitelist_set and owned by the context: it survives any number of runs of any kind until it
+ * is replaced, cleared (n = 0) or the context destroyed.  The correction is one pass over the reads
+ * in front of the unchanged keyed pass: every lane looks its own key up (one lookup per run of equal
+ * keys inside a wave); for a key that missed, the 64 lanes of the wave look up its 3K one-substitution
+ * variants side by side, and a ballot counts the hits.  Option "whitelist_coop" 0 selects the
+ * lane-serial form of that kernel (every missing lane walks its own 3K variants; same results).  The
+ * pass has no host wait of its own: the five counts are read by humid_get_barcode_status.
+ *   humid_whitelist_set: barcodes[n] is a HOST array; duplicates collapse.  n = 0 clears the
+ *     whitelist.  HUMID_E_INVALID when barcode_nt is outside 1 .. 32 or a barcode is >= 4^K,
+ *     HUMID_E_OVERFLOW for n > 2^30, HUMID_E_NOMEM when an allocation fails; in all three cases the
+ *     previous whitelist stays in place and the context usable.
+ *   humid_whitelist_info: distinct barcodes (0: no whitelist), K, log2 of the table's slots.  Any
+ *     pointer may be NULL.
+ *   humid_whitelist_correct: key[n_reads], filtered[n_reads] in; key_out[n_reads] (u64),
+ *     status[n_reads] (u8) and counts[5] (reads per status, indexed by the status value) out; host
+ *     buffers; any of the three outputs may be NULL.
+ *   humid_whitelist_correct_device: the same with DEVICE pointers for key, filtered, key_out and
+ *     status; counts stays on the host.  Returns after the stream has drained.
+ *     Both return HUMID_E_STATE without a whitelist, and neither touches the results of the last run:
+ *     every accessor, humid_get_barcode_status included, still answers for that run afterwards.
+ *   humid_dedup_run_keyed_corrected(_device): the corrected keyed run; arguments as
+ *     humid_dedup_run_keyed(_device).  HUMID_E_STATE without a whitelist.  A keyed run for every
+ *     accessor.
+ *   humid_get_barcode_status: the status of the first min(cap, n_reads) reads and the five counts
+ *     of the last corrected keyed run.  Either pointer may be NULL.  HUMID_E_STATE unless the last
+ *     run was a corrected one. */
+#define HUMID_BC_FILTERED  0u
+#define HUMID_BC_EXACT     1u
+#define HUMID_BC_CORRECTED 2u
+#define HUMID_BC_AMBIGUOUS 3u
+#define HUMID_BC_UNMATCHED 4u
+int humid_whitelist_set(humid_ctx *ctx, const uint64_t *barcodes, uint64_t n, uint32_t barcode_nt);
+int humid_whitelist_info(humid_ctx *ctx, uint64_t *n_distinct, uint32_t *barcode_nt,
+                         uint32_t *table_log2);
+int humid_whitelist_correct(humid_ctx *ctx, const uint64_t *key, const uint8_t *filtered,
+                            uint64_t n_reads, uint64_t *key_out, uint8_t *status, uint64_t counts[5]);
+int humid_whitelist_correct_device(humid_ctx *ctx, const uint64_t *d_key, const uint8_t *d_filtered,
+                                   uint64_t n_reads, uint64_t *d_key_out, uint8_t *d_status,
+                                   uint64_t counts[5]);
+int humid_dedup_run_keyed_corrected(humid_ctx *ctx, const uint64_t *words, const uint64_t *key,
+                                    const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                                    uint32_t distance, uint32_t method, uint32_t *cluster_id,
+                                    uint8_t *keep, humid_summary *summary);
+int humid_dedup_run_keyed_corrected_device(humid_ctx *ctx, const uint64_t *d_words,
+                                           const uint64_t *d_key, const uint8_t *d_filtered,
+                                           uint64_t n_reads, uint32_t word_nt, uint32_t distance,
+                                           uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                           humid_summary *summary);
+int humid_get_barcode_status(humid_ctx *ctx, uint8_t *status, uint64_t cap, uint64_t counts[5]);
+
 /* ---- per-group statistics: how many molecules every group holds ---------------------------------
  * (the UMI count per cell, or per (cell, gene): the count matrix.)  After a successful single-GPU run let G be
  * its number of groups: n_groups as passed to humid_dedup_run_grouped*; after humid_dedup_run_keyed* the number
