@@ -19,6 +19,11 @@ from . import _lib
 DIRECTIONAL = 0
 MAXIMUM = 1
 
+# which reads of a cluster Dedup.select_best chooses among (include/humid_hip.h, HUMID_BEST_*); rep of a read without a cluster
+BEST_LEAF, BEST_CLUSTER = 0, 1
+NO_READ = 0xffffffff
+_BEST_SCOPES = {"leaf": BEST_LEAF, "cluster": BEST_CLUSTER, BEST_LEAF: BEST_LEAF, BEST_CLUSTER: BEST_CLUSTER}
+
 # per-read status of the barcode correction (include/humid_hip.h, HUMID_BC_*); also the index into its five counts
 BC_FILTERED, BC_EXACT, BC_CORRECTED, BC_AMBIGUOUS, BC_UNMATCHED = range(5)
 
@@ -282,6 +287,46 @@ class Dedup(Context):
         status, counts = np.zeros(n, np.uint8), np.zeros(5, np.uint64)
         self._check(self._lib.humid_get_barcode_status(self._h, _vp(status), n, _vp(counts)))
         return status, counts
+
+    def select_best(self, words, cluster_id, keep, scores, word_nt=24, scope="leaf", rep=True):
+        """After a run: the best-scoring read of every cluster instead of the first one (include/humid_hip.h,
+        humid_select_best).  words, cluster_id and keep are that run's words and outputs, scores u32[N], larger is
+        better, ties to the smallest read index.  scope "leaf" (BEST_LEAF): among the reads that carry the word of the
+        run's representative; "cluster" (BEST_CLUSTER): among all reads of the cluster.
+        Returns (keep_out u8[N], rep u32[N], n_changed): rep[i] is the representative of read i's cluster (NO_READ
+        for cluster_id == 0; None with rep=False), n_changed the number of clusters whose representative changed."""
+        if scope not in _BEST_SCOPES:
+            raise ValueError('scope must be "leaf" or "cluster"')
+        cid = np.ascontiguousarray(cluster_id, dtype=np.uint32)
+        n = len(cid)
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        sc = np.asarray(scores)
+        if sc.dtype.kind not in "ui" or sc.shape != (n,) or (n and (int(sc.min()) < 0 or int(sc.max()) > 0xffffffff)):
+            raise ValueError("scores must be integers in [0, 2**32) with shape (%d,)" % n)
+        sc = np.ascontiguousarray(sc, dtype=np.uint32)
+        want = (n, 2) if word_nt > 32 else (n,)
+        if cid.ndim != 1 or w.shape != want or k.shape != (n,):
+            raise ValueError("words must have shape %r for word_nt=%d, keep %r" % (want, word_nt, (n,)))
+        keep_out = np.zeros(n, np.uint8)
+        rep_out = np.zeros(n, np.uint32) if rep else None
+        changed = C.c_uint64()
+        self._check(self._lib.humid_select_best(self._h, _vp(w), _vp(cid), _vp(k), _vp(sc), n, word_nt, _BEST_SCOPES[scope],
+                                                _vp(keep_out), _vp(rep_out), C.byref(changed)))
+        return keep_out, rep_out, changed.value
+
+    def select_best_device(self, d_words, d_cluster_id, d_keep, d_scores, d_keep_out, d_rep_out, n_reads, word_nt=24,
+                           scope="leaf"):
+        """select_best on device pointers (ints, e.g. tensor.data_ptr(); d_rep_out may be 0, d_keep_out may be
+        d_keep); results stay in HBM.  Returns n_changed."""
+        if scope not in _BEST_SCOPES:
+            raise ValueError('scope must be "leaf" or "cluster"')
+        changed = C.c_uint64()
+        self._check(self._lib.humid_select_best_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.c_void_p(d_scores), n_reads,
+            word_nt, _BEST_SCOPES[scope], C.c_void_p(d_keep_out), C.c_void_p(d_rep_out) if d_rep_out else None,
+            C.byref(changed)))
+        return changed.value
 
     def group_keys(self):
         """after a keyed run: the distinct keys of the usable reads, ascending (u64[G]); group g is key [g]"""

@@ -56,11 +56,13 @@ struct Args {
   bool keyed = false;          // -b given (not in the reference): the first `barcode` nucleotides of the word are matched exactly
   size_t barcode = 0;          // -b
   std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
+  bool best = false;           // -Q (not in the reference): every cluster keeps its record with the best base qualities
+  std::string dump_scores;     // --dump-scores (development: the -Q scores of pass 1, then stop, no GPU)
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -73,7 +75,11 @@ void usage(const char *argv0) {
                "  -w  whitelist FILE for -b: plain text, one barcode of K letters per line (a trailing -1 is dropped, lines\n"
                "      starting with # are skipped).  A barcode that is not listed but has exactly one listed barcode one\n"
                "      substitution away becomes that barcode; reads whose barcode has several or none are left out like\n"
-               "      reads with an N; with -s also barcodes.dat: exact / corrected / ambiguous / unmatched reads\n",
+               "      reads with an N; with -s also barcodes.dat: exact / corrected / ambiguous / unmatched reads\n"
+               "  -Q  keep the record with the best base qualities of every cluster instead of the first one: among the\n"
+               "      records that carry the cluster's most abundant word, the one with the largest sum of Phred qualities\n"
+               "      >= 15 over all input files (Picard's SUM_OF_BASE_QUALITIES; ties: the first; one GPU).  Only the\n"
+               "      _dedup files change\n",
                argv0);
 }
 
@@ -93,6 +99,8 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-b") { const char *v = need("-b"); if (!v) return false; a.keyed = true; a.barcode = std::strtoull(v, nullptr, 10); }
     else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelist = v; }
     else if (t == "--dump-words") { const char *v = need("--dump-words"); if (!v) return false; a.dump_words = v; }
+    else if (t == "--dump-scores") { const char *v = need("--dump-scores"); if (!v) return false; a.dump_scores = v; }
+    else if (t == "-Q") a.best = !a.best;
     else if (t == "-s") a.stats = !a.stats;
     else if (t == "-q") a.filter = !a.filter;
     else if (t == "-a") a.annotate = !a.annotate;
@@ -202,6 +210,18 @@ bool read_whitelist(const std::string &path, size_t barcode_nt, std::vector<uint
   if (out.empty()) { err = "-w: " + path + " holds no barcode"; return false; }
   return true;
 }
+
+// -Q: the score of a record is Picard's SUM_OF_BASE_QUALITIES over its quality lines in all input files: the sum of
+// q = byte - 33 over the bytes with q >= 15 (a line terminator never counts: '\r' and '\n' are below 33 + 15)
+inline uint64_t quality_sum(const char *q, size_t n) {
+  uint64_t t = 0;
+  for (size_t i = 0; i < n; i++) {
+    const unsigned v = (unsigned char)q[i];
+    t += v >= 48u ? v - 33u : 0u;
+  }
+  return t;
+}
+inline uint32_t clamp_score(uint64_t t) { return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t; }
 
 // Plain (uncompressed) output of the fast path, written through a shared mapping of the output file:
 // every worker copies its share of the records straight to their final place, so the page cache is
@@ -319,6 +339,12 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -b runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
     return 2;
   }
+  if (a.best && sharded) {
+    std::fprintf(stderr, "humid: -Q runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
+    return 2;
+  }
+  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty();   // development: stop after pass 1, no GPU
+  const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
   std::vector<uint64_t> whitelist;
   if (!a.whitelist.empty()) {
     if (!a.keyed) {
@@ -349,8 +375,8 @@ int main(int argc, char **argv) {
   uint64_t pin_bytes = 0;
   // -g: the ranks (threads with a context, a stream and a communicator each) come up the same way
   std::unique_ptr<ShardedSession> ranks;
-  if (a.dump_words.empty() && sharded) ranks.reset(new ShardedSession(a.gpus));
-  if (a.dump_words.empty() && !sharded)
+  if (!dump_only && sharded) ranks.reset(new ShardedSession(a.gpus));
+  if (!dump_only && !sharded)
     ctx_init.th = std::thread([&] {
       const auto ti = std::chrono::steady_clock::now();
       auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - ti).count(); };
@@ -431,8 +457,10 @@ int main(int argc, char **argv) {
   // HUMID_DEVICE_PACK=1: the host only gathers the raw symbols and the GPU packs them
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
-  const bool device_pack = fast && a.dump_words.empty() && !sharded && !a.keyed && getenv("HUMID_DEVICE_PACK") != nullptr;
+  // (-Q: the selection compares the packed words, so the host packs them)
+  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
+  std::vector<uint32_t> scores;                    // -Q: one per record
   if (fast) {
     size_t n = maps[0].records();
     for (auto &m : maps) n = m.records() < n ? m.records() : n;     // stop at the shortest file
@@ -454,13 +482,17 @@ int main(int argc, char **argv) {
     } else {
     words.resize(n * wpr);
     filtered.resize(n);
+    if (scoring) scores.resize(n);
     parallel_ranges(n, threads, [&](size_t b, size_t e, unsigned) {
       std::string_view seqs[64], name0, nm, st, ql;
       for (size_t i = b; i < e; i++) {
+        uint64_t qsum = 0;
         for (size_t f = 0; f < nf; f++) {
           maps[f].lines(i, nm, seqs[f], st, ql);
           if (f == 0) name0 = nm;
+          if (scoring) qsum += quality_sum(ql.data(), ql.size());
         }
+        if (scoring) scores[i] = clamp_score(qsum);
         if (wpr == 2) {
           filtered[i] = make_word_wide(name0, seqs, nf, plan, &words[2 * i]) ? 1 : 0;
         } else {
@@ -482,6 +514,11 @@ int main(int argc, char **argv) {
       words.push_back(w[0]);
       if (wpr == 2) words.push_back(w[1]);
       filtered.push_back(f ? 1 : 0);
+      if (scoring) {
+        uint64_t qsum = 0;
+        for (const FastqRecord &r : recs) qsum += quality_sum(r.quality.data(), r.quality.size());
+        scores.push_back(clamp_score(qsum));
+      }
     }
   }
   end_message(log, t);
@@ -492,8 +529,13 @@ int main(int argc, char **argv) {
     out.write((const char *)&N, 8);
     out.write((const char *)words.data(), (std::streamsize)(N * 8 * wpr));
     out.write((const char *)filtered.data(), (std::streamsize)N);
-    return 0;
   }
+  if (!a.dump_scores.empty()) {  // ... and the -Q scores: a u64 count, then u32 scores
+    std::ofstream out(a.dump_scores, std::ios::out | std::ios::binary);
+    out.write((const char *)&N, 8);
+    out.write((const char *)scores.data(), (std::streamsize)(N * 4));
+  }
+  if (dump_only) return 0;
 
   // -b K: the packed n-nucleotide word splits into the key (its first K nucleotides, one uint64) and the word the
   // run clusters (the remaining n - K, one uint64 up to 32 nucleotides, two beyond): a shift per read
@@ -598,9 +640,22 @@ int main(int argc, char **argv) {
     return 1;
   }
   end_message(log, t);
+  uint64_t n_changed = 0;
+  if (a.best) {
+    // every cluster keeps its best record among those of its most abundant word; keep is rewritten in place and
+    // pass 2 follows it (the ids do not move: the annotated files and the statistics are those of the run)
+    if (humid_select_best(ctx, run_words, cluster_id, keep, scores.data(), N, (uint32_t)run_nt, HUMID_BEST_LEAF, keep, nullptr,
+                          &n_changed) != HUMID_OK) {
+      log << "failed.\n";
+      std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+      humid_ctx_destroy(ctx);
+      return 1;
+    }
+  }
   if (corrected)
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
+  if (a.best) log << "  quality: " << n_changed << " clusters keep another record\n";
   phase("device path done");
   if (getenv("HUMID_TIMING"))
     std::fprintf(stderr, "[humid]   of which on the device: upload%s %.1f ms, hot path %.2f ms, download %.1f ms\n",
@@ -609,6 +664,7 @@ int main(int argc, char **argv) {
   end_message(log, t);
   std::vector<uint64_t>().swap(words);
   std::vector<uint64_t>().swap(keys);
+  std::vector<uint32_t>().swap(scores);
   std::vector<uint8_t>().swap(bases);
 
   make_dirs(a.dir_name);

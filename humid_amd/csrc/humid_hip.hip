@@ -25,6 +25,7 @@
 // include/humid_hip.h; humid_exchange.hip = the exchange pass and the multi-GPU stage entry points; shm.cpp = the
 // shared-memory gather (no HIP); pipeline.hip.h = the pipeline itself, with internal linkage, compiled into both.
 #include "pipeline.hip.h"
+#include "kernels_best.hip.h"
 
 static std::string g_err;
 // (the error text of calls without a context: also set from humid_exchange.hip and shm.cpp)
@@ -99,7 +100,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->bs_rep, &c->bs_best, &c->bs_ctr, &c->bs_words, &c->bs_cid, &c->bs_keep, &c->bs_score, &c->bs_keep_out, &c->bs_rep_out, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -775,6 +776,91 @@ int humid_group_stats_device(humid_ctx *c, uint64_t *n_out, const uint64_t **d_r
   if (d_leaf_off) *d_leaf_off = c->gs_loff.as<u32>();
   if (d_cluster_off) *d_cluster_off = c->gs_coff.as<u32>();
   if (d_edges) *d_edges = c->gs_edges.as<u32>();
+  return HUMID_OK;
+}
+
+// ---- best-scoring read per cluster (kernels_best.hip.h) --------------------------------------------------------
+// what both entry points refuse before anything moves; n_reads == 0 is the caller's to return HUMID_OK on
+static int select_best_args(humid_ctx *c, const void *words, const void *cid, const void *keep, const void *score,
+                            uint64_t n_reads, uint32_t word_nt, uint32_t scope, const void *keep_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (scope > HUMID_BEST_CLUSTER) return fail(c, HUMID_E_INVALID, "scope must be 0 (leaf) or 1 (cluster)");
+  if (!c->have_run || c->graph_mode)
+    return fail(c, HUMID_E_INVALID, "humid_select_best needs a completed single-GPU humid_dedup_run* in this context");
+  if (n_reads != c->N || word_nt != c->word_nt)
+    return fail(c, HUMID_E_INVALID, "humid_select_best: %llu reads of %u nt, the last run had %llu of %u", (ull)n_reads, word_nt,
+                (ull)c->N, c->word_nt);
+  if (n_reads && (!words || !cid || !keep || !score || !keep_out)) return fail(c, HUMID_E_INVALID, "null buffer");
+  return HUMID_OK;
+}
+
+int humid_select_best_device(humid_ctx *c, const uint64_t *d_words, const uint32_t *d_cluster_id, const uint8_t *d_keep,
+                             const uint32_t *d_score, uint64_t n_reads, uint32_t word_nt, uint32_t scope,
+                             uint8_t *d_keep_out, uint32_t *d_rep_out, uint64_t *n_changed) {
+  TRY(select_best_args(c, d_words, d_cluster_id, d_keep, d_score, n_reads, word_nt, scope, d_keep_out));
+  if (n_changed) *n_changed = 0;
+  if (n_reads == 0) return HUMID_OK;
+  const bool wide = word_nt > 32, leaf = scope == HUMID_BEST_LEAF;
+  if (wide && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const u32 N = (u32)n_reads, C = (u32)c->C;
+  ENSURE(c->bs_rep, ((size_t)C + 1) * 4);
+  ENSURE(c->bs_best, ((size_t)C + 1) * 8);
+  ENSURE(c->bs_ctr, BEST_CTRS * 4);
+  u32 *rep = c->bs_rep.as<u32>(), *ctr = c->bs_ctr.as<u32>();
+  ull *best = c->bs_best.as<ull>();
+  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
+  HIPCHK(hipMemsetAsync(best, 0, ((size_t)C + 1) * 8, st));
+  HIPCHK(hipMemsetAsync(ctr, 0, BEST_CTRS * 4, st));
+  hipLaunchKernelGGL(k_best_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, N, C, rep, ctr);
+  const dim3 grid(blocks_for(N)), block(256);
+  if (wide && leaf)
+    hipLaunchKernelGGL((k_best_vote<W2, true>), grid, block, 0, st, (const W2 *)d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
+  else if (wide)
+    hipLaunchKernelGGL((k_best_vote<W2, false>), grid, block, 0, st, (const W2 *)d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
+  else if (leaf)
+    hipLaunchKernelGGL((k_best_vote<u64, true>), grid, block, 0, st, d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
+  else
+    hipLaunchKernelGGL((k_best_vote<u64, false>), grid, block, 0, st, d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
+  hipLaunchKernelGGL(k_best_write, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, N, C, (const u32 *)rep, (const ull *)best,
+                     d_keep_out, d_rep_out, ctr);
+  HIPCHK(hipGetLastError());
+  u32 h[BEST_CTRS] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          // the pass's one host wait
+  if (h[BEST_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_select_best: a cluster id above the %u clusters of the last run", C);
+  if (h[BEST_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_select_best: a cluster has more than one read with keep == 1");
+  if (h[BEST_CLAIMS] != C)
+    return fail(c, HUMID_E_INVALID, "humid_select_best: %u reads with keep == 1 for the %u clusters of the last run", h[BEST_CLAIMS], C);
+  if (n_changed) *n_changed = h[BEST_CHANGED];
+  return HUMID_OK;
+}
+
+int humid_select_best(humid_ctx *c, const uint64_t *words, const uint32_t *cluster_id, const uint8_t *keep,
+                      const uint32_t *score, uint64_t n_reads, uint32_t word_nt, uint32_t scope, uint8_t *keep_out,
+                      uint32_t *rep_out, uint64_t *n_changed) {
+  TRY(select_best_args(c, words, cluster_id, keep, score, n_reads, word_nt, scope, keep_out));
+  if (n_changed) *n_changed = 0;
+  if (n_reads == 0) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
+  ENSURE(c->bs_words, n * wbytes + 16);
+  ENSURE(c->bs_cid, n * 4 + 16);
+  ENSURE(c->bs_keep, n + 16);
+  ENSURE(c->bs_score, n * 4 + 16);
+  ENSURE(c->bs_keep_out, n + 16);
+  if (rep_out) ENSURE(c->bs_rep_out, n * 4 + 16);
+  HIPCHK(hipMemcpyAsync(c->bs_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->bs_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->bs_keep.p, keep, n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->bs_score.p, score, n * 4, hipMemcpyHostToDevice, st));
+  TRY(humid_select_best_device(c, c->bs_words.as<u64>(), c->bs_cid.as<u32>(), c->bs_keep.as<u8>(), c->bs_score.as<u32>(), n_reads,
+                               word_nt, scope, c->bs_keep_out.as<u8>(), rep_out ? c->bs_rep_out.as<u32>() : nullptr, n_changed));
+  D2H(keep_out, c->bs_keep_out.p, n);
+  D2H(rep_out, c->bs_rep_out.p, n * 4);
+  HIPCHK(hipStreamSynchronize(st));
   return HUMID_OK;
 }
 

@@ -190,6 +190,9 @@ struct humid_ctx {
   bool gs_valid = false;     // gs_* hold that run's statistics for gs_G groups
   u32 gs_G = 0;
   DBuf gs_reads, gs_loff, gs_coff, gs_edges, gs_ps;   // reads u64[G], leaf / cluster offsets u32[G + 1], pairs u32[G]; scan of (count | degree << 32)
+  // best-scoring read per cluster (humid_select_best*, kernels_best.hip.h): memory of its own, read by no accessor
+  DBuf bs_rep, bs_best, bs_ctr;                              // u32[C + 1] representatives, u64[C + 1] votes, the pass's counters
+  DBuf bs_words, bs_cid, bs_keep, bs_score, bs_keep_out, bs_rep_out;   // host entry point staging
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;

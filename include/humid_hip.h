@@ -346,6 +346,54 @@ int humid_group_stats_device(humid_ctx *ctx, uint64_t *n_out, const uint64_t **d
                              const uint32_t **d_leaf_off, const uint32_t **d_cluster_off,
                              const uint32_t **d_edges);
 
+/* ---- the best-scoring read of every cluster: which read of a family survives ---------------------
+ * (Picard MarkDuplicates keeps the pair with the largest sum of base qualities, UMICollapse the highest average
+ * quality, UMI-tools the highest MAPQ.)  A run's keep[i] marks the FIRST read, in input order, whose word is its
+ * cluster's maxLeaf.  This pass, run after it, picks by a caller-defined score instead.  Per read i < n_reads:
+ *   words[i]       the caller's words of the run that produced the ids: one uint64, or two when word_nt > 32, in
+ *                  the layout of humid_dedup_run.
+ *   cluster_id[i], keep[i]   that run's outputs, unmodified.
+ *   score[i]       uint32, larger is better.
+ * A read with cluster_id == 0 (filtered; after a corrected run also ambiguous and unmatched) is no candidate:
+ * neither its score nor its word is read.  For every cluster c let r_c be the one read with keep == 1 and
+ * cluster_id == c.  The candidates of c are
+ *   scope HUMID_BEST_LEAF (0):     its reads whose word equals words[r_c] -- the reads of the cluster's maxLeaf,
+ *                                  so the survivor still carries the most abundant word, as in the reference;
+ *   scope HUMID_BEST_CLUSTER (1):  all its reads.
+ * (No group array is needed: two reads of ONE cluster with equal words are in the same group.)  The new
+ * representative b_c is the candidate with the largest score; ties go to the smallest read index.  Outputs:
+ *   keep_out[i]  = (i == b_c) for c = cluster_id[i]; 0 for cluster_id == 0.
+ *   rep_out[i]   = b_c, the read's pointer to its family's representative; HUMID_NO_READ for cluster_id == 0.
+ *                  May be NULL.
+ *   *n_changed   = the number of clusters with b_c != r_c.  May be NULL.
+ * So equal scores under scope LEAF give back keep exactly, sum(keep_out) == summary.clusters, and the result is a maximum over a
+ * total order: it does not depend on the order the device takes the reads in.
+ * Both entry points are valid only after a successful single-GPU humid_dedup_run* (plain, bases, grouped, keyed
+ * or corrected) on this context with the same n_reads and word_nt -- the cluster count is that run's; in any
+ * other case (no run, a multi-GPU pass, a humid_stage_* call or humid_cluster_graph since) they return
+ * HUMID_E_INVALID, as for scope > 1, a NULL buffer and wide words that are not 16-byte aligned on the device.
+ * n_reads == 0 returns HUMID_OK.  keep_out may be the same buffer as keep.  Malformed input -- an id above the
+ * run's cluster count, a cluster without a read with keep == 1, or with two -- is detected on the device and
+ * reported as HUMID_E_INVALID at the pass's one host wait; nothing is then written and no unchecked index followed.
+ * The pass launches nothing unless it is called, works in memory of its own, and leaves the context usable and
+ * every accessor of the last run valid, whatever it returns.
+ * On the device (kernels_best.hip.h): the kept reads claim a table u32[C + 1]; every candidate votes
+ * score << 32 | (0xffffffff - i) into a table u64[C + 1] with a 64-bit atomic maximum (runs of equal ids inside
+ * a wave vote once); one more pass writes the outputs.
+ *   humid_select_best: host buffers.
+ *   humid_select_best_device: DEVICE pointers for all arrays; n_changed stays a host pointer.  Returns after
+ *     the stream has drained. */
+#define HUMID_BEST_LEAF    0u
+#define HUMID_BEST_CLUSTER 1u
+#define HUMID_NO_READ 0xffffffffu
+int humid_select_best(humid_ctx *ctx, const uint64_t *words, const uint32_t *cluster_id,
+                      const uint8_t *keep, const uint32_t *score, uint64_t n_reads, uint32_t word_nt,
+                      uint32_t scope, uint8_t *keep_out, uint32_t *rep_out, uint64_t *n_changed);
+int humid_select_best_device(humid_ctx *ctx, const uint64_t *d_words, const uint32_t *d_cluster_id,
+                             const uint8_t *d_keep, const uint32_t *d_score, uint64_t n_reads,
+                             uint32_t word_nt, uint32_t scope, uint8_t *d_keep_out, uint32_t *d_rep_out,
+                             uint64_t *n_changed);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
