@@ -33,6 +33,14 @@ class HumidSummary(C.Structure):
         return d
 
 
+class HumidConsensusSummary(C.Structure):
+    """humid_consensus_summary of include/humid_hip.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_clusters", "total_bytes", "multi_read", "bases_changed", "votes", "errors")]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
@@ -104,6 +112,13 @@ SYMBOLS = {
                                     C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "humid_select_best_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "humid_consensus": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                  C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(HumidConsensusSummary)]),
+    "humid_consensus_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.POINTER(HumidConsensusSummary)]),
+    "humid_get_consensus": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
+    "humid_consensus_result_device": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
     "humid_get_leaves": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "humid_get_adjacency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_get_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -328,6 +328,63 @@ class Dedup(Context):
             C.byref(changed)))
         return changed.value
 
+    def consensus(self, bases, quals, cluster_id, keep, off=None, n_clusters=None, min_q=10, cap_q=93):
+        """One consensus record per cluster from all of its reads (include/humid_hip.h, humid_consensus): per column
+        every read votes for its base (A C G T, quality >= max(min_q, 1)) with the weight of its Phred quality; the
+        output is the base with the largest sum and 33 + min(margin to the second, cap_q) as quality, 'N' / '!' on a
+        tie, the representative's own bytes where nobody voted.  bases / quals: u8[N, L] matrices (off is implied) or
+        flat ASCII blobs with off u64[N + 1]; cluster_id / keep from any run (keep possibly from select_best); one
+        call per FastQ file.  n_clusters defaults to cluster_id.max().
+        Returns dict(out_off u64[C + 1], bases u8[total], quals u8[total], depth u32[C], errors u64[C], summary):
+        the consensus of cluster c is bytes [out_off[c - 1], out_off[c]) of bases and quals."""
+        cid = np.ascontiguousarray(cluster_id, dtype=np.uint32)
+        n = len(cid)
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        b = np.ascontiguousarray(bases, dtype=np.uint8)
+        q = np.ascontiguousarray(quals, dtype=np.uint8)
+        if cid.ndim != 1 or k.shape != (n,) or b.shape != q.shape:
+            raise ValueError("cluster_id and keep must have shape (N,), bases and quals the same shape")
+        if off is None:
+            if b.ndim != 2 or b.shape[0] != n:
+                raise ValueError("without off, bases and quals must be u8[N, L] matrices")
+            o = np.arange(n + 1, dtype=np.uint64) * np.uint64(b.shape[1])
+        else:
+            o = np.ascontiguousarray(off, dtype=np.uint64)
+            if b.ndim != 1 or o.shape != (n + 1,):
+                raise ValueError("with off, bases and quals must be flat blobs and off u64[N + 1]")
+        if n_clusters is None:
+            n_clusters = int(cid.max()) if n else 0
+        sm = _lib.HumidConsensusSummary()
+        self._check(self._lib.humid_consensus(self._h, _vp(b), _vp(q), _vp(o), b.size, _vp(cid), _vp(k), n, int(n_clusters),
+                                              int(min_q), int(cap_q), C.byref(sm)))
+        return self._consensus_result(sm.asdict())
+
+    def _consensus_result(self, sm):
+        c, t = sm["n_clusters"], sm["total_bytes"]
+        out = dict(out_off=np.zeros(c + 1, np.uint64), bases=np.zeros(t, np.uint8), quals=np.zeros(t, np.uint8),
+                   depth=np.zeros(c, np.uint32), errors=np.zeros(c, np.uint64), summary=sm)
+        self._check(self._lib.humid_get_consensus(self._h, t, _vp(out["out_off"]), _vp(out["bases"]), _vp(out["quals"]),
+                                                  _vp(out["depth"]), _vp(out["errors"])))
+        return out
+
+    def consensus_device(self, d_bases, d_quals, d_off, n_bytes, d_cluster_id, d_keep, n_reads, n_clusters, min_q=10,
+                         cap_q=93):
+        """consensus on device pointers (ints, e.g. tensor.data_ptr()); the results stay in HBM
+        (consensus_result_device).  Returns the summary dict."""
+        sm = _lib.HumidConsensusSummary()
+        self._check(self._lib.humid_consensus_device(
+            self._h, C.c_void_p(d_bases), C.c_void_p(d_quals), C.c_void_p(d_off), n_bytes, C.c_void_p(d_cluster_id),
+            C.c_void_p(d_keep), n_reads, n_clusters, int(min_q), int(cap_q), C.byref(sm)))
+        return sm.asdict()
+
+    def consensus_result_device(self):
+        """The results of the last consensus call left in HBM: dict(out_off, bases, quals, depth, errors) of integer
+        device pointers (u64[C + 1], u8[total], u8[total], u32[C], u64[C]).  The memory belongs to this object: it is
+        valid until its next consensus call or close()."""
+        p = [C.c_void_p() for _ in range(5)]
+        self._check(self._lib.humid_consensus_result_device(self._h, *[C.byref(x) for x in p]))
+        return dict(zip(("out_off", "bases", "quals", "depth", "errors"), [x.value or 0 for x in p]))
+
     def group_keys(self):
         """after a keyed run: the distinct keys of the usable reads, ascending (u64[G]); group g is key [g]"""
         n = C.c_uint64()

@@ -186,7 +186,7 @@ bool MappedFastq::open(const std::string &path, unsigned threads, size_t max_inf
   }
   if (data[0] != '@' || data[size - 1] != '\n') return false;    // missing final newline, not FastQ...
   const char *const end = data + size;
-  if (threads == 0) threads = 1;
+  if (threads == 0 || size < 4096) threads = 1;           // (below 4096 items parallel_ranges runs everything as worker 0)
   std::vector<std::vector<uint64_t>> part(threads);
   std::vector<uint64_t> first_pos(threads, 0), last_end(threads, 0);
   std::vector<char> ok(threads, 1);

@@ -58,11 +58,14 @@ struct Args {
   std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
   bool best = false;           // -Q (not in the reference): every cluster keeps its record with the best base qualities
   std::string dump_scores;     // --dump-scores (development: the -Q scores of pass 1, then stop, no GPU)
+  bool consensus = false;      // -C (not in the reference): every kept record carries the consensus of its cluster's reads
+  unsigned consensus_min_q = 10;   // --consensus-min-q
+  std::string dump_consensus;  // --dump-consensus-input (development: what -C hands to the GPU, then stop, no GPU)
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -79,7 +82,12 @@ void usage(const char *argv0) {
                "  -Q  keep the record with the best base qualities of every cluster instead of the first one: among the\n"
                "      records that carry the cluster's most abundant word, the one with the largest sum of Phred qualities\n"
                "      >= 15 over all input files (Picard's SUM_OF_BASE_QUALITIES; ties: the first; one GPU).  Only the\n"
-               "      _dedup files change\n",
+               "      _dedup files change\n"
+               "  -C  write consensus reads: the sequence and quality lines of every kept record are replaced by the\n"
+               "      consensus of all reads of its cluster, file by file: per column the base with the largest sum of\n"
+               "      Phred qualities, the margin to the second largest as its quality (at most 93), N and ! on a tie;\n"
+               "      bases below --consensus-min-q N (default 10) and letters outside ACGT do not vote.  Record lengths\n"
+               "      do not change; only the _dedup files change; one GPU, inputs held in memory (no CRLF files)\n",
                argv0);
 }
 
@@ -100,7 +108,10 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelist = v; }
     else if (t == "--dump-words") { const char *v = need("--dump-words"); if (!v) return false; a.dump_words = v; }
     else if (t == "--dump-scores") { const char *v = need("--dump-scores"); if (!v) return false; a.dump_scores = v; }
+    else if (t == "--dump-consensus-input") { const char *v = need("--dump-consensus-input"); if (!v) return false; a.dump_consensus = v; }
+    else if (t == "--consensus-min-q") { const char *v = need("--consensus-min-q"); if (!v) return false; a.consensus_min_q = (unsigned)std::strtoul(v, nullptr, 10); }
     else if (t == "-Q") a.best = !a.best;
+    else if (t == "-C") a.consensus = !a.consensus;
     else if (t == "-s") a.stats = !a.stats;
     else if (t == "-q") a.filter = !a.filter;
     else if (t == "-a") a.annotate = !a.annotate;
@@ -223,6 +234,32 @@ inline uint64_t quality_sum(const char *q, size_t n) {
 }
 inline uint32_t clamp_score(uint64_t t) { return t > 0xffffffffull ? 0xffffffffu : (uint32_t)t; }
 
+// -C: one layer of reads as humid_consensus takes it -- the sequence lines of a mapped file in one blob, its quality
+// lines in another, off[i] .. off[i + 1] the bytes of record i in both (a record whose two lines differ in length
+// gives the shorter one)
+void gather_layer(const MappedFastq &m, size_t n, unsigned threads, std::vector<uint64_t> &off, std::vector<uint8_t> &b,
+                  std::vector<uint8_t> &q) {
+  off.assign(n + 1, 0);
+  parallel_ranges(n, threads, [&](size_t lo, size_t hi, unsigned) {
+    std::string_view nm, sq, st, ql;
+    for (size_t i = lo; i < hi; i++) {
+      m.lines(i, nm, sq, st, ql);
+      off[i + 1] = sq.size() < ql.size() ? sq.size() : ql.size();
+    }
+  });
+  for (size_t i = 0; i < n; i++) off[i + 1] += off[i];
+  b.resize(off[n]);
+  q.resize(off[n]);
+  parallel_ranges(n, threads, [&](size_t lo, size_t hi, unsigned) {
+    std::string_view nm, sq, st, ql;
+    for (size_t i = lo; i < hi; i++) {
+      m.lines(i, nm, sq, st, ql);
+      const size_t len = (size_t)(off[i + 1] - off[i]);
+      if (len) { memcpy(&b[off[i]], sq.data(), len); memcpy(&q[off[i]], ql.data(), len); }
+    }
+  });
+}
+
 // Plain (uncompressed) output of the fast path, written through a shared mapping of the output file:
 // every worker copies its share of the records straight to their final place, so the page cache is
 // filled by all cores at once (one writer through pwrite() is bound by a single core's copy rate,
@@ -343,7 +380,16 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -Q runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
     return 2;
   }
-  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty();   // development: stop after pass 1, no GPU
+  if (a.consensus && sharded) {                          // (the reads of a cluster lie on several ranks)
+    std::fprintf(stderr, "humid: -C runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
+    return 1;
+  }
+  if (a.consensus_min_q > 93) {
+    std::fprintf(stderr, "humid: --consensus-min-q takes 0 .. 93\n");
+    return 2;
+  }
+  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty();   // development: stop after pass 1, no GPU
+  const bool want_reads = a.consensus || !a.dump_consensus.empty();         // the reads themselves are gathered from the mappings
   const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
   std::vector<uint64_t> whitelist;
   if (!a.whitelist.empty()) {
@@ -376,7 +422,8 @@ int main(int argc, char **argv) {
   // -g: the ranks (threads with a context, a stream and a communicator each) come up the same way
   std::unique_ptr<ShardedSession> ranks;
   if (!dump_only && sharded) ranks.reset(new ShardedSession(a.gpus));
-  if (!dump_only && !sharded)
+  // (-C: the GPU is opened only once the inputs are known to be held in memory, see below)
+  auto start_ctx = [&] {
     ctx_init.th = std::thread([&] {
       const auto ti = std::chrono::steady_clock::now();
       auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - ti).count(); };
@@ -403,6 +450,8 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "[humid]   init thread: context %.3f s, read count known %.3f s, page-locked staging %.3f s, slab + code object %.3f s\n",
                      t_ctx, t_wait, t_pin, t_slab);
     });
+  };
+  if (!dump_only && !sharded && !a.consensus) start_ctx();
   struct Release {                                      // every early return lets the thread go on
     std::atomic<long long> &n;
     ~Release() { long long e = -1; n.compare_exchange_strong(e, 0); }
@@ -448,6 +497,12 @@ int main(int argc, char **argv) {
   }
 
   phase("files opened / indexed");
+  if (want_reads && !fast) {
+    std::fprintf(stderr, "humid: -C needs the input files held in memory: not on the streaming input path (CRLF line ends, files over\n"
+                         "       HUMID_RETAIN_GB, HUMID_HOST_SLOW), where the reads are not retained\n");
+    return 1;
+  }
+  if (!dump_only && a.consensus) start_ctx();
   // ---- pass 1: readData (src/humid.cc:89-100) ----
   t = start_message(log, "Reading data");
   const size_t wpr = a.word_length > 32 ? 2 : 1;   // uint64 per word (include/humid_hip.h)
@@ -534,6 +589,18 @@ int main(int argc, char **argv) {
     std::ofstream out(a.dump_scores, std::ios::out | std::ios::binary);
     out.write((const char *)&N, 8);
     out.write((const char *)scores.data(), (std::streamsize)(N * 4));
+  }
+  if (!a.dump_consensus.empty()) {   // ... and what -C hands to the GPU: a u64 count, then per file off u64[n + 1] and the two blobs
+    std::ofstream out(a.dump_consensus, std::ios::out | std::ios::binary);
+    out.write((const char *)&N, 8);
+    for (size_t f = 0; f < maps.size(); f++) {
+      std::vector<uint64_t> off;
+      std::vector<uint8_t> lb, lq;
+      gather_layer(maps[f], N, threads, off, lb, lq);
+      out.write((const char *)off.data(), (std::streamsize)((N + 1) * 8));
+      out.write((const char *)lb.data(), (std::streamsize)lb.size());
+      out.write((const char *)lq.data(), (std::streamsize)lq.size());
+    }
   }
   if (dump_only) return 0;
 
@@ -656,6 +723,54 @@ int main(int argc, char **argv) {
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
   if (a.best) log << "  quality: " << n_changed << " clusters keep another record\n";
+  // -C: one consensus pass per input file, one after the other (a file's blobs are freed before the next is gathered);
+  // what pass 2 needs stays on the host: per file the offsets and the two consensus blobs, in cluster-id order
+  std::vector<std::vector<uint64_t>> cons_off(a.consensus ? maps.size() : 0);
+  std::vector<std::vector<uint8_t>> cons_b(cons_off.size()), cons_q(cons_off.size());
+  if (a.consensus) {
+    uint64_t changed = 0, disagree = 0, multi = 0;
+    for (size_t f = 0; f < maps.size(); f++) {
+      humid_consensus_summary cs;
+      std::memset(&cs, 0, sizeof cs);
+      int crc;
+      {
+        std::vector<uint64_t> off;
+        std::vector<uint8_t> lb, lq;
+        gather_layer(maps[f], N, threads, off, lb, lq);
+        crc = humid_consensus(ctx, lb.data(), lq.data(), off.data(), off[N], cluster_id, keep, N, sum.clusters, a.consensus_min_q, 93, &cs);
+      }
+      if (crc == HUMID_OK) {
+        cons_off[f].resize(cs.n_clusters + 1);
+        cons_b[f].resize(cs.total_bytes ? cs.total_bytes : 1);
+        cons_q[f].resize(cs.total_bytes ? cs.total_bytes : 1);
+        crc = humid_get_consensus(ctx, cs.total_bytes, cons_off[f].data(), cons_b[f].data(), cons_q[f].data(), nullptr, nullptr);
+      }
+      if (crc == HUMID_OK && cs.n_clusters != sum.clusters && N) crc = HUMID_E_STATE;   // (cannot happen: C was passed in)
+      if (crc != HUMID_OK) {
+        log << "failed.\n";
+        std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+        humid_ctx_destroy(ctx);
+        return 1;
+      }
+      changed += cs.bases_changed;
+      disagree += cs.errors;
+      multi = cs.multi_read;
+    }
+    // (clusters and multi-read clusters are those of the run; bases changed and disagreeing votes add up over the files)
+    log << "  consensus: " << sum.clusters << " clusters, " << multi << " multi-read, " << changed << " bases changed, "
+        << disagree << " disagreeing votes\n";
+  }
+  // the kept record i of file f, copied to dst, takes the consensus of its cluster on its sequence and quality lines
+  auto put_consensus = [&](size_t f, size_t i, char *dst) {
+    std::string_view nm, sq, st, ql;
+    maps[f].lines(i, nm, sq, st, ql);
+    const char *r0 = maps[f].raw(i).data();
+    const uint64_t o = cons_off[f][cluster_id[i] - 1], len = cons_off[f][cluster_id[i]] - o;
+    if (len) {
+      memcpy(dst + (sq.data() - r0), &cons_b[f][o], (size_t)len);
+      memcpy(dst + (ql.data() - r0), &cons_q[f][o], (size_t)len);
+    }
+  };
   phase("device path done");
   if (getenv("HUMID_TIMING"))
     std::fprintf(stderr, "[humid]   of which on the device: upload%s %.1f ms, hot path %.2f ms, download %.1f ms\n",
@@ -705,6 +820,7 @@ int main(int argc, char **argv) {
                 if (!keep[i]) return q;
                 const std::string_view rr = maps[f].raw(i);
                 memcpy(q, rr.data(), rr.size());
+                if (a.consensus) put_consensus(f, i, q);
                 return q + rr.size();
               });
           if (r > 0) done_dedup[f] = 1;
@@ -757,7 +873,11 @@ int main(int argc, char **argv) {
               o.clear();
               if (what == 0) {
                 for (size_t i = b0 + rb; i < b0 + re; i++)
-                  if (keep[i]) { std::string_view r = maps[f].raw(i); o.append(r.data(), r.size()); }
+                  if (keep[i]) {
+                    std::string_view r = maps[f].raw(i);
+                    o.append(r.data(), r.size());
+                    if (a.consensus) put_consensus(f, i, &o[o.size() - r.size()]);
+                  }
               } else if (re > rb) {
                 // annotated record = header + ':' + cluster id + the rest of the record verbatim
                 // (src/humid.cc:281); written with pointer arithmetic into a buffer sized up front

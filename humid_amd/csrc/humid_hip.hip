@@ -26,6 +26,7 @@
 // shared-memory gather (no HIP); pipeline.hip.h = the pipeline itself, with internal linkage, compiled into both.
 #include "pipeline.hip.h"
 #include "kernels_best.hip.h"
+#include "kernels_consensus.hip.h"
 
 static std::string g_err;
 // (the error text of calls without a context: also set from humid_exchange.hip and shm.cpp)
@@ -100,7 +101,7 @@ void humid_ctx_destroy(humid_ctx *c) {
                   &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
                   &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
                   &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->bs_rep, &c->bs_best, &c->bs_ctr, &c->bs_words, &c->bs_cid, &c->bs_keep, &c->bs_score, &c->bs_keep_out, &c->bs_rep_out, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
+                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->bs_rep, &c->bs_best, &c->bs_ctr, &c->bs_words, &c->bs_cid, &c->bs_keep, &c->bs_score, &c->bs_keep_out, &c->bs_rep_out, &c->cs_rep, &c->cs_cnt, &c->cs_moff, &c->cs_cur, &c->cs_mem, &c->cs_ctr, &c->cs_big, &c->cs_piece, &c->cs_tab, &c->cs_ooff, &c->cs_ob, &c->cs_oq, &c->cs_depth, &c->cs_errors, &c->cs_in_bases, &c->cs_in_quals, &c->cs_in_off, &c->cs_in_cid, &c->cs_in_keep, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
                   &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
                   &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
                   &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
@@ -861,6 +862,160 @@ int humid_select_best(humid_ctx *c, const uint64_t *words, const uint32_t *clust
   D2H(keep_out, c->bs_keep_out.p, n);
   D2H(rep_out, c->bs_rep_out.p, n * 4);
   HIPCHK(hipStreamSynchronize(st));
+  return HUMID_OK;
+}
+
+// ---- consensus reads per cluster (kernels_consensus.hip.h) -------------------------------------------------------
+// (memory of the pass: plain allocations, never the slab a run carves its buffers from)
+#define CS_ENSURE(buf, bytes) HIPCHK((buf).ensure((bytes)))
+
+static int consensus_args(humid_ctx *c, const void *bases, const void *quals, const void *off, const void *cid, const void *keep,
+                          uint64_t n_reads, uint32_t min_q, uint32_t cap_q) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  c->cs_valid = false;                                       // the last results end with the next call, whatever it returns
+  if (min_q > 93) return fail(c, HUMID_E_INVALID, "humid_consensus: min_q must be 0 .. 93");
+  if (cap_q < 1 || cap_q > 93) return fail(c, HUMID_E_INVALID, "humid_consensus: cap_q must be 1 .. 93");
+  if (n_reads && (!bases || !quals || !off || !cid || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads >= 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "humid_consensus: more than 2^32 - 2 reads");
+  return HUMID_OK;
+}
+
+int humid_consensus_device(humid_ctx *c, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_off, uint64_t n_bytes,
+                           const uint32_t *d_cluster_id, const uint8_t *d_keep, uint64_t n_reads, uint64_t n_clusters,
+                           uint32_t min_q, uint32_t cap_q, humid_consensus_summary *summary) {
+  TRY(consensus_args(c, d_bases, d_quals, d_off, d_cluster_id, d_keep, n_reads, min_q, cap_q));
+  if (summary) memset(summary, 0, sizeof *summary);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  if (n_reads == 0 || n_clusters == 0) {                     // an empty result: out_off = {0}
+    CS_ENSURE(c->cs_ooff, 8);
+    HIPCHK(hipMemsetAsync(c->cs_ooff.p, 0, 8, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->cs_sum = humid_consensus_summary{};
+    c->cs_valid = true;
+    return HUMID_OK;
+  }
+  if (n_clusters > n_reads)                                  // (some cluster then has no read at all, so no kept one)
+    return fail(c, HUMID_E_INVALID, "humid_consensus: %llu clusters for %llu reads: a cluster without a read with keep == 1",
+                (ull)n_clusters, (ull)n_reads);
+  const u32 N = (u32)n_reads, C = (u32)n_clusters, min_q1 = min_q < 1 ? 1u : min_q;
+  const size_t max_big = (size_t)N / CONS_BIG + 2, max_piece = (size_t)N / CONS_PIECE + max_big + 2;
+  CS_ENSURE(c->cs_rep, ((size_t)C + 1) * 4);
+  CS_ENSURE(c->cs_cnt, ((size_t)C + 2) * 4);
+  CS_ENSURE(c->cs_moff, ((size_t)C + 1) * 4);
+  CS_ENSURE(c->cs_ctr, CONS_CTRS * 8);
+  CS_ENSURE(c->cs_ooff, ((size_t)C + 1) * 8);
+  CS_ENSURE(c->cs_big, max_big * sizeof(ConsBig));
+  CS_ENSURE(c->cs_piece, max_piece * sizeof(ConsPiece));
+  u32 *rep = c->cs_rep.as<u32>(), *cnt = c->cs_cnt.as<u32>(), *moff = c->cs_moff.as<u32>();
+  ull *ctr = c->cs_ctr.as<ull>();
+  u64 *ooff = c->cs_ooff.as<u64>();
+  ConsBig *big = c->cs_big.as<ConsBig>();
+  ConsPiece *piece = c->cs_piece.as<ConsPiece>();
+  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
+  HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)C + 2) * 4, st));
+  HIPCHK(hipMemsetAsync(ctr, 0, CONS_CTRS * 8, st));
+  hipLaunchKernelGGL(k_cons_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, d_off, N, (u64)n_bytes, C, rep, cnt, ctr);
+  TRY(exscan_in<u64>(c, ConsLenIn{rep, d_off, ctr, C}, ooff, (u64)C + 1));
+  TRY(exscan_in<u32>(c, PtrIn<u32>{cnt + 1}, moff, (u64)C + 1));
+  hipLaunchKernelGGL(k_cons_big_list, dim3(grid_stride_blocks(C)), dim3(256), 0, st, (const u32 *)cnt, (const u64 *)ooff, C, big, piece, ctr);
+  HIPCHK(hipGetLastError());
+  ull h[CONS_CTRS] = {};
+  u64 total = 0;
+  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&total, ooff + C, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          // the first host wait: is the input well formed, and the total that sizes the output
+  if (h[CONS_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_consensus: a cluster id above the %u clusters given", C);
+  if (h[CONS_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_consensus: a cluster has more than one read with keep == 1");
+  if (h[CONS_ERR] & 4u) return fail(c, HUMID_E_INVALID, "humid_consensus: off decreases");
+  if (h[CONS_ERR] & 8u) return fail(c, HUMID_E_INVALID, "humid_consensus: off[n_reads] lies beyond the %llu bytes given", (ull)n_bytes);
+  if (h[CONS_CLAIMS] != C)
+    return fail(c, HUMID_E_INVALID, "humid_consensus: %llu reads with keep == 1 for %u clusters", h[CONS_CLAIMS], C);
+  if (h[CONS_ERR] & 16u)
+    return fail(c, HUMID_E_OVERFLOW, "humid_consensus: a cluster of more than %u reads (32-bit sums)", CONS_MAX_DEPTH);
+  const u32 n_big = (u32)h[CONS_NBIG], n_pieces = (u32)h[CONS_NPIECES];
+  CS_ENSURE(c->cs_ob, (size_t)total + 16);
+  CS_ENSURE(c->cs_oq, (size_t)total + 16);
+  CS_ENSURE(c->cs_depth, (size_t)C * 4);
+  CS_ENSURE(c->cs_errors, (size_t)C * 8);
+  CS_ENSURE(c->cs_cur, ((size_t)C + 1) * 4);
+  CS_ENSURE(c->cs_mem, (size_t)N * 4);
+  HIPCHK(hipMemsetAsync(c->cs_cur.p, 0, ((size_t)C + 1) * 4, st));
+  hipLaunchKernelGGL(k_cons_scatter, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, N, (const u32 *)moff, c->cs_cur.as<u32>(), c->cs_mem.as<u32>());
+  hipLaunchKernelGGL(k_cons_small, dim3(blocks_for(C, 4)), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)rep, (const u32 *)moff,
+                     (const u32 *)c->cs_mem.p, (const u64 *)ooff, C, min_q1, cap_q, c->cs_ob.as<u8>(), c->cs_oq.as<u8>(),
+                     c->cs_depth.as<u32>(), c->cs_errors.as<u64>(), ctr);
+  if (n_big) {
+    const size_t tab_bytes = (size_t)h[CONS_TABCOLS] * 32;
+    CS_ENSURE(c->cs_tab, tab_bytes + 16);
+    HIPCHK(hipMemsetAsync(c->cs_tab.p, 0, tab_bytes, st));
+    hipLaunchKernelGGL(k_cons_piece, dim3(n_pieces), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)moff, (const u32 *)c->cs_mem.p,
+                       (const u64 *)ooff, (const ConsBig *)big, (const ConsPiece *)piece, min_q1, c->cs_tab.as<u32>());
+    hipLaunchKernelGGL(k_cons_final, dim3(n_big), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)rep, (const u32 *)moff,
+                       (const u64 *)ooff, (const ConsBig *)big, (const u32 *)c->cs_tab.p, cap_q, c->cs_ob.as<u8>(), c->cs_oq.as<u8>(),
+                       c->cs_depth.as<u32>(), c->cs_errors.as<u64>(), ctr);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          // the second host wait: the summary
+  c->cs_sum = humid_consensus_summary{(u64)C, total, (u64)h[CONS_MULTI], (u64)h[CONS_CHANGED], (u64)h[CONS_VOTES], (u64)h[CONS_ERRORS]};
+  c->cs_valid = true;
+  if (summary) *summary = c->cs_sum;
+  return HUMID_OK;
+}
+
+int humid_consensus(humid_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t n_bytes,
+                    const uint32_t *cluster_id, const uint8_t *keep, uint64_t n_reads, uint64_t n_clusters, uint32_t min_q,
+                    uint32_t cap_q, humid_consensus_summary *summary) {
+  TRY(consensus_args(c, bases, quals, off, cluster_id, keep, n_reads, min_q, cap_q));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads, nb = (size_t)n_bytes;
+  if (n) {
+    CS_ENSURE(c->cs_in_bases, nb + 16);
+    CS_ENSURE(c->cs_in_quals, nb + 16);
+    CS_ENSURE(c->cs_in_off, (n + 1) * 8);
+    CS_ENSURE(c->cs_in_cid, n * 4 + 16);
+    CS_ENSURE(c->cs_in_keep, n + 16);
+    if (nb) {
+      HIPCHK(hipMemcpyAsync(c->cs_in_bases.p, bases, nb, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(c->cs_in_quals.p, quals, nb, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(c->cs_in_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->cs_in_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->cs_in_keep.p, keep, n, hipMemcpyHostToDevice, st));
+  }
+  return humid_consensus_device(c, c->cs_in_bases.as<u8>(), c->cs_in_quals.as<u8>(), c->cs_in_off.as<u64>(), n_bytes,
+                                c->cs_in_cid.as<u32>(), c->cs_in_keep.as<u8>(), n_reads, n_clusters, min_q, cap_q, summary);
+}
+
+int humid_get_consensus(humid_ctx *c, uint64_t cap_bytes, uint64_t *out_off, uint8_t *cons_bases, uint8_t *cons_quals,
+                        uint32_t *depth, uint64_t *errors) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->cs_valid) return fail(c, HUMID_E_STATE, "no completed humid_consensus* call in this context");
+  const humid_consensus_summary &s = c->cs_sum;
+  if ((cons_bases || cons_quals) && cap_bytes < s.total_bytes)
+    return fail(c, HUMID_E_INVALID, "humid_get_consensus: room for %llu bytes, the consensus has %llu", (ull)cap_bytes, (ull)s.total_bytes);
+  HIPCHK(hipSetDevice(c->device));
+  D2H(out_off, c->cs_ooff.p, ((size_t)s.n_clusters + 1) * 8);
+  D2H(cons_bases, c->cs_ob.p, (size_t)s.total_bytes);
+  D2H(cons_quals, c->cs_oq.p, (size_t)s.total_bytes);
+  D2H(depth, c->cs_depth.p, (size_t)s.n_clusters * 4);
+  D2H(errors, c->cs_errors.p, (size_t)s.n_clusters * 8);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_consensus_result_device(humid_ctx *c, const uint64_t **d_out_off, const uint8_t **d_bases, const uint8_t **d_quals,
+                                  const uint32_t **d_depth, const uint64_t **d_errors) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->cs_valid) return fail(c, HUMID_E_STATE, "no completed humid_consensus* call in this context");
+  const bool any = c->cs_sum.n_clusters != 0;
+  if (d_out_off) *d_out_off = c->cs_ooff.as<u64>();
+  if (d_bases) *d_bases = any ? c->cs_ob.as<u8>() : nullptr;
+  if (d_quals) *d_quals = any ? c->cs_oq.as<u8>() : nullptr;
+  if (d_depth) *d_depth = any ? c->cs_depth.as<u32>() : nullptr;
+  if (d_errors) *d_errors = any ? c->cs_errors.as<u64>() : nullptr;
   return HUMID_OK;
 }
 

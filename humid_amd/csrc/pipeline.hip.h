@@ -193,6 +193,13 @@ struct humid_ctx {
   // best-scoring read per cluster (humid_select_best*, kernels_best.hip.h): memory of its own, read by no accessor
   DBuf bs_rep, bs_best, bs_ctr;                              // u32[C + 1] representatives, u64[C + 1] votes, the pass's counters
   DBuf bs_words, bs_cid, bs_keep, bs_score, bs_keep_out, bs_rep_out;   // host entry point staging
+  // consensus reads (humid_consensus*, kernels_consensus.hip.h): results in memory of their own, kept until the next
+  // humid_consensus* call; no run and no other accessor touches them
+  DBuf cs_rep, cs_cnt, cs_moff, cs_cur, cs_mem, cs_ctr, cs_big, cs_piece, cs_tab;   // representatives, reads per cluster, member lists, large clusters
+  DBuf cs_ooff, cs_ob, cs_oq, cs_depth, cs_errors;           // results: u64[C + 1], two byte blobs, u32[C], u64[C]
+  DBuf cs_in_bases, cs_in_quals, cs_in_off, cs_in_cid, cs_in_keep;   // host entry point staging
+  bool cs_valid = false;     // a humid_consensus* call succeeded: cs_sum and the result buffers are its
+  humid_consensus_summary cs_sum = {};
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;

@@ -262,3 +262,30 @@ def fast_fastq(path: str, n_reads: int, seed: int, read_len: int = 150, umi_len:
             buf[:, p] = ord("\n")
             buf.tofile(fh)
     return os.path.getsize(path)
+
+
+def synth_reads(cluster_id: np.ndarray, seed: int, read_len: int = 150, p_sub: float = 5e-3, p_q40: float = 0.8,
+                chunk: int = 1_000_000):
+    """Reads for the consensus pass (tools/bench_consensus.py): u8[N, read_len] ASCII bases and Phred+33 qualities.
+    Every cluster has one random template; a read is its cluster's template with substitutions at rate p_sub (to one
+    of the three other bases); reads with cluster id 0 get a template of their own.  Qualities: Phred 40 with
+    probability p_q40, else uniform in 2 .. 39 -- independent of the errors.  Everything depends on `seed` only."""
+    cid = np.asarray(cluster_id, dtype=np.int64)
+    n = len(cid)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    tmpl = rng.integers(0, 4, size=(int(cid.max(initial=0)) + 1, read_len), dtype=np.uint8)
+    bases = np.empty((n, read_len), np.uint8)
+    quals = np.empty((n, read_len), np.uint8)
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        x = tmpl[cid[lo:hi]]
+        lone = cid[lo:hi] == 0
+        if lone.any():
+            x[lone] = rng.integers(0, 4, size=(int(lone.sum()), read_len), dtype=np.uint8)
+        sub = rng.random(x.shape, dtype=np.float32) < p_sub
+        x[sub] = (x[sub] + rng.integers(1, 4, size=int(sub.sum()), dtype=np.uint8)) & 3
+        bases[lo:hi] = _ALPHA[x]
+        q = rng.integers(2, 40, size=x.shape, dtype=np.uint8)
+        q[rng.random(x.shape, dtype=np.float32) < p_q40] = 40
+        quals[lo:hi] = q + 33
+    return bases, quals

@@ -394,6 +394,70 @@ int humid_select_best_device(humid_ctx *ctx, const uint64_t *d_words, const uint
                              uint32_t word_nt, uint32_t scope, uint8_t *d_keep_out, uint32_t *d_rep_out,
                              uint64_t *n_changed);
 
+/* ---- consensus reads: one record per cluster, built from all of its reads --------------------------------------
+ * (fgbio CallMolecularConsensusReads, gencore: errors are voted out, qualities reflect the agreement.)  The
+ * definition is exact, in integers.  One call handles one LAYER of reads -- one FastQ file; a paired run calls once
+ * per file:
+ *   bases[n_bytes], quals[n_bytes]   raw ASCII; qualities are Phred+33.
+ *   off[n_reads + 1] (u64)           read i owns bytes [off[i], off[i + 1]) of both blobs; len_i = off[i + 1] - off[i].
+ *                                    Lengths may differ and may be 0.
+ *   cluster_id[n_reads], keep[n_reads]   from any run (also from a sharded pass), keep possibly rewritten by
+ *                                    humid_select_best.
+ *   n_clusters = C                   passed explicitly: the pass needs no prior run on the context.
+ *   min_q in 0 .. 93, cap_q in 1 .. 93.
+ * A read with cluster_id == 0 is no member; none of its bytes are read.  r_c is the one read with keep == 1 and
+ * cluster_id == c.
+ * Votes.  p(byte) = min(max(byte - 33, 0), 93).  Read i casts a vote at column j when j < len_i, its base byte is one
+ * of the uppercase A C G T and p(quality byte) >= max(min_q, 1); the vote's weight is p.  Anything else (N, lowercase,
+ * IUPAC codes, a quality below the threshold) casts nothing.
+ * Output of cluster c: len(r_c) base bytes and as many quality bytes.  For column j let S_b be the sum of the weights
+ * and n_b the number of the votes for base b over ALL reads of c (not only those that share the representative's
+ * word; reads longer than r_c are cut, shorter ones stop voting):
+ *   no vote was cast                     both bytes are r_c's own, verbatim;
+ *   the largest S_b is reached twice     'N' and '!' (a tie carries no information; no tie-break rule exists);
+ *   otherwise                            the base with the largest S_b, and 33 + min(S_first - S_second, cap_q).
+ * So a singleton's consensus is its own record wherever cap_q >= p.
+ *   depth[c - 1]  (u32) = reads of c.
+ *   errors[c - 1] (u64) = over the decided columns (neither verbatim nor tie) the votes cast minus n_winner.
+ *   out_off[C + 1] (u64): the consensus of cluster c is bytes [out_off[c - 1], out_off[c]) of both output blobs
+ *                 (cluster-id order; a scan over len(r_c) on the device).
+ *   summary: n_clusters = C; total_bytes = out_off[C]; multi_read = clusters with depth >= 2; bases_changed = output
+ *     base bytes that differ from r_c's; votes = all votes cast at columns below len(r_c); errors = sum of errors[].
+ * Sums are 32-bit: a cluster of more than 46 182 444 reads (93 x that reaches 2^32) returns HUMID_E_OVERFLOW, decided
+ * from the member counts before anything is summed (the other of the two possible answers, 64-bit sums, would double
+ * the registers of every column for a cluster size no data set has).
+ * Malformed input -- an id above C, a cluster with no kept read or with two, off decreasing anywhere, off[n_reads] >
+ * n_bytes -- is found on the device and reported as HUMID_E_INVALID at the pass's first host wait; nothing is then
+ * written and no unchecked index followed.  min_q / cap_q out of range and a NULL buffer with n_reads > 0 are refused
+ * on the host (HUMID_E_INVALID).  n_reads == 0 or C == 0 returns HUMID_OK with an empty result (n_clusters = 0).  The
+ * context stays usable and every accessor of the last run valid, whatever the pass returns; it launches nothing
+ * unless it is called.  Two host waits: the total that sizes the output (with the checks), and the summary.
+ * On the device (kernels_consensus.hip.h): the kept reads claim their clusters as in humid_select_best; the read
+ * indices are grouped by cluster (count, scan, cursor scatter -- the order inside a cluster is that of the atomics,
+ * which integer sums do not see); one wave per cluster with lanes over 64 columns and a loop over the members; a
+ * cluster of more than 1024 reads is cut into pieces of 1024 whose partial sums meet in a table through 32-bit
+ * atomic adds before one workgroup decides its columns.
+ *   humid_consensus: host buffers.   humid_consensus_device: DEVICE pointers (summary stays a host pointer; may be
+ *     NULL); returns after the stream has drained.
+ *   humid_get_consensus: host copies of the last successful call's results; any pointer may be NULL; cap_bytes is the
+ *     room of cons_bases / cons_quals: cap_bytes < total_bytes with either given returns HUMID_E_INVALID.
+ *   humid_consensus_result_device: the same arrays left in HBM (as humid_group_stats_device), owned by the context.
+ * The results live in buffers of their own: they last until the next humid_consensus* call (successful or not) or
+ * humid_ctx_destroy, and survive any run.  Both getters return HUMID_E_STATE before a successful call. */
+typedef struct humid_consensus_summary {
+  uint64_t n_clusters, total_bytes, multi_read, bases_changed, votes, errors;
+} humid_consensus_summary;
+int humid_consensus(humid_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t n_bytes,
+                    const uint32_t *cluster_id, const uint8_t *keep, uint64_t n_reads, uint64_t n_clusters,
+                    uint32_t min_q, uint32_t cap_q, humid_consensus_summary *summary);
+int humid_consensus_device(humid_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_off,
+                           uint64_t n_bytes, const uint32_t *d_cluster_id, const uint8_t *d_keep, uint64_t n_reads,
+                           uint64_t n_clusters, uint32_t min_q, uint32_t cap_q, humid_consensus_summary *summary);
+int humid_get_consensus(humid_ctx *ctx, uint64_t cap_bytes, uint64_t *out_off, uint8_t *cons_bases,
+                        uint8_t *cons_quals, uint32_t *depth, uint64_t *errors);
+int humid_consensus_result_device(humid_ctx *ctx, const uint64_t **d_out_off, const uint8_t **d_bases,
+                                  const uint8_t **d_quals, const uint32_t **d_depth, const uint64_t **d_errors);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
