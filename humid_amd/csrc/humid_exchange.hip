@@ -136,10 +136,12 @@ int humid_dedup_run_exchange(humid_ctx *c, const humid_comm *cm, const uint64_t 
                              uint64_t n_local, uint32_t word_nt, uint32_t distance, uint32_t method,
                              uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary, humid_exchange_info *info) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
   c->x_hist_done = false;
   c->x_peer_failed = false;
   c->x_gathers = 0;
   const int rc = run_exchange_impl(c, cm, d_words, d_filtered, n_local, word_nt, distance, method, d_cluster_id, d_keep, summary, info);
+  if (rc != HUMID_OK) state_reset(c);                        // (the count inside the pass had published itself)
   if (rc != HUMID_OK && cm) {
     // the size of the pass's first gather, should this rank have failed before it: the histogram table
     // (the same arithmetic as in run_exchange_impl; word lengths it refuses are refused on every rank alike)
@@ -267,11 +269,9 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
                                 &usable_local));
   } else {
     // counts by sorting (kernels_wide.hip.h), as on one GPU; every received read is usable
-    c->have_run = c->have_graph = false;
-    c->graph_mode = false;
+    state_reset(c);
     c->N = c->U = c->E = c->M = c->C = c->usable = 0;
     c->word_nt = n;
-    c->dense_mode = true;
     c->stage_map_timed = false;
     if (n_recv) {
       ENSURE(c->xr_zero, n_recv + 16);
@@ -283,6 +283,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
       HIPCHK(hipStreamSynchronize(st));
       if (c->usable != n_recv) return fail(c, HUMID_E_INVALID, "a filtered read among the routed wide words");
     }
+    state_publish_count(c, true);                                  // (a later failure of the pass: humid_dedup_run_exchange resets)
     u_local = c->U;
     usable_local = c->usable;
   }
@@ -449,8 +450,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
       HIPCHK(bigger.ensure((e_mine + n_rec) * 32, nullptr));
       if (e_mine) HIPCHK(hipMemcpyAsync(bigger.p, c->xr_eloc.p, e_mine * 16, hipMemcpyDeviceToDevice, st));
       HIPCHK(hipStreamSynchronize(st));
-      c->xr_eloc.release();
-      c->xr_eloc = bigger;                                           // (DBuf owns nothing by itself: a plain hand-over)
+      c->xr_eloc = std::move(bigger);
     }
     HIPCHK(hipMemcpyAsync(c->xr_eloc.as<u8>() + e_mine * 16, rec, n_rec * 16, hipMemcpyDeviceToDevice, st));
     e_mine += n_rec;
@@ -953,9 +953,7 @@ int humid_stage_count(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_fi
                       uint32_t word_nt, uint64_t range_lo, uint64_t range_hi, uint64_t expected_reads,
                       uint64_t *n_unique, uint64_t *n_usable) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = false;
-  c->graph_mode = false;
-  c->dense_mode = false;
+  state_reset(c);
   TRY(check_run_args(c, n_reads, word_nt, 0));
   if (n_reads && (!d_words || !d_filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
   HIPCHK(hipSetDevice(c->device));
@@ -967,7 +965,7 @@ int humid_stage_count(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_fi
   HIPCHK(hipStreamSynchronize(c->stream));
   if (n_unique) *n_unique = c->U;
   if (n_usable) *n_usable = c->usable;
-  return HUMID_OK;
+  return state_publish_count(c, false);
 }
 
 // Dense variant for a multi-GPU rank: the usable reads of [range_lo, range_hi] are first compacted
@@ -979,9 +977,7 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
                             const uint64_t *shard_begin, uint32_t n_shards, uint64_t *counts,
                             uint64_t *n_unique, uint64_t *n_usable) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = false;
-  c->graph_mode = false;
-  c->dense_mode = false;
+  state_reset(c);
   TRY(check_run_args(c, n_reads, word_nt, 0, 64));
   const bool wide = word_nt > 32;
   if (wide && d_filtered == nullptr)
@@ -1005,18 +1001,20 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
   for (u32 q = 0; q < n_shards; q++) counts[q] = 0;
   if (n_unique) *n_unique = 0;
   if (n_usable) *n_usable = 0;
-  c->dense_mode = true;
   c->stage_map_timed = false;
-  if (N == 0) return HUMID_OK;
+  auto counted = [&] {                                       // every successful end of the count
+    if (n_unique) *n_unique = c->U;
+    if (n_usable) *n_usable = c->usable;
+    return state_publish_count(c, true);
+  };
+  if (N == 0) return counted();
   if (all_owned) {
     for (u32 q = 0; q < n_shards; q++) counts[q] = shard_begin[q + 1] - shard_begin[q];
     c->N = N;
     TRY(stage_count(c, d_words, nullptr, N, word_nt, range_lo, range_hi, 0, s, true));
     HIPCHK(hipStreamSynchronize(st));
     if (c->usable != N) return fail(c, HUMID_E_INVALID, "a read outside [range_lo, range_hi] in an all-owned count");
-    if (n_unique) *n_unique = c->U;
-    if (n_usable) *n_usable = c->usable;
-    return HUMID_OK;
+    return counted();
   }
   ENSURE(c->opos, ((size_t)N + 1) * 4);
   const u64 *range_keys = d_words;                      // what the range is a range of: the words, or their heads
@@ -1032,7 +1030,7 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
   const u32 n_own = got[n_shards];
   for (u32 q = 0; q < n_shards; q++) counts[q] = got[q + 1] - got[q];
   c->N = n_own;
-  if (n_own == 0) return HUMID_OK;
+  if (n_own == 0) return counted();
   ENSURE(c->own_words, (size_t)n_own * (wide ? 16 : 8));
   if (wide) {
     hipLaunchKernelGGL(k_gather_owned_w2, dim3(grid_stride_blocks(N)), dim3(256), 0, st, (const W2 *)d_words, range_keys, d_filtered,
@@ -1040,18 +1038,14 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
     HIPCHK(hipGetLastError());
     TRY(stage_count_wide(c, c->own_words.as<W2>(), nullptr, n_own, word_nt, s));
     HIPCHK(hipStreamSynchronize(st));
-    if (n_unique) *n_unique = c->U;
-    if (n_usable) *n_usable = c->usable;
-    return HUMID_OK;
+    return counted();
   }
   hipLaunchKernelGGL(k_gather_owned, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_words, d_filtered,
                      c->opos.as<u32>(), range_lo, range_hi, N, c->own_words.as<u64>());
   HIPCHK(hipGetLastError());
   TRY(stage_count(c, c->own_words.as<u64>(), nullptr, n_own, word_nt, 0ull, ~0ull, 0, s));
   HIPCHK(hipStreamSynchronize(st));
-  if (n_unique) *n_unique = c->U;
-  if (n_usable) *n_usable = c->usable;
-  return HUMID_OK;
+  return counted();
 }
 
 // The result stream of the dense variant: packed (cluster_id | keep << 31) of this rank's reads in
@@ -1059,7 +1053,7 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
 int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, const uint8_t *d_local_is_max,
                           const uint32_t **d_packed, uint64_t *n_packed) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->dense_mode) return fail(c, HUMID_E_STATE, "no preceding humid_stage_count_dense");
+  if (!state_dense_count(c)) return fail(c, HUMID_E_STATE, "no preceding humid_stage_count_dense");
   if (!d_packed || !n_packed) return fail(c, HUMID_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -1110,9 +1104,7 @@ int humid_stage_graph(humid_ctx *c, const uint64_t *d_g_word, const uint32_t *d_
                       uint64_t n_unique, uint32_t word_nt, uint32_t distance, uint32_t method,
                       const uint32_t **d_cluster_id, const uint8_t **d_is_max, humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_graph = false;
-  c->gs_run = false;
-  c->graph_mode = false;
+  state_begin_graph(c);
   TRY(check_run_args(c, n_unique, word_nt, method, 64));
   HIPCHK(hipSetDevice(c->device));
   humid_summary s;
@@ -1137,8 +1129,7 @@ int humid_stage_graph(humid_ctx *c, const uint64_t *d_g_word, const uint32_t *d_
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   if (summary) *summary = s;
-  c->have_graph = true;
-  return HUMID_OK;
+  return state_publish(c, CtxState::STAGE_GRAPH);
 }
 
 int humid_stage_map(humid_ctx *c, const uint32_t *d_local_cluster_id, const uint8_t *d_local_is_max,
@@ -1176,9 +1167,7 @@ int humid_stage_graph_edges(humid_ctx *c, const uint64_t *d_g_word, const uint32
                             uint32_t method, const uint32_t **d_cluster_id, const uint8_t **d_is_max,
                             humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_graph = false;
-  c->gs_run = false;
-  c->graph_mode = false;
+  state_begin_graph(c);
   TRY(check_run_args(c, n_unique, word_nt, method, 64));
   if (n_edges >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "2*edges exceeds 32 bits");
   HIPCHK(hipSetDevice(c->device));
@@ -1207,8 +1196,7 @@ int humid_stage_graph_edges(humid_ctx *c, const uint64_t *d_g_word, const uint32
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   if (summary) *summary = s;
-  c->have_graph = true;
-  return HUMID_OK;
+  return state_publish(c, CtxState::STAGE_GRAPH);
 }
 
 // ---- multi-GPU exchange mode (humid_amd/sharded.py, mode "exchange") -------------------------
@@ -1660,7 +1648,7 @@ int humid_stage_unique_edges(humid_ctx *c, const uint64_t *d_edges, uint64_t n_e
 // this context (bench.py's roofline leg in multi-GPU runs); waits for the stream.
 int humid_stage_kernel_ms(humid_ctx *c, float *ms_k_insert, float *ms_k_map, uint32_t *count_mode_used) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->dense_mode || (c->N && !c->stage_map_timed))
+  if (!state_dense_count(c) || (c->N && !c->stage_map_timed))
     return fail(c, HUMID_E_STATE, "no completed humid_stage_count_dense + humid_stage_map_dense");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));

@@ -95,18 +95,6 @@ void humid_ctx_destroy(humid_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  DBuf *bufs[] = {&c->in_words, &c->in_filt, &c->in_bases, &c->out_cid, &c->out_keep, &c->table, &c->pk_keys, &c->pk_vals,
-                  &c->pbeg, &c->ucount, &c->pusable, &c->ubase, &c->pad_word, &c->pad_cf, &c->pslot,
-                  &c->opos, &c->own_packed, &c->owner, &c->owner_sorted, &c->perm, &c->small, &c->pc, &c->poff, &c->share_edges, &c->own_words, &c->heads, &c->had, &c->big_runs, &c->small_roots, &c->e_kx, &c->e_vx, &c->e_ky, &c->e_vy, &c->e_raw, &c->e_sorted, &c->e_edges, &c->e_head, &c->e_hpos, &c->e_runlo, &c->e_nch, &c->e_choff, &c->e_pc2, &c->e_poff2, &c->x_slot, &c->x_slot_s, &c->x_cnt, &c->x_cnts, &c->x_rec, &c->x_ncnt, &c->x_route, &c->x_creator, &c->x_base, &c->x_mark, &c->x_markcr, &c->x_scan, &c->x_lcid, &c->x_lismax, &c->x_items, &c->x_w, &c->x_id, &c->x_ids, &c->x_ends, &c->x_ends_s, &c->x_head, &c->x_hpos, &c->x_nodes, &c->x_cedges, &c->w_heads, &c->w_sorted, &c->w_head, &c->w_hpos, &c->w_start, &c->pt_work, &c->unperm_rec, &c->route_tiles, &c->xr_hist, &c->xr_recv, &c->xr_eloc, &c->xr_got, &c->xr_eall, &c->xr_ret, &c->xr_heads, &c->xr_send, &c->xr_zero,
-                  &c->xo_gw, &c->xo_gc, &c->xo_regs, &c->xo_inv, &c->xo_send, &c->xo_int, &c->xo_cross, &c->xo_sel, &c->xo_selall, &c->xo_parent, &c->xo_flag, &c->xo_xroot, &c->xo_xcbits, &c->xo_xcblk,
-                  &c->xo_xcid, &c->xo_xcall, &c->xo_ldeg, &c->xo_cnt, &c->pw_a, &c->pw_ai, &c->pw_b, &c->pw_bi, &c->gf_cur, &c->p8_a, &c->p8_b, &c->p8_cur, &c->p8_status, &c->cg_edges, &c->cg_cur, &c->cg_far, &c->cg_bits, &c->cg_nbits, &c->cg_blk, &c->cg_nblk, &c->cg_nodes, &c->cg_ncnt, &c->cg_deg,
-                  &c->cg_off, &c->cg_idx, &c->cg_parent, &c->cg_csize, &c->cg_curs, &c->cg_cl_of, &c->cg_maxleaf, &c->cg_cl_size,
-                  &c->gk_words, &c->gk_group_in, &c->gk_bad, &c->kr_table, &c->kr_raw, &c->kr_rawslot, &c->kr_keys, &c->kr_slot, &c->kr_key_in, &c->wl_table, &c->bc_key, &c->bc_filt, &c->bc_status, &c->bc_counts, &c->wc_key, &c->wc_filt, &c->wc_out, &c->wc_status, &c->wc_counts, &c->bs_rep, &c->bs_best, &c->bs_ctr, &c->bs_words, &c->bs_cid, &c->bs_keep, &c->bs_score, &c->bs_keep_out, &c->bs_rep_out, &c->cs_rep, &c->cs_cnt, &c->cs_moff, &c->cs_cur, &c->cs_mem, &c->cs_ctr, &c->cs_big, &c->cs_piece, &c->cs_tab, &c->cs_ooff, &c->cs_ob, &c->cs_oq, &c->cs_depth, &c->cs_errors, &c->cs_in_bases, &c->cs_in_quals, &c->cs_in_off, &c->cs_in_cid, &c->cs_in_keep, &c->gs_reads, &c->gs_loff, &c->gs_coff, &c->gs_edges, &c->gs_ps, &c->slot_out, &c->slot_of_read, &c->uniq_slot, &c->uniq_word, &c->s_word, &c->s_slot,
-                  &c->s_cnt, &c->s_first, &c->deg, &c->nbr_off, &c->nbr_idx, &c->seg_k0, &c->seg_ks,
-                  &c->seg_v0, &c->seg_vs, &c->seg_ws, &c->csize, &c->cur, &c->parent, &c->mk0, &c->mk1, &c->cl_of,
-                  &c->maxleaf, &c->cl_size, &c->flag, &c->pos, &c->cid, &c->ismax, &c->stk, &c->tmp,
-                  &c->scratch};
-  for (DBuf *b : bufs) b->release();
 #ifdef HUMID_PHASE_CLOCKS                                    // (experiment builds only: common.hip.h)
   {
     static const char *names[PH_KERNELS] = {"k_dedup_rec", "k_p8_scatter1", "k_p8_scatter2", "k_unperm_bins8", "k_group_fine", "k_pairs_append", "k_unperm_window", "-"};
@@ -127,7 +115,7 @@ void humid_ctx_destroy(humid_ctx *c) {
   for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : c->kev) if (ev) (void)hipEventDestroy(ev);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;                                                  // every DBuf frees its block here, after the slab (carved blocks free nothing)
 }
 
 void *humid_host_alloc(uint64_t bytes) {
@@ -241,9 +229,9 @@ int humid_dedup_run_device(humid_ctx *c, const uint64_t *d_words, const uint8_t 
                            uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
                            uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (word_nt > 32)
-    return run_device<W2>(c, (const W2 *)d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
-  return run_device<u64>(c, d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_device(c, (decltype(w))d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+  });
 }
 
 int humid_dedup_run_grouped_device(humid_ctx *c, const uint64_t *d_words, const uint32_t *d_group,
@@ -251,26 +239,49 @@ int humid_dedup_run_grouped_device(humid_ctx *c, const uint64_t *d_words, const 
                                    uint32_t distance, uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep,
                                    humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (word_nt > 32)
-    return run_grouped_device<W2>(c, (const W2 *)d_words, d_group, d_filtered, n_reads, word_nt, n_groups, distance, method,
-                                  d_cluster_id, d_keep, summary);
-  return run_grouped_device<u64>(c, d_words, d_group, d_filtered, n_reads, word_nt, n_groups, distance, method,
-                                 d_cluster_id, d_keep, summary);
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_grouped_device(c, (decltype(w))d_words, d_group, d_filtered, n_reads, word_nt, n_groups, distance, method,
+                              d_cluster_id, d_keep, summary);
+  });
+}
+
+int humid_dedup_run_keyed_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
+                                 uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_keyed_device(c, (decltype(w))d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep,
+                            summary);
+  });
+}
+
+int humid_dedup_run_keyed_corrected_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key,
+                                           const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
+                                           uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_keyed_corrected_device(c, (decltype(w))d_words, d_key, d_filtered, n_reads, word_nt, distance, method,
+                                      d_cluster_id, d_keep, summary);
+  });
 }
 
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
-// grouped: humid_dedup_run_grouped (group may be null with n_groups = 1); key != null: humid_dedup_run_keyed, or
-// (corrected) humid_dedup_run_keyed_corrected
-static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
-                    uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
-                    uint8_t *keep, humid_summary *summary, bool grouped = false, const uint32_t *group = nullptr,
-                    uint32_t n_groups = 1, const uint64_t *key = nullptr, bool corrected = false) {
+// kind: what the run is (RUN_GROUPED: group may be null with n_groups = 1; RUN_KEYED on: key, null only without reads).
+// Everything the kind refuses is refused here, before any copy: a refused shape moves nothing.
+static int run_host(humid_ctx *c, RunKind kind, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
+                    const uint32_t *group, uint32_t n_groups, const uint64_t *key, uint64_t n_reads, uint32_t word_nt,
+                    uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
+  if (kind == RUN_CORRECTED && !c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (kind >= RUN_KEYED) {
+    TRY(check_run_args(c, n_reads, word_nt, method, 64));
+    if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
+  }
   if (n_reads && (!(bases || (words && filtered)) || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
   if (bases) TRY(check_run_args(c, n_reads, word_nt, method, 64));
-  if (grouped) {                                             // (before any copy: a refused shape moves nothing)
-    c->have_run = c->have_graph = c->gk_leaves = false;
+  if (kind == RUN_GROUPED) {
     TRY(check_run_args(c, n_reads, word_nt, method, 64));
     TRY(check_grouped_args(c, word_nt, n_groups));
     if (!group && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
@@ -303,35 +314,29 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
     HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
   }
-  if (n && grouped && group) {
+  if (n && kind == RUN_GROUPED && group) {
     ENSURE(c->gk_group_in, n * 4 + 8);
     HIPCHK(hipMemcpyAsync(c->gk_group_in.p, group, n * 4, hipMemcpyHostToDevice, st));
   }
-  if (n && key) {
+  if (n && kind >= RUN_KEYED) {
     ENSURE(c->kr_key_in, n * 8 + 8);
     HIPCHK(hipMemcpyAsync(c->kr_key_in.p, key, n * 8, hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipEventRecord(e1, st));
-  int rc = key && corrected ? (word_nt > 32
-               ? run_keyed_corrected_device<W2>(c, c->in_words.as<W2>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads,
-                                                word_nt, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
-               : run_keyed_corrected_device<u64>(c, c->in_words.as<u64>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads,
-                                                 word_nt, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
-           : key ? (word_nt > 32
-               ? run_keyed_device<W2>(c, c->in_words.as<W2>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
-                                      distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
-               : run_keyed_device<u64>(c, c->in_words.as<u64>(), c->kr_key_in.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt,
-                                       distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
-           : grouped ? (word_nt > 32
-               ? run_grouped_device<W2>(c, c->in_words.as<W2>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
-                                        n_reads, word_nt, n_groups, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
-               : run_grouped_device<u64>(c, c->in_words.as<u64>(), group ? c->gk_group_in.as<u32>() : nullptr, c->in_filt.as<u8>(),
-                                         n_reads, word_nt, n_groups, distance, method, c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s))
-           : word_nt > 32
-               ? run_device<W2>(c, c->in_words.as<W2>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
-                                c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s)
-               : run_device<u64>(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
-                                 c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s);
+  int rc = with_word_type(word_nt, [&](auto *w) {
+    auto *d_w = (decltype(w))c->in_words.p;
+    const u8 *d_f = c->in_filt.as<u8>();
+    const u64 *d_k = c->kr_key_in.as<u64>();
+    u32 *d_cid = c->out_cid.as<u32>();
+    u8 *d_keep = c->out_keep.as<u8>();
+    switch (kind) {
+      case RUN_CORRECTED: return run_keyed_corrected_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
+      case RUN_KEYED: return run_keyed_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
+      case RUN_GROUPED: return run_grouped_device(c, d_w, group ? c->gk_group_in.as<u32>() : nullptr, d_f, n_reads, word_nt, n_groups,
+                                                  distance, method, d_cid, d_keep, &s);
+      default: return run_device(c, d_w, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
+    }
+  });
   if (rc == HUMID_OK) {
     hipError_t he = hipEventRecord(e2, st);
     if (he == hipSuccess && n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
@@ -340,7 +345,7 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
-    if (he != hipSuccess) rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he));
+    if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
   }
   (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
   if (rc == HUMID_OK && summary) *summary = s;
@@ -350,50 +355,42 @@ static int run_host(humid_ctx *c, const uint64_t *words, const uint8_t *filtered
 int humid_dedup_run(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads,
                     uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                     uint8_t *keep, humid_summary *summary) {
-  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary);
+  return run_host(c, RUN_PLAIN, words, filtered, nullptr, nullptr, 1, nullptr, n_reads, word_nt, distance, method, cluster_id, keep,
+                  summary);
 }
 
 int humid_dedup_run_grouped(humid_ctx *c, const uint64_t *words, const uint32_t *group, const uint8_t *filtered,
                             uint64_t n_reads, uint32_t word_nt, uint32_t n_groups, uint32_t distance, uint32_t method,
                             uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
-  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, true, group,
-                  n_groups);
-}
-
-int humid_dedup_run_keyed_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
-                                 uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
-                                 uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
-  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (word_nt > 32)
-    return run_keyed_device<W2>(c, (const W2 *)d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id,
-                                d_keep, summary);
-  return run_keyed_device<u64>(c, d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+  return run_host(c, RUN_GROUPED, words, filtered, nullptr, group, n_groups, nullptr, n_reads, word_nt, distance, method,
+                  cluster_id, keep, summary);
 }
 
 int humid_dedup_run_keyed(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
                           uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                           uint8_t *keep, humid_summary *summary) {
-  if (c) {                                                   // (before any copy: a refused shape moves nothing)
-    c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
-    TRY(check_run_args(c, n_reads, word_nt, method, 64));
-    if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
-  }
-  static const uint64_t no_key = 0;                          // (n_reads == 0: nothing is read)
-  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, false, nullptr, 1,
-                  key ? key : &no_key);
+  return run_host(c, RUN_KEYED, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id, keep,
+                  summary);
+}
+
+int humid_dedup_run_keyed_corrected(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
+                                    uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
+                                    uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  return run_host(c, RUN_CORRECTED, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id,
+                  keep, summary);
 }
 
 int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
                           uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   if (n_reads && !bases) return fail(c, HUMID_E_INVALID, "null buffer");
-  return run_host(c, nullptr, nullptr, bases ? bases : (const uint8_t *)"", n_reads, word_nt, distance, method,
-                  cluster_id, keep, summary);
+  return run_host(c, RUN_PLAIN, nullptr, nullptr, bases ? bases : (const uint8_t *)"", nullptr, 1, nullptr, n_reads, word_nt, distance,
+                  method, cluster_id, keep, summary);
 }
 
 // the packed words and flags of the last humid_dedup_run_bases (what makeWord would have returned)
 int humid_get_packed_words(humid_ctx *c, uint64_t *words, uint8_t *filtered) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->have_run) return fail(c, HUMID_E_STATE, "no completed dedup run in this context");
+  if (!state_has_run(c)) return fail(c, HUMID_E_STATE, "no completed dedup run in this context");
   HIPCHK(hipSetDevice(c->device));
   const size_t n = (size_t)c->N, wbytes = c->word_nt > 32 ? 16 : 8;
   if (n * wbytes > c->in_words.cap || n > c->in_filt.cap) return fail(c, HUMID_E_STATE, "the last run did not go through a host entry point");
@@ -419,10 +416,10 @@ static void gkey_split(const humid_ctx *c, const std::vector<u64> &iw, size_t U,
   }
 }
 
-#define NEED_RUN()                                                                            \
+#define NEED_LEAVES()                                                                         \
   do {                                                                                        \
     if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");                             \
-    if (!c->have_graph || c->graph_mode) return fail(c, HUMID_E_STATE, "no completed dedup run / graph stage in this context"); \
+    if (!state_has_leaves(c)) return fail(c, HUMID_E_STATE, "no completed dedup run / graph stage in this context"); \
     HIPCHK(hipSetDevice(c->device));                                                          \
     TRY(expand_compact(c));                                                                   \
   } while (0)
@@ -432,12 +429,12 @@ static void gkey_split(const humid_ctx *c, const std::vector<u64> &iw, size_t U,
 
 int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *first_read,
                      uint32_t *degree, uint32_t *cluster_id, uint8_t *is_max_leaf) {
-  NEED_RUN();
+  NEED_LEAVES();
   size_t U = (size_t)c->gU;
   if (U == 0) return HUMID_OK;
-  if (first_read && !c->have_run)
+  if (first_read && !state_has_run(c))
     return fail(c, HUMID_E_STATE, "first_read is only available after a single-GPU humid_dedup_run*");
-  if (word && c->gk_leaves && (c->gk_leaf_nt || c->g_wpr != (c->gk_word_nt > 32 ? 2u : 1u))) {
+  if (word && state_run_is(c, RUN_GROUPED) && (c->gk_leaf_nt || c->g_wpr != (c->gk_word_nt > 32 ? 2u : 1u))) {
     // grouped internal words -> the caller's words (the group goes to humid_get_leaf_groups)
     std::vector<u64> iw(U * c->g_wpr);
     HIPCHK(hipMemcpyAsync(iw.data(), c->g_word, U * 8 * c->g_wpr, hipMemcpyDeviceToHost, c->stream));
@@ -455,8 +452,8 @@ int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *fi
 }
 
 int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
-  NEED_RUN();
-  if (!c->gk_leaves) return fail(c, HUMID_E_STATE, "the last run was not a grouped run");
+  NEED_LEAVES();
+  if (!state_run_is(c, RUN_GROUPED)) return fail(c, HUMID_E_STATE, "the last run was not a grouped run");
   size_t U = (size_t)c->gU;
   if (U == 0 || !group) return HUMID_OK;
   if (!c->gk_leaf_nt) { memset(group, 0, U * 4); return HUMID_OK; }
@@ -468,8 +465,8 @@ int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
 }
 
 int humid_get_group_keys(humid_ctx *c, uint64_t *keys, uint64_t cap, uint64_t *n_out) {
-  NEED_RUN();
-  if (!c->kr_leaves) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
+  NEED_LEAVES();
+  if (!state_run_is(c, RUN_KEYED)) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
   if (!n_out) return fail(c, HUMID_E_INVALID, "null argument");
   *n_out = c->kr_n;
   const u64 take = c->kr_n < cap ? c->kr_n : cap;
@@ -481,8 +478,8 @@ int humid_get_group_keys(humid_ctx *c, uint64_t *keys, uint64_t cap, uint64_t *n
 }
 
 int humid_keyed_rank_info(humid_ctx *c, uint64_t *n_keys, uint32_t *table_log2, uint32_t *n_redo) {
-  NEED_RUN();
-  if (!c->kr_leaves) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
+  NEED_LEAVES();
+  if (!state_run_is(c, RUN_KEYED)) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
   if (n_keys) *n_keys = c->kr_n;
   if (table_log2) *table_log2 = c->kr_last_log2;
   if (n_redo) *n_redo = c->kr_redo;
@@ -513,27 +510,18 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   while (((u64)1 << log2) < 2 * n) log2++;
   const size_t cap = (size_t)1 << log2;
   // the new table is built beside the old one, which stays in place until the new one is complete
-  DBuf fresh, stage;
-  hipError_t e = fresh.ensure((cap + 2) * 8);
-  if (e == hipSuccess) e = stage.ensure((size_t)n * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(fresh.p, 0xff, (cap + 1) * 8, st);
-  if (e == hipSuccess) e = hipMemsetAsync(fresh.as<u64>() + cap + 1, 0, 8, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(stage.p, barcodes, (size_t)n * 8, hipMemcpyHostToDevice, st);
+  DBuf fresh, stage;                                         // (both free themselves on every early return)
+  HIPCHK(fresh.ensure((cap + 2) * 8));
+  HIPCHK(stage.ensure((size_t)n * 8));
+  HIPCHK(hipMemsetAsync(fresh.p, 0xff, (cap + 1) * 8, st));
+  HIPCHK(hipMemsetAsync(fresh.as<u64>() + cap + 1, 0, 8, st));
+  HIPCHK(hipMemcpyAsync(stage.p, barcodes, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_wl_insert, dim3(grid_stride_blocks(n)), dim3(256), 0, st, (const u64 *)stage.p, (u32)n, fresh.as<u64>(), log2);
+  HIPCHK(hipGetLastError());
   u64 distinct = 0;
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_wl_insert, dim3(grid_stride_blocks(n)), dim3(256), 0, st, (const u64 *)stage.p, (u32)n, fresh.as<u64>(), log2);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&distinct, fresh.as<u64>() + cap + 1, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  stage.release();
-  if (e != hipSuccess) {
-    fresh.release();
-    (void)hipGetLastError();
-    return fail(c, e == hipErrorOutOfMemory ? HUMID_E_NOMEM : HUMID_E_HIP, "humid_whitelist_set: %s", hipGetErrorString(e));
-  }
-  c->wl_table.release();
-  c->wl_table = fresh;
+  HIPCHK(hipMemcpyAsync(&distinct, fresh.as<u64>() + cap + 1, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->wl_table = std::move(fresh);
   c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
   return HUMID_OK;
 }
@@ -589,34 +577,9 @@ int humid_whitelist_correct(humid_ctx *c, const uint64_t *key, const uint8_t *fi
   return HUMID_OK;
 }
 
-int humid_dedup_run_keyed_corrected_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key,
-                                           const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
-                                           uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep, humid_summary *summary) {
-  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (word_nt > 32)
-    return run_keyed_corrected_device<W2>(c, (const W2 *)d_words, d_key, d_filtered, n_reads, word_nt, distance, method,
-                                          d_cluster_id, d_keep, summary);
-  return run_keyed_corrected_device<u64>(c, d_words, d_key, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep,
-                                         summary);
-}
-
-int humid_dedup_run_keyed_corrected(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
-                                    uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
-                                    uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
-  if (c) {                                                   // (before any copy: a refused shape moves nothing)
-    c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = c->bc_leaves = false;
-    if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
-    TRY(check_run_args(c, n_reads, word_nt, method, 64));
-    if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
-  }
-  static const uint64_t no_key = 0;                          // (n_reads == 0: nothing is read)
-  return run_host(c, words, filtered, nullptr, n_reads, word_nt, distance, method, cluster_id, keep, summary, false, nullptr, 1,
-                  key ? key : &no_key, true);
-}
-
 int humid_get_barcode_status(humid_ctx *c, uint8_t *status, uint64_t cap, uint64_t counts[5]) {
-  NEED_RUN();
-  if (!c->have_run || !c->bc_leaves) return fail(c, HUMID_E_STATE, "the last run was not a corrected keyed run");
+  NEED_LEAVES();
+  if (!state_run_is(c, RUN_CORRECTED)) return fail(c, HUMID_E_STATE, "the last run was not a corrected keyed run");
   const size_t take = (size_t)(c->bc_N < cap ? c->bc_N : cap);
   D2H(status, c->bc_status.p, take);
   D2H(counts, c->bc_counts.p, 5 * sizeof(ull));
@@ -639,7 +602,7 @@ int humid_grouped_plan_info(humid_ctx *c, uint32_t word_nt, uint32_t n_groups, u
 }
 
 int humid_get_adjacency(humid_ctx *c, uint32_t *nbr_off, uint32_t *nbr_idx) {
-  NEED_RUN();
+  NEED_LEAVES();
   size_t U = (size_t)c->gU;
   if (U == 0) { if (nbr_off) nbr_off[0] = 0; return HUMID_OK; }
   D2H(nbr_off, c->nbr_off.p, (U + 1) * 4);
@@ -666,13 +629,13 @@ static int export_clusters(humid_ctx *c, u32 U, u64 C, uint64_t *size, uint32_t 
 }
 
 int humid_get_clusters(humid_ctx *c, uint64_t *size, uint32_t *max_count, uint32_t *max_leaf) {
-  NEED_RUN();
+  NEED_LEAVES();
   return export_clusters(c, c->gU, c->C, size, max_count, max_leaf);
 }
 
 int humid_get_histogram(humid_ctx *c, uint32_t which, uint64_t *keys, uint64_t *values, uint64_t cap,
                         uint64_t *n_out) {
-  NEED_RUN();
+  NEED_LEAVES();
   if (which > 2 || !n_out) return fail(c, HUMID_E_INVALID, "bad histogram selector");
   *n_out = 0;
   const u32 U = c->gU;
@@ -715,13 +678,13 @@ int humid_get_histogram(humid_ctx *c, uint32_t which, uint64_t *keys, uint64_t *
 
 // Per-group statistics of the last single-GPU run, left in c->gs_* (kernels_gstats.hip.h): one exclusive scan over
 // the leaves, one lower-bound search per group boundary, one difference per group.  Runs on the first call after a
-// run; every later call finds gs_valid.  Nothing of g_word is copied to the host.
+// run; every later call finds the record's stats_current.  Nothing of g_word is copied to the host.
 static int group_stats(humid_ctx *c) {
-  if (!c->have_run || !c->gs_run) return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
-  if (c->gs_valid) return HUMID_OK;
+  if (!state_has_run(c)) return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
+  if (c->state.stats_current) return HUMID_OK;
   hipStream_t st = c->stream;
   const u32 U = c->gU;
-  const u32 G = c->kr_leaves ? c->kr_n : c->gk_leaves ? c->gk_groups : 1u;
+  const u32 G = state_run_is(c, RUN_KEYED) ? c->kr_n : state_run_is(c, RUN_GROUPED) ? c->gk_groups : 1u;
   const size_t off_bytes = ((size_t)G + 1) * 4;
   ENSURE(c->gs_loff, off_bytes);
   ENSURE(c->gs_coff, off_bytes);
@@ -735,7 +698,7 @@ static int group_stats(humid_ctx *c) {
   } else {
     ENSURE(c->gs_ps, (size_t)U * 8);
     TRY(exscan_in<u64>(c, GsPairIn{c->g_cnt, c->deg.as<u32>()}, c->gs_ps.as<u64>(), U));
-    const u32 gnt = c->gk_leaves ? c->gk_leaf_nt : 0u, wb = 2 * c->gk_word_nt;
+    const u32 gnt = state_run_is(c, RUN_GROUPED) ? c->gk_leaf_nt : 0u, wb = 2 * c->gk_word_nt;
     const u32 nb = grid_stride_blocks((u64)G + 1);
     if (c->g_wpr == 2)
       hipLaunchKernelGGL(k_gs_offsets<W2>, dim3(nb), dim3(256), 0, st, (const W2 *)c->g_word, c->pos.as<u32>(), U, (u32)c->C, wb,
@@ -750,13 +713,13 @@ static int group_stats(humid_ctx *c) {
   }
   HIPCHK(hipStreamSynchronize(st));
   c->gs_G = G;
-  c->gs_valid = true;
+  c->state.stats_current = true;
   return HUMID_OK;
 }
 
 int humid_get_group_stats(humid_ctx *c, uint64_t cap, uint64_t *n_out, uint64_t *reads, uint32_t *leaf_off,
                           uint32_t *cluster_off, uint32_t *edges) {
-  NEED_RUN();
+  NEED_LEAVES();
   TRY(group_stats(c));
   if (n_out) *n_out = c->gs_G;
   const size_t take = (size_t)(c->gs_G < cap ? c->gs_G : cap);
@@ -770,7 +733,7 @@ int humid_get_group_stats(humid_ctx *c, uint64_t cap, uint64_t *n_out, uint64_t 
 
 int humid_group_stats_device(humid_ctx *c, uint64_t *n_out, const uint64_t **d_reads, const uint32_t **d_leaf_off,
                              const uint32_t **d_cluster_off, const uint32_t **d_edges) {
-  NEED_RUN();
+  NEED_LEAVES();
   TRY(group_stats(c));
   if (n_out) *n_out = c->gs_G;
   if (d_reads) *d_reads = c->gs_reads.as<u64>();
@@ -786,7 +749,7 @@ static int select_best_args(humid_ctx *c, const void *words, const void *cid, co
                             uint64_t n_reads, uint32_t word_nt, uint32_t scope, const void *keep_out) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (scope > HUMID_BEST_CLUSTER) return fail(c, HUMID_E_INVALID, "scope must be 0 (leaf) or 1 (cluster)");
-  if (!c->have_run || c->graph_mode)
+  if (!state_has_run(c))
     return fail(c, HUMID_E_INVALID, "humid_select_best needs a completed single-GPU humid_dedup_run* in this context");
   if (n_reads != c->N || word_nt != c->word_nt)
     return fail(c, HUMID_E_INVALID, "humid_select_best: %llu reads of %u nt, the last run had %llu of %u", (ull)n_reads, word_nt,
@@ -1024,6 +987,7 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
                         uint32_t *leaf_cluster, uint64_t *cl_size, uint32_t *cl_max_count,
                         uint32_t *cl_max_leaf, uint32_t *n_clusters) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
   if (method > 1) return fail(c, HUMID_E_INVALID, "method must be 0 or 1");
   if (n_clusters) *n_clusters = 0;
   const u32 U = n_leaves;
@@ -1037,10 +1001,6 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
     if (nbr_idx[k] >= U) return fail(c, HUMID_E_INVALID, "nbr_idx[%u] = %u out of range", k, nbr_idx[k]);
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  c->have_run = false;
-  c->have_graph = false;
-  c->gs_run = false;
-  c->graph_mode = true;
   c->cg_valid = false;
   ENSURE(c->s_cnt, (size_t)U * 4);
   c->g_cnt = c->s_cnt.as<u32>();
@@ -1098,7 +1058,8 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
   D2H(leaf_cluster, c->cid.p, (size_t)U * 4);
   HIPCHK(hipStreamSynchronize(st));
   if (n_clusters) *n_clusters = (u32)C;
-  return export_clusters(c, U, C, cl_size, cl_max_count, cl_max_leaf);
+  TRY(export_clusters(c, U, C, cl_size, cl_max_count, cl_max_leaf));
+  return state_publish(c, CtxState::HAND_GRAPH);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <type_traits>
+#include <utility>
 
 #include "common.hip.h"
 #include "prims.hip.h"
@@ -50,14 +52,24 @@ struct Arena {
   }
 };
 
+// One device buffer, grown on demand.  It owns its block: move-only, freed by the destructor -- except a block carved
+// from the slab, which is never freed one by one (the slab goes as a whole, humid_ctx_destroy).
 struct DBuf {
   void *p = nullptr;
   size_t cap = 0;
   bool in_arena = false;
+  DBuf() = default;
+  DBuf(const DBuf &) = delete;
+  DBuf &operator=(const DBuf &) = delete;
+  DBuf(DBuf &&o) noexcept { *this = std::move(o); }
+  DBuf &operator=(DBuf &&o) noexcept {                       // the source ends empty; what the target owned is freed
+    if (this != &o) { release(); p = o.p; cap = o.cap; in_arena = o.in_arena; o.p = nullptr; o.cap = 0; o.in_arena = false; }
+    return *this;
+  }
+  ~DBuf() { release(); }
   hipError_t ensure(size_t bytes, Arena *arena = nullptr) {
     if (bytes <= cap) return hipSuccess;
-    if (p && !in_arena) (void)hipFree(p);
-    p = nullptr; cap = 0; in_arena = false;
+    release();
     size_t want = bytes + bytes / 8 + 256;
     if (arena) {
       if (void *q = arena->take(bytes + 256)) { p = q; cap = bytes + 256; in_arena = true; return hipSuccess; }
@@ -70,9 +82,40 @@ struct DBuf {
   void release() { if (p && !in_arena) (void)hipFree(p); p = nullptr; cap = 0; in_arena = false; }
   template <class T> T *as() const { return (T *)p; }
 };
+static_assert(!std::is_copy_constructible<DBuf>::value && !std::is_copy_assignable<DBuf>::value, "DBuf is move-only");
+static_assert(std::is_nothrow_move_constructible<DBuf>::value && std::is_nothrow_move_assignable<DBuf>::value, "DBuf is move-only");
+
+// ---- what a context holds: ONE record of what the last mutating call left behind ----------------------------------
+// Every mutating entry point starts with state_reset and ends, on success only, with state_publish; a stage graph,
+// which builds on the count before it, starts with state_begin_graph instead.  Accessors ask the predicates below.
+//
+//   holds        leaf accessors (a)   run accessors (b)   kind accessors (c)
+//   NOTHING      E_STATE              E_STATE             E_STATE            (no call yet, or the last one failed)
+//   COUNT        E_STATE              E_STATE             E_STATE            (humid_stage_count*, the exchange pass)
+//   STAGE_GRAPH  answer               E_STATE             E_STATE            (humid_stage_graph*: leaves, no reads)
+//   HAND_GRAPH   E_STATE              E_STATE             E_STATE            (humid_cluster_graph returns all it has: recorded, read by nobody)
+//   RUN          answer               answer              answer from its kind on, E_STATE below it
+//
+//   (a) humid_get_leaves without first_read, humid_get_adjacency, humid_get_clusters, humid_get_histogram
+//   (b) first_read of humid_get_leaves, humid_get_packed_words, humid_get_group_stats / humid_group_stats_device,
+//       humid_select_best* (which refuses with HUMID_E_INVALID)
+//   (c) humid_get_leaf_groups: RUN_GROUPED; humid_get_group_keys, humid_keyed_rank_info: RUN_KEYED;
+//       humid_get_barcode_status: RUN_CORRECTED.  The data of a kind (gk_word_nt, gk_leaf_nt, gk_groups; kr_n; bc_N)
+//       is valid exactly when the record says the run is of that kind.
+//   dense is orthogonal: humid_stage_map_dense and humid_stage_kernel_ms answer while it is set, whatever holds says.
+// The results of humid_consensus* are no part of this: they survive runs (cs_valid).
+enum RunKind : u8 { RUN_PLAIN, RUN_GROUPED, RUN_KEYED, RUN_CORRECTED };   // ordered: each kind is a case of the one before
+struct CtxState {
+  enum Holds : u8 { NOTHING, COUNT, STAGE_GRAPH, HAND_GRAPH, RUN } holds = NOTHING;
+  RunKind kind = RUN_PLAIN;    // of a RUN
+  bool dense = false;          // the last count ran on a compacted list of this rank's reads; a stage graph after it keeps this
+  bool stats_current = false;  // derived on demand from a RUN: gs_* hold its group statistics for gs_G groups
+};
 
 struct humid_ctx {
   int device = 0;
+  CtxState state;
+  RunKind pass_kind = RUN_PLAIN;   // the kind of the pass now running (PassKind below); RUN_PLAIN between calls
   Arena arena;               // humid_ctx_reserve
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -145,7 +188,6 @@ struct humid_ctx {
   bool stage_map_timed = false;                                                   // kev[37..38] bracket the last humid_stage_map_dense
   bool last_count_sorted = false;                                                 // last count was the wide-word sort
   u32 g_wpr = 1;                                                                  // uint64 per word of g_word
-  bool dense_mode = false;   // last count ran on a compacted list of this rank's reads
   bool slots_done = false;   // slot_out already written by k_finalize_nodes (one-GPU fusion)
   int count_mode = 0;        // 0: hash-partitioned LDS tables (default), 1: one global HBM table
   u32 force_segments = 0;    // 0: automatic pigeonhole plan; else the number of segments s
@@ -158,16 +200,12 @@ struct humid_ctx {
   // grouped runs (humid_dedup_run_grouped*): the pass runs over internal words that carry the group ("gkey")
   // in gk_nt nucleotides above the caller's word; the count sorts them into (group, word) walk order and every
   // combination of the plan starts with the whole group field (make_plan), so buckets never mix groups
-  bool gk_on = false;        // a grouped pass is running (reset on every exit: stage entry points never see it)
-  u32 gk_nt = 0;             // its group field (nucleotides); 0 unless gk_on
+  u32 gk_nt = 0;             // the group field (nucleotides) of the pass now running; 0 unless pass_kind >= RUN_GROUPED
   u32 gk_epoch = 0;          // value k_gkey_words stores into h_ctr[CTR_N + 1] when a usable read's group is out of range
-  bool gk_leaves = false;    // the leaf arrays of the last graph stage hold grouped internal words ...
-  u32 gk_word_nt = 0, gk_leaf_nt = 0;   // ... of this caller word length and group field
+  u32 gk_word_nt = 0, gk_leaf_nt = 0;   // RUN_GROUPED on: the leaf arrays hold internal words of this caller word length and group field
   DBuf gk_words, gk_group_in, gk_bad;   // internal words; host entry point staging of the groups; device flag (no mapped memory)
   // keyed runs (humid_dedup_run_keyed*): grouped runs whose groups are the ranks of 64-bit keys (kernels_keyrank.hip.h)
-  bool kr_on = false;        // a keyed pass is running (reset on every exit, like gk_on)
-  bool kr_leaves = false;    // the last run was a keyed run: kr_keys holds its kr_n sorted distinct keys
-  u32 kr_n = 0;
+  u32 kr_n = 0;              // RUN_KEYED on: kr_keys holds the run's kr_n sorted distinct keys
   u32 kr_cap_log2 = 0;       // log2 of the table size of the next ranking (0: 16); remembered from pass to pass, grown on demand
   u32 kr_force_log2 = 0;     // option "keyrank_table_log2": every ranking starts with this table size (test hook)
   u32 kr_last_log2 = 0, kr_redo = 0;    // the last ranking: its final table size and how often it was repeated
@@ -178,16 +216,12 @@ struct humid_ctx {
   u64 wl_n = 0;              // distinct barcodes (0: no whitelist)
   u32 wl_nt = 0, wl_log2 = 0;   // nucleotides of a barcode; log2 of the table's slots
   bool wl_coop = true;       // option "whitelist_coop": 0 = the lane-serial correction kernel (measurement / cross-check)
-  bool bc_on = false;        // a corrected keyed pass is running (reset on every exit, like kr_on)
-  bool bc_leaves = false;    // the last run was a corrected keyed run: bc_status / bc_counts are those of its bc_N reads
-  u64 bc_N = 0;
+  u64 bc_N = 0;              // RUN_CORRECTED: bc_status / bc_counts are those of the run's bc_N reads
   DBuf bc_key, bc_filt, bc_status, bc_counts;            // corrected run: key_out, filtered', status, u64[5]
   DBuf wc_key, wc_filt, wc_out, wc_status, wc_counts;    // humid_whitelist_correct*: staging and counts of its own
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
-  bool gs_run = false;       // the leaf arrays are those of a completed humid_dedup_run* (no stage or graph call since)
-  bool gs_valid = false;     // gs_* hold that run's statistics for gs_G groups
   u32 gs_G = 0;
   DBuf gs_reads, gs_loff, gs_coff, gs_edges, gs_ps;   // reads u64[G], leaf / cluster offsets u32[G + 1], pairs u32[G]; scan of (count | degree << 32)
   // best-scoring read per cluster (humid_select_best*, kernels_best.hip.h): memory of its own, read by no accessor
@@ -208,9 +242,6 @@ struct humid_ctx {
                              // (an event record between two kernels is a marker the second one waits behind: ~4 us of idle GPU each, 8 per pass)
   bool kev_on = false;       // option "kernel_timing": events around the single kernels beyond the count kernel's kev[0..1] (13 more records per pass: 20-45 us)
   hipEvent_t kev[44] = {};   // per-kernel timing: [0,1] insert, [2,3] cluster, [4..19] pairs fill, [20..35] pairs count
-  bool have_run = false;     // a full dedup run completed (all accessors valid)
-  bool have_graph = false;   // stage B completed (leaf/adjacency/cluster accessors valid)
-  bool graph_mode = false;   // last call was humid_cluster_graph
   const void *g_word = nullptr;  // arrays stage B ran on (u64 or W2 per word)
   const u32 *g_cnt = nullptr;
   u32 gU = 0;
@@ -337,6 +368,29 @@ static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *
 }
 
 #define TRY(...) do { int _rc = (__VA_ARGS__); if (_rc != HUMID_OK) return _rc; } while (0)
+
+// ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
+static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; }
+static inline void state_begin_graph(humid_ctx *c) { const bool dense = c->state.dense; state_reset(c); c->state.dense = dense; }
+// the last statement of a mutating entry point that succeeded (a RUN is of the kind of the pass that ran it)
+static inline int state_publish(humid_ctx *c, CtxState::Holds holds) {
+  const bool dense = holds == CtxState::STAGE_GRAPH && c->state.dense;   // (what state_begin_graph kept of the count)
+  c->state = CtxState{holds, holds == CtxState::RUN ? c->pass_kind : RUN_PLAIN, dense, false};
+  return HUMID_OK;
+}
+static inline int state_publish_count(humid_ctx *c, bool dense) { state_publish(c, CtxState::COUNT); c->state.dense = dense; return HUMID_OK; }
+static inline bool state_has_leaves(const humid_ctx *c) { return c->state.holds == CtxState::RUN || c->state.holds == CtxState::STAGE_GRAPH; }
+static inline bool state_has_run(const humid_ctx *c) { return c->state.holds == CtxState::RUN; }   // a complete single-GPU run
+static inline bool state_dense_count(const humid_ctx *c) { return c->state.dense; }   // what humid_stage_map_dense builds on
+static inline bool state_run_is(const humid_ctx *c, RunKind at_least) { return state_has_run(c) && c->state.kind >= at_least; }
+// The kind of the pass now running: set by the outermost of run_grouped_device, run_keyed_device and
+// run_keyed_corrected_device, read by gkey_check, copied into the record by run_device's state_publish.
+struct PassKind {
+  humid_ctx *c;
+  const bool outermost;
+  PassKind(humid_ctx *c_, RunKind k) : c(c_), outermost(c_->pass_kind == RUN_PLAIN) { if (outermost) c->pass_kind = k; }
+  ~PassKind() { if (outermost) { c->pass_kind = RUN_PLAIN; c->gk_nt = 0; } }
+};
 
 // Plan of the generalised pigeonhole search (see ComboPlan).  s is chosen so that combo keys are
 // long enough for buckets to be small at this U (>= ~log4(U) nucleotides) without exceeding
@@ -1339,9 +1393,6 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   c->g_wpr = (u32)(sizeof(WT) / 8);
   c->g_cnt = g_cnt;
   c->gU = U;
-  c->gk_leaves = c->gk_on;
-  c->kr_leaves = c->kr_on;
-  c->bc_leaves = c->bc_on;
   c->cg_valid = false;
   // ---------------- 3. neighbours -----------------
   // deg has U+1 entries (last stays 0) so that one exclusive scan yields nbr_off[U] = 2E
@@ -1678,9 +1729,6 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->g_wpr = (u32)(sizeof(WT) / 8);
   c->g_cnt = g_cnt;
   c->gU = U;
-  c->gk_leaves = c->gk_on;
-  c->kr_leaves = c->kr_on;
-  c->bc_leaves = c->bc_on;
   c->cg_valid = false;
   c->cg_expanded = false;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
@@ -2060,8 +2108,7 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
           HIPCHK(bigger.ensure((size_t)((raw + found) * 8 * 2)));
           if (raw) HIPCHK(hipMemcpyAsync(bigger.p, c->e_raw.p, (size_t)raw * 8, hipMemcpyDeviceToDevice, st));
           HIPCHK(hipStreamSynchronize(st));
-          c->e_raw.release();
-          c->e_raw = bigger;
+          c->e_raw = std::move(bigger);
         }
         if (n_pieces) {
           if (k32) { if (D <= 1) EDIT_CHUNKS(true, u32, 1, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
@@ -2373,9 +2420,9 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
 
 // grouped runs: did k_gkey_words see a usable read with group >= n_groups?  Read after a host wait that followed it.
 static int gkey_check(humid_ctx *c) {
-  if (!c->gk_on) return HUMID_OK;
+  if (c->pass_kind == RUN_PLAIN) return HUMID_OK;
   const u32 seen = *(volatile u32 *)&c->h_ctr[CTR_N + 1];
-  if (seen == c->gk_epoch && c->kr_on) return fail(c, HUMID_E_INVALID, "internal: a usable read's key was not ranked");
+  if (seen == c->gk_epoch && c->pass_kind >= RUN_KEYED) return fail(c, HUMID_E_INVALID, "internal: a usable read's key was not ranked");
   if (seen == c->gk_epoch) return fail(c, HUMID_E_INVALID, "a usable read has a group >= n_groups");
   return HUMID_OK;
 }
@@ -2388,6 +2435,10 @@ static int check_run_args(humid_ctx *c, u64 n_reads, u32 word_nt, u32 method, u3
   return HUMID_OK;
 }
 
+// word_nt > 32 as the word type: f is called with a null pointer to u64 (one uint64 per word) or W2 (two)
+template <class F>
+static int with_word_type(u32 word_nt, F f) { return word_nt > 32 ? f((const W2 *)nullptr) : f((const u64 *)nullptr); }
+
 // ---- the full pipeline on device buffers (one GPU) -------------------------------------------
 // WT = u64: word_nt <= 32, one uint64 per read.  WT = W2: 33 <= word_nt <= 64, two per read.
 template <class WT>
@@ -2395,14 +2446,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
                       u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
   if (!c) return HUMID_E_INVALID;
   constexpr bool WIDE = sizeof(WT) == 16;
-  c->have_run = false;
-  c->graph_mode = false;
-  c->have_graph = false;
-  c->gs_run = c->gs_valid = false;
-  c->dense_mode = false;
-  c->gk_leaves = c->gk_on;
-  c->kr_leaves = c->kr_on;
-  c->bc_leaves = c->bc_on;
+  state_reset(c);
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (WIDE != (word_nt > 32)) return fail(c, HUMID_E_INVALID, "word layout does not match word_nt");
   if (WIDE && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
@@ -2417,7 +2461,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
   c->word_nt = word_nt; c->distance = distance; c->method = method;
   c->gU = 0;
-  if (N == 0) { if (sum) *sum = s; c->have_run = c->have_graph = c->gs_run = true; return HUMID_OK; }
+  if (N == 0) { if (sum) *sum = s; return state_publish(c, CtxState::RUN); }
   // the stages' own events only with the per-kernel timing (ms_count .. ms_map are 0 without it; ms_total and the
   // count kernel's time are always measured)
   struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = false; } } lean_guard{c};
@@ -2431,8 +2475,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)N, st));
     HIPCHK(hipStreamSynchronize(st));
     if (sum) *sum = s;
-    c->have_run = c->have_graph = c->gs_run = true;
-    return HUMID_OK;
+    return state_publish(c, CtxState::RUN);
   }
   u32 n_pair_segs = 0;
   if (c->edit && distance >= 2) {
@@ -2486,10 +2529,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     }
   }
   if (sum) *sum = s;
-  c->have_run = true;
-  c->have_graph = true;
-  c->gs_run = true;
-  return HUMID_OK;
+  return state_publish(c, CtxState::RUN);
 }
 
 // ---- grouped runs (humid_dedup_run_grouped*): one pass over many groups ------------------------------------
@@ -2514,7 +2554,7 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
                               u32 word_nt, u32 n_groups, u32 distance, u32 method, u32 *d_cid, u8 *d_keep,
                               humid_summary *sum, const u64 *d_key = nullptr) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
+  state_reset(c);
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   TRY(check_grouped_args(c, word_nt, n_groups));
   if (!d_group && !d_key && n_groups > 1) return fail(c, HUMID_E_INVALID, "group is null with n_groups = %u > 1", n_groups);
@@ -2522,8 +2562,7 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
   if (sizeof(WI) == 16 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
   HIPCHK(hipSetDevice(c->device));
   const u32 gnt = gkey_nt_for(n_groups), n_int = word_nt + gnt, N = (u32)n_reads;
-  struct GkGuard { humid_ctx *c; ~GkGuard() { c->gk_on = false; c->gk_nt = 0; } } gk_guard{c};
-  c->gk_on = true;
+  PassKind pass(c, RUN_GROUPED);
   c->gk_nt = gnt;
   c->gk_word_nt = word_nt;
   c->gk_leaf_nt = gnt;
@@ -2563,9 +2602,8 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
     else if (wide) rc = run_device<W2>(c, c->gk_words.as<W2>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
     else rc = run_device<u64>(c, c->gk_words.as<u64>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
   }
-  if (rc != HUMID_OK) { c->have_run = c->have_graph = c->gk_leaves = false; return rc; }
-  c->word_nt = word_nt;
-  return HUMID_OK;
+  if (rc == HUMID_OK) c->word_nt = word_nt;
+  return rc;
 }
 
 // ---- keyed runs (humid_dedup_run_keyed*): grouped runs whose groups are the ranks of 64-bit keys ---------------
@@ -2624,18 +2662,15 @@ template <class WI>
 static int run_keyed_device(humid_ctx *c, const WI *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads, u32 word_nt,
                             u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = false;
+  state_reset(c);
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (n_reads && (!d_words || !d_key || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   HIPCHK(hipSetDevice(c->device));
-  struct KrGuard { humid_ctx *c; ~KrGuard() { c->kr_on = false; } } kr_guard{c};
-  c->kr_on = true;
+  PassKind pass(c, RUN_KEYED);
   c->kr_n = 0;
   if (n_reads) TRY(rank_keys(c, d_key, d_filt, (u32)n_reads));
-  const int rc = run_grouped_device<WI>(c, d_words, nullptr, d_filt, n_reads, word_nt, std::max(c->kr_n, 1u), distance, method,
-                                        d_cid, d_keep, sum, n_reads ? d_key : nullptr);
-  if (rc != HUMID_OK) c->kr_leaves = false;
-  return rc;
+  return run_grouped_device<WI>(c, d_words, nullptr, d_filt, n_reads, word_nt, std::max(c->kr_n, 1u), distance, method,
+                                d_cid, d_keep, sum, n_reads ? d_key : nullptr);
 }
 
 // ---- barcode whitelist (humid_whitelist_*, humid_dedup_run_keyed_corrected*; kernels_whitelist.hip.h) -----------
@@ -2661,7 +2696,7 @@ template <class WI>
 static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads,
                                       u32 word_nt, u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->have_run = c->have_graph = c->gk_leaves = c->kr_leaves = c->bc_leaves = false;
+  state_reset(c);
   if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (n_reads && (!d_words || !d_key || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
@@ -2673,13 +2708,10 @@ static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64
   ENSURE(c->bc_counts, 5 * sizeof(ull));
   TRY(wl_correct_launch(c, d_key, d_filt, N, c->bc_key.as<u64>(), c->bc_status.as<u8>(), c->bc_filt.as<u8>(),
                         c->bc_counts.as<ull>()));
-  struct BcGuard { humid_ctx *c; ~BcGuard() { c->bc_on = false; } } bc_guard{c};
-  c->bc_on = true;
+  PassKind pass(c, RUN_CORRECTED);
   c->bc_N = n_reads;
-  const int rc = run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method,
-                                      d_cid, d_keep, sum);
-  if (rc != HUMID_OK) c->bc_leaves = false;
-  return rc;
+  return run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method, d_cid,
+                              d_keep, sum);
 }
 
 #endif  // HUMID_PIPELINE_HIP_H
