@@ -13,6 +13,8 @@ static int combo_route_wide(humid_ctx *c, const W2 *d_word, const u32 *d_count, 
                             u32 combo, u32 n_ranks, const Item3 **d_items, u64 *counts);
 static int pairs_keyed_wide(humid_ctx *c, const void *d_items, u32 n, bool interleaved, u64 id_base, const u32 *d_count,
                             const ComboPlan &plan, u32 combo, u32 distance, const u64 **d_records, u64 *n_edges);
+static int stage_pairs_share(humid_ctx *c, const u64 *g_word, u32 U, u32 word_nt, u32 distance, u32 part_rank, u32 part_world,
+                             u64 *n_edges_out);
 // ---- the exchange-mode pass of one rank (include/humid_hip.h: humid_dedup_run_exchange) ----------
 namespace {
 struct XRange { u64 lo = 1, hi = 0; };                         // lo > hi: empty
@@ -534,8 +536,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
     u32 *over = (u32 *)&c->d_ctr[CTR_EOVER];
 #define PAIRS_RECORDS(WT, P0, W, V, NN, CB, IDOF, IDBASE, CNTOF)                                                              \
   do {                                                                                                                        \
-    EarlierMasksT<WT> em_;                                                                                                    \
-    for (u32 t_ = 0; t_ < MAX_COMBOS; t_++) em_.m[t_] = w_from<WT>(plan.mask[t_]);                                            \
+    const EarlierMasksT<WT> em_ = earlier_masks<WT>(plan);                                                                    \
     hipLaunchKernelGGL((k_pairs_records<P0, WT>), dim3(blocks_for(NN, PA_PPT * 256)), dim3(256), 0, st, (const WT *)(W), (const u32 *)(V), \
                        (u32)(NN), w_from<WT>(plan.mask[CB]), em_, (u32)(CB), d, c->walk_max, (const u32 *)(IDOF), (u32)(IDBASE), \
                        (const u32 *)(CNTOF), mine, big, over);                                                                \
@@ -569,11 +570,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
       if (n_got > 1 && !moves) {
         // one rank, nothing travels: the unique array itself is the item list (ids goff + position, counts lc)
         const u32 ng = (u32)u_local;
-        ENSURE(c->seg_k0, (size_t)ng * 8);
-        ENSURE(c->seg_v0, (size_t)ng * 4);
-        ENSURE(c->seg_ks, (size_t)ng * 8);
-        ENSURE(c->seg_vs, (size_t)ng * 4);
-        ENSURE(c->seg_ws, (size_t)ng * (wide ? 16 : 8));
+        TRY(wide ? ensure_seg_scratch<W2>(c, 2, ng) : ensure_seg_scratch<u64>(c, 2, ng));   // (one order)
         if (wide) {
           TRY(bucket_order<W2>(c, plan, cb, (const W2 *)lw, ng, c->seg_ws.as<W2>(), c->seg_vs.as<u32>()));
           PAIRS_RECORDS(W2, false, c->seg_ws.p, c->seg_vs.p, ng, cb, nullptr, goff, lc);
@@ -586,11 +583,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
         ENSURE(c->x_w, (size_t)ng * (wide ? 16 : 8));
         ENSURE(c->x_id, (size_t)ng * 4);
         ENSURE(c->x_cnt, (size_t)ng * 4);
-        ENSURE(c->seg_k0, (size_t)ng * 8);
-        ENSURE(c->seg_v0, (size_t)ng * 4);
-        ENSURE(c->seg_ks, (size_t)ng * 8);
-        ENSURE(c->seg_vs, (size_t)ng * 4);
-        ENSURE(c->seg_ws, (size_t)ng * (wide ? 16 : 8));
+        TRY(wide ? ensure_seg_scratch<W2>(c, 2, ng) : ensure_seg_scratch<u64>(c, 2, ng));   // (one order)
         if (wide) {
           hipLaunchKernelGGL(k_split_items_w2, dim3(blocks_for(ng)), dim3(256), 0, st, (const Item3 *)got, ng, c->x_w.as<W2>(),
                              c->x_id.as<u32>(), c->x_cnt.as<u32>());
@@ -1284,84 +1277,136 @@ int humid_stage_combo_route(humid_ctx *c, const uint64_t *d_word, const uint32_t
   return HUMID_OK;
 }
 
-// pairs among W[0, n) walked in bucket order of combination cb -> c->share_edges, as
-// (V[i] << 32 | V[j]) ordered by value; V == null: positions themselves
+// ---- the emit driver: pairs of a short list of walked orders -> c->share_edges ----------------
 extern "C++" {
 template <class WT>
-static int emit_pairs(humid_ctx *c, const WT *W, const u32 *V, u32 n, const ComboPlan &plan, u32 cb,
-                      u32 distance, u64 *E_out) {
+struct EmitOrder {
+  Walked<WT> w;
+  u32 i_lo, i_hi;       // first positions of the pairs looked for (i_hi = 0xffffffff: to the end of the order)
+  u64 base;             // where the positions of its slice start in pc / poff
+  u32 slot, cap_n;      // find_big_runs: the slot of its run list and the length the slots are sized by (0: w.n)
+};
+// Pairs (V[i] << 32 | V[j]) ordered by value (V == null: the positions themselves) of every order's slice, T positions
+// in all: counted per position, scanned, filled in position order at poff; the pairs further apart than the walk inside
+// large buckets are counted as tiles and appended behind the others.  Host waits: one for the counts, one per order
+// with large buckets (find_big_runs) and one for the tiles' count, one to seed the tiles' cursor.
+template <class WT>
+static int emit_orders(humid_ctx *c, const PairSearch<WT> &ps, const EmitOrder<WT> *ord, u32 n_ord, u64 T, u64 *E_out) {
   hipStream_t st = c->stream;
   *E_out = 0;
-  EarlierMasksT<WT> d_masks;
-  for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = w_from<WT>(plan.mask[t]);
-  const WT cmask = w_from<WT>(plan.mask[cb]);
-  ENSURE(c->pc, ((size_t)n + 1) * 4);
-  ENSURE(c->poff, ((size_t)n + 1) * 4);
-  HIPCHK(hipMemsetAsync(c->pc.as<u32>() + n, 0, 4, st));
+  ENSURE(c->pc, (size_t)(T + 1) * 4);
+  ENSURE(c->poff, (size_t)(T + 1) * 4);
+  HIPCHK(hipMemsetAsync(c->pc.as<u32>() + T, 0, 4, st));
   HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
-  // the walk of a position is bounded as on one GPU; buckets beyond it are finished as tiles below
-  const u32 walk_max = c->walk_max;
-  const dim3 grid(blocks_for(n)), blk(256);
-  if (V)
-    hipLaunchKernelGGL((k_pairs<false, PM_EMIT_COUNT, WT>), grid, blk, 0, st, W, V, n, 0u, n, cmask, d_masks,
-                       cb, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr,
-                       (u32 *)nullptr, c->pc.as<u32>(), c->poff.as<u32>(), c->share_edges.as<u64>(), (u32 *)nullptr, walk_max,
-                       &c->d_ctr[CTR_BIGMASK]);
-  else
-    hipLaunchKernelGGL((k_pairs<true, PM_EMIT_COUNT, WT>), grid, blk, 0, st, W, V, n, 0u, n, cmask, d_masks,
-                       cb, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr,
-                       (u32 *)nullptr, c->pc.as<u32>(), c->poff.as<u32>(), c->share_edges.as<u64>(), (u32 *)nullptr, walk_max,
-                       &c->d_ctr[CTR_BIGMASK]);
-  TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), (u64)n + 1));
+  auto sink = [&](const EmitOrder<WT> &o) {            // (share_edges as it is at the time of the launch)
+    return EmitSink{c->pc.as<u32>() + o.base, c->poff.as<u32>() + o.base, c->share_edges.as<u64>(), &c->d_ctr[CTR_SPECIAL]};
+  };
+  auto pairs = [&](int mode) {
+    for (u32 k = 0; k < n_ord; k++) {
+      const EmitOrder<WT> &o = ord[k];
+      pairs_emit<WT>(c, ps, o.w, mode, o.i_lo, std::min(o.i_hi, o.w.n) - o.i_lo, sink(o), &c->d_ctr[CTR_BIGMASK]);
+    }
+  };
+  std::vector<std::vector<BigRun>> runs(n_ord);
+  std::vector<const BigRun *> d_runs(n_ord, nullptr);
+  auto tiles = [&](int mode) {
+    for (u32 k = 0; k < n_ord; k++) tiles_emit<WT>(c, ps, ord[k].w, d_runs[k], runs[k], mode, sink(ord[k]), ord[k].i_lo, ord[k].i_hi);
+  };
+  pairs(PM_EMIT_COUNT);
+  TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), T + 1));
   HIPCHK(hipGetLastError());
-  TRY(read_counters(c, c->poff.as<u32>() + n));
-  u64 E = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-  // pairs further apart than the walk inside large buckets: counted, then appended behind the others
-  std::vector<BigRun> runs;
-  const BigRun *d_runs = nullptr;
+  TRY(read_counters(c, c->poff.as<u32>() + T));
+  const u64 E_near = c->h_ctr[CTR_N - 1] & 0xffffffffull, big_mask = c->h_ctr[CTR_BIGMASK];
   u64 E_far = 0;
-  ull tiles = 0;
-  if (c->h_ctr[CTR_BIGMASK]) {
-    TRY(find_big_runs<WT>(c, W, n, cmask, walk_max, 0, runs, &d_runs));
-    tiles = runs.back().tile0;
-  }
-  const u32 tgrid = (u32)std::min<ull>(tiles ? tiles : 1, 1u << 20);
-#define EMIT_TILES(P0, M)                                                                                              \
-  hipLaunchKernelGGL((k_pairs_tiles<P0, M, WT>), dim3(tgrid), dim3(PT2_THREADS), 0, st, W, V, d_runs, (u32)runs.size() - 1, \
-                     tiles, d_masks, cb, distance, walk_max, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,         \
-                     (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, c->share_edges.as<u64>(), &c->d_ctr[CTR_SPECIAL])
-  if (tiles) {
+  if (big_mask) {
     HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SPECIAL], 0, sizeof(ull), st));
-    if (V) EMIT_TILES(false, PM_EMIT_COUNT); else EMIT_TILES(true, PM_EMIT_COUNT);
+    for (u32 k = 0; k < n_ord; k++)
+      if (big_mask >> ord[k].w.cb & 1)
+        TRY(find_big_runs<WT>(c, ord[k].w.W, ord[k].w.n, ord[k].w.mask, ps.walk_max, ord[k].slot, runs[k], &d_runs[k], ord[k].cap_n));
+    tiles(PM_EMIT_COUNT);
     HIPCHK(hipGetLastError());
     TRY(read_counters(c));
     E_far = c->h_ctr[CTR_SPECIAL];
   }
-  if (E + E_far > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu neighbour pairs in one share", (ull)(E + E_far));
-  *E_out = E + E_far;
-  if (E + E_far == 0) return HUMID_OK;
-  ENSURE(c->share_edges, (size_t)(E + E_far) * 8);
-  if (E) {
-    if (V)
-      hipLaunchKernelGGL((k_pairs<false, PM_EMIT_FILL, WT>), grid, blk, 0, st, W, V, n, 0u, n, cmask, d_masks,
-                         cb, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr,
-                         (u32 *)nullptr, c->pc.as<u32>(), c->poff.as<u32>(), c->share_edges.as<u64>(), (u32 *)nullptr, walk_max);
-    else
-      hipLaunchKernelGGL((k_pairs<true, PM_EMIT_FILL, WT>), grid, blk, 0, st, W, V, n, 0u, n, cmask, d_masks,
-                         cb, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr,
-                         (u32 *)nullptr, c->pc.as<u32>(), c->poff.as<u32>(), c->share_edges.as<u64>(), (u32 *)nullptr, walk_max);
-  }
+  if (E_near + E_far > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu neighbour pairs in one share", (ull)(E_near + E_far));
+  *E_out = E_near + E_far;
+  if (E_near + E_far == 0) return HUMID_OK;
+  ENSURE(c->share_edges, (size_t)(E_near + E_far) * 8);
+  if (E_near) pairs(PM_EMIT_FILL);
   if (E_far) {
-    const ull at = E;                                               // the cursor of the append starts behind k_pairs' pairs
+    const ull at = E_near;                             // the tiles append behind k_pairs' pairs
     HIPCHK(hipMemcpyAsync(&c->d_ctr[CTR_SPECIAL], &at, sizeof(ull), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));                               // (`at` is a host temporary)
-    if (V) EMIT_TILES(false, PM_EMIT_FILL); else EMIT_TILES(true, PM_EMIT_FILL);
+    HIPCHK(hipStreamSynchronize(st));                  // (`at` is a host temporary)
+    tiles(PM_EMIT_FILL);
   }
-#undef EMIT_TILES
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
+// pairs among W[0, n) walked in bucket order of combination cb -> c->share_edges; V == null: pairs of positions
+template <class WT>
+static int emit_pairs(humid_ctx *c, const WT *W, const u32 *V, u32 n, const ComboPlan &plan, u32 cb, u32 distance, u64 *E_out) {
+  const EmitOrder<WT> o{Walked<WT>{W, V, n, w_from<WT>(plan.mask[cb]), cb}, 0u, 0xffffffffu, 0, 0u, 0u};
+  return emit_orders<WT>(c, pair_search<WT>(c, plan, distance), &o, 1, n, E_out);
+}
 }  // extern "C++"
+
+// ---- all-gather mode: this rank's share of the neighbour search -------------------------------
+// Every rank holds the whole ascending unique array.  Rank r of P looks for the pairs whose
+// first element lies in its slice: for the prefix combo the r-th P-th of the positions, for a
+// sorted combo the words whose combo key falls into the r-th P-th of the key space (a bucket is
+// never split).  The union over ranks is every pair exactly once; pairs come out as
+// (smaller rank << 32 | larger rank), unordered.
+static int stage_pairs_share(humid_ctx *c, const u64 *g_word, u32 U, u32 word_nt, u32 distance,
+                             u32 part_rank, u32 part_world, u64 *n_edges_out) {
+  hipStream_t st = c->stream;
+  *n_edges_out = 0;
+  if (distance == 0 || U < 2) return HUMID_OK;
+  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments);
+  const u32 nseg = plan.ncombo;
+  const u32 kb = plan.key_bits ? plan.key_bits : 1;
+  TRY(ensure_seg_scratch<u64>(c, nseg, U));
+  // what is walked per combination: the whole array, first positions in this rank's equal slice of the positions
+  // (prefix combination), or this rank's selected words (the others); the run lists are sized by U, one slot each
+  std::vector<EmitOrder<u64>> ord;
+  u64 T = 0;
+  const u32 p_lo = (u32)((u64)U * part_rank / part_world), p_hi = (u32)((u64)U * (part_rank + 1) / part_world);
+  if (p_hi > p_lo) {
+    ord.push_back(EmitOrder<u64>{walked_seg<u64>(c, plan, 0, g_word, U), p_lo, p_hi, T, 0u, U});
+    T += p_hi - p_lo;
+  }
+  // key range of this rank: [floor(r 2^kb / P), floor((r+1) 2^kb / P) - 1]
+  const unsigned __int128 span = (unsigned __int128)1 << kb;
+  const u64 klo = (u64)(span * part_rank / part_world);
+  const u64 khi = (u64)(span * (part_rank + 1) / part_world - 1);
+  for (u32 seg = 1; seg < nseg; seg++) {
+    u32 *vs = seg_vs(c, seg, U);
+    HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SPECIAL], 0, sizeof(ull), st));
+    if (kb <= 32)
+      hipLaunchKernelGGL(k_select_keyrange<u32>, dim3(COMPACT_BLOCKS), dim3(256), 0, st, g_word, U, plan_fields(plan, seg),
+                         klo, khi, c->seg_k0.as<u32>(), c->seg_v0.as<u32>(), c->d_ctr);
+    else
+      hipLaunchKernelGGL(k_select_keyrange<u64>, dim3(COMPACT_BLOCKS), dim3(256), 0, st, g_word, U, plan_fields(plan, seg),
+                         klo, khi, c->seg_k0.as<u64>(), c->seg_v0.as<u32>(), c->d_ctr);
+    HIPCHK(hipGetLastError());
+    TRY(read_counters(c));
+    const u32 n_sel = (u32)c->h_ctr[CTR_SPECIAL];
+    if (n_sel > 1) {
+      if (kb <= 32) TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), c->seg_ks.as<u32>(), c->seg_v0.as<u32>(), vs, n_sel, 0, kb));
+      else TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->seg_ks.as<u64>(), c->seg_v0.as<u32>(), vs, n_sel, 0, kb));
+    } else if (n_sel == 1) {
+      HIPCHK(hipMemcpyAsync(vs, c->seg_v0.p, 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (n_sel == 0) continue;
+    hipLaunchKernelGGL(k_gather_bucket_words<u64>, dim3(blocks_for(n_sel)), dim3(256), 0, st, g_word, vs, n_sel, seg_ws<u64>(c, seg, U));
+    Walked<u64> w = walked_seg<u64>(c, plan, seg, g_word, U);
+    w.n = n_sel;
+    ord.push_back(EmitOrder<u64>{w, 0u, 0xffffffffu, T, seg, U});
+    T += n_sel;
+  }
+  if (T == 0) return HUMID_OK;
+  if (T + 1 >= 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "too many positions in one share");
+  return emit_orders<u64>(c, pair_search<u64>(c, plan, distance), ord.data(), (u32)ord.size(), T, n_edges_out);
+}
 
 // ---- two-word (wide) words in the exchange pass: items of 24 bytes (hi, lo, id | count << 32) ----
 // humid_stage_combo_route for W2: this rank's unique words in destination-major order
@@ -1417,11 +1462,7 @@ static int pairs_keyed_wide(humid_ctx *c, const void *d_items, u32 n, bool inter
     ENSURE(c->x_w, (size_t)n * sizeof(W2));
     ENSURE(c->x_id, (size_t)n * 4);
     ENSURE(c->x_cnt, (size_t)n * 4);
-    ENSURE(c->seg_k0, (size_t)n * 8);
-    ENSURE(c->seg_v0, (size_t)n * 4);
-    ENSURE(c->seg_ks, (size_t)n * 8);
-    ENSURE(c->seg_vs, (size_t)n * 4);
-    ENSURE(c->seg_ws, (size_t)n * sizeof(W2));
+    TRY(ensure_seg_scratch<W2>(c, 2, n));               // (one order)
     hipLaunchKernelGGL(k_split_items_w2, dim3(blocks_for(n)), dim3(256), 0, st, (const Item3 *)d_items, n, c->x_w.as<W2>(),
                        c->x_id.as<u32>(), c->x_cnt.as<u32>());
     const u32 kb = plan.key_bits ? plan.key_bits : 1;
@@ -1476,11 +1517,7 @@ int humid_stage_pairs_keyed(humid_ctx *c, const uint64_t *d_items, uint64_t n_it
     ENSURE(c->x_w, (size_t)n * 8);
     ENSURE(c->x_id, (size_t)n * 4);
     ENSURE(c->x_cnt, (size_t)n * 4);
-    ENSURE(c->seg_k0, (size_t)n * 8);
-    ENSURE(c->seg_v0, (size_t)n * 4);
-    ENSURE(c->seg_ks, (size_t)n * 8);
-    ENSURE(c->seg_vs, (size_t)n * 4);
-    ENSURE(c->seg_ws, (size_t)n * 8);
+    TRY(ensure_seg_scratch<u64>(c, 2, n));              // (one order)
     hipLaunchKernelGGL(k_split_items, dim3(blocks_for(n)), dim3(256), 0, st, (const ulonglong2 *)d_items, n,
                        c->x_w.as<u64>(), c->x_id.as<u32>(), c->x_cnt.as<u32>());
     const u32 kb = plan.key_bits ? plan.key_bits : 1;

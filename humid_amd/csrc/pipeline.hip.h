@@ -1377,6 +1377,131 @@ static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *
   return HUMID_OK;
 }
 
+// ---- the launch layer of the Hamming neighbour search ------------------------------------
+// A driver of the search (stage_graph, stage_graph_compact, emit_orders in humid_exchange.hip) says WHAT is
+// walked (Walked) and WHERE a found pair goes (CsrSink, EmitSink); k_pairs, k_pairs_tiles and k_pairs_append are
+// launched by the five functions below and nowhere else.  Each holds the one (PASS0, MODE) dispatch of its
+// kernel and the only spelling of the null pointers for the sinks a mode does not use, so a change to how a
+// bucket is walked -- a kernel argument, a bound, a bucket left out -- is made here.
+template <class WT>
+struct Walked {            // the walked order of one combination
+  const WT *W;             // the words in the order walked
+  const u32 *V;            // their walk indices; null: the positions themselves (the prefix combination, PASS0)
+  u32 n;
+  WT mask;                 // the combination's mask
+  u32 cb;                  // and its number
+};
+template <class WT>
+struct PairSearch { EarlierMasksT<WT> em; u32 distance, walk_max; };   // what the combinations of one search share
+struct CsrSink { u32 *deg, *parent; const u32 *nbr_off; u32 *cur, *nbr_idx, *had; const u32 *join_cnt; };
+struct EmitSink { u32 *pc; const u32 *poff; u64 *edges; ull *ecount; };
+
+template <class WT>
+static EarlierMasksT<WT> earlier_masks(const ComboPlan &plan) {   // masks of all combinations, for the first-combination rule
+  EarlierMasksT<WT> em;
+  for (u32 t = 0; t < MAX_COMBOS; t++) em.m[t] = w_from<WT>(plan.mask[t]);
+  return em;
+}
+template <class WT>
+static PairSearch<WT> pair_search(const humid_ctx *c, const ComboPlan &plan, u32 distance) {
+  return PairSearch<WT>{earlier_masks<WT>(plan), distance, c->walk_max};
+}
+// a driver that keeps the orders of combinations 1 .. nseg-1 over U words: order seg at seg_ws / seg_vs + (seg-1) U
+template <class WT>
+static int ensure_seg_scratch(humid_ctx *c, u32 nseg, u32 U) {
+  if (nseg < 2) return HUMID_OK;
+  ENSURE(c->seg_k0, (size_t)U * 8);
+  ENSURE(c->seg_v0, (size_t)U * 4);
+  ENSURE(c->seg_ks, (size_t)U * 8);                          // sorted keys: scratch, not kept
+  ENSURE(c->seg_vs, (size_t)(nseg - 1) * U * 4);             // walk indices in bucket order, per combination
+  ENSURE(c->seg_ws, (size_t)(nseg - 1) * U * sizeof(WT));    // words in bucket order, per combination
+  return HUMID_OK;
+}
+template <class WT>
+static WT *seg_ws(humid_ctx *c, u32 seg, u32 U) { return c->seg_ws.as<WT>() + (size_t)(seg - 1) * U; }
+static u32 *seg_vs(humid_ctx *c, u32 seg, u32 U) { return c->seg_vs.as<u32>() + (size_t)(seg - 1) * U; }
+template <class WT>
+static Walked<WT> walked_seg(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *g_word, u32 U) {
+  return Walked<WT>{seg ? seg_ws<WT>(c, seg, U) : g_word, seg ? seg_vs(c, seg, U) : nullptr, U, w_from<WT>(plan.mask[seg]), seg};
+}
+
+// f(PASS0, MODE) as integral constants, MODE = fill ? M_FILL : M_COUNT
+template <int M_COUNT, int M_FILL, class F>
+static void for_pass_mode(bool pass0, bool fill, F f) {
+  const std::integral_constant<int, M_COUNT> mc;
+  const std::integral_constant<int, M_FILL> mf;
+  if (pass0) { if (fill) f(std::true_type{}, mf); else f(std::true_type{}, mc); }
+  else { if (fill) f(std::false_type{}, mf); else f(std::false_type{}, mc); }
+}
+
+// k_pairs over the positions [i0, i0 + n_i) of an order; mode PM_COUNT (`big`: where a bucket beyond the walk sets the
+// combination's bit) or PM_FILL
+template <class WT>
+static void pairs_csr(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, int mode, u32 i0, u32 n_i, const CsrSink &k, ull *big) {
+  const bool fill = mode == PM_FILL;
+  for_pass_mode<PM_COUNT, PM_FILL>(!w.V, fill, [&](auto p0, auto m) {
+    hipLaunchKernelGGL((k_pairs<decltype(p0)::value, decltype(m)::value, WT>), dim3(blocks_for(n_i)), dim3(256), 0, c->stream, w.W, w.V,
+                       w.n, i0, n_i, w.mask, s.em, w.cb, s.distance, fill ? nullptr : k.deg, fill ? nullptr : k.parent,
+                       fill ? k.nbr_off : nullptr, fill ? k.cur : nullptr, fill ? k.nbr_idx : nullptr, (u32 *)nullptr,
+                       (const u32 *)nullptr, (u64 *)nullptr, k.had, s.walk_max, fill ? nullptr : big, fill ? nullptr : k.join_cnt);
+  });
+}
+// the same with mode PM_EMIT_COUNT or PM_EMIT_FILL
+template <class WT>
+static void pairs_emit(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, int mode, u32 i0, u32 n_i, const EmitSink &k, ull *big) {
+  const bool fill = mode == PM_EMIT_FILL;
+  for_pass_mode<PM_EMIT_COUNT, PM_EMIT_FILL>(!w.V, fill, [&](auto p0, auto m) {
+    hipLaunchKernelGGL((k_pairs<decltype(p0)::value, decltype(m)::value, WT>), dim3(blocks_for(n_i)), dim3(256), 0, c->stream, w.W, w.V,
+                       w.n, i0, n_i, w.mask, s.em, w.cb, s.distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,
+                       (u32 *)nullptr, (u32 *)nullptr, k.pc, k.poff, k.edges, (u32 *)nullptr, s.walk_max, fill ? nullptr : big,
+                       (const u32 *)nullptr);
+  });
+}
+// k_pairs_tiles over the large buckets of an order (find_big_runs: device list d_runs, host copy runs): the pairs
+// further apart than the walk.  Nothing is launched where there is no such bucket.
+template <class WT>
+static void tiles_csr(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const BigRun *d_runs, const std::vector<BigRun> &runs,
+                      int mode, const CsrSink &k) {
+  if (runs.size() < 2) return;
+  const ull tiles = runs.back().tile0;
+  for_pass_mode<PM_COUNT, PM_FILL>(!w.V, mode == PM_FILL, [&](auto p0, auto m) {
+    hipLaunchKernelGGL((k_pairs_tiles<decltype(p0)::value, decltype(m)::value, WT>), dim3((u32)std::min<ull>(tiles, 1u << 20)),
+                       dim3(PT2_THREADS), 0, c->stream, w.W, w.V, d_runs, (u32)runs.size() - 1, tiles, s.em, w.cb, s.distance, s.walk_max,
+                       k.deg, k.parent, k.nbr_off, k.cur, k.nbr_idx, k.join_cnt, (u64 *)nullptr, (ull *)nullptr, 0u, 0xffffffffu);
+  });
+}
+// the same for the emit modes; [i_lo, i_hi): only pairs whose first position lies in that range
+template <class WT>
+static void tiles_emit(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const BigRun *d_runs, const std::vector<BigRun> &runs,
+                       int mode, const EmitSink &k, u32 i_lo = 0, u32 i_hi = 0xffffffffu) {
+  if (runs.size() < 2) return;
+  const ull tiles = runs.back().tile0;
+  for_pass_mode<PM_EMIT_COUNT, PM_EMIT_FILL>(!w.V, mode == PM_EMIT_FILL, [&](auto p0, auto m) {
+    hipLaunchKernelGGL((k_pairs_tiles<decltype(p0)::value, decltype(m)::value, WT>), dim3((u32)std::min<ull>(tiles, 1u << 20)),
+                       dim3(PT2_THREADS), 0, c->stream, w.W, w.V, d_runs, (u32)runs.size() - 1, tiles, s.em, w.cb, s.distance, s.walk_max,
+                       (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,
+                       k.edges, k.ecount, i_lo, i_hi);
+  });
+}
+// k_pairs_append over a whole order; n_valid: the words a padded grouping holds (bucket_order with may_pad)
+template <class WT>
+static void pairs_append(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const EdgeRegs &er, u32 *bits, ull *big, u32 *overflow,
+                         const u32 *n_valid) {
+  const dim3 grid(blocks_for(w.n, PA_PPT * 256)), blk(256);
+  if (w.V)
+    hipLaunchKernelGGL((k_pairs_append<false, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, w.mask, s.em, w.cb, s.distance, s.walk_max, er, bits,
+                       big, overflow, n_valid);
+  else
+    hipLaunchKernelGGL((k_pairs_append<true, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, w.mask, s.em, w.cb, s.distance, s.walk_max, er, bits,
+                       big, overflow, n_valid);
+}
+// component sizes and what is read from them (M, Mbig, 2E, the roots of the small components) for deg / parent over U nodes
+static void comp_stats(humid_ctx *c, u32 U) {
+  hipLaunchKernelGGL(k_comp_stats, dim3(blocks_for(U)), dim3(256), 0, c->stream, c->deg.as<u32>(), c->parent.as<u32>(), U, c->csize.as<u32>());
+  hipLaunchKernelGGL(k_comp_count, dim3(512), dim3(256), 0, c->stream, c->deg.as<u32>(), c->parent.as<u32>(), c->csize.as<u32>(), U, c->d_ctr,
+                     c->small_roots.as<u32>());
+}
+
 // ---- stage B: neighbours + clusters over a sorted unique array ---------------------------
 // g_word[U] ascending, g_cnt[U] (device; the context's own arrays on one GPU, the gathered
 // arrays of all ranks on several).  Leaves deg/nbr_off/nbr_idx/cl_of/maxleaf/cl_size/flag/
@@ -1408,14 +1533,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   u64 E = 0, M = 0, Mbig = 0;
   u32 n_pair_segs = 0;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
-  EarlierMasksT<WT> d_masks;                         // masks of all combos, for the first-combo rule
-  for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = w_from<WT>(plan.mask[t]);
-  auto fields_of = [&](u32 cb) {
-    ComboFields cf;
-    cf.nf = plan.nfield[cb];
-    for (u32 f = 0; f < MAX_FIELDS; f++) { cf.shift[f] = plan.shift[cb][f]; cf.width[f] = plan.width[cb][f]; }
-    return cf;
-  };
+  const PairSearch<WT> ps = pair_search<WT>(c, plan, distance);
   const bool given = ext_edges != nullptr;
   const bool search = !given && distance > 0 && U > 1;
   // directional method: only neighbour pairs a climb or a flood can cross join two components
@@ -1432,83 +1550,38 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     hipLaunchKernelGGL(k_edges_apply<false>, dim3(grid_stride_blocks(n_ext_edges)), dim3(256), 0, st, ext_edges,
                        n_ext_edges, U, c->deg.as<u32>(), c->parent.as<u32>(), (const u32 *)nullptr,
                        (u32 *)nullptr, (u32 *)nullptr, c->d_ctr, join_cnt);
-    hipLaunchKernelGGL(k_comp_stats, dim3(blocks_for(U)), dim3(256), 0, st, c->deg.as<u32>(),
-                       c->parent.as<u32>(), U, c->csize.as<u32>());
-    hipLaunchKernelGGL(k_comp_count, dim3(512), dim3(256), 0, st, c->deg.as<u32>(), c->parent.as<u32>(),
-                       c->csize.as<u32>(), U, c->d_ctr, c->small_roots.as<u32>());
+    comp_stats(c, U);
   }
   // buckets beyond k_pairs' bounded walk (c->walk_max words; 0 = walk to the end of the bucket)
-  const u32 walk_max = c->walk_max;
   u64 big_mask = 0;
   std::vector<BigRun> h_runs[MAX_COMBOS];
-  auto walked = [&](u32 seg, const WT *&W, const u32 *&V) {
-    W = seg ? c->seg_ws.as<WT>() + (size_t)(seg - 1) * U : g_word;
-    V = seg ? c->seg_vs.as<u32>() + (size_t)(seg - 1) * U : nullptr;
+  const BigRun *d_runs[MAX_COMBOS] = {nullptr};
+  // where the pairs of combination seg go (the arrays as they are at the time of the launch)
+  auto sink = [&](u32 seg) {
+    return CsrSink{c->deg.as<u32>(), c->parent.as<u32>(), c->nbr_off.as<u32>(), c->cur.as<u32>(), c->nbr_idx.as<u32>(),
+                   c->had.as<u32>() + (size_t)seg * U, join_cnt};
   };
-  auto big_find = [&](u32 seg) -> int {
-    const WT *W; const u32 *V;
-    walked(seg, W, V);
-    const BigRun *d_runs = nullptr;
-    return find_big_runs<WT>(c, W, U, w_from<WT>(plan.mask[seg]), walk_max, seg, h_runs[seg], &d_runs);
-  };
-  auto big_tiles = [&](u32 seg, int mode) -> int {
-    const std::vector<BigRun> &r = h_runs[seg];
-    if (r.size() < 2) return HUMID_OK;
-    const WT *W; const u32 *V;
-    walked(seg, W, V);
-    const u32 cap = U / (walk_max + 2) + 1;
-    const ull tiles = r.back().tile0;
-    const u32 grid = (u32)std::min<ull>(tiles, 1u << 20);
-#define BIG_TILES(P0, M)                                                                                          \
-  hipLaunchKernelGGL((k_pairs_tiles<P0, M, WT>), dim3(grid), dim3(PT2_THREADS), 0, st, W, V,                       \
-                     c->big_runs.as<BigRun>() + (size_t)seg * cap, (u32)r.size() - 1, tiles, d_masks, seg, distance, \
-                     walk_max, c->deg.as<u32>(), c->parent.as<u32>(), c->nbr_off.as<u32>(), c->cur.as<u32>(),      \
-                     c->nbr_idx.as<u32>(), join_cnt)
-    if (seg == 0 && mode == PM_COUNT) BIG_TILES(true, PM_COUNT);
-    else if (seg == 0) BIG_TILES(true, PM_FILL);
-    else if (mode == PM_COUNT) BIG_TILES(false, PM_COUNT);
-    else BIG_TILES(false, PM_FILL);
-#undef BIG_TILES
+  // one pass over the combinations: PM_COUNT makes the bucket orders and leaves degrees and the component forest,
+  // PM_FILL walks the same orders again and writes the CSR rows, the tiles of the large buckets behind each
+  auto search_pass = [&](int mode) -> int {
+    const u32 ev0 = mode == PM_COUNT ? 20 : 4;
+    for (u32 seg = 0; seg < plan.ncombo; seg++) {
+      if (seg && mode == PM_COUNT) TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U)));
+      const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
+      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[ev0 + 2 * seg], st));
+      pairs_csr<WT>(c, ps, w, mode, 0u, U, sink(seg), &c->d_ctr[CTR_BIGMASK]);
+      if (mode == PM_FILL && (big_mask >> seg & 1)) tiles_csr<WT>(c, ps, w, d_runs[seg], h_runs[seg], PM_FILL, sink(seg));
+      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[ev0 + 1 + 2 * seg], st));
+    }
     HIPCHK(hipGetLastError());
     return HUMID_OK;
   };
   if (search) {
-    const u32 nseg = plan.ncombo;
-    n_pair_segs = nseg < 8 ? nseg : 8;
-    ENSURE(c->had, (size_t)nseg * U * 4);                   // per combination and position: pairs found, distance to the first
-    if (nseg > 1) {
-      ENSURE(c->seg_k0, (size_t)U * 8);
-      ENSURE(c->seg_v0, (size_t)U * 4);
-      ENSURE(c->seg_ks, (size_t)U * 8);                     // sorted keys: scratch, not kept
-      ENSURE(c->seg_vs, (size_t)(nseg - 1) * U * 4);        // ranks in bucket order, per combo
-      ENSURE(c->seg_ws, (size_t)(nseg - 1) * U * sizeof(WT));   // words in bucket order, per combo
-    }
-    // phase A: bucket order per combo; degrees and component forest
-    for (u32 seg = 0; seg < nseg; seg++) {
-      if (seg == 0) {
-        if (c->kev_on) HIPCHK(hipEventRecord(c->kev[20], st));
-        hipLaunchKernelGGL((k_pairs<true, PM_COUNT, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word,
-                           (const u32 *)nullptr, U, 0u, U, w_from<WT>(plan.mask[seg]), d_masks, seg, distance, c->deg.as<u32>(),
-                           c->parent.as<u32>(), (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr,
-                           (u32 *)nullptr, (const u32 *)nullptr, (u64 *)nullptr, c->had.as<u32>(), walk_max,
-                           &c->d_ctr[CTR_BIGMASK], join_cnt);
-      } else {
-        u32 *vs = c->seg_vs.as<u32>() + (size_t)(seg - 1) * U;
-        WT *ws = c->seg_ws.as<WT>() + (size_t)(seg - 1) * U;
-        TRY(bucket_order<WT>(c, plan, seg, g_word, U, ws, vs));
-        if (seg < 8) if (c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
-        hipLaunchKernelGGL((k_pairs<false, PM_COUNT, WT>), dim3(blocks_for(U)), dim3(256), 0, st, ws,
-                           vs, U, 0u, U, w_from<WT>(plan.mask[seg]), d_masks, seg, distance, c->deg.as<u32>(), c->parent.as<u32>(),
-                           (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr,
-                           (const u32 *)nullptr, (u64 *)nullptr, c->had.as<u32>() + (size_t)seg * U, walk_max,
-                           &c->d_ctr[CTR_BIGMASK], join_cnt);
-      }
-      if (seg < 8) if (c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
-    }
-    hipLaunchKernelGGL(k_comp_stats, dim3(blocks_for(U)), dim3(256), 0, st, c->deg.as<u32>(),
-                       c->parent.as<u32>(), U, c->csize.as<u32>());
-    hipLaunchKernelGGL(k_comp_count, dim3(512), dim3(256), 0, st, c->deg.as<u32>(), c->parent.as<u32>(),
-                       c->csize.as<u32>(), U, c->d_ctr, c->small_roots.as<u32>());
+    n_pair_segs = plan.ncombo < 8 ? plan.ncombo : 8;
+    ENSURE(c->had, (size_t)plan.ncombo * U * 4);            // per combination and position: pairs found, distance to the first
+    TRY(ensure_seg_scratch<WT>(c, plan.ncombo, U));
+    TRY(search_pass(PM_COUNT));
+    comp_stats(c, U);
   }
   TRY(exscan_u32(c, c->deg.as<u32>(), c->nbr_off.as<u32>(), (u64)U + 1));
   if (search || (given && n_ext_edges)) {
@@ -1524,16 +1597,15 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
       // tiles, and take the component statistics and the offsets again
       for (u32 seg = 0; seg < plan.ncombo; seg++)
         if (big_mask >> seg & 1) {
-          TRY(big_find(seg));
-          TRY(big_tiles(seg, PM_COUNT));
+          const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
+          TRY(find_big_runs<WT>(c, w.W, U, w.mask, ps.walk_max, seg, h_runs[seg], &d_runs[seg]));
+          tiles_csr<WT>(c, ps, w, d_runs[seg], h_runs[seg], PM_COUNT, sink(seg));
+          HIPCHK(hipGetLastError());
         }
       HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_EDGES], 0, 3 * sizeof(ull), st));
       HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SMALLROOTS], 0, sizeof(ull), st));
       HIPCHK(hipMemsetAsync(c->csize.p, 0, (size_t)U * 4, st));
-      hipLaunchKernelGGL(k_comp_stats, dim3(blocks_for(U)), dim3(256), 0, st, c->deg.as<u32>(),
-                         c->parent.as<u32>(), U, c->csize.as<u32>());
-      hipLaunchKernelGGL(k_comp_count, dim3(512), dim3(256), 0, st, c->deg.as<u32>(), c->parent.as<u32>(),
-                         c->csize.as<u32>(), U, c->d_ctr, c->small_roots.as<u32>());
+      comp_stats(c, U);
       TRY(exscan_u32(c, c->deg.as<u32>(), c->nbr_off.as<u32>(), (u64)U + 1));
       HIPCHK(hipGetLastError());
       TRY(read_counters(c, c->nbr_off.as<u32>() + U));
@@ -1553,27 +1625,8 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
       hipLaunchKernelGGL(k_edges_apply<true>, dim3(grid_stride_blocks(n_ext_edges)), dim3(256), 0, st, ext_edges,
                          n_ext_edges, U, (u32 *)nullptr, (u32 *)nullptr, c->nbr_off.as<u32>(),
                          c->cur.as<u32>(), c->nbr_idx.as<u32>(), c->d_ctr);
-    // phase B: same loops, now writing the CSR rows
-    for (u32 seg = 0; !given && seg < plan.ncombo; seg++) {
-      if (seg < 8) if (c->kev_on) HIPCHK(hipEventRecord(c->kev[4 + 2 * seg], st));
-      if (seg == 0) {
-        hipLaunchKernelGGL((k_pairs<true, PM_FILL, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word,
-                           (const u32 *)nullptr, U, 0u, U, w_from<WT>(plan.mask[seg]), d_masks, seg, distance, (u32 *)nullptr,
-                           (u32 *)nullptr, c->nbr_off.as<u32>(), c->cur.as<u32>(), c->nbr_idx.as<u32>(),
-                           (u32 *)nullptr, (const u32 *)nullptr, (u64 *)nullptr, c->had.as<u32>(), walk_max);
-        if (big_mask & 1) TRY(big_tiles(0, PM_FILL));
-      } else {
-        const u32 *vs = c->seg_vs.as<u32>() + (size_t)(seg - 1) * U;
-        const WT *ws = c->seg_ws.as<WT>() + (size_t)(seg - 1) * U;
-        hipLaunchKernelGGL((k_pairs<false, PM_FILL, WT>), dim3(blocks_for(U)), dim3(256), 0, st, ws,
-                           vs, U, 0u, U, w_from<WT>(plan.mask[seg]), d_masks, seg, distance, (u32 *)nullptr, (u32 *)nullptr,
-                           c->nbr_off.as<u32>(), c->cur.as<u32>(), c->nbr_idx.as<u32>(),
-                           (u32 *)nullptr, (const u32 *)nullptr, (u64 *)nullptr, c->had.as<u32>() + (size_t)seg * U,
-                           walk_max);
-        if (big_mask >> seg & 1) TRY(big_tiles(seg, PM_FILL));
-      }
-      if (seg < 8) if (c->kev_on) HIPCHK(hipEventRecord(c->kev[5 + 2 * seg], st));
-    }
+    else
+      TRY(search_pass(PM_FILL));
     hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(U)), dim3(256), 0, st, c->nbr_off.as<u32>(), U,
                        c->nbr_idx.as<u32>());
   }
@@ -1732,15 +1785,13 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->cg_valid = false;
   c->cg_expanded = false;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
-  EarlierMasksT<WT> d_masks;
-  for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = w_from<WT>(plan.mask[t]);
+  const PairSearch<WT> ps = pair_search<WT>(c, plan, distance);
   const bool given = ext_edges != nullptr;
   const bool search = !given && distance > 0 && U > 1;
   if (search && plan.ncombo == 1 && plan.key_bits == 0 && U > (1u << 18))
     return fail(c, HUMID_E_OVERFLOW, "distance %u over %u-nt words compares all pairs of %u unique words: too many neighbour pairs",
                 distance, word_nt, U);
   if (given && n_ext_edges > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
-  const u32 walk_max = c->walk_max;
   const u32 nseg = search ? plan.ncombo : 0;
   const u32 n_words = (((U + 31) / 32) + 7) & ~7u, n_blk = n_words / 8;
   c->cg_nblocks = n_blk;
@@ -1751,13 +1802,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   ENSURE(c->cg_cur, (size_t)(ER_REGIONS * ER_STRIDE + 8) * 4);
   ENSURE(c->small_roots, ((size_t)U / 3 + 2) * 4);
   ENSURE(c->small, 64);
-  if (nseg > 1) {
-    ENSURE(c->seg_k0, (size_t)U * 8);
-    ENSURE(c->seg_v0, (size_t)U * 4);
-    ENSURE(c->seg_ks, (size_t)U * 8);
-    ENSURE(c->seg_vs, (size_t)(nseg - 1) * U * 4);
-    ENSURE(c->seg_ws, (size_t)(nseg - 1) * U * sizeof(WT));
-  }
+  TRY(ensure_seg_scratch<WT>(c, nseg, U));
   u32 *bad = c->cg_cur.as<u32>() + ER_REGIONS * ER_STRIDE;       // malformed given pair
   const u64 *far = given ? ext_edges : nullptr;
   u64 n_far = given ? n_ext_edges : 0;
@@ -1790,27 +1835,19 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       hipLaunchKernelGGL(k_zero_many, dim3(64), dim3(256), 0, st, z);
     }
     for (u32 seg = 0; seg < nseg; seg++) {
-      if (seg == 0) {
-        if (c->kev_on) HIPCHK(hipEventRecord(c->kev[20], st));
-        hipLaunchKernelGGL((k_pairs_append<true, WT>), dim3(blocks_for(U, PA_PPT * 256)), dim3(256), 0, st, g_word, (const u32 *)nullptr, U,
-                           w_from<WT>(plan.mask[0]), d_masks, 0u, distance, walk_max, er, c->cg_bits.as<u32>(),
-                           &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
-      } else {
-        u32 *vs = c->seg_vs.as<u32>() + (size_t)(seg - 1) * U;
-        WT *ws = c->seg_ws.as<WT>() + (size_t)(seg - 1) * U;
+      if (seg) {
         // the count of words a padded grouping holds (pt_work: the next grouping overwrites it only behind this search,
         // in stream order); an order kept from an earlier attempt is complete, or that attempt would have been discarded
         seg_valid[seg] = nullptr;
         if (!ordered_seg[seg]) {
-          TRY(bucket_order<WT>(c, plan, seg, g_word, U, ws, vs, true));
+          TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true));
           seg_valid[seg] = c->gf_valid;
         }
         ordered_seg[seg] = true;
-        if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
-        hipLaunchKernelGGL((k_pairs_append<false, WT>), dim3(blocks_for(U, PA_PPT * 256)), dim3(256), 0, st, (const WT *)ws, (const u32 *)vs, U,
-                           w_from<WT>(plan.mask[seg]), d_masks, seg, distance, walk_max, er, c->cg_bits.as<u32>(),
-                           &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
       }
+      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
+      pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK],
+                       (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
       if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
     }
     if (n_far)
@@ -1846,24 +1883,16 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
         u64 at = 0;
         for (u32 seg = 0; seg < nseg; seg++) {
           if (!(big_mask >> seg & 1)) continue;
-          const WT *W = seg ? c->seg_ws.as<WT>() + (size_t)(seg - 1) * U : g_word;
-          const u32 *V = seg ? c->seg_vs.as<u32>() + (size_t)(seg - 1) * U : nullptr;
+          const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
           std::vector<BigRun> runs;
           const BigRun *d_runs = nullptr;
-          TRY(find_big_runs<WT>(c, W, U, w_from<WT>(plan.mask[seg]), walk_max, seg, runs, &d_runs));
-          const ull tiles = runs.back().tile0;
-          if (!tiles) continue;
-          const u32 tgrid = (u32)std::min<ull>(tiles, 1u << 20);
+          TRY(find_big_runs<WT>(c, w.W, U, w.mask, ps.walk_max, seg, runs, &d_runs));
+          if (!runs.back().tile0) continue;
           const ull start = phase ? at : 0;
           HIPCHK(hipMemcpyAsync(&c->d_ctr[CTR_SPECIAL], &start, sizeof(ull), hipMemcpyHostToDevice, st));
           HIPCHK(hipStreamSynchronize(st));
-#define CG_TILES(P0, MD)                                                                                              \
-  hipLaunchKernelGGL((k_pairs_tiles<P0, MD, WT>), dim3(tgrid), dim3(PT2_THREADS), 0, st, W, V, d_runs, (u32)runs.size() - 1, \
-                     tiles, d_masks, seg, distance, walk_max, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,       \
-                     (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, c->cg_far.as<u64>(), &c->d_ctr[CTR_SPECIAL])
-          if (phase == 0) { if (V) CG_TILES(false, PM_EMIT_COUNT); else CG_TILES(true, PM_EMIT_COUNT); }
-          else { if (V) CG_TILES(false, PM_EMIT_FILL); else CG_TILES(true, PM_EMIT_FILL); }
-#undef CG_TILES
+          tiles_emit<WT>(c, ps, w, d_runs, runs, phase ? PM_EMIT_FILL : PM_EMIT_COUNT,
+                         EmitSink{nullptr, nullptr, c->cg_far.as<u64>(), &c->d_ctr[CTR_SPECIAL]});
           HIPCHK(hipGetLastError());
           TRY(read_counters(c));
           if (phase == 0) got += c->h_ctr[CTR_SPECIAL]; else at = c->h_ctr[CTR_SPECIAL];
@@ -2160,165 +2189,6 @@ static int unique_edges(humid_ctx *c, const u64 *d_edges, u64 raw, u32 U, u64 *n
                      c->e_head.as<u32>(), c->e_hpos.as<u32>(), R, c->e_edges.as<u64>());
   HIPCHK(hipGetLastError());
   *n_edges_out = E;
-  return HUMID_OK;
-}
-
-// ---- multi-GPU: this rank's share of the neighbour search ----------------------------------
-// Every rank holds the whole ascending unique array.  Rank r of P looks for the pairs whose
-// first element lies in its slice: for the prefix combo the r-th P-th of the positions, for a
-// sorted combo the words whose combo key falls into the r-th P-th of the key space (a bucket is
-// never split).  The union over ranks is every pair exactly once; pairs come out as
-// (smaller rank << 32 | larger rank), unordered.
-static int stage_pairs_share(humid_ctx *c, const u64 *g_word, u32 U, u32 word_nt, u32 distance,
-                             u32 part_rank, u32 part_world, u64 *n_edges_out) {
-  hipStream_t st = c->stream;
-  *n_edges_out = 0;
-  if (distance == 0 || U < 2) return HUMID_OK;
-  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments);
-  EarlierMasksT<u64> d_masks;
-  for (u32 t = 0; t < MAX_COMBOS; t++) d_masks.m[t] = plan.mask[t].lo;
-  auto fields_of = [&](u32 cb) {
-    ComboFields cf;
-    cf.nf = plan.nfield[cb];
-    for (u32 f = 0; f < MAX_FIELDS; f++) { cf.shift[f] = plan.shift[cb][f]; cf.width[f] = plan.width[cb][f]; }
-    return cf;
-  };
-  const u32 nseg = plan.ncombo;
-  const u32 kb = plan.key_bits ? plan.key_bits : 1;
-  // share of the prefix combo: an equal slice of the positions
-  const u32 p_lo = (u32)((u64)U * part_rank / part_world), p_hi = (u32)((u64)U * (part_rank + 1) / part_world);
-  std::vector<u32> n_sel(nseg, 0);
-  n_sel[0] = p_hi - p_lo;
-  if (nseg > 1) {
-    ENSURE(c->seg_k0, (size_t)U * 8);
-    ENSURE(c->seg_v0, (size_t)U * 4);
-    ENSURE(c->seg_ks, (size_t)U * 8);
-    ENSURE(c->seg_vs, (size_t)(nseg - 1) * U * 4);
-    ENSURE(c->seg_ws, (size_t)(nseg - 1) * U * 8);
-  }
-  // key range of this rank: [floor(r 2^kb / P), floor((r+1) 2^kb / P) - 1]
-  const unsigned __int128 span = (unsigned __int128)1 << kb;
-  const u64 klo = (u64)(span * part_rank / part_world);
-  const u64 khi = (u64)(span * (part_rank + 1) / part_world - 1);
-  for (u32 seg = 1; seg < nseg; seg++) {
-    u32 *vs = c->seg_vs.as<u32>() + (size_t)(seg - 1) * U;
-    HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SPECIAL], 0, sizeof(ull), st));
-    if (kb <= 32)
-      hipLaunchKernelGGL(k_select_keyrange<u32>, dim3(COMPACT_BLOCKS), dim3(256), 0, st, g_word, U, fields_of(seg),
-                         klo, khi, c->seg_k0.as<u32>(), c->seg_v0.as<u32>(), c->d_ctr);
-    else
-      hipLaunchKernelGGL(k_select_keyrange<u64>, dim3(COMPACT_BLOCKS), dim3(256), 0, st, g_word, U, fields_of(seg),
-                         klo, khi, c->seg_k0.as<u64>(), c->seg_v0.as<u32>(), c->d_ctr);
-    HIPCHK(hipGetLastError());
-    TRY(read_counters(c));
-    n_sel[seg] = (u32)c->h_ctr[CTR_SPECIAL];
-    if (n_sel[seg] > 1) {
-      if (kb <= 32) TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), c->seg_ks.as<u32>(), c->seg_v0.as<u32>(), vs, n_sel[seg], 0, kb));
-      else TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->seg_ks.as<u64>(), c->seg_v0.as<u32>(), vs, n_sel[seg], 0, kb));
-    } else if (n_sel[seg] == 1) {
-      HIPCHK(hipMemcpyAsync(vs, c->seg_v0.p, 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (n_sel[seg])
-      hipLaunchKernelGGL(k_gather_bucket_words<u64>, dim3(blocks_for(n_sel[seg])), dim3(256), 0, st, g_word, vs,
-                         n_sel[seg], c->seg_ws.as<u64>() + (size_t)(seg - 1) * U);
-  }
-  u64 T = 0;
-  std::vector<u64> base(nseg, 0);
-  for (u32 seg = 0; seg < nseg; seg++) { base[seg] = T; T += n_sel[seg]; }
-  if (T == 0) return HUMID_OK;
-  if (T + 1 >= 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "too many positions in one share");
-  ENSURE(c->pc, (size_t)(T + 1) * 4);
-  ENSURE(c->poff, (size_t)(T + 1) * 4);
-  HIPCHK(hipMemsetAsync(c->pc.as<u32>() + T, 0, 4, st));
-  HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
-  // the walk of a position is bounded as on one GPU (round 3: a bucket of 10^5 words made a lane walk it all);
-  // what lies beyond it inside large buckets is finished by the tiles below
-  const u32 walk_max = c->walk_max;
-  u64 E_near = 0, E_far = 0;
-  std::vector<std::vector<BigRun>> runs(nseg);
-  std::vector<const BigRun *> d_runs(nseg, nullptr);
-  u64 big_mask = 0;
-  // what the tiles of combination `seg` walk: the whole array, first positions in this rank's slice (prefix
-  // combination), or this rank's selected words (the others)
-  auto tile_launch = [&](u32 seg, int mode) -> int {
-    const ull tiles = runs[seg].back().tile0;
-    if (!tiles) return HUMID_OK;
-    const u32 tgrid = (u32)std::min<ull>(tiles, 1u << 20);
-    const u32 *vs = seg ? c->seg_vs.as<u32>() + (size_t)(seg - 1) * U : nullptr;
-    const u64 *ws = seg ? c->seg_ws.as<u64>() + (size_t)(seg - 1) * U : g_word;
-    const u32 lo = seg ? 0u : p_lo, hi = seg ? 0xffffffffu : p_hi;
-#define SHARE_TILES(P0, MD)                                                                                                     \
-  hipLaunchKernelGGL((k_pairs_tiles<P0, MD, u64>), dim3(tgrid), dim3(PT2_THREADS), 0, st, ws, vs, d_runs[seg],                    \
-                     (u32)runs[seg].size() - 1, tiles, d_masks, seg, distance, walk_max, (u32 *)nullptr, (u32 *)nullptr,          \
-                     (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr, c->share_edges.as<u64>(),       \
-                     &c->d_ctr[CTR_SPECIAL], lo, hi)
-    if (seg == 0 && mode == PM_EMIT_COUNT) SHARE_TILES(true, PM_EMIT_COUNT);
-    else if (seg == 0) SHARE_TILES(true, PM_EMIT_FILL);
-    else if (mode == PM_EMIT_COUNT) SHARE_TILES(false, PM_EMIT_COUNT);
-    else SHARE_TILES(false, PM_EMIT_FILL);
-#undef SHARE_TILES
-    HIPCHK(hipGetLastError());
-    return HUMID_OK;
-  };
-  for (int phase = 0; phase < 2; phase++) {
-    for (u32 seg = 0; seg < nseg; seg++) {
-      if (n_sel[seg] == 0) continue;
-      u32 *pcs = c->pc.as<u32>() + base[seg];
-      const u32 *pos = c->poff.as<u32>() + base[seg];
-      const u32 *vs = seg ? c->seg_vs.as<u32>() + (size_t)(seg - 1) * U : nullptr;
-      const u64 *ws = seg ? c->seg_ws.as<u64>() + (size_t)(seg - 1) * U : g_word;
-      u64 *ed = c->share_edges.as<u64>();
-      const dim3 grid(blocks_for(n_sel[seg])), blk(256);
-      if (seg == 0 && phase == 0)
-        hipLaunchKernelGGL((k_pairs<true, PM_EMIT_COUNT, u64>), grid, blk, 0, st, g_word, vs, U, p_lo, n_sel[0], plan.mask[0].lo,
-                           d_masks, 0u, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,
-                           (u32 *)nullptr, (u32 *)nullptr, pcs, pos, ed, (u32 *)nullptr, walk_max, &c->d_ctr[CTR_BIGMASK]);
-      else if (seg == 0)
-        hipLaunchKernelGGL((k_pairs<true, PM_EMIT_FILL, u64>), grid, blk, 0, st, g_word, vs, U, p_lo, n_sel[0], plan.mask[0].lo,
-                           d_masks, 0u, distance, (u32 *)nullptr, (u32 *)nullptr, (const u32 *)nullptr,
-                           (u32 *)nullptr, (u32 *)nullptr, pcs, pos, ed, (u32 *)nullptr, walk_max);
-      else if (phase == 0)
-        hipLaunchKernelGGL((k_pairs<false, PM_EMIT_COUNT, u64>), grid, blk, 0, st, ws, vs, n_sel[seg], 0u, n_sel[seg],
-                           plan.mask[seg].lo, d_masks, seg, distance, (u32 *)nullptr, (u32 *)nullptr,
-                           (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, pcs, pos, ed, (u32 *)nullptr, walk_max,
-                           &c->d_ctr[CTR_BIGMASK]);
-      else
-        hipLaunchKernelGGL((k_pairs<false, PM_EMIT_FILL, u64>), grid, blk, 0, st, ws, vs, n_sel[seg], 0u, n_sel[seg],
-                           plan.mask[seg].lo, d_masks, seg, distance, (u32 *)nullptr, (u32 *)nullptr,
-                           (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, pcs, pos, ed, (u32 *)nullptr, walk_max);
-    }
-    if (phase == 0) {
-      TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), T + 1));
-      HIPCHK(hipGetLastError());
-      TRY(read_counters(c, c->poff.as<u32>() + T));
-      E_near = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-      big_mask = c->h_ctr[CTR_BIGMASK];
-      if (big_mask) {
-        HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SPECIAL], 0, sizeof(ull), st));
-        for (u32 seg = 0; seg < nseg; seg++) {
-          if (!(big_mask >> seg & 1) || n_sel[seg] == 0) continue;
-          const u64 *ws = seg ? c->seg_ws.as<u64>() + (size_t)(seg - 1) * U : g_word;
-          TRY(find_big_runs<u64>(c, ws, seg ? n_sel[seg] : U, plan.mask[seg].lo, walk_max, seg, runs[seg], &d_runs[seg], U));
-          TRY(tile_launch(seg, PM_EMIT_COUNT));
-        }
-        TRY(read_counters(c));
-        E_far = c->h_ctr[CTR_SPECIAL];
-      }
-      if (E_near + E_far > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu neighbour pairs in one share", (ull)(E_near + E_far));
-      *n_edges_out = E_near + E_far;
-      if (E_near + E_far == 0) return HUMID_OK;
-      ENSURE(c->share_edges, (size_t)(E_near + E_far) * 8);
-      if (E_near == 0) break;                          // (only far pairs: no fill launches of k_pairs)
-    }
-  }
-  if (E_far) {
-    const ull at = E_near;                             // the tiles append behind k_pairs' pairs
-    HIPCHK(hipMemcpyAsync(&c->d_ctr[CTR_SPECIAL], &at, sizeof(ull), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));                  // (`at` is a host temporary)
-    for (u32 seg = 0; seg < nseg; seg++)
-      if ((big_mask >> seg & 1) && n_sel[seg] && runs[seg].size() > 1) TRY(tile_launch(seg, PM_EMIT_FILL));
-  }
-  HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
 

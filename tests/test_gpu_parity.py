@@ -453,6 +453,63 @@ def test_tiles_take_over_beyond_the_bucket_walk(dd1, walk, cfg):
         dd1.set_option("bucket_walk", 1024)
 
 
+@pytest.mark.parametrize("walk", [1, 7])
+@pytest.mark.parametrize("cfg", [(60_000, 12, 2), (20_000, 40, 2)])
+def test_per_unique_word_graph_with_a_small_walk(dd1, walk, cfg):
+    """compact_graph 0: the search fills the CSR rows per unique word (k_pairs PM_COUNT / PM_FILL), the form the
+    multi-GPU all-gather mode builds on.  With a tiny walk the buckets of three words and more of every
+    combination are completed by the CSR modes of k_pairs_tiles, for one-word and two-word words: all arrays
+    against the oracle (the shapes of test_tiles_take_over_beyond_the_bucket_walk, there on the compact graph)."""
+    n_reads, n, d = cfg
+    dd1.set_option("compact_graph", 0)
+    dd1.set_option("bucket_walk", walk)
+    try:
+        if n <= 32:
+            words, filt = synth_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
+            check_against_oracle(dd1, words, filt, n, d, False)
+            check_against_oracle(dd1, words, filt, n, d, True)
+        else:
+            from humid_amd.synth import synth_wide_words
+            words, filt = synth_wide_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
+            check_against_oracle(dd1, words, filt, n, d, False)
+    finally:
+        dd1.set_option("bucket_walk", 1024)
+        dd1.set_option("compact_graph", 1)
+
+
+def test_stage_graph_with_a_small_walk():
+    """the same search inside humid_stage_graph (one rank owning the whole value range): histogram, count,
+    unique, graph and map with bucket_walk 7, both methods against the oracle"""
+    import torch
+    from humid_amd.sharded import HipStageOps, splitters_from_hist
+    n_reads, n, d = 60_000, 12, 2
+    words, filt = synth_words(n_reads, 12, n, p_sub=8e-3, p_n=1e-3)
+    dev = torch.device("cuda:0")
+    g_w = torch.from_numpy(words.view(np.int64)).to(dev)
+    g_f = torch.from_numpy(filt).to(dev)
+    ops = HipStageOps(0)
+    try:
+        ops.set_option("bucket_walk", 7)
+        bits = min(12, 2 * n)
+        hist = ops.histogram(g_w, g_f, n, bits).cpu().numpy()
+        (lo, hi, exp), = splitters_from_hist(hist, 1, n, bits)
+        u, usable = ops.count(g_w, g_f, n, lo, hi, max(exp, 1))
+        uw, uc = ops.unique()
+        uw, uc = uw.clone(), uc.clone()
+        for method in (0, 1):
+            ocid, okeep, osum, _ = orc.dedup_run(words, filt, n, d, method)
+            assert int(hist.sum()) == osum["usable"] == usable and u == osum["unique"]
+            cid_g, ismax_g, gs = ops.graph(uw, uc, n, d, method)
+            assert gs["clusters"] == osum["clusters"] and gs["edges"] == osum["edges"]
+            o_c = torch.empty(n_reads, dtype=torch.int32, device=dev)
+            o_k = torch.empty(n_reads, dtype=torch.uint8, device=dev)
+            ops.map(cid_g.clone(), ismax_g.clone(), o_c, o_k)
+            assert np.array_equal(o_c.cpu().numpy().view(np.uint32), ocid)
+            assert np.array_equal(o_k.cpu().numpy(), okeep)
+    finally:
+        ops.close()
+
+
 def one_prefix_words(rng, n_words, n, prefix_nt, reads_per_word=1.3):
     """n_words DISTINCT n-nt words that all start with the same prefix_nt nucleotides, each read once
     or a few times; read order shuffled"""
@@ -464,6 +521,25 @@ def one_prefix_words(rng, n_words, n, prefix_nt, reads_per_word=1.3):
     words = np.repeat(uniq, reps)
     rng.shuffle(words)
     return words
+
+
+@pytest.mark.parametrize("d", [1, 2])
+def test_multi_square_run_on_the_per_unique_word_graph(dd1, d):
+    """compact_graph 0 and a walk of 300: one bucket of 5000 words is five tiles a side, fifteen squares of the
+    triangle, the diagonal ones partly near (left to k_pairs) and filtered pair by pair -- through the CSR modes
+    of k_pairs_tiles"""
+    rng = np.random.default_rng(70 + d)
+    words = one_prefix_words(rng, 5000, 24, 12)
+    filt = np.zeros(len(words), np.uint8)
+    dd1.set_option("compact_graph", 0)
+    dd1.set_option("bucket_walk", 300)
+    try:
+        s = check_against_oracle(dd1, words, filt, 24, d, False)
+        assert s["unique"] == 5000 and s["edges"] > 0
+        check_against_oracle(dd1, words, filt, 24, d, True, deep=False)
+    finally:
+        dd1.set_option("bucket_walk", 1024)
+        dd1.set_option("compact_graph", 1)
 
 
 @pytest.mark.parametrize("d", [1, 2])
