@@ -204,6 +204,10 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->group_buckets = value != 0;
     return HUMID_OK;
   }
+  if (strcmp(key, "fused_search") == 0) {
+    c->fused_search = value != 0;
+    return HUMID_OK;
+  }
   if (strcmp(key, "padded_partition") == 0) {
     c->pt_padded = value != 0;
     return HUMID_OK;

@@ -119,99 +119,177 @@ k_zero_many(ZeroList z) {
 // ...): the first two words of all its walks are requested together, and a launch has a quarter of the workgroups --
 // with one position per thread the 10^4 workgroups of ~3 us each were bound by how fast workgroups can be started.
 #define PA_PPT 4u
+
+// The search exists ONCE, as the two device functions below: pa_walk (what one position finds in its bucket) and
+// pa_emit (where a workgroup's pairs go).  They read the walked order through an accessor word(j) -- global memory
+// (WordsGlobal), or the LDS of a kernel that already holds the words (k_group_fine with a search,
+// kernels_part.hip.h) -- and take walk indices from idx(j).  Positions are those of the accessor: an order of n words.
+template <class WT>
+struct WordsGlobal {
+  const WT *W;
+  __device__ __forceinline__ WT operator()(u32 j) const { return W[j]; }
+};
+struct IdxSelf { __device__ __forceinline__ u32 operator()(u32 j) const { return j; } };       // the prefix combination: walk index = position
+struct IdxGlobal {
+  const u32 *V;
+  __device__ __forceinline__ u32 operator()(u32 j) const { return V[j]; }
+};
+// what every combination's search is given
+template <class WT>
+struct PairRule {
+  WT mask;                       // the combination's mask
+  EarlierMasksT<WT> em;
+  u32 cb, distance, walk_max;
+};
+// a pair inside the bucket (x = the xor of its words): within the distance, and no earlier combination finds it
+template <class WT>
+__device__ __forceinline__ bool pa_pair(WT x, const PairRule<WT> &r) {
+  if (w_mismatch(x) > r.distance) return false;
+  for (u32 t = 0; t < r.cb; t++)                     // (uniform: the masks are read from the kernel's arguments as they are needed)
+    if (!w_hits(x, r.em.m[t])) return false;
+  return true;
+}
+// where the walk of position i ends: walk_max words on, or with the order
+__device__ __forceinline__ u32 pa_jend(u32 i, u32 n, u32 walk_max) { return (walk_max && n - i > walk_max + 1) ? i + walk_max + 1 : n; }
+// the walk of position i < n (wi = word(i); w1 = word(i + 1), requested beside it: most walks end at this word): how
+// many pairs (i, j > i) the position has, and how far off the first one is; a walk cut by walk_max whose next word
+// is still in the bucket sets the combination's bit in *big (k_pairs_tiles completes such a bucket)
+template <class WT, class ACC>
+__device__ __forceinline__ void pa_walk(const ACC &word, WT wi, WT w1, u32 i, u32 n, const PairRule<WT> &r, ull *big, u32 &found, u32 &first_off) {
+  const u32 jend = pa_jend(i, n, r.walk_max);
+  u32 j = i + 1;
+  for (; j < jend; j++) {
+    const WT x = w_xor(wi, j == i + 1 ? w1 : word(j));
+    if (w_hits(x, r.mask)) break;                    // left the bucket
+    if (!pa_pair(x, r)) continue;
+    if (!found) first_off = j - i;
+    found++;
+  }
+  if (big && j == jend && jend < n && !w_hits(w_xor(wi, word(jend)), r.mask)) atomicOr(big, 1ull << r.cb);
+}
+// the emit, called by ALL threads of a workgroup of NW waves: thread-local positions i0 + q * stride (q < NP) with
+// found[q] pairs, the first at first_off[q].  Room for the workgroup's pairs comes from ONE atomic on the cursor of
+// region blockIdx.x % ER_REGIONS; a region that is full keeps counting and sets *overflow.  A single pair is written
+// from first_off, several walk again.  lds: NW + 1 words.
+template <u32 NP, u32 NW, class WT, class ACC, class IDX>
+__device__ __forceinline__ void pa_emit(const ACC &word, const IDX &idx, u32 i0, u32 stride, u32 n, const u32 (&found)[NP],
+                                        const u32 (&first_off)[NP], const PairRule<WT> &r, const EdgeRegs &er, u32 *bits, u32 *overflow,
+                                        u32 *lds) {
+  u32 total_found = 0;
+#pragma unroll
+  for (u32 q = 0; q < NP; q++) total_found += found[q];
+  // exclusive position of this thread's pairs among the workgroup's
+  const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const u32 incl = wave_incl_scan(total_found);
+  if (lane == 63) lds[wv] = incl;
+  __syncthreads();
+  u32 before = 0, total = 0;
+#pragma unroll
+  for (u32 k = 0; k < NW; k++) { const u32 x = lds[k]; if (k < wv) before += x; total += x; }
+  if (total == 0) return;                            // (uniform)
+  const u32 region = blockIdx.x % ER_REGIONS;
+  if (threadIdx.x == 0) lds[NW] = atomicAdd(&er.cur[region * ER_STRIDE], total);
+  __syncthreads();
+  if (!total_found) return;
+  u32 at = lds[NW] + before + incl - total_found;
+  if (at + total_found > er.cap_r) { *overflow = 1; if (at >= er.cap_r) return; }
+  u64 *out = er.e + (size_t)region * er.cap_r;
+#pragma unroll
+  for (u32 q = 0; q < NP; q++) {
+    if (!found[q]) continue;
+    const u32 i = i0 + q * stride;
+    const u32 ri = idx(i);
+    auto emit = [&](u32 j) {
+      if (at >= er.cap_r) return;
+      const u32 rj = idx(j);
+      out[at++] = ri < rj ? (((u64)ri << 32) | rj) : (((u64)rj << 32) | ri);
+      atomicOr(&bits[rj >> 5], 1u << (rj & 31));
+    };
+    atomicOr(&bits[ri >> 5], 1u << (ri & 31));
+    if (found[q] == 1) { emit(i + first_off[q]); continue; }
+    const WT wi = word(i);
+    const u32 jend = pa_jend(i, n, r.walk_max);
+    for (u32 j = i + first_off[q]; j < jend; j++) {
+      const WT x = w_xor(wi, word(j));
+      if (w_hits(x, r.mask)) break;
+      if (pa_pair(x, r)) emit(j);
+    }
+  }
+}
+
 template <bool PASS0, class WT>
 __global__ void __launch_bounds__(256)
-k_pairs_append(const WT *__restrict__ W, const u32 *__restrict__ V, u32 n, WT mask, EarlierMasksT<WT> em, u32 cb,
-               u32 distance, u32 walk_max, EdgeRegs er, u32 *bits, ull *big, u32 *overflow,
+k_pairs_append(const WT *__restrict__ W, const u32 *__restrict__ V, u32 n, PairRule<WT> rule, EdgeRegs er, u32 *bits, ull *big, u32 *overflow,
                const u32 *__restrict__ n_valid = nullptr) {
   HUMID_GUARD_LAST_VGPR();
-  __shared__ u32 lds[8];
-  __shared__ u32 s_base;
+  __shared__ u32 lds[5];
   PH_DECL;
   PH(0);
   // n_valid: the walked order came from a padded grouping; had a coarse bin been full, words were dropped and the
   // order ends at *n_valid (what lies behind it was never written; the caller discards this search)
   if (n_valid && *n_valid < n) n = *n_valid;
   const u32 i0 = blockIdx.x * (PA_PPT * 256u) + threadIdx.x;
-  u32 found[PA_PPT], first_off[PA_PPT], jend[PA_PPT];
+  const WordsGlobal<WT> word{W};
+  u32 found[PA_PPT], first_off[PA_PPT];
   WT wi[PA_PPT], w1[PA_PPT];
 #pragma unroll
   for (u32 q = 0; q < PA_PPT; q++) {
     const u32 i = i0 + q * 256u;
-    found[q] = 0; first_off[q] = 0; jend[q] = 0;
+    found[q] = 0; first_off[q] = 0;
     if (i < n) {
       wi[q] = W[i];
       w1[q] = W[i + 1 < n ? i + 1 : i];                // requested together with W[i]: most walks end at this word
     }
   }
-  u32 total_found = 0;
 #pragma unroll
   for (u32 q = 0; q < PA_PPT; q++) {
     const u32 i = i0 + q * 256u;
-    if (i >= n) continue;
-    jend[q] = (walk_max && n - i > walk_max + 1) ? i + walk_max + 1 : n;
-    u32 j = i + 1;
-    for (; j < jend[q]; j++) {
-      const WT x = w_xor(wi[q], j == i + 1 ? w1[q] : W[j]);
-      if (w_hits(x, mask)) break;                    // left the bucket
-      if (w_mismatch(x) > distance) continue;
-      bool first = true;
-#pragma unroll
-      for (u32 t = 0; t < MAX_COMBOS; t++)
-        first = first && !(t < cb && !w_hits(x, em.m[t]));
-      if (!first) continue;
-      if (!found[q]) first_off[q] = j - i;
-      found[q]++;
-    }
-    if (big && j == jend[q] && jend[q] < n && !w_hits(w_xor(wi[q], W[jend[q]]), mask)) atomicOr(big, 1ull << cb);
-    total_found += found[q];
+    if (i < n) pa_walk(word, wi[q], w1[q], i, n, rule, big, found[q], first_off[q]);
   }
   PH(1);
-  // room for the workgroup's pairs: exclusive position of this thread's, one atomic per workgroup
-  const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  u32 incl = total_found;
-  incl = wave_incl_scan(incl);
-  if (lane == 63) lds[wv] = incl;
-  __syncthreads();
-  u32 before = 0, total = 0;
-#pragma unroll
-  for (u32 k = 0; k < 4; k++) { if (k < wv) before += lds[k]; total += lds[k]; }
-  PH(2);
-  if (total == 0) { PH(3); PH(4); PH_END(5, 4, (blockIdx.x & 15u) == 5u); return; }                              // (uniform)
-  const u32 region = blockIdx.x % ER_REGIONS;
-  if (threadIdx.x == 0) s_base = atomicAdd(&er.cur[region * ER_STRIDE], total);
-  __syncthreads();
-  PH(3);
-  if (threadIdx.x == 0) { PH(4); PH_END(5, 4, (blockIdx.x & 15u) == 5u); }   // 1 walks | 2 block scan | 3 region cursor | (4 -)
-  if (!total_found) return;
-  u32 at = s_base + before + incl - total_found;
-  if (at + total_found > er.cap_r) { *overflow = 1; if (at >= er.cap_r) return; }
-  u64 *out = er.e + (size_t)region * er.cap_r;
-#pragma unroll
-  for (u32 q = 0; q < PA_PPT; q++) {
-    if (!found[q]) continue;
-    const u32 i = i0 + q * 256u;
-    const u32 ri = PASS0 ? i : V[i];
-    auto emit = [&](u32 j) {
-      if (at >= er.cap_r) return;
-      const u32 rj = PASS0 ? j : V[j];
-      out[at++] = ri < rj ? (((u64)ri << 32) | rj) : (((u64)rj << 32) | ri);
-      atomicOr(&bits[rj >> 5], 1u << (rj & 31));
-    };
-    atomicOr(&bits[ri >> 5], 1u << (ri & 31));
-    if (found[q] == 1) { emit(i + first_off[q]); continue; }
-    for (u32 j = i + first_off[q]; j < jend[q]; j++) {
-      const WT x = w_xor(wi[q], W[j]);
-      if (w_hits(x, mask)) break;
-      if (w_mismatch(x) > distance) continue;
-      bool first = true;
-#pragma unroll
-      for (u32 t = 0; t < MAX_COMBOS; t++)
-        first = first && !(t < cb && !w_hits(x, em.m[t]));
-      if (first) emit(j);
-    }
-  }
+  if (PASS0) pa_emit<PA_PPT, 4>(word, IdxSelf{}, i0, 256u, n, found, first_off, rule, er, bits, overflow, lds);
+  else pa_emit<PA_PPT, 4>(word, IdxGlobal{V}, i0, 256u, n, found, first_off, rule, er, bits, overflow, lds);
+  PH(2); PH(3); PH(4);
+  PH_END(5, 4, (blockIdx.x & 15u) == 5u);              // 1 walks | 2 block scan, region cursor, writes | (3, 4 -)
 }
+
+// ---- the search inside a kernel that holds the walked words --------------------------------------------
+// The SEARCH argument of k_group_fine (SIZE 0, kernels_part.hip.h): the words of a combination's order were in that
+// kernel's registers a moment ago, and a launch of k_pairs_append would fetch them from memory again -- a chain of
+// round trips per workgroup (profiles/r03l_phase_clocks.txt: 8.6 of 9.8 us).  From LDS the same walk is a few
+// reads.  It calls pa_walk / pa_emit: the rule is the one above.
+struct WordsLds {
+  const u64 *sw;
+  __device__ __forceinline__ u64 operator()(u32 j) const { return sw[j]; }
+};
+// walk index of bin position j: through the inverse permutation of the grouping (hits are rare)
+struct IdxGrouped {
+  const unsigned short *inv;
+  const u32 *v_in;
+  __device__ __forceinline__ u32 operator()(u32 j) const { return v_in[inv[j]]; }
+};
+struct PairSearchDev {
+  static constexpr bool on = true;
+  PairRule<u64> rule;
+  EdgeRegs er;
+  u32 *bits;
+  ull *big;
+  u32 *overflow;
+  // k_group_fine: the n grouped words of ONE coarse bin at sw (output order; a bucket never leaves its bin, so the
+  // bin's end ends a walk as the first word of the next bin would); thread t has the positions t, t + T, ...
+  template <u32 NP, u32 T>
+  __device__ __forceinline__ void in_bin(const u64 *sw, u32 n, const unsigned short *inv, const u32 *v_in, u32 *scratch) const {
+    const WordsLds word{sw};
+    u32 found[NP], first_off[NP];
+#pragma unroll
+    for (u32 q = 0; q < NP; q++) {
+      const u32 i = threadIdx.x + q * T;
+      found[q] = 0; first_off[q] = 0;
+      if (i < n) pa_walk(word, sw[i], sw[i + 1 < n ? i + 1 : i], i, n, rule, big, found[q], first_off[q]);
+    }
+    pa_emit<NP, T / 64u>(word, IdxGrouped{inv, v_in}, threadIdx.x, T, n, found, first_off, rule, er, bits, overflow, scratch);
+  }
+};
 
 // both ends of a plain pair list marked in the bitmap (pairs that were not found by k_pairs_append: the
 // large-bucket tiles, the edit-distance joins)

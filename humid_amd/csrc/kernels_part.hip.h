@@ -312,6 +312,9 @@ k_pt_hist2(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ tprefi
 // bin, so a bin of any size is handled (slowly when one key prefix holds 10^6 words).  Replaces three
 // library radix passes with their per-pass memsets, the copy of the input they start with and the
 // gather of the words behind them: 0.18 -> 0.05 ms at 2.7 M words and 24 key bits.
+// no search rides in k_group_fine: its SEARCH argument in every launch but the fused one of the compact graph's
+// neighbour search (PairSearchDev, kernels_cgraph.hip.h)
+struct NoSearch { static constexpr bool on = false; };
 #define GF_THREADS 1024u
 #define GF_MAXBITS 15u
 #define GF_SMALL 7872u           // a coarse bin of up to this many words: 79.4 KB of LDS, two workgroups per CU (2 x 80 KB is ALL of a CU's LDS: the second workgroup did not get in)
@@ -323,14 +326,20 @@ k_pt_hist2(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ tprefi
 // counters, a bin of any size, the words placed with scattered stores.
 // SIZE 0: bins of <= GF_SMALL words, SIZE 1: <= GF_MID (the same road with room for a longer permutation),
 // SIZE 2: the rest.  Three launches, each takes its own bins and leaves the others at once.
-template <class SRC, int SIZE>
+// SEARCH (SIZE 0, the words themselves as payload): the combination's neighbour search rides in the launch.  Every
+// bucket lies inside one bin; once the inverse permutation is placed the counter area is dead, and the grouped words
+// (in registers for the stores) go into it in output order: GF_SMALL x 8 B fit its 64 KB.  After a barrier every
+// thread walks its 8 positions there (PairSearchDev::in_bin, kernels_cgraph.hip.h).
+template <class SRC, int SIZE, class SEARCH = NoSearch>
 __global__ void __launch_bounds__(GF_THREADS, SIZE == 0 ? 8 : 4)       // SIZE 0: <= 64 registers, two workgroups per CU
 k_group_fine(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in, const u32 *__restrict__ cbase, u32 d1,
-             u32 d2, u64 *__restrict__ k_out, u32 *__restrict__ v_out, u32 cap1) {
+             u32 d2, u64 *__restrict__ k_out, u32 *__restrict__ v_out, u32 cap1, SEARCH srch = SEARCH()) {
   HUMID_GUARD_LAST_VGPR();
+  static_assert(SIZE == 0 || !SEARCH::on, "the search rides in the launch of the small bins");
+  static_assert(GF_SMALL * 2u + 32u <= (1u << (GF_MAXBITS - 1)), "the grouped words and the emit's words fit the counter area");
   constexpr bool BIG = SIZE == 2;
   constexpr u32 INV_WORDS = SIZE == 0 ? GF_SMALL / 2u + 16u : (1u << (GF_MAXBITS - 1)) + 16u;       // 16-bit entries, two per word, + the wave sums
-  __shared__ u32 gf_lds[BIG ? (1u << GF_MAXBITS) + 16 : (1u << (GF_MAXBITS - 1)) + INV_WORDS];
+  __shared__ __attribute__((aligned(8))) u32 gf_lds[BIG ? (1u << GF_MAXBITS) + 16 : (1u << (GF_MAXBITS - 1)) + INV_WORDS];
   const u32 nb = 1u << d2, c = blockIdx.x;
   PH_DECL;
   PH(0);
@@ -436,6 +445,16 @@ k_group_fine(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in
       for (u32 t = 0; t < GF_RPT; t++) {
         const u32 q = threadIdx.x + t * GF_THREADS;
         if (q < n) { k_out[q] = ko[t]; v_out[q] = vo[t]; }
+      }
+      if constexpr (SEARCH::on) {
+        u64 *sw = (u64 *)gf_lds;                     // the counters are dead: all of inv[] was placed before the barrier above
+#pragma unroll
+        for (u32 t = 0; t < GF_RPT; t++) {
+          const u32 q = threadIdx.x + t * GF_THREADS;
+          if (q < n) sw[q] = ko[t];
+        }
+        __syncthreads();
+        srch.template in_bin<GF_RPT, GF_THREADS>(sw, n, inv, v_in, gf_lds + 2u * GF_SMALL);
       }
       PH(7);
       PH_END(4, 7, (c & 7u) == 3u);    // 1 bounds + loads issued + clear | 2 count | 3 barrier | 4 scan | 5 place | 6 barrier | 7 gather + store

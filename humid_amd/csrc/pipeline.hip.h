@@ -171,6 +171,7 @@ struct humid_ctx {
   const u32 *rec_cursor2 = nullptr; // reads per bucket of that count
   DBuf pt_work, unperm_rec, route_tiles;                                                     // LDS-staged partition / un-permute (kernels_part.hip.h)
   bool group_buckets = true;        // option "group_buckets": bucket order of stretch keys by two-level grouping instead of a library sort
+  bool fused_search = true;         // option "fused_search": the compact graph's neighbour search of a grouped combination rides in k_group_fine (0: a launch of k_pairs_append per combination)
   bool pt_padded = true;            // level 1 of the tile partition into padded coarse bins (no histogram pass); false after an overflow
   bool use_tile_partition = true;   // option "tile_partition": 0 = library radix passes + one-kernel un-permute (round 1)
   bool last_part_tiled = false;     // kev[39]..kev[40] bracket the second-level scatter of the last count
@@ -1261,9 +1262,21 @@ static ComboFields plan_fields(const ComboPlan &plan, u32 cb) {
   for (u32 f = 0; f < MAX_FIELDS; f++) { cf.shift[f] = plan.shift[cb][f]; cf.width[f] = plan.width[cb][f]; }
   return cf;
 }
+// A neighbour search that may ride in a grouping (stage_graph_compact): `group` is the search of the combination
+// being grouped, walked inside k_group_fine.  Taken only where every coarse bin is certain to be a small one (padded
+// bins of at most GF_SMALL words) -- did_group says whether; if not the caller launches k_pairs_append.
+// ev_group: events around the launch the search rode in (null: none).
+struct GroupRide {
+  PairSearchDev group;
+  bool did_group = false;
+  hipEvent_t ev_group[2] = {nullptr, nullptr};
+};
+// (the launch layer of the neighbour search, below)
+static void group_fine_with_search(humid_ctx *c, const FieldsSrc &src, const u64 *k0, const u32 *v0, const u32 *cbase, u32 d1, u32 d2, u64 *ws,
+                                   u32 *vs, u32 cap1, const PairSearchDev &s);
 template <class SRC, class WT>
 static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, const WT *W, u32 n, u64 *ws, u32 *vs, bool *done,
-                                  bool may_pad = false) {
+                                  bool may_pad = false, GroupRide *ride = nullptr) {
   hipStream_t st = c->stream;
   u32 bit_n = 0;
   for (u32 f = 0; f < plan.nfield[cb]; f++) bit_n += plan.width[cb][f];
@@ -1298,6 +1311,7 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)hist1, d1, 0u, cbase, tprefix, dummy, dummy + 513, 0u);
   }
   static const bool gs_small = getenv("HUMID_GS_THREADS") ? atoi(getenv("HUMID_GS_THREADS")) == 512 : false;  // (experiments: 512-thread tiles are 7 us slower -- shorter runs per bin)
+  const bool ride_ok = ride && std::is_same<SRC, FieldsSrc>::value && padded && cap1 <= GF_SMALL;   // every bin is a SIZE-0 bin
   if (gs_small)
     hipLaunchKernelGGL((k_pt_scatter<1, SRC, 512>), dim3((n + 4095) / 4096), dim3(512), 0, st, src, n, (const u64 *)nullptr,
                        (const u32 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, (const u32 *)cbase, cursor1,
@@ -1313,6 +1327,14 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
   // ones are left out
   c->gf_valid = padded ? (const u32 *)(cbase + nb1) : (const u32 *)nullptr;    // words the order holds (< n: a bin was full)
   const u32 largest = padded ? cap1 : n;
+  if (ride_ok) {
+    if constexpr (std::is_same<SRC, FieldsSrc>::value) {
+      if (ride->ev_group[0]) HIPCHK(hipEventRecord(ride->ev_group[0], st));
+      group_fine_with_search(c, src, c->seg_k0.as<u64>(), c->seg_v0.as<u32>(), cbase, d1, d2, ws, vs, cap1, ride->group);
+      if (ride->ev_group[1]) HIPCHK(hipEventRecord(ride->ev_group[1], st));
+      ride->did_group = true;
+    }
+  } else
   hipLaunchKernelGGL((k_group_fine<SRC, 0>), dim3(nb1), dim3(GF_THREADS), 0, st, src,
                      (const u64 *)c->seg_k0.as<u64>(), (const u32 *)c->seg_v0.as<u32>(), (const u32 *)cbase, d1, d2, ws, vs, cap1);
   if (largest > GF_SMALL)
@@ -1347,14 +1369,15 @@ static int sort_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, co
 // position i, vs[i] = its walk index.  Keys of <= 24 bits: two-level grouping; one stretch of the word:
 // the words themselves as sort keys; else keys + sort + gather.  Scratch: seg_k0 / seg_v0 / seg_ks.
 template <class WT>
-static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *g_word, u32 U, WT *ws, u32 *vs, bool may_pad = false) {
+static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *g_word, u32 U, WT *ws, u32 *vs, bool may_pad = false,
+                        GroupRide *ride = nullptr) {
   hipStream_t st = c->stream;
   u32 kb = 0;                                            // key bits of THIS combination
   for (u32 f = 0; f < plan.nfield[seg]; f++) kb += plan.width[seg][f];
   if (kb == 0) kb = 1;
   bool stretch = false;
   if (std::is_same<WT, u64>::value) {
-    TRY((group_words_by_stretch<FieldsSrc, u64>(c, plan, seg, (const u64 *)g_word, U, (u64 *)ws, vs, &stretch, may_pad)));
+    TRY((group_words_by_stretch<FieldsSrc, u64>(c, plan, seg, (const u64 *)g_word, U, (u64 *)ws, vs, &stretch, may_pad, ride)));
     if (!stretch) TRY(sort_words_by_stretch(c, plan, seg, (const u64 *)g_word, U, (u64 *)ws, vs, &stretch));
   } else {
     // two-word words: the keys are grouped (scratch), the words follow through the grouped positions
@@ -1379,8 +1402,8 @@ static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *
 
 // ---- the launch layer of the Hamming neighbour search ------------------------------------
 // A driver of the search (stage_graph, stage_graph_compact, emit_orders in humid_exchange.hip) says WHAT is
-// walked (Walked) and WHERE a found pair goes (CsrSink, EmitSink); k_pairs, k_pairs_tiles and k_pairs_append are
-// launched by the five functions below and nowhere else.  Each holds the one (PASS0, MODE) dispatch of its
+// walked (Walked) and WHERE a found pair goes (CsrSink, EmitSink); k_pairs, k_pairs_tiles, k_pairs_append and the
+// k_group_fine that a search rides in (GroupRide) are launched by the six functions below and nowhere else.  Each holds the one (PASS0, MODE) dispatch of its
 // kernel and the only spelling of the null pointers for the sinks a mode does not use, so a change to how a
 // bucket is walked -- a kernel argument, a bound, a bucket left out -- is made here.
 template <class WT>
@@ -1488,12 +1511,21 @@ template <class WT>
 static void pairs_append(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const EdgeRegs &er, u32 *bits, ull *big, u32 *overflow,
                          const u32 *n_valid) {
   const dim3 grid(blocks_for(w.n, PA_PPT * 256)), blk(256);
+  const PairRule<WT> rule{w.mask, s.em, w.cb, s.distance, s.walk_max};
   if (w.V)
-    hipLaunchKernelGGL((k_pairs_append<false, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, w.mask, s.em, w.cb, s.distance, s.walk_max, er, bits,
-                       big, overflow, n_valid);
+    hipLaunchKernelGGL((k_pairs_append<false, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, big, overflow, n_valid);
   else
-    hipLaunchKernelGGL((k_pairs_append<true, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, w.mask, s.em, w.cb, s.distance, s.walk_max, er, bits,
-                       big, overflow, n_valid);
+    hipLaunchKernelGGL((k_pairs_append<true, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, big, overflow, n_valid);
+}
+// the same search as an argument of the kernel that holds the combination's words while it groups them (GroupRide)
+static PairSearchDev pairs_append_dev(const PairSearch<u64> &s, u64 mask, u32 cb, const EdgeRegs &er, u32 *bits, ull *big, u32 *overflow) {
+  return PairSearchDev{PairRule<u64>{mask, s.em, cb, s.distance, s.walk_max}, er, bits, big, overflow};
+}
+// level 2 of a grouping whose coarse bins all hold at most GF_SMALL words, with the grouped combination's search in it
+static void group_fine_with_search(humid_ctx *c, const FieldsSrc &src, const u64 *k0, const u32 *v0, const u32 *cbase, u32 d1, u32 d2, u64 *ws,
+                                   u32 *vs, u32 cap1, const PairSearchDev &s) {
+  hipLaunchKernelGGL((k_group_fine<FieldsSrc, 0, PairSearchDev>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, k0, v0, cbase, d1, d2, ws,
+                     vs, cap1, s);
 }
 // component sizes and what is read from them (M, Mbig, 2E, the roots of the small components) for deg / parent over U nodes
 static void comp_stats(humid_ctx *c, u32 U) {
@@ -1834,21 +1866,39 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       z.p[3] = (u32 *)&c->d_ctr[CTR_EDGES]; z.n[3] = 2 * (CTR_GOVER - CTR_EDGES + 1);
       hipLaunchKernelGGL(k_zero_many, dim3(64), dim3(256), 0, st, z);
     }
+    // a launch of k_pairs_append over the order of combination seg, between its two events
+    auto search_alone = [&](u32 seg) -> int {
+      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
+      pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK],
+                       (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
+      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
+      return HUMID_OK;
+    };
+    // fused_search: while an order is MADE its search rides in the grouping (GroupRide; the events then bracket the
+    // launch it rode in) -- where the grouping takes it.  An order kept from an earlier attempt, and the prefix
+    // combination's (the walk order itself), are searched by k_pairs_append.
+    const bool ride_on = c->fused_search && std::is_same<WT, u64>::value;
     for (u32 seg = 0; seg < nseg; seg++) {
+      bool searched = false;
       if (seg) {
         // the count of words a padded grouping holds (pt_work: the next grouping overwrites it only behind this search,
         // in stream order); an order kept from an earlier attempt is complete, or that attempt would have been discarded
         seg_valid[seg] = nullptr;
         if (!ordered_seg[seg]) {
-          TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true));
+          GroupRide ride;
+          if constexpr (std::is_same<WT, u64>::value) {
+            if (ride_on) {
+              ride.group = pairs_append_dev(ps, w_from<u64>(plan.mask[seg]), seg, er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
+              if (seg < 8 && c->kev_on) { ride.ev_group[0] = c->kev[20 + 2 * seg]; ride.ev_group[1] = c->kev[21 + 2 * seg]; }
+            }
+          }
+          TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true, ride_on ? &ride : nullptr));
           seg_valid[seg] = c->gf_valid;
+          searched = ride.did_group;
         }
         ordered_seg[seg] = true;
       }
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
-      pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK],
-                       (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
+      if (!searched) TRY(search_alone(seg));
     }
     if (n_far)
       hipLaunchKernelGGL(k_mark_pairs, dim3(blocks_for(n_far)), dim3(256), 0, st, far, (u32)n_far, U, c->cg_bits.as<u32>(), bad);
@@ -1866,6 +1916,11 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     if (cgs.overflow) {                                  // a region was full: more room, once more
       c->cg_ecap = cgs.wanted + cgs.wanted / 2 + ER_REGIONS * 64;
+      // cg_build has relabelled the pairs of the tiles IN PLACE (k_pairs_relabel): that list cannot be used again,
+      // the tiles make it once more behind the next search.  (A search that rode in the groupings spreads its pairs
+      // over one region per coarse bin, k_pairs_append over one per 1024 positions: the search behind the tiles can
+      // fill a region where the one in front of them did not.)
+      if (!given) { far = nullptr; n_far = 0; }
       continue;
     }
     if (given) {
