@@ -620,6 +620,93 @@ uint64_t orc_find_edit_neighbours(orc_ctx *c, uint32_t distance) {
   return c->unique;
 }
 
+/* ---- all-pairs Levenshtein truth (tests of the -e search) ---------------------------------
+ * Shares nothing with the trie search above: the symbols of both words in plain arrays and the
+ * literal two-row dynamic programme over the whole (n + 1) x (n + 1) matrix -- no band, no bit
+ * vectors, no pruning. */
+static unsigned lev_two_rows(const uint8_t *a, const uint8_t *b, uint32_t n) {
+  unsigned r0[65], r1[65];
+  unsigned *prev = r0, *row = r1;
+  for (uint32_t j = 0; j <= n; j++) prev[j] = j;
+  for (uint32_t i = 1; i <= n; i++) {
+    const unsigned ai = a[i - 1];
+    unsigned left = i;                                   /* row[j - 1] */
+    row[0] = i;
+    for (uint32_t j = 1; j <= n; j++) {
+      const unsigned sub = prev[j - 1] + (ai != b[j - 1]), del = prev[j] + 1;
+      const unsigned up = sub < del ? sub : del;
+      left = left + 1 < up ? left + 1 : up;
+      row[j] = left;
+    }
+    unsigned *t = prev; prev = row; row = t;
+  }
+  return prev[n];
+}
+
+static uint8_t *unpack_symbols(const uint64_t *words, uint64_t count, uint32_t n) {
+  const uint32_t wpr = n > 32 ? 2 : 1;
+  uint8_t *s = (uint8_t *)xmalloc((size_t)(count ? count : 1) * n);
+  for (uint64_t r = 0; r < count; r++)
+    for (uint32_t i = 0; i < n; i++) s[r * n + i] = (uint8_t)sym(words + r * wpr, n, i);
+  return s;
+}
+
+void orc_lev_pairs(const uint64_t *x, const uint64_t *y, uint64_t count, uint32_t n, uint8_t *dist) {
+  if (n == 0 || n > 64) return;
+  uint8_t *sx = unpack_symbols(x, count, n), *sy = unpack_symbols(y, count, n);
+  for (uint64_t r = 0; r < count; r++) dist[r] = (uint8_t)lev_two_rows(sx + r * n, sy + r * n, n);
+  free(sx);
+  free(sy);
+}
+
+struct orc_allpairs {
+  uint64_t n_unique, n_pairs, cap;
+  uint32_t *a, *b;                    /* a < b, in (a, b) order */
+};
+
+orc_allpairs *orc_allpairs_create(const uint64_t *uwords, uint64_t n_unique, uint32_t n, uint32_t distance) {
+  if (n == 0 || n > 64) return NULL;
+  orc_allpairs *p = (orc_allpairs *)xcalloc(1, sizeof(*p));
+  p->n_unique = n_unique;
+  uint8_t *s = unpack_symbols(uwords, n_unique, n);
+  for (uint64_t i = 0; i < n_unique; i++)
+    for (uint64_t j = i + 1; j < n_unique; j++) {
+      if (lev_two_rows(s + i * n, s + j * n, n) > distance) continue;
+      if (p->n_pairs == p->cap) {
+        p->cap = p->cap ? 2 * p->cap : 1024;
+        p->a = (uint32_t *)xrealloc(p->a, p->cap * sizeof(uint32_t));
+        p->b = (uint32_t *)xrealloc(p->b, p->cap * sizeof(uint32_t));
+      }
+      p->a[p->n_pairs] = (uint32_t)i;
+      p->b[p->n_pairs++] = (uint32_t)j;
+    }
+  free(s);
+  return p;
+}
+
+uint64_t orc_allpairs_edges(const orc_allpairs *p) { return p->n_pairs; }
+
+void orc_allpairs_export(const orc_allpairs *p, uint64_t *nbr_off, uint32_t *nbr_idx) {
+  const uint64_t u = p->n_unique;
+  for (uint64_t i = 0; i <= u; i++) nbr_off[i] = 0;
+  for (uint64_t e = 0; e < p->n_pairs; e++) { nbr_off[p->a[e] + 1]++; nbr_off[p->b[e] + 1]++; }
+  for (uint64_t i = 0; i < u; i++) nbr_off[i + 1] += nbr_off[i];
+  uint64_t *cur = (uint64_t *)xmalloc((size_t)(u + 1) * sizeof(uint64_t));
+  memcpy(cur, nbr_off, (size_t)(u + 1) * sizeof(uint64_t));
+  /* pairs come in (a, b) order: row b receives its smaller neighbours a ascending in a first pass, then every
+   * row a its larger neighbours b ascending -- rows end up ascending */
+  for (uint64_t e = 0; e < p->n_pairs; e++) nbr_idx[cur[p->b[e]]++] = p->a[e];
+  for (uint64_t e = 0; e < p->n_pairs; e++) nbr_idx[cur[p->a[e]]++] = p->b[e];
+  free(cur);
+}
+
+void orc_allpairs_destroy(orc_allpairs *p) {
+  if (!p) return;
+  free(p->a);
+  free(p->b);
+  free(p);
+}
+
 typedef struct { orc_ctx *c; int maximum; size_t id; } ClArg;
 static void clusters_cb(OLeaf *l, const uint64_t *w, void *arg) {
   (void)w;

@@ -134,6 +134,20 @@ void     orc_export_adjacency(const orc_ctx *c, uint64_t *nbr_off, uint32_t *nbr
 void     orc_export_clusters(const orc_ctx *c, uint64_t *size, uint64_t *max_count,
                              uint32_t *max_leaf_rank);
 
+/* ---- all-pairs Levenshtein truth: independent of the trie search (the literal two-row dynamic
+ * programme over symbol arrays, n <= 64; no band, no bit vectors, no pruning).  uwords: the ascending
+ * unique words (one uint64 per word, two -- [hi, lo] -- beyond 32 nt).  Quadratic: a few thousand words. */
+typedef struct orc_allpairs orc_allpairs;
+orc_allpairs *orc_allpairs_create(const uint64_t *uwords, uint64_t n_unique, uint32_t word_nt,
+                                  uint32_t distance);
+uint64_t orc_allpairs_edges(const orc_allpairs *p);       /* undirected pairs */
+/* CSR as orc_export_adjacency gives it: nbr_off has n_unique+1 entries, nbr_idx 2*edges, rows ascending */
+void     orc_allpairs_export(const orc_allpairs *p, uint64_t *nbr_off, uint32_t *nbr_idx);
+void     orc_allpairs_destroy(orc_allpairs *p);
+/* dist[r] = Levenshtein distance of x[r] and y[r] (the same programme) */
+void     orc_lev_pairs(const uint64_t *x, const uint64_t *y, uint64_t count, uint32_t word_nt,
+                       uint8_t *dist);
+
 /* one-call convenience: read -> neighbours -> clusters -> map; returns 0.
  * method bit 0: maximum clustering (-x); bit 1: Levenshtein instead of Hamming neighbours (-e).
  * summary5 (may be NULL): total, usable, unique, clusters, neighbour pairs.

@@ -89,6 +89,13 @@ def lib():
         L.orc_dedup_run.argtypes = [u64p, u8p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_uint32, u32p, u8p, u64p, f64p]
         L.orc_dedup_run.restype = C.c_int
+        L.orc_allpairs_create.argtypes = [u64p, C.c_uint64, C.c_uint32, C.c_uint32]
+        L.orc_allpairs_create.restype = C.c_void_p
+        L.orc_allpairs_edges.argtypes = [C.c_void_p]
+        L.orc_allpairs_edges.restype = C.c_uint64
+        L.orc_allpairs_export.argtypes = [C.c_void_p, u64p, u32p]
+        L.orc_allpairs_destroy.argtypes = [C.c_void_p]
+        L.orc_lev_pairs.argtypes = [u64p, u64p, C.c_uint64, C.c_uint32, u8p]
         _LIB = L
     return _LIB
 
@@ -290,6 +297,36 @@ class Pipeline:
         ml = np.zeros(max(c, 1), dtype=np.uint32)
         lib().orc_export_clusters(self.h, _p(size, u64p), _p(mc, u64p), _p(ml, u32p))
         return dict(size=size[:c], max_count=mc[:c], max_leaf=ml[:c])
+
+
+def edit_adjacency_allpairs(uwords, word_nt, distance):
+    """(nbr_off u64[U + 1], nbr_idx u32[2 E]) under Levenshtein distance over the ASCENDING UNIQUE words (u64[U], or
+    u64[U, 2] beyond 32 nt) -- the format of Pipeline.adjacency(), from the literal two-row dynamic programme on every
+    pair (nothing shared with the trie search; quadratic, a few thousand words)."""
+    w = np.ascontiguousarray(uwords, dtype=np.uint64).reshape(-1, 2 if word_nt > 32 else 1)
+    u = len(w)
+    h = lib().orc_allpairs_create(_p(w, u64p), u, word_nt, distance)
+    if not h:
+        raise ValueError("word_nt must be 1..64")
+    try:
+        e = int(lib().orc_allpairs_edges(h))
+        off = np.zeros(u + 1, dtype=np.uint64)
+        idx = np.zeros(max(2 * e, 1), dtype=np.uint32)
+        lib().orc_allpairs_export(h, _p(off, u64p), _p(idx, u32p))
+    finally:
+        lib().orc_allpairs_destroy(h)
+    return off, idx[:2 * e]
+
+
+def lev_pairs(x, y, word_nt):
+    """u8[P]: Levenshtein distance of x[r] and y[r] by the same two-row programme"""
+    wpr = 2 if word_nt > 32 else 1
+    a = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wpr)
+    b = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, wpr)
+    assert a.shape == b.shape and 1 <= word_nt <= 64
+    out = np.zeros(len(a), dtype=np.uint8)
+    lib().orc_lev_pairs(_p(a, u64p), _p(b, u64p), len(a), word_nt, _p(out, u8p))
+    return out
 
 
 def dedup_run(words, filtered, word_nt, distance=1, method=0, edit=False):
