@@ -41,6 +41,14 @@ class HumidConsensusSummary(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class HumidOpticalSummary(C.Structure):
+    """humid_optical_summary of include/humid_hip.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_clusters", "members", "duplicates", "optical", "groups", "largest_group")]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
@@ -119,6 +127,10 @@ SYMBOLS = {
                                          C.POINTER(HumidConsensusSummary)]),
     "humid_get_consensus": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "humid_consensus_result_device": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "humid_optical_duplicates": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32] + [C.c_void_p] * 3 +
+                                 [C.POINTER(HumidOpticalSummary)]),
+    "humid_optical_duplicates_device": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32] +
+                                        [C.c_void_p] * 3 + [C.POINTER(HumidOpticalSummary)]),
     "humid_get_leaves": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "humid_get_adjacency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_get_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

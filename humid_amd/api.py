@@ -22,6 +22,7 @@ MAXIMUM = 1
 # which reads of a cluster Dedup.select_best chooses among (include/humid_hip.h, HUMID_BEST_*); rep of a read without a cluster
 BEST_LEAF, BEST_CLUSTER = 0, 1
 NO_READ = 0xffffffff
+NO_TILE = 0xffffffff   # tile of a read without a position (HUMID_NO_TILE, Dedup.optical_duplicates)
 _BEST_SCOPES = {"leaf": BEST_LEAF, "cluster": BEST_CLUSTER, BEST_LEAF: BEST_LEAF, BEST_CLUSTER: BEST_CLUSTER}
 
 # per-read status of the barcode correction (include/humid_hip.h, HUMID_BC_*); also the index into its five counts
@@ -384,6 +385,59 @@ class Dedup(Context):
         p = [C.c_void_p() for _ in range(5)]
         self._check(self._lib.humid_consensus_result_device(self._h, *[C.byref(x) for x in p]))
         return dict(zip(("out_off", "bases", "quals", "depth", "errors"), [x.value or 0 for x in p]))
+
+    def optical_duplicates(self, cluster_id, keep, tile, x, y, distance=100, n_clusters=None):
+        """After a run: which duplicates of every cluster are optical ones (include/humid_hip.h,
+        humid_optical_duplicates).  Two reads of a cluster are close when they lie on the same tile (NO_TILE: the read
+        has no position) and |dx| <= distance and |dy| <= distance; the connected groups of close reads each keep one
+        origin -- the cluster's kept read where the group holds it, else its smallest read index -- and every other
+        read of a group is optical.  cluster_id / keep from any run (keep possibly from select_best); tile, x, y
+        u32[N].  n_clusters defaults to the last run's count.  All five arrays are numpy arrays, or all five torch
+        tensors on this object's device (int32 / uint8 storage is read as u32 / u8): the results then stay there.
+        Returns (optical u8[N], origin u32[N], per_cluster u32[C], summary dict): origin is NO_READ for
+        cluster_id == 0; pcr duplicates are summary["duplicates"] - summary["optical"]."""
+        if n_clusters is None:
+            n_clusters = int(self.summary["clusters"])
+        n_clusters = int(n_clusters)
+        distance = int(distance)
+        if not 0 <= distance <= 0xffffffff:
+            raise ValueError("distance must be in [0, 2**32)")
+        sm = _lib.HumidOpticalSummary()
+        arrays = (cluster_id, keep, tile, x, y)
+        if all(hasattr(a, "data_ptr") for a in arrays):
+            import torch
+            n = cluster_id.numel()
+            for a, size in zip(arrays, (4, 1, 4, 4, 4)):
+                if not a.is_cuda or not a.is_contiguous() or a.element_size() != size or a.numel() != n or a.dim() != 1:
+                    raise ValueError("device tensors must be contiguous, one-dimensional, of %d elements: cluster_id, tile, "
+                                     "x, y of 4 bytes each, keep of 1" % n)
+            dev = cluster_id.device
+            optical = torch.zeros(n, dtype=torch.uint8, device=dev)
+            origin = torch.zeros(n, dtype=torch.int32, device=dev)
+            per_cluster = torch.zeros(n_clusters, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            self._check(self._lib.humid_optical_duplicates_device(
+                self._h, *[C.c_void_p(a.data_ptr()) for a in arrays], n, n_clusters, distance, C.c_void_p(optical.data_ptr()),
+                C.c_void_p(origin.data_ptr()), C.c_void_p(per_cluster.data_ptr()) if n_clusters else None, C.byref(sm)))
+            return optical, origin, per_cluster, sm.asdict()
+        cid = np.ascontiguousarray(cluster_id, dtype=np.uint32)
+        n = len(cid)
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        pos = []
+        for name, a in (("tile", tile), ("x", x), ("y", y)):
+            a = np.asarray(a)
+            if a.dtype.kind not in "ui" or a.shape != (n,) or (n and (int(a.min()) < 0 or int(a.max()) > 0xffffffff)):
+                raise ValueError("%s must be integers in [0, 2**32) with shape (%d,)" % (name, n))
+            pos.append(np.ascontiguousarray(a, dtype=np.uint32))
+        if cid.ndim != 1 or k.shape != (n,):
+            raise ValueError("cluster_id and keep must have shape (N,)")
+        optical = np.zeros(n, np.uint8)
+        origin = np.zeros(n, np.uint32)
+        per_cluster = np.zeros(n_clusters, np.uint32)
+        self._check(self._lib.humid_optical_duplicates(
+            self._h, _vp(cid), _vp(k), _vp(pos[0]), _vp(pos[1]), _vp(pos[2]), n, n_clusters, distance, _vp(optical), _vp(origin),
+            _vp(per_cluster) if n_clusters else None, C.byref(sm)))
+        return optical, origin, per_cluster, sm.asdict()
 
     def group_keys(self):
         """after a keyed run: the distinct keys of the usable reads, ascending (u64[G]); group g is key [g]"""

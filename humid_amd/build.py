@@ -55,7 +55,7 @@ HOST_EXE = os.path.join(HERE, "humid")
 def build_host(force: bool = False, verbose: bool = False) -> str:
     """The `humid` command-line host (C++17, g++): FastQ streaming + the C ABI."""
     srcs = [os.path.join(HOST_DIR, f) for f in ("main.cpp", "sharded.cpp", "fastq_io.cpp", "fastq_mmap.cpp", "fast_inflate.cpp", "words.cpp")]
-    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("fastq_io.hpp", "fastq_mmap.hpp", "fast_inflate.hpp", "words.hpp", "sharded.hpp")] + [HDR]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("fastq_io.hpp", "fastq_mmap.hpp", "fast_inflate.hpp", "words.hpp", "sharded.hpp", "position.hpp")] + [HDR]
     build_hip(force=False, verbose=verbose)
     if not force and os.path.exists(HOST_EXE) and \
             all(os.path.getmtime(p) <= os.path.getmtime(HOST_EXE) for p in deps + [SO]):

@@ -33,6 +33,7 @@
 #include <thread>
 
 #include "fast_inflate.hpp"
+#include "position.hpp"
 #include "sharded.hpp"
 #include "words.hpp"
 
@@ -61,11 +62,14 @@ struct Args {
   bool consensus = false;      // -C (not in the reference): every kept record carries the consensus of its cluster's reads
   unsigned consensus_min_q = 10;   // --consensus-min-q
   std::string dump_consensus;  // --dump-consensus-input (development: what -C hands to the GPU, then stop, no GPU)
+  bool optical = false;        // -O given (not in the reference): the duplicates of every cluster are split into optical and other ones
+  uint32_t optical_distance = 0;   // -O
+  std::string dump_positions;  // --dump-positions (development: the -O positions of pass 1, then stop, no GPU)
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -87,7 +91,12 @@ void usage(const char *argv0) {
                "      consensus of all reads of its cluster, file by file: per column the base with the largest sum of\n"
                "      Phred qualities, the margin to the second largest as its quality (at most 93), N and ! on a tie;\n"
                "      bases below --consensus-min-q N (default 10) and letters outside ACGT do not vote.  Record lengths\n"
-               "      do not change; only the _dedup files change; one GPU, inputs held in memory (no CRLF files)\n",
+               "      do not change; only the _dedup files change; one GPU, inputs held in memory (no CRLF files)\n"
+               "  -O  count optical duplicates within D pixels: records of one cluster on the same lane and tile whose x and\n"
+               "      y both differ by at most D, chains of such records taken as one group (names of the first file as\n"
+               "      @inst:run:flowcell:lane:tile:x:y; the file is taken to be ONE flowcell; records without such a name\n"
+               "      have no position).  Every group counts all its records but one -- the cluster's kept record where\n"
+               "      the group holds it -- as optical.  A log line, and with -s optical.dat; no other output changes; one GPU\n",
                argv0);
 }
 
@@ -110,6 +119,16 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "--dump-scores") { const char *v = need("--dump-scores"); if (!v) return false; a.dump_scores = v; }
     else if (t == "--dump-consensus-input") { const char *v = need("--dump-consensus-input"); if (!v) return false; a.dump_consensus = v; }
     else if (t == "--consensus-min-q") { const char *v = need("--consensus-min-q"); if (!v) return false; a.consensus_min_q = (unsigned)std::strtoul(v, nullptr, 10); }
+    else if (t == "--dump-positions") { const char *v = need("--dump-positions"); if (!v) return false; a.dump_positions = v; }
+    else if (t == "-O") {
+      const char *v = need("-O");
+      if (!v) return false;
+      char *end = nullptr;
+      const unsigned long long d = std::strtoull(v, &end, 10);
+      if (*v < '0' || *v > '9' || *end != 0 || d > 0xffffffffull) { std::fprintf(stderr, "humid: -O takes a distance of 0 .. 4294967295 pixels\n"); return false; }
+      a.optical = true;
+      a.optical_distance = (uint32_t)d;
+    }
     else if (t == "-Q") a.best = !a.best;
     else if (t == "-C") a.consensus = !a.consensus;
     else if (t == "-s") a.stats = !a.stats;
@@ -384,13 +403,18 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -C runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
     return 1;
   }
+  if (a.optical && sharded) {                            // (the reads of a cluster lie on several ranks)
+    std::fprintf(stderr, "humid: -O runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
+    return 1;
+  }
   if (a.consensus_min_q > 93) {
     std::fprintf(stderr, "humid: --consensus-min-q takes 0 .. 93\n");
     return 2;
   }
-  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty();   // development: stop after pass 1, no GPU
+  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty() || !a.dump_positions.empty();   // development: stop after pass 1, no GPU
   const bool want_reads = a.consensus || !a.dump_consensus.empty();         // the reads themselves are gathered from the mappings
   const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
+  const bool positions = a.optical || !a.dump_positions.empty();            // (nor without -O)
   std::vector<uint64_t> whitelist;
   if (!a.whitelist.empty()) {
     if (!a.keyed) {
@@ -513,9 +537,10 @@ int main(int argc, char **argv) {
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
   // (-Q: the selection compares the packed words, so the host packs them)
-  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && getenv("HUMID_DEVICE_PACK") != nullptr;
+  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
   std::vector<uint32_t> scores;                    // -Q: one per record
+  std::vector<uint32_t> pos_tile, pos_x, pos_y;    // -O: the position of every record (position.hpp)
   if (fast) {
     size_t n = maps[0].records();
     for (auto &m : maps) n = m.records() < n ? m.records() : n;     // stop at the shortest file
@@ -538,6 +563,7 @@ int main(int argc, char **argv) {
     words.resize(n * wpr);
     filtered.resize(n);
     if (scoring) scores.resize(n);
+    if (positions) { pos_tile.resize(n); pos_x.resize(n); pos_y.resize(n); }
     parallel_ranges(n, threads, [&](size_t b, size_t e, unsigned) {
       std::string_view seqs[64], name0, nm, st, ql;
       for (size_t i = b; i < e; i++) {
@@ -548,6 +574,7 @@ int main(int argc, char **argv) {
           if (scoring) qsum += quality_sum(ql.data(), ql.size());
         }
         if (scoring) scores[i] = clamp_score(qsum);
+        if (positions) { const Position ps = parse_position(name0); pos_tile[i] = ps.tile; pos_x[i] = ps.x; pos_y[i] = ps.y; }
         if (wpr == 2) {
           filtered[i] = make_word_wide(name0, seqs, nf, plan, &words[2 * i]) ? 1 : 0;
         } else {
@@ -574,6 +601,10 @@ int main(int argc, char **argv) {
         for (const FastqRecord &r : recs) qsum += quality_sum(r.quality.data(), r.quality.size());
         scores.push_back(clamp_score(qsum));
       }
+      if (positions) {
+        const Position ps = parse_position(recs[0].name);
+        pos_tile.push_back(ps.tile); pos_x.push_back(ps.x); pos_y.push_back(ps.y);
+      }
     }
   }
   end_message(log, t);
@@ -589,6 +620,13 @@ int main(int argc, char **argv) {
     std::ofstream out(a.dump_scores, std::ios::out | std::ios::binary);
     out.write((const char *)&N, 8);
     out.write((const char *)scores.data(), (std::streamsize)(N * 4));
+  }
+  if (!a.dump_positions.empty()) {   // ... and the -O positions: a u64 count, then tile, x and y as three u32 arrays
+    std::ofstream out(a.dump_positions, std::ios::out | std::ios::binary);
+    out.write((const char *)&N, 8);
+    out.write((const char *)pos_tile.data(), (std::streamsize)(N * 4));
+    out.write((const char *)pos_x.data(), (std::streamsize)(N * 4));
+    out.write((const char *)pos_y.data(), (std::streamsize)(N * 4));
   }
   if (!a.dump_consensus.empty()) {   // ... and what -C hands to the GPU: a u64 count, then per file off u64[n + 1] and the two blobs
     std::ofstream out(a.dump_consensus, std::ios::out | std::ios::binary);
@@ -723,6 +761,23 @@ int main(int argc, char **argv) {
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
   if (a.best) log << "  quality: " << n_changed << " clusters keep another record\n";
+  // -O: after -Q, so that the origin of a group follows the final keep
+  humid_optical_summary osum;
+  std::memset(&osum, 0, sizeof osum);
+  uint64_t n_positioned = 0;
+  if (a.optical) {
+    std::vector<uint8_t> is_optical(N ? N : 1);
+    if (humid_optical_duplicates(ctx, cluster_id, keep, pos_tile.data(), pos_x.data(), pos_y.data(), N, sum.clusters, a.optical_distance,
+                                 is_optical.data(), nullptr, nullptr, &osum) != HUMID_OK) {
+      log << "failed.\n";
+      std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+      humid_ctx_destroy(ctx);
+      return 1;
+    }
+    for (uint64_t i = 0; i < N; i++) n_positioned += pos_tile[i] != HUMID_NO_TILE;
+    log << "  optical: " << osum.optical << " of " << osum.duplicates << " duplicates in " << osum.groups << " groups\n";
+    log << "  positions: " << n_positioned << " of " << N << " records\n";
+  }
   // -C: one consensus pass per input file, one after the other (a file's blobs are freed before the next is gathered);
   // what pass 2 needs stays on the host: per file the offsets and the two consensus blobs, in cluster-id order
   std::vector<std::vector<uint64_t>> cons_off(a.consensus ? maps.size() : 0);
@@ -780,6 +835,9 @@ int main(int argc, char **argv) {
   std::vector<uint64_t>().swap(words);
   std::vector<uint64_t>().swap(keys);
   std::vector<uint32_t>().swap(scores);
+  std::vector<uint32_t>().swap(pos_tile);
+  std::vector<uint32_t>().swap(pos_x);
+  std::vector<uint32_t>().swap(pos_y);
   std::vector<uint8_t>().swap(bases);
 
   make_dirs(a.dir_name);
@@ -975,6 +1033,18 @@ int main(int argc, char **argv) {
       out << "corrected: " << bc_counts[HUMID_BC_CORRECTED] << '\n';
       out << "ambiguous: " << bc_counts[HUMID_BC_AMBIGUOUS] << '\n';
       out << "unmatched: " << bc_counts[HUMID_BC_UNMATCHED] << '\n';
+      out.close();
+      if (out.fail()) ok = -1;
+    }
+    if (ok == 1 && a.optical) {
+      std::ofstream out(a.dir_name + "/optical.dat", std::ios::out | std::ios::binary);
+      out << "members " << osum.members << '\n';
+      out << "duplicates " << osum.duplicates << '\n';
+      out << "optical " << osum.optical << '\n';
+      out << "pcr " << osum.duplicates - osum.optical << '\n';
+      out << "groups " << osum.groups << '\n';
+      out << "largest_group " << osum.largest_group << '\n';
+      out << "records_without_position " << N - n_positioned << '\n';
       out.close();
       if (out.fail()) ok = -1;
     }

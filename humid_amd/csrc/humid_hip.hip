@@ -27,6 +27,8 @@
 #include "pipeline.hip.h"
 #include "kernels_best.hip.h"
 #include "kernels_consensus.hip.h"
+#include "kernels_optical.hip.h"
+static_assert(OPT_WALK_DEFAULT == 64u, "humid_ctx::op_walk starts at the default");
 
 static std::string g_err;
 // (the error text of calls without a context: also set from humid_exchange.hip and shm.cpp)
@@ -219,6 +221,11 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
   if (strcmp(key, "bucket_walk") == 0) {
     if (value < 0 || value > (1 << 24)) return fail(c, HUMID_E_INVALID, "bucket_walk must be 0 (no limit) .. 2^24");
     c->walk_max = (u32)value;
+    return HUMID_OK;
+  }
+  if (strcmp(key, "optical_walk") == 0) {
+    if (value < 0 || value > (1 << 24)) return fail(c, HUMID_E_INVALID, "optical_walk must be 0 (no limit) .. 2^24");
+    c->op_walk = (u32)value;
     return HUMID_OK;
   }
   if (strcmp(key, "plan_segments") == 0) {
@@ -983,6 +990,119 @@ int humid_consensus_result_device(humid_ctx *c, const uint64_t **d_out_off, cons
   if (d_quals) *d_quals = any ? c->cs_oq.as<u8>() : nullptr;
   if (d_depth) *d_depth = any ? c->cs_depth.as<u32>() : nullptr;
   if (d_errors) *d_errors = any ? c->cs_errors.as<u64>() : nullptr;
+  return HUMID_OK;
+}
+
+// ---- optical duplicates per cluster (kernels_optical.hip.h) -------------------------------------------------------
+// what both entry points refuse before anything moves
+static int optical_args(humid_ctx *c, const void *cid, const void *keep, const void *tile, const void *x, const void *y,
+                        uint64_t n_reads, const void *optical_out, humid_optical_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (summary) memset(summary, 0, sizeof *summary);
+  if (n_reads && (!cid || !keep || !tile || !x || !y || !optical_out)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "humid_optical_duplicates: more than 2^31 - 1 reads");
+  return HUMID_OK;
+}
+
+int humid_optical_duplicates_device(humid_ctx *c, const uint32_t *d_cluster_id, const uint8_t *d_keep, const uint32_t *d_tile,
+                                    const uint32_t *d_x, const uint32_t *d_y, uint64_t n_reads, uint64_t n_clusters,
+                                    uint32_t distance, uint8_t *d_optical_out, uint32_t *d_origin_out,
+                                    uint32_t *d_per_cluster_out, humid_optical_summary *summary) {
+  TRY(optical_args(c, d_cluster_id, d_keep, d_tile, d_x, d_y, n_reads, d_optical_out, summary));
+  if (n_reads == 0) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  if (n_clusters == 0) {                                     // no read is a member
+    HIPCHK(hipMemsetAsync(d_optical_out, 0, (size_t)n_reads, st));
+    if (d_origin_out) HIPCHK(hipMemsetAsync(d_origin_out, 0xff, (size_t)n_reads * 4, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return HUMID_OK;
+  }
+  if (n_clusters > n_reads)                                  // (some cluster then has no read at all, so no kept one)
+    return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: %llu clusters for %llu reads: a cluster without a read with keep == 1",
+                (ull)n_clusters, (ull)n_reads);
+  const u32 N = (u32)n_reads, C = (u32)n_clusters;
+  const size_t n = (size_t)N;
+  CS_ENSURE(c->op_rep, ((size_t)C + 1) * 4);
+  CS_ENSURE(c->op_bctr, BEST_CTRS * 4);
+  CS_ENSURE(c->op_ctr, OPT_CTRS * 8);
+  CS_ENSURE(c->op_k0, n * 4);
+  CS_ENSURE(c->op_v0, n * 4);
+  CS_ENSURE(c->op_v1, n * 4);
+  CS_ENSURE(c->op_ct, n * 8);
+  CS_ENSURE(c->op_xy, n * 8);
+  CS_ENSURE(c->op_vote, n * 8);
+  CS_ENSURE(c->op_parent, n * 4);
+  CS_ENSURE(c->op_root, n * 4);
+  CS_ENSURE(c->op_best, n * 8);
+  CS_ENSURE(c->op_gsize, n * 4);
+  u32 *rep = c->op_rep.as<u32>(), *bctr = c->op_bctr.as<u32>(), *k0 = c->op_k0.as<u32>(), *v0 = c->op_v0.as<u32>(), *v1 = c->op_v1.as<u32>();
+  u32 *parent = c->op_parent.as<u32>(), *root = c->op_root.as<u32>(), *gsize = c->op_gsize.as<u32>();
+  u64 *ct = c->op_ct.as<u64>(), *xy = c->op_xy.as<u64>(), *vote = c->op_vote.as<u64>();
+  ull *best = c->op_best.as<ull>(), *ctr = c->op_ctr.as<ull>();
+  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
+  HIPCHK(hipMemsetAsync(bctr, 0, BEST_CTRS * 4, st));
+  HIPCHK(hipMemsetAsync(ctr, 0, OPT_CTRS * 8, st));
+  HIPCHK(hipMemsetAsync(best, 0xff, n * 8, st));
+  HIPCHK(hipMemsetAsync(gsize, 0, n * 4, st));
+  hipLaunchKernelGGL(k_best_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, N, C, rep, bctr);
+  // the read indices by (cluster_id, tile, x): three stable sorts, least significant key first.  The sorts follow no
+  // index of the input (an id above C only lands at the wrong place of an order nobody reads then).
+  TRY((sort_pairs_in<u32, u32>(c, OptKeyX{d_cluster_id, d_x}, k0, IotaIn{}, v0, N, 0, 32)));
+  TRY((sort_pairs_in<u32, u32>(c, OptKeyTile{d_cluster_id, d_tile, v0}, k0, PtrIn<u32>{v0}, v1, N, 0, 32)));
+  TRY((sort_pairs_in<u32, u32>(c, OptKeyCid{d_cluster_id, v1}, k0, PtrIn<u32>{v1}, v0, N, 0, bits_for((u64)C + 1))));
+  const dim3 grid(blocks_for(N)), block(256);
+  hipLaunchKernelGGL(k_opt_gather, dim3(grid_stride_blocks(N)), block, 0, st, (const u32 *)k0, (const u32 *)v0, d_keep, d_tile, d_x, d_y, N, C,
+                     (const u32 *)bctr, ct, xy, vote, parent, d_per_cluster_out);
+  hipLaunchKernelGGL(k_opt_walk, grid, block, 0, st, (const u64 *)ct, (const u64 *)xy, N, C, distance, c->op_walk, (const u32 *)bctr, parent);
+  hipLaunchKernelGGL(k_opt_root, grid, block, 0, st, (const u64 *)ct, (const u64 *)vote, N, C, (const u32 *)bctr, (const u32 *)parent, root,
+                     best, gsize);
+  hipLaunchKernelGGL(k_opt_write, dim3(grid_stride_blocks(N)), block, 0, st, (const u64 *)ct, (const u64 *)vote, (const u32 *)root,
+                     (const ull *)best, (const u32 *)gsize, N, C, (const u32 *)bctr, d_optical_out, d_origin_out, d_per_cluster_out, ctr);
+  HIPCHK(hipGetLastError());
+  u32 hb[BEST_CTRS] = {0, 0, 0, 0};
+  ull h[OPT_CTRS] = {};
+  HIPCHK(hipMemcpyAsync(hb, bctr, sizeof hb, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          // the pass's one host wait
+  if (hb[BEST_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: a cluster id above the %u clusters given", C);
+  if (hb[BEST_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: a cluster has more than one read with keep == 1");
+  if (hb[BEST_CLAIMS] != C)
+    return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: %u reads with keep == 1 for %u clusters", hb[BEST_CLAIMS], C);
+  if (summary)
+    *summary = humid_optical_summary{(u64)C, (u64)h[OPT_MEMBERS], (u64)h[OPT_MEMBERS] - C, (u64)h[OPT_OPTICAL], (u64)h[OPT_GROUPS],
+                                     (u64)h[OPT_LARGEST]};
+  return HUMID_OK;
+}
+
+int humid_optical_duplicates(humid_ctx *c, const uint32_t *cluster_id, const uint8_t *keep, const uint32_t *tile, const uint32_t *x,
+                             const uint32_t *y, uint64_t n_reads, uint64_t n_clusters, uint32_t distance, uint8_t *optical_out,
+                             uint32_t *origin_out, uint32_t *per_cluster_out, humid_optical_summary *summary) {
+  TRY(optical_args(c, cluster_id, keep, tile, x, y, n_reads, optical_out, summary));
+  if (n_reads == 0) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads, nc = n_clusters <= n_reads ? (size_t)n_clusters : 0;   // (more clusters than reads: refused below)
+  CS_ENSURE(c->op_cid, n * 4);
+  CS_ENSURE(c->op_keep, n);
+  CS_ENSURE(c->op_tile, n * 4);
+  CS_ENSURE(c->op_x, n * 4);
+  CS_ENSURE(c->op_y, n * 4);
+  CS_ENSURE(c->op_optical, n);
+  if (origin_out) CS_ENSURE(c->op_origin, n * 4);
+  if (per_cluster_out && nc) CS_ENSURE(c->op_pc, nc * 4);
+  HIPCHK(hipMemcpyAsync(c->op_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->op_keep.p, keep, n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->op_tile.p, tile, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->op_x.p, x, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->op_y.p, y, n * 4, hipMemcpyHostToDevice, st));
+  TRY(humid_optical_duplicates_device(c, c->op_cid.as<u32>(), c->op_keep.as<u8>(), c->op_tile.as<u32>(), c->op_x.as<u32>(), c->op_y.as<u32>(),
+                                      n_reads, n_clusters, distance, c->op_optical.as<u8>(), origin_out ? c->op_origin.as<u32>() : nullptr,
+                                      per_cluster_out && nc ? c->op_pc.as<u32>() : nullptr, summary));
+  D2H(optical_out, c->op_optical.p, n);
+  D2H(origin_out, c->op_origin.p, n * 4);
+  D2H(per_cluster_out, c->op_pc.p, nc * 4);
+  HIPCHK(hipStreamSynchronize(st));
   return HUMID_OK;
 }
 

@@ -235,6 +235,10 @@ struct humid_ctx {
   DBuf cs_in_bases, cs_in_quals, cs_in_off, cs_in_cid, cs_in_keep;   // host entry point staging
   bool cs_valid = false;     // a humid_consensus* call succeeded: cs_sum and the result buffers are its
   humid_consensus_summary cs_sum = {};
+  // optical duplicates (humid_optical_duplicates*, kernels_optical.hip.h): memory of its own, read by no accessor
+  DBuf op_rep, op_bctr, op_ctr, op_k0, op_v0, op_v1, op_ct, op_xy, op_vote, op_parent, op_root, op_best, op_gsize;
+  DBuf op_cid, op_keep, op_tile, op_x, op_y, op_optical, op_origin, op_pc;   // host entry point staging
+  u32 op_walk = 64;          // option "optical_walk" (OPT_WALK_DEFAULT): followers a position walks before its wave takes over; 0 = no bound
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;

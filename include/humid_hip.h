@@ -121,7 +121,11 @@ const char *humid_last_error(const humid_ctx *ctx);   /* ctx may be NULL */
  * "bucket_walk": how many following words of its pigeonhole bucket a position is compared with by
  * its own thread (default 1024); the pairs further apart inside longer buckets are compared as
  * 1024 x 1024 tiles by whole workgroups.  0 = no bound (every pair by the position's thread, the
- * round-1 form: quadratic per lane on buckets of 10^5 words).  Results do not depend on it. */
+ * round-1 form: quadratic per lane on buckets of 10^5 words).  Results do not depend on it.
+ * "optical_walk": how many following reads of its window (same cluster and tile, x no more than the distance ahead)
+ * a sorted position of humid_optical_duplicates* is compared with by its own lane (default 64); the rest of a longer
+ * window is compared by the 64 lanes of the position's wave side by side.  0 = no bound (quadratic per lane on a
+ * cluster of 10^5 reads on one spot).  Results do not depend on it. */
 int  humid_ctx_set_option(humid_ctx *ctx, const char *key, int64_t value);
 /* Optional: one slab of device memory for a run over about n_reads reads, so that the first run does
  * not pay ~35 separate allocations (the `humid` host calls it while pass 1 still parses).  Never
@@ -457,6 +461,59 @@ int humid_get_consensus(humid_ctx *ctx, uint64_t cap_bytes, uint64_t *out_off, u
                         uint8_t *cons_quals, uint32_t *depth, uint64_t *errors);
 int humid_consensus_result_device(humid_ctx *ctx, const uint64_t **d_out_off, const uint8_t **d_bases,
                                   const uint8_t **d_quals, const uint32_t **d_depth, const uint64_t **d_errors);
+
+/* ---- optical duplicates: which duplicates of a cluster come from the instrument -------------------------------------
+ * (Picard MarkDuplicates READ_PAIR_OPTICAL_DUPLICATES, clumpify dedupe optical: reads of the same tile within a few
+ * hundred -- on patterned flowcells a few thousand -- pixels of each other.)  The definition is exact, in integers.
+ * Per read i < n_reads:
+ *   cluster_id[i], keep[i]   from any run (also from a sharded pass), keep possibly rewritten by humid_select_best.
+ *   tile[i]  (u32)           any value is a key (e.g. lane << 24 | tile); HUMID_NO_TILE: the read has no position.
+ *   x[i], y[i]  (u32)        every value is legal.
+ *   n_clusters = C           passed explicitly: the pass needs no prior run on the context.
+ *   distance = D  (u32)      every value is legal.
+ * A read with cluster_id == 0 is no member; none of its other fields are read.  Two members i != j are CLOSE when
+ *   cluster_id[i] == cluster_id[j],  tile[i] == tile[j] != HUMID_NO_TILE,  |x[i] - x[j]| <= D  and  |y[i] - y[j]| <= D
+ * (absolute differences of unsigned values: nothing wraps, no x + D is ever formed).  The OPTICAL GROUPS are the
+ * connected components of "close" among the members: the relation is taken transitively, as in Picard's graph form
+ * for large duplicate sets, so a chain of reads each within D of the next is one group; a member without a position
+ * is a group of its own.  r_c is the one read with keep == 1 and cluster_id == c.  The ORIGIN of a group is r_c when
+ * the group holds it, else the smallest read index of the group.  Outputs:
+ *   optical_out[i]  (u8)        1 when i is a member and not the origin of its group, else 0.
+ *   origin_out[i]   (u32)       the origin of i's group; HUMID_NO_READ for cluster_id == 0.  May be NULL.
+ *   per_cluster_out[c - 1] (u32[C])  the optical reads of cluster c.  May be NULL.
+ *   summary (may be NULL): n_clusters = C; members = reads with cluster_id != 0; duplicates = members - C; optical =
+ *     the sum of per_cluster = the sum over the groups of (size - 1); groups = groups of at least 2 reads;
+ *     largest_group = the reads of the largest group (1 when no two members are close, 0 without members).
+ *     pcr = duplicates - optical is the caller's to form.
+ * The result is a set partition plus a minimum over a total order: it does not depend on the order the device takes
+ * the reads or performs its atomics in.
+ * Malformed input -- an id above C, a cluster in 1 .. C with no kept read or with two -- is found on the device and
+ * reported as HUMID_E_INVALID at the pass's one host wait; nothing is then written and no unchecked index followed
+ * (C > n_reads is such a case, refused at once).  n_reads == 0 returns HUMID_OK with a zero summary and so does
+ * C == 0, where every read counts as no member (optical 0, origin HUMID_NO_READ).  n_reads > 2^31 - 1 returns
+ * HUMID_E_OVERFLOW; a NULL required buffer with n_reads > 0 HUMID_E_INVALID.  The pass launches nothing unless it is
+ * called, works in memory of its own, and leaves the context usable and every accessor of the last run valid, whatever
+ * it returns.
+ * On the device (kernels_optical.hip.h): the kept reads claim their clusters as in humid_select_best; the read indices
+ * are sorted by (cluster_id, tile, x) (three stable radix sorts); every sorted position walks forward while cluster
+ * and tile are equal and x is no more than D ahead, and joins what it meets with |dy| <= D in a lock-free forest; per
+ * root a 64-bit atomic minimum of (kept ? 0 : 1) << 32 | read index picks the origin; one more pass writes the
+ * outputs.  Option "optical_walk" bounds the walk of one lane (see humid_ctx_set_option).
+ *   humid_optical_duplicates: host buffers.
+ *   humid_optical_duplicates_device: DEVICE pointers for all arrays; summary stays a host pointer.  Returns after the
+ *     stream has drained. */
+#define HUMID_NO_TILE 0xffffffffu
+typedef struct humid_optical_summary {
+  uint64_t n_clusters, members, duplicates, optical, groups, largest_group;
+} humid_optical_summary;
+int humid_optical_duplicates(humid_ctx *ctx, const uint32_t *cluster_id, const uint8_t *keep, const uint32_t *tile,
+                             const uint32_t *x, const uint32_t *y, uint64_t n_reads, uint64_t n_clusters,
+                             uint32_t distance, uint8_t *optical_out, uint32_t *origin_out, uint32_t *per_cluster_out,
+                             humid_optical_summary *summary);
+int humid_optical_duplicates_device(humid_ctx *ctx, const uint32_t *d_cluster_id, const uint8_t *d_keep,
+                                    const uint32_t *d_tile, const uint32_t *d_x, const uint32_t *d_y, uint64_t n_reads,
+                                    uint64_t n_clusters, uint32_t distance, uint8_t *d_optical_out,
+                                    uint32_t *d_origin_out, uint32_t *d_per_cluster_out, humid_optical_summary *summary);
 
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
