@@ -49,6 +49,14 @@ class HumidOpticalSummary(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class HumidStrandSummary(C.Structure):
+    """humid_strand_summary of include/humid_hip.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_clusters", "duplex", "top_only", "bottom_only", "top_reads", "bottom_reads")]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
@@ -131,6 +139,16 @@ SYMBOLS = {
                                  [C.POINTER(HumidOpticalSummary)]),
     "humid_optical_duplicates_device": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32] +
                                         [C.c_void_p] * 3 + [C.POINTER(HumidOpticalSummary)]),
+    "humid_paired_canonical": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                         C.c_void_p]),
+    "humid_paired_canonical_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                C.c_void_p]),
+    "humid_dedup_run_paired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
+    "humid_dedup_run_paired_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
+    "humid_get_strands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                    C.POINTER(HumidStrandSummary)]),
     "humid_get_leaves": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "humid_get_adjacency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_get_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

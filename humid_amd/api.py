@@ -25,6 +25,9 @@ NO_READ = 0xffffffff
 NO_TILE = 0xffffffff   # tile of a read without a position (HUMID_NO_TILE, Dedup.optical_duplicates)
 _BEST_SCOPES = {"leaf": BEST_LEAF, "cluster": BEST_CLUSTER, BEST_LEAF: BEST_LEAF, BEST_CLUSTER: BEST_CLUSTER}
 
+# strand of a read in a strand-symmetric run (include/humid_hip.h, HUMID_STRAND_*)
+STRAND_TOP, STRAND_BOTTOM, STRAND_NONE = 0, 1, 2
+
 # per-read status of the barcode correction (include/humid_hip.h, HUMID_BC_*); also the index into its five counts
 BC_FILTERED, BC_EXACT, BC_CORRECTED, BC_AMBIGUOUS, BC_UNMATCHED = range(5)
 
@@ -239,6 +242,69 @@ class Dedup(Context):
         self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
         self._wide = word_nt > 32
         return self.summary
+
+    def run_paired(self, words, filtered, word_nt=24, distance=1, method=DIRECTIONAL):
+        """Strand-symmetric (duplex) deduplication (include/humid_hip.h, humid_dedup_run_paired): a word A.B and its
+        mirror B.A (halves of word_nt / 2 nucleotides exchanged) are one molecule read from its two strands.  The
+        leaves are the canonical words min(w, mirror(w)); two leaves u, v are neighbours when
+        min(ham(u, v), ham(u, mirror(v))) <= distance.  word_nt must be even.
+        Returns (cluster_id, keep, summary) like run(); leaves() gives the canonical words, strands() the strand of
+        every read and the reads of each strand per cluster."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        want = (len(f), 2) if word_nt > 32 else (len(f),)
+        if f.ndim != 1 or w.shape != want:
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % (want, word_nt, f.shape))
+        n = len(f)
+        self._wide = word_nt > 32
+        cid = np.zeros(n, dtype=np.uint32)
+        keep = np.zeros(n, dtype=np.uint8)
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_paired(self._h, _vp(w), _vp(f), n, word_nt, distance, method,
+                                                     _vp(cid), _vp(keep), C.byref(s)))
+        self.summary = s.asdict()
+        return cid, keep, self.summary
+
+    def run_paired_device(self, d_words, d_filtered, d_cluster_id, d_keep, n_reads, word_nt=24, distance=1,
+                          method=DIRECTIONAL):
+        """run_paired on device pointers (ints, e.g. tensor.data_ptr()); results stay in HBM."""
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_paired_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_filtered), n_reads, word_nt, distance, method,
+            C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = s.asdict()
+        self._wide = word_nt > 32
+        return self.summary
+
+    def canonical_words(self, words, filtered, word_nt=24):
+        """Canonical word and strand of every read without running anything else (humid_paired_canonical): returns
+        (words_out like words, strand u8[N] of STRAND_TOP / STRAND_BOTTOM / STRAND_NONE).  A filtered read keeps its
+        word.  The results of the last run stay untouched."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        want = (len(f), 2) if word_nt > 32 else (len(f),)
+        if f.ndim != 1 or w.shape != want:
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % (want, word_nt, f.shape))
+        out = w.copy()
+        strand = np.zeros(len(f), np.uint8)
+        self._check(self._lib.humid_paired_canonical(self._h, _vp(out), _vp(f), len(f), word_nt, _vp(out), _vp(strand)))
+        return out, strand
+
+    def canonical_words_device(self, d_words, d_filtered, d_words_out, d_strand, n_reads, word_nt=24):
+        """canonical_words on device pointers (ints; d_words_out may be d_words)"""
+        self._check(self._lib.humid_paired_canonical_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_filtered), n_reads, word_nt, C.c_void_p(d_words_out),
+            C.c_void_p(d_strand)))
+
+    def strands(self):
+        """after run_paired: (strand u8[N], top u32[C], bottom u32[C], summary dict) -- the strand of every read, the
+        reads of each strand of cluster c at [c - 1], and dict(n_clusters, duplex, top_only, bottom_only, top_reads,
+        bottom_reads); a cluster is duplex when it has reads of both strands (humid_get_strands)"""
+        n, c = int(self.summary["total"]), int(self.summary["clusters"])
+        strand, top, bottom = np.zeros(n, np.uint8), np.zeros(c, np.uint32), np.zeros(c, np.uint32)
+        sm = _lib.HumidStrandSummary()
+        self._check(self._lib.humid_get_strands(self._h, _vp(strand), n, _vp(top), _vp(bottom), C.byref(sm)))
+        return strand, top, bottom, sm.asdict()
 
     def set_whitelist(self, barcodes, barcode_nt=16):
         """The known barcodes (include/humid_hip.h, humid_whitelist_set): integers of at most 64 bits, each a

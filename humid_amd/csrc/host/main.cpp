@@ -65,11 +65,12 @@ struct Args {
   bool optical = false;        // -O given (not in the reference): the duplicates of every cluster are split into optical and other ones
   uint32_t optical_distance = 0;   // -O
   std::string dump_positions;  // --dump-positions (development: the -O positions of pass 1, then stop, no GPU)
+  bool paired = false;         // -P (not in the reference): strand-symmetric words -- R1/R2 exchanged is the same molecule
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] [-P] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -96,7 +97,13 @@ void usage(const char *argv0) {
                "      y both differ by at most D, chains of such records taken as one group (names of the first file as\n"
                "      @inst:run:flowcell:lane:tile:x:y; the file is taken to be ONE flowcell; records without such a name\n"
                "      have no position).  Every group counts all its records but one -- the cluster's kept record where\n"
-               "      the group holds it -- as optical.  A log line, and with -s optical.dat; no other output changes; one GPU\n",
+               "      the group holds it -- as optical.  A log line, and with -s optical.dat; no other output changes; one GPU\n"
+               "  -P  strand-symmetric (duplex) deduplication of exactly two files R1 R2, no UMI in the headers, even -n: a\n"
+               "      pair and the pair with R1 and R2 exchanged (the same molecule read from its other strand) are one word,\n"
+               "      and -m allows its mismatches against either orientation.  One record pair per cluster is kept; -a\n"
+               "      appends :<id>/A to a record read as given, :<id>/B to one read exchanged, :0 to an unusable one; a log\n"
+               "      line, and with -s strands.dat: clusters with reads of both orientations (duplex) and of one only.\n"
+               "      Works with -x, -Q, -O, -a, -s; not with -b, -w, -g, -e, -C; one GPU\n",
                argv0);
 }
 
@@ -129,6 +136,7 @@ bool parse(int argc, char **argv, Args &a) {
       a.optical = true;
       a.optical_distance = (uint32_t)d;
     }
+    else if (t == "-P") a.paired = !a.paired;
     else if (t == "-Q") a.best = !a.best;
     else if (t == "-C") a.consensus = !a.consensus;
     else if (t == "-s") a.stats = !a.stats;
@@ -407,6 +415,17 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -O runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)\n");
     return 1;
   }
+  if (a.paired) {
+    const char *why = nullptr;
+    if (a.files.size() != 2) why = "-P takes exactly two input files (R1 and R2)";
+    else if (a.word_length % 2 != 0) why = "-P needs an even word length (-n): half of the word comes from each file";
+    else if (a.keyed) why = "-P does not work with -b";
+    else if (!a.whitelist.empty()) why = "-P does not work with -w";
+    else if (sharded) why = "-P runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+    else if (a.edit) why = "-P does not work with -e (edit distance against an exchanged pair is not defined here)";
+    else if (a.consensus) why = "-P does not work with -C (a duplex consensus has to exchange the files of half of the reads)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
   if (a.consensus_min_q > 93) {
     std::fprintf(stderr, "humid: --consensus-min-q takes 0 .. 93\n");
     return 2;
@@ -495,6 +514,10 @@ int main(int argc, char **argv) {
     FastqRecord r;
     if (peek.read(r)) first_umi = header_umi(r.name).size();   // empty file: no UMI (the reference crashes)
   }
+  if (a.paired && first_umi != 0) {
+    std::fprintf(stderr, "humid: -P takes the word from the two reads alone: %s has a UMI in its headers\n", a.files.front().c_str());
+    return 2;
+  }
   WordPlan plan = make_plan(first_umi, a.files.size(), a.word_length);
   time_t t = start_message(log, "Determing nucleotides to take");
   end_message(log, t);
@@ -537,7 +560,7 @@ int main(int argc, char **argv) {
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
   // (-Q: the selection compares the packed words, so the host packs them)
-  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && getenv("HUMID_DEVICE_PACK") != nullptr;
+  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && !a.paired && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
   std::vector<uint32_t> scores;                    // -Q: one per record
   std::vector<uint32_t> pos_tile, pos_x, pos_y;    // -O: the position of every record (position.hpp)
@@ -610,11 +633,24 @@ int main(int argc, char **argv) {
   end_message(log, t);
   const uint64_t N = device_pack ? n_records : filtered.size();
 
+  // -P: the canonical words (what -Q compares and --dump-words shows; the run itself takes the words as they are and
+  // returns the strands) and, for the dump, the strand of every read
+  std::vector<uint64_t> cwords;
+  std::vector<uint8_t> strand;
+  if (a.paired && (a.best || !a.dump_words.empty())) {
+    cwords = words;
+    strand.assign(N ? N : 1, HUMID_STRAND_NONE);
+    parallel_ranges(N, threads, [&](size_t b, size_t e, unsigned) {
+      for (size_t i = b; i < e; i++)
+        if (!filtered[i]) strand[i] = canonical_word(&cwords[i * wpr], wpr, a.word_length) ? HUMID_STRAND_BOTTOM : HUMID_STRAND_TOP;
+    });
+  }
   if (!a.dump_words.empty()) {   // development aid: host-side parsing can be checked without a GPU
     std::ofstream out(a.dump_words, std::ios::out | std::ios::binary);
     out.write((const char *)&N, 8);
-    out.write((const char *)words.data(), (std::streamsize)(N * 8 * wpr));
+    out.write((const char *)(a.paired ? cwords : words).data(), (std::streamsize)(N * 8 * wpr));
     out.write((const char *)filtered.data(), (std::streamsize)N);
+    if (a.paired) out.write((const char *)strand.data(), (std::streamsize)N);   // -P: the canonical words, then one strand byte per read
   }
   if (!a.dump_scores.empty()) {  // ... and the -Q scores: a u64 count, then u32 scores
     std::ofstream out(a.dump_scores, std::ios::out | std::ios::binary);
@@ -721,6 +757,9 @@ int main(int argc, char **argv) {
   } else if (corrected)
     rc = humid_dedup_run_keyed_corrected(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
                                          method, cluster_id, keep, &sum);
+  else if (a.paired)
+    rc = humid_dedup_run_paired(ctx, run_words, run_filt, N, (uint32_t)a.word_length, (uint32_t)a.distance, method, cluster_id,
+                                keep, &sum);
   else if (a.keyed)
     rc = humid_dedup_run_keyed(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance, method,
                                cluster_id, keep, &sum);
@@ -738,6 +777,12 @@ int main(int argc, char **argv) {
   }
   uint64_t bc_counts[5] = {0, 0, 0, 0, 0};
   if (rc == HUMID_OK && corrected) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
+  humid_strand_summary ssum;
+  std::memset(&ssum, 0, sizeof ssum);
+  if (rc == HUMID_OK && a.paired) {
+    strand.assign(N ? N : 1, HUMID_STRAND_NONE);
+    rc = humid_get_strands(ctx, strand.data(), N, nullptr, nullptr, &ssum);
+  }
   if (rc != HUMID_OK) {
     log << "failed.\n";
     std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
@@ -749,7 +794,7 @@ int main(int argc, char **argv) {
   if (a.best) {
     // every cluster keeps its best record among those of its most abundant word; keep is rewritten in place and
     // pass 2 follows it (the ids do not move: the annotated files and the statistics are those of the run)
-    if (humid_select_best(ctx, run_words, cluster_id, keep, scores.data(), N, (uint32_t)run_nt, HUMID_BEST_LEAF, keep, nullptr,
+    if (humid_select_best(ctx, a.paired ? cwords.data() : run_words, cluster_id, keep, scores.data(), N, (uint32_t)run_nt, HUMID_BEST_LEAF, keep, nullptr,
                           &n_changed) != HUMID_OK) {
       log << "failed.\n";
       std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
@@ -760,6 +805,9 @@ int main(int argc, char **argv) {
   if (corrected)
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
+  if (a.paired)
+    log << "  strands: " << ssum.n_clusters << " clusters, " << ssum.duplex << " duplex, " << ssum.top_only << " top only, "
+        << ssum.bottom_only << " bottom only; " << ssum.top_reads << " top reads, " << ssum.bottom_reads << " bottom reads\n";
   if (a.best) log << "  quality: " << n_changed << " clusters keep another record\n";
   // -O: after -Q, so that the origin of a group follows the final keep
   humid_optical_summary osum;
@@ -826,6 +874,23 @@ int main(int argc, char **argv) {
       memcpy(dst + (ql.data() - r0), &cons_q[f][o], (size_t)len);
     }
   };
+  // what -a appends to the header of record i: ':' + cluster id (src/humid.cc:281) and, with -P, "/A" for a read taken
+  // as given, "/B" for one taken exchanged (nothing for an unusable read: ":0")
+  auto tag_size = [&](size_t i) {
+    size_t d = 1;
+    for (uint32_t v = cluster_id[i]; v >= 10; v /= 10) d++;
+    return 1 + d + ((a.paired && strand[i] != HUMID_STRAND_NONE) ? (size_t)2 : (size_t)0);
+  };
+  auto put_tag = [&](size_t i, char *q) {
+    *q++ = ':';
+    char dig[10];
+    unsigned nd = 0;
+    uint32_t v = cluster_id[i];
+    do { dig[nd++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (nd) *q++ = dig[--nd];
+    if (a.paired && strand[i] != HUMID_STRAND_NONE) { *q++ = '/'; *q++ = strand[i] == HUMID_STRAND_BOTTOM ? 'B' : 'A'; }
+    return q;
+  };
   phase("device path done");
   if (getenv("HUMID_TIMING"))
     std::fprintf(stderr, "[humid]   of which on the device: upload%s %.1f ms, hot path %.2f ms, download %.1f ms\n",
@@ -833,6 +898,7 @@ int main(int argc, char **argv) {
   t = start_message(log, a.maximum ? "Calculating maximum clusters" : "Calculating directional clusters");
   end_message(log, t);
   std::vector<uint64_t>().swap(words);
+  std::vector<uint64_t>().swap(cwords);
   std::vector<uint64_t>().swap(keys);
   std::vector<uint32_t>().swap(scores);
   std::vector<uint32_t>().swap(pos_tile);
@@ -861,7 +927,6 @@ int main(int argc, char **argv) {
     std::vector<char> done_dedup(a.files.size(), 0), done_annot(a.files.size(), 0);
     bool mapped_failed = false;
     if (fast && getenv("HUMID_NO_MAPPED_WRITE") == nullptr) {
-      auto digits = [](uint32_t v) { size_t d = 1; while (v >= 10) { v /= 10; d++; } return d; };
       // the files of a pair are written side by side (page-cache filling scales per file), each with
       // its share of the workers
       const unsigned per_file = threads / (unsigned)maps.size() ? threads / (unsigned)maps.size() : 1;
@@ -888,19 +953,13 @@ int main(int argc, char **argv) {
           // annotated record = header + ':' + cluster id + the rest of the record verbatim (src/humid.cc:281)
           const std::string path = make_file_name(a.files[f], a.dir_name, "annotated");
           const int r = write_mapped(path, N, threads,
-              [&](size_t i) { return maps[f].raw(i).size() + 1 + digits(cluster_id[i]); },
+              [&](size_t i) { return maps[f].raw(i).size() + tag_size(i); },
               [&](size_t i, char *q) {
                 const std::string_view rr = maps[f].raw(i);
                 const char *nl = (const char *)memchr(rr.data(), '\n', rr.size());
                 const size_t hl = nl ? (size_t)(nl - rr.data()) : rr.size();
                 memcpy(q, rr.data(), hl);
-                q += hl;
-                *q++ = ':';
-                char dig[10];
-                unsigned nd = 0;
-                uint32_t v = cluster_id[i];
-                do { dig[nd++] = (char)('0' + v % 10); v /= 10; } while (v);
-                while (nd) *q++ = dig[--nd];
+                q = put_tag(i, q + hl);
                 memcpy(q, rr.data() + hl, rr.size() - hl);
                 return q + (rr.size() - hl);
               });
@@ -941,20 +1000,14 @@ int main(int argc, char **argv) {
                 // (src/humid.cc:281); written with pointer arithmetic into a buffer sized up front
                 const size_t first = b0 + rb, last = b0 + re;
                 const size_t in_bytes = (size_t)(maps[f].rec_off[last] - maps[f].rec_off[first]);
-                o.resize(in_bytes + 11 * (last - first));
+                o.resize(in_bytes + 13 * (last - first));
                 char *q = &o[0];
                 for (size_t i = first; i < last; i++) {
                   const std::string_view r = maps[f].raw(i);
                   const char *nl = (const char *)memchr(r.data(), '\n', r.size());
                   const size_t hl = nl ? (size_t)(nl - r.data()) : r.size();
                   memcpy(q, r.data(), hl);
-                  q += hl;
-                  *q++ = ':';
-                  char dig[10];
-                  unsigned nd = 0;
-                  uint32_t v = cluster_id[i];
-                  do { dig[nd++] = (char)('0' + v % 10); v /= 10; } while (v);
-                  while (nd) *q++ = dig[--nd];
+                  q = put_tag(i, q + hl);
                   memcpy(q, r.data() + hl, r.size() - hl);
                   q += r.size() - hl;
                 }
@@ -984,7 +1037,8 @@ int main(int argc, char **argv) {
         }
       }
       if (a.annotate) {
-        const std::string tag = ":" + std::to_string(cluster_id[i]);   // src/humid.cc:281
+        char tagbuf[16];
+        const std::string tag(tagbuf, (size_t)(put_tag(i, tagbuf) - tagbuf));
         for (size_t f = 0; f < recs.size(); f++) {
           recs[f].name += tag;
           s.clear();
@@ -1033,6 +1087,17 @@ int main(int argc, char **argv) {
       out << "corrected: " << bc_counts[HUMID_BC_CORRECTED] << '\n';
       out << "ambiguous: " << bc_counts[HUMID_BC_AMBIGUOUS] << '\n';
       out << "unmatched: " << bc_counts[HUMID_BC_UNMATCHED] << '\n';
+      out.close();
+      if (out.fail()) ok = -1;
+    }
+    if (ok == 1 && a.paired) {
+      std::ofstream out(a.dir_name + "/strands.dat", std::ios::out | std::ios::binary);
+      out << "clusters: " << ssum.n_clusters << '\n';
+      out << "duplex: " << ssum.duplex << '\n';
+      out << "top_only: " << ssum.top_only << '\n';
+      out << "bottom_only: " << ssum.bottom_only << '\n';
+      out << "top_reads: " << ssum.top_reads << '\n';
+      out << "bottom_reads: " << ssum.bottom_reads << '\n';
       out.close();
       if (out.fail()) ok = -1;
     }

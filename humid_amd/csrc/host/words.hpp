@@ -43,6 +43,19 @@ bool make_word_wide(const std::vector<FastqRecord> &recs, const WordPlan &plan, 
 bool make_word_wide(std::string_view first_header, const std::string_view *seqs, size_t n_files,
                     const WordPlan &plan, uint64_t word[2]);
 
+// -P (strand-symmetric words, include/humid_hip.h): the word A.B of word_nt = 2 h nucleotides becomes the smaller of
+// itself and its mirror B.A, in place (wpr uint64 per word: 1 up to 32 nucleotides, 2 beyond).  Returns true when the
+// mirror was the smaller one (a bottom-strand read).
+inline bool canonical_word(uint64_t *w, size_t wpr, size_t word_nt) {
+  const unsigned n = (unsigned)word_nt;
+  const unsigned __int128 v = wpr == 2 ? ((unsigned __int128)w[0] << 64) | w[1] : (unsigned __int128)w[0];
+  const unsigned __int128 m = ((v & ((((unsigned __int128)1) << n) - 1)) << n) | (v >> n);
+  if (!(m < v)) return false;
+  if (wpr == 2) { w[0] = (uint64_t)(m >> 64); w[1] = (uint64_t)m; }
+  else w[0] = (uint64_t)m;
+  return true;
+}
+
 // getNucleotides (src/fastq.cc:116-144) as raw bytes, for the device-side packing of
 // humid_dedup_run_bases: out[plan.word_nt] = the header UMI cut or padded with 'N' to plan.header_umi
 // symbols, then the first plan.take[f] bytes of every file's read, 'N' where a read is short.  The

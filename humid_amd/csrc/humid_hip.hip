@@ -754,6 +754,113 @@ int humid_group_stats_device(humid_ctx *c, uint64_t *n_out, const uint64_t **d_r
   return HUMID_OK;
 }
 
+// ---- strand-symmetric (duplex) deduplication (kernels_paired.hip.h) ------------------------------------------------
+static int paired_canonical_args(humid_ctx *c, const void *words, const void *filtered, uint64_t n_reads, uint32_t word_nt,
+                                 const void *words_out, const void *strand_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  TRY(check_paired_args(c, word_nt));
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
+  if (n_reads && (!words || !filtered || !words_out || !strand_out)) return fail(c, HUMID_E_INVALID, "null buffer");
+  return HUMID_OK;
+}
+
+int humid_paired_canonical_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                  uint32_t word_nt, uint64_t *d_words_out, uint8_t *d_strand_out) {
+  TRY(paired_canonical_args(c, d_words, d_filtered, n_reads, word_nt, d_words_out, d_strand_out));
+  if (word_nt > 32 && (((uintptr_t)d_words | (uintptr_t)d_words_out) & 15))
+    return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  HIPCHK(hipSetDevice(c->device));
+  TRY(with_word_type(word_nt, [&](auto *w) {
+    typedef typename std::remove_const<typename std::remove_pointer<decltype(w)>::type>::type WT;
+    return pd_canonical_launch<WT>(c, (const WT *)d_words, d_filtered, (u32)n_reads, word_nt, (WT *)d_words_out, d_strand_out);
+  }));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_paired_canonical(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                           uint64_t *words_out, uint8_t *strand_out) {
+  TRY(paired_canonical_args(c, words, filtered, n_reads, word_nt, words_out, strand_out));
+  if (n_reads == 0) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
+  ENSURE(c->pd_in_words, n * wbytes + 16);
+  ENSURE(c->pd_in_filt, n + 16);
+  ENSURE(c->pd_out_strand, n + 16);
+  HIPCHK(hipMemcpyAsync(c->pd_in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->pd_in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
+  TRY(with_word_type(word_nt, [&](auto *w) {
+    typedef typename std::remove_const<typename std::remove_pointer<decltype(w)>::type>::type WT;
+    return pd_canonical_launch<WT>(c, c->pd_in_words.as<WT>(), c->pd_in_filt.as<u8>(), (u32)n, word_nt, c->pd_in_words.as<WT>(),
+                                   c->pd_out_strand.as<u8>());
+  }));
+  // (in place on the device: the staged copy of a filtered read's word comes back as it went in)
+  HIPCHK(hipMemcpyAsync(words_out, c->pd_in_words.p, n * wbytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(strand_out, c->pd_out_strand.p, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return HUMID_OK;
+}
+
+int humid_dedup_run_paired_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                  uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *d_cluster_id,
+                                  uint8_t *d_keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
+  TRY(check_paired_args(c, word_nt));
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_paired_device(c, (decltype(w))d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+  });
+}
+
+int humid_dedup_run_paired(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                           uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
+  TRY(check_paired_args(c, word_nt));                        // (a refused shape moves nothing)
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (c->edit && distance >= 2)
+    return fail(c, HUMID_E_UNSUPPORTED, "edit distance %u against a mirrored word is not supported (option edit_distance)", distance);
+  if (n_reads && (!words || !filtered || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
+  ENSURE(c->in_words, n * wbytes + 16);
+  ENSURE(c->in_filt, n + 8);
+  ENSURE(c->out_cid, n * 4 + 8);
+  ENSURE(c->out_keep, n + 8);
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
+  }
+  humid_summary s;
+  memset(&s, 0, sizeof s);
+  TRY(with_word_type(word_nt, [&](auto *w) {
+    return run_paired_device(c, (decltype(w))c->in_words.p, c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
+                             c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s);
+  }));
+  hipError_t he = hipSuccess;
+  if (n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) { state_reset(c); return fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
+  if (summary) *summary = s;
+  return HUMID_OK;
+}
+
+int humid_get_strands(humid_ctx *c, uint8_t *strand, uint64_t cap, uint32_t *top, uint32_t *bottom, humid_strand_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!state_has_run(c) || !c->state.paired) return fail(c, HUMID_E_STATE, "the last run was not a strand-symmetric run");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t take = (size_t)(c->pd_N < cap ? c->pd_N : cap), C = (size_t)c->pd_sum.n_clusters;
+  D2H(strand, c->pd_strand.p, take);
+  D2H(top, c->pd_top.as<u32>() + 1, C * 4);
+  D2H(bottom, c->pd_bottom.as<u32>() + 1, C * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (summary) *summary = c->pd_sum;
+  return HUMID_OK;
+}
+
 // ---- best-scoring read per cluster (kernels_best.hip.h) --------------------------------------------------------
 // what both entry points refuse before anything moves; n_reads == 0 is the caller's to return HUMID_OK on
 static int select_best_args(humid_ctx *c, const void *words, const void *cid, const void *keep, const void *score,

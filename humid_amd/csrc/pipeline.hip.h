@@ -32,6 +32,7 @@
 #include "kernels_keyrank.hip.h"
 #include "kernels_gstats.hip.h"
 #include "kernels_whitelist.hip.h"
+#include "kernels_paired.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -110,6 +111,7 @@ struct CtxState {
   RunKind kind = RUN_PLAIN;    // of a RUN
   bool dense = false;          // the last count ran on a compacted list of this rank's reads; a stage graph after it keeps this
   bool stats_current = false;  // derived on demand from a RUN: gs_* hold its group statistics for gs_G groups
+  bool paired = false;         // the RUN was humid_dedup_run_paired*: pd_strand / pd_top / pd_bottom / pd_sum are its (humid_get_strands)
 };
 
 struct humid_ctx {
@@ -239,6 +241,12 @@ struct humid_ctx {
   DBuf op_rep, op_bctr, op_ctr, op_k0, op_v0, op_v1, op_ct, op_xy, op_vote, op_parent, op_root, op_best, op_gsize;
   DBuf op_cid, op_keep, op_tile, op_x, op_y, op_optical, op_origin, op_pc;   // host entry point staging
   u32 op_walk = 64;          // option "optical_walk" (OPT_WALK_DEFAULT): followers a position walks before its wave takes over; 0 = no bound
+  // strand-symmetric runs (humid_dedup_run_paired*, kernels_paired.hip.h): the pass runs over the canonical words
+  bool pd_run = false;       // a paired pass is running: run_device takes its neighbour pairs from paired_edges
+  DBuf pd_words, pd_strand, pd_mir, pd_top, pd_bottom, pd_ctr;   // canonical words, strands, mirrored leaves, tallies u32[C + 1], ull[PD_CTRS]
+  DBuf pd_in_words, pd_in_filt, pd_out_strand;   // humid_paired_canonical: staging of its own (the words in place)
+  u64 pd_N = 0;              // state.paired: pd_strand holds the strands of the run's pd_N reads
+  humid_strand_summary pd_sum = {};
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -2251,6 +2259,121 @@ static int unique_edges(humid_ctx *c, const u64 *d_edges, u64 raw, u32 U, u64 *n
   return HUMID_OK;
 }
 
+// ---- strand-symmetric neighbours (humid_dedup_run_paired*, kernels_paired.hip.h) ----------------------------------
+// Pairs of leaves u < v with min(ham(u, v), ham(u, m(v))) <= distance, as a duplicate-free ascending edge list in
+// c->e_edges.  g_word: the U canonical leaves, ascending.  For every combination of the pigeonhole plan two joins
+// over the leaves' keys X: against themselves (plain pairs) and against the keys of the mirrored leaves (mirror
+// pairs, verified against m(v)).  The host waits are those of edit_edges: one per join for the number of pairs, two
+// more where a run of equal keys is longer than one lane walks.
+template <class WT>
+static int paired_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 distance, u64 *n_edges_out) {
+  hipStream_t st = c->stream;
+  *n_edges_out = 0;
+  if (U < 2 || distance == 0) return HUMID_OK;
+  const ComboPlan plan = make_plan(word_nt, distance, U, c->force_segments);
+  if (plan.ncombo == 1 && plan.key_bits == 0 && U > (1u << 18))
+    return fail(c, HUMID_E_OVERFLOW, "distance %u over %u-nt words compares all pairs of %u unique words: too many neighbour pairs",
+                distance, word_nt, U);
+  const u32 kb = plan.key_bits ? plan.key_bits : 1;
+  const bool k32 = kb <= 32;
+  ENSURE(c->pd_mir, (size_t)U * sizeof(WT) + 16);
+  ENSURE(c->e_kx, (size_t)U * 8);
+  ENSURE(c->e_vx, (size_t)U * 4);
+  ENSURE(c->e_ky, (size_t)U * 8);
+  ENSURE(c->e_vy, (size_t)U * 4);
+  ENSURE(c->seg_k0, (size_t)U * 8);
+  ENSURE(c->seg_v0, (size_t)U * 4);
+  ENSURE(c->pc, ((size_t)U + 1) * 4);
+  ENSURE(c->poff, ((size_t)U + 1) * 4);
+  const WT *mir = c->pd_mir.as<WT>();
+  hipLaunchKernelGGL(k_pd_mirror<WT>, dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, word_nt, c->pd_mir.as<WT>());
+  auto sort_keys_of = [&](const WT *src, const ComboFields &cf, DBuf &kout, DBuf &vout) -> int {
+    if (k32) {
+      hipLaunchKernelGGL((k_combo_keys<u32, WT>), dim3(blocks_for(U)), dim3(256), 0, st, src, U, cf,
+                         c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
+      TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), kout.as<u32>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
+    } else {
+      hipLaunchKernelGGL((k_combo_keys<u64, WT>), dim3(blocks_for(U)), dim3(256), 0, st, src, U, cf,
+                         c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
+      TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), kout.as<u64>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
+    }
+    return HUMID_OK;
+  };
+  u64 raw = 0;                                   // pairs collected so far (with duplicates)
+  const u32 jwalk = c->walk_max;                 // candidates one lane verifies for one entry (0: all)
+  for (u32 cb = 0; cb < plan.ncombo; cb++) {
+    const ComboFields cf = plan_fields(plan, cb);
+    TRY(sort_keys_of(g_word, cf, c->e_kx, c->e_vx));
+    TRY(sort_keys_of(mir, cf, c->e_ky, c->e_vy));
+    for (u32 side = 0; side < 2; side++) {       // 0: the leaves themselves, 1: their mirrors
+      const void *ky = side ? c->e_ky.p : c->e_kx.p;
+      const u32 *vy = side ? c->e_vy.as<u32>() : c->e_vx.as<u32>();
+      const WT *yw = side ? mir : g_word;
+      HIPCHK(hipMemsetAsync(c->pc.as<u32>() + U, 0, 4, st));
+      HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
+#define PD_JOIN(FILL, KT, PC, POFF, OUT)                                                                              \
+  hipLaunchKernelGGL((k_pd_join<FILL, KT, WT>), dim3(blocks_for(U)), dim3(256), 0, st, c->e_kx.as<KT>(), c->e_vx.as<u32>(), \
+                     (const KT *)ky, vy, U, g_word, yw, distance, PC, POFF, OUT, jwalk, &c->d_ctr[CTR_BIGMASK])
+#define PD_CHUNKS(FILL, KT, NP, PC, POFF, OUT)                                                                        \
+  hipLaunchKernelGGL((k_pd_join_chunks<FILL, KT, WT>), dim3(blocks_for(NP)), dim3(256), 0, st, c->e_kx.as<KT>(),     \
+                     c->e_vx.as<u32>(), (const KT *)ky, vy, U, (const u32 *)c->e_runlo.as<u32>(),                     \
+                     (const u32 *)c->e_choff.as<u32>(), (u32)(NP), jwalk, g_word, yw, distance, PC, POFF, OUT)
+      if (k32) PD_JOIN(false, u32, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+      else PD_JOIN(false, u64, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+      TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), (u64)U + 1));
+      HIPCHK(hipGetLastError());
+      TRY(read_counters(c, c->poff.as<u32>() + U));
+      u64 found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+      u64 n_pieces = 0;                          // > 0: this join goes through the pieces
+      if (c->h_ctr[CTR_BIGMASK]) {
+        // some run of equal keys is longer than one lane walks: every run in pieces of jwalk candidates
+        ENSURE(c->e_runlo, ((size_t)U + 1) * 4);
+        ENSURE(c->e_nch, ((size_t)U + 1) * 4);
+        ENSURE(c->e_choff, ((size_t)U + 1) * 4);
+        if (k32) hipLaunchKernelGGL(k_edit_chunks<u32>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u32>(), (const u32 *)ky, U,
+                                    jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
+        else hipLaunchKernelGGL(k_edit_chunks<u64>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u64>(), (const u64 *)ky, U,
+                                jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
+        TRY(exscan_u32(c, c->e_nch.as<u32>(), c->e_choff.as<u32>(), (u64)U + 1));
+        HIPCHK(hipGetLastError());
+        TRY(read_counters(c, c->e_choff.as<u32>() + U));
+        n_pieces = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+        if (n_pieces >= 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pieces in the strand-symmetric search");
+        ENSURE(c->e_pc2, ((size_t)n_pieces + 1) * 4);
+        ENSURE(c->e_poff2, ((size_t)n_pieces + 1) * 4);
+        HIPCHK(hipMemsetAsync(c->e_pc2.as<u32>() + n_pieces, 0, 4, st));
+        if (k32) PD_CHUNKS(false, u32, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+        else PD_CHUNKS(false, u64, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+        TRY(exscan_u32(c, c->e_pc2.as<u32>(), c->e_poff2.as<u32>(), n_pieces + 1));
+        HIPCHK(hipGetLastError());
+        TRY(read_counters(c, c->e_poff2.as<u32>() + n_pieces));
+        found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+      }
+      if (found == 0) continue;
+      if (raw + found >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pairs in the strand-symmetric search");
+      if ((raw + found) * 8 > c->e_raw.cap) {                 // grow, keeping what is there
+        DBuf bigger;
+        HIPCHK(bigger.ensure((size_t)((raw + found) * 8 * 2)));
+        if (raw) HIPCHK(hipMemcpyAsync(bigger.p, c->e_raw.p, (size_t)raw * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        c->e_raw = std::move(bigger);
+      }
+      if (n_pieces) {
+        if (k32) PD_CHUNKS(true, u32, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
+        else PD_CHUNKS(true, u64, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
+      } else if (k32) PD_JOIN(true, u32, (u32 *)nullptr, (const u32 *)c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
+      else PD_JOIN(true, u64, (u32 *)nullptr, (const u32 *)c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
+#undef PD_CHUNKS
+#undef PD_JOIN
+      raw += found;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  if (raw == 0) return HUMID_OK;
+  TRY(unique_edges(c, c->e_raw.as<u64>(), raw, U, n_edges_out));
+  return HUMID_OK;
+}
+
 // The un-permute in two coalesced passes (kernels_part.hip.h): position i of the partition order
 // (pk_vals = read, pslot = padded slot of its word) -> cluster_id / keep in read order, or, packed,
 // cluster id | keep << 31 per read.  *done = false: the read set is too large for the bin table
@@ -2407,7 +2530,18 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     return state_publish(c, CtxState::RUN);
   }
   u32 n_pair_segs = 0;
-  if (c->edit && distance >= 2) {
+  if (c->pd_run && distance >= 1) {
+    // strand-symmetric run: the pairs of the plain and of the mirror join (paired_edges), given to the graph stage
+    u64 E = 0;
+    TRY(paired_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &E));
+    static const u64 no_edges = 0;
+    if (c->use_compact)
+      TRY(stage_graph_compact<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
+                                  E ? c->e_edges.as<u64>() : &no_edges, E));
+    else
+      TRY(stage_graph<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
+                          E ? c->e_edges.as<u64>() : &no_edges, E));
+  } else if (c->edit && distance >= 2) {
     // -e: Levenshtein neighbours (src/humid.cc:140-158); distance <= 1 IS the Hamming search
     u64 E = 0;
     TRY(edit_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &E));
@@ -2641,6 +2775,77 @@ static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64
   c->bc_N = n_reads;
   return run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method, d_cid,
                               d_keep, sum);
+}
+
+// ---- strand-symmetric runs (humid_dedup_run_paired*) ------------------------------------------------------------
+static int check_paired_args(humid_ctx *c, u32 word_nt) {
+  if (word_nt == 0) return fail(c, HUMID_E_INVALID, "word_nt must be >= 1");
+  if (word_nt > 64) return fail(c, HUMID_E_UNSUPPORTED, "word_nt %u > 64 is not supported", word_nt);
+  if (word_nt & 1u) return fail(c, HUMID_E_INVALID, "a strand-symmetric word has two halves: word_nt %u is odd", word_nt);
+  return HUMID_OK;
+}
+
+// canonical words and strands of device arrays; nothing waits here
+template <class WT>
+static int pd_canonical_launch(humid_ctx *c, const WT *d_words, const u8 *d_filt, u32 N, u32 word_nt, WT *d_out, u8 *d_strand) {
+  if (N == 0) return HUMID_OK;
+  hipLaunchKernelGGL(k_pd_canonical<WT>, dim3(blocks_for(N)), dim3(256), 0, c->stream, d_words, d_filt, N, word_nt, d_out, d_strand);
+  HIPCHK(hipGetLastError());
+  return HUMID_OK;
+}
+
+// The whole paired pass: canonical words and strands into context buffers, run_device over the canonical words with
+// the neighbour pairs of paired_edges, then the strand tallies of the clusters and their summary (one host wait).
+template <class WT>
+static int run_paired_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_reads, u32 word_nt, u32 distance,
+                             u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
+  TRY(check_paired_args(c, word_nt));
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (c->edit && distance >= 2)
+    return fail(c, HUMID_E_UNSUPPORTED, "edit distance %u against a mirrored word is not supported (option edit_distance)", distance);
+  if (n_reads && (!d_words || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (sizeof(WT) == 16 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const u32 N = (u32)n_reads;
+  ENSURE(c->pd_words, (size_t)N * sizeof(WT) + 16);
+  ENSURE(c->pd_strand, (size_t)N + 16);
+  TRY(pd_canonical_launch<WT>(c, d_words, d_filt, N, word_nt, c->pd_words.as<WT>(), c->pd_strand.as<u8>()));
+  struct Running { humid_ctx *c; ~Running() { c->pd_run = false; } } running{c};
+  c->pd_run = true;
+  TRY(run_device<WT>(c, c->pd_words.as<WT>(), d_filt, n_reads, word_nt, distance, method, d_cid, d_keep, sum));
+  c->pd_run = false;
+  const u32 C = (u32)c->C;
+  humid_strand_summary ps;
+  memset(&ps, 0, sizeof ps);
+  ps.n_clusters = C;
+  auto undo = [&](int rc) { state_reset(c); return rc; };      // (a failure here leaves no run behind)
+  if (N && C) {
+    hipError_t e = c->pd_top.ensure(((size_t)C + 1) * 4, &c->arena);
+    if (e == hipSuccess) e = c->pd_bottom.ensure(((size_t)C + 1) * 4, &c->arena);
+    if (e == hipSuccess) e = c->pd_ctr.ensure(PD_CTRS * sizeof(ull), &c->arena);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pd_top.p, 0, ((size_t)C + 1) * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pd_bottom.p, 0, ((size_t)C + 1) * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pd_ctr.p, 0, PD_CTRS * sizeof(ull), st);
+    if (e != hipSuccess) return undo(fail(c, e == hipErrorOutOfMemory ? HUMID_E_NOMEM : HUMID_E_HIP, "strand tally: %s", hipGetErrorString(e)));
+    hipLaunchKernelGGL(k_pd_tally, dim3(blocks_for(N)), dim3(256), 0, st, (const u32 *)d_cid, (const u8 *)c->pd_strand.p, N, C,
+                       c->pd_top.as<u32>(), c->pd_bottom.as<u32>());
+    hipLaunchKernelGGL(k_pd_summary, dim3(grid_stride_blocks(C)), dim3(256), 0, st, (const u32 *)c->pd_top.p,
+                       (const u32 *)c->pd_bottom.p, C, c->pd_ctr.as<ull>());
+    ull h[PD_CTRS];
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h, c->pd_ctr.p, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return undo(fail(c, HUMID_E_HIP, "strand tally: %s", hipGetErrorString(e)));
+    ps.duplex = h[PD_DUPLEX]; ps.top_only = h[PD_TOP_ONLY]; ps.bottom_only = h[PD_BOTTOM_ONLY];
+    ps.top_reads = h[PD_TOP_READS]; ps.bottom_reads = h[PD_BOTTOM_READS];
+  }
+  c->pd_sum = ps;
+  c->pd_N = n_reads;
+  c->state.paired = true;
+  return HUMID_OK;
 }
 
 #endif  // HUMID_PIPELINE_HIP_H

@@ -515,6 +515,57 @@ int humid_optical_duplicates_device(humid_ctx *ctx, const uint32_t *d_cluster_id
                                     uint64_t n_clusters, uint32_t distance, uint8_t *d_optical_out,
                                     uint32_t *d_origin_out, uint32_t *d_per_cluster_out, humid_optical_summary *summary);
 
+/* ---- strand-symmetric (duplex) deduplication --------------------------------
+ * For duplex UMIs and unstranded paired-end libraries: a molecule read from its other strand arrives with the two
+ * halves of its word exchanged.  word_nt = n must be even, 2 <= n <= 64; h = n / 2; a word is A.B, the first h
+ * nucleotides followed by the last h (word layout as everywhere: one uint64 for n <= 32, two for n > 32).
+ *   mirror      m(A.B) = B.A: on the packed 2n-bit value v, m(v) = ((v & (2^n - 1)) << n) | (v >> n).
+ *   canonical   c(w) = min(w, m(w)) by unsigned value.
+ *   strand      of a usable read: HUMID_STRAND_TOP when w == c(w) (palindromes w == m(w) included), else
+ *               HUMID_STRAND_BOTTOM; a filtered read has HUMID_STRAND_NONE and its word is not read.
+ *   leaves      the distinct canonical words of the usable reads, ascending; count = the reads of either strand,
+ *               first_read = the smallest read index.
+ *   neighbours  two different leaves u, v with min(ham(u, v), ham(u, m(v))) <= distance; lists ascending, every
+ *               neighbour once, a leaf never its own neighbour (even when ham(u, m(u)) <= distance).
+ * Clusters, cluster_id, keep, the numbering and the summary are those of humid_dedup_run over these leaves and
+ * neighbour lists: keep[r] = 1 for the first read whose CANONICAL word is its cluster's maxLeaf.  distance == 0 is the
+ * plain run on the canonical words.  (min() in front of a plain run is not enough: an error near the start of a half
+ * flips which of w and m(w) is smaller, and two reads one substitution apart then sit n / 2 apart.)
+ *
+ * humid_paired_canonical*: words_out (may be words; a filtered read's entry is left as it is) and strand_out (u8[N])
+ * per read.  Stand-alone: needs no run and leaves the results of the last run alone.
+ * humid_dedup_run_paired*: the whole pass.  It counts as a plain run for every accessor: humid_get_leaves (canonical
+ * words), humid_get_adjacency, humid_get_clusters, humid_get_histogram and humid_get_group_stats (G = 1) answer for it,
+ * and humid_select_best* is valid after it when given the CANONICAL words.  Odd word_nt returns HUMID_E_INVALID,
+ * word_nt > 64 HUMID_E_UNSUPPORTED, option "edit_distance" together with distance >= 2 HUMID_E_UNSUPPORTED.
+ * n_reads == 0 and an all-filtered input return HUMID_OK with empty results.  Not available for grouped or keyed
+ * runs or the multi-GPU pass.  The context stays usable whatever is returned.
+ * On the device (kernels_paired.hip.h): canonical words; the count stage over them; per combination of the pigeonhole
+ * plan two sorted-key joins over the leaves, one against themselves and one against their mirrors, verified by
+ * popcount; the pairs made unique and given to the graph stage; per-read outputs; strand tallies per cluster.
+ * humid_get_strands: after a paired run (HUMID_E_STATE otherwise) strand[i] of the first min(cap, n_reads) reads,
+ * top[c - 1] / bottom[c - 1] (u32[clusters]) the reads of each strand of cluster c, and the summary: n_clusters;
+ * duplex = clusters with both; top_only / bottom_only; top_reads / bottom_reads.  Any pointer may be NULL.
+ *   *_device: DEVICE pointers for the per-read arrays; summary stays a host pointer. */
+#define HUMID_STRAND_TOP 0u
+#define HUMID_STRAND_BOTTOM 1u
+#define HUMID_STRAND_NONE 2u
+typedef struct humid_strand_summary {
+  uint64_t n_clusters, duplex, top_only, bottom_only, top_reads, bottom_reads;
+} humid_strand_summary;
+int humid_paired_canonical(humid_ctx *ctx, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads,
+                           uint32_t word_nt, uint64_t *words_out, uint8_t *strand_out);
+int humid_paired_canonical_device(humid_ctx *ctx, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                  uint32_t word_nt, uint64_t *d_words_out, uint8_t *d_strand_out);
+int humid_dedup_run_paired(humid_ctx *ctx, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads,
+                           uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep,
+                           humid_summary *summary);
+int humid_dedup_run_paired_device(humid_ctx *ctx, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                  uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *d_cluster_id,
+                                  uint8_t *d_keep, humid_summary *summary);
+int humid_get_strands(humid_ctx *ctx, uint8_t *strand, uint64_t cap, uint32_t *top, uint32_t *bottom,
+                      humid_strand_summary *summary);
+
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
  * NLeaf src/leaf.h:6-9; Cluster src/cluster.h:12-18).  Host output buffers sized by
