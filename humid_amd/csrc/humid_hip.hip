@@ -23,12 +23,10 @@
 //
 // Translation units (round 3): this file = the context, the single-GPU entry points and the accessors of
 // include/humid_hip.h; humid_exchange.hip = the exchange pass and the multi-GPU stage entry points; shm.cpp = the
-// shared-memory gather (no HIP); pipeline.hip.h = the pipeline itself, with internal linkage, compiled into both.
+// shared-memory gather (no HIP); pipeline.hip.h = the pipeline itself, with internal linkage, compiled into both;
+// passes.hip.h = the post-run passes (best read, consensus, optical duplicates) over device arrays, into this file only.
 #include "pipeline.hip.h"
-#include "kernels_best.hip.h"
-#include "kernels_consensus.hip.h"
-#include "kernels_optical.hip.h"
-static_assert(OPT_WALK_DEFAULT == 64u, "humid_ctx::op_walk starts at the default");
+#include "passes.hip.h"
 
 static std::string g_err;
 // (the error text of calls without a context: also set from humid_exchange.hip and shm.cpp)
@@ -277,13 +275,15 @@ int humid_dedup_run_keyed_corrected_device(humid_ctx *c, const uint64_t *d_words
 }
 
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
-// kind: what the run is (RUN_GROUPED: group may be null with n_groups = 1; RUN_KEYED on: key, null only without reads).
+// kind: what the run is (RUN_GROUPED: group may be null with n_groups = 1; RUN_KEYED on: key, null only without reads);
+// paired: the strand-symmetric run (RUN_PLAIN only; CtxState::paired).
 // Everything the kind refuses is refused here, before any copy: a refused shape moves nothing.
-static int run_host(humid_ctx *c, RunKind kind, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
+static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
                     const uint32_t *group, uint32_t n_groups, const uint64_t *key, uint64_t n_reads, uint32_t word_nt,
                     uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   state_reset(c);
+  if (paired) TRY(check_paired_run_args(c, n_reads, word_nt, distance, method));
   if (kind == RUN_CORRECTED && !c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
   if (kind >= RUN_KEYED) {
     TRY(check_run_args(c, n_reads, word_nt, method, 64));
@@ -340,6 +340,7 @@ static int run_host(humid_ctx *c, RunKind kind, const uint64_t *words, const uin
     const u64 *d_k = c->kr_key_in.as<u64>();
     u32 *d_cid = c->out_cid.as<u32>();
     u8 *d_keep = c->out_keep.as<u8>();
+    if (paired) return run_paired_device(c, d_w, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
     switch (kind) {
       case RUN_CORRECTED: return run_keyed_corrected_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
       case RUN_KEYED: return run_keyed_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
@@ -366,35 +367,35 @@ static int run_host(humid_ctx *c, RunKind kind, const uint64_t *words, const uin
 int humid_dedup_run(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads,
                     uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                     uint8_t *keep, humid_summary *summary) {
-  return run_host(c, RUN_PLAIN, words, filtered, nullptr, nullptr, 1, nullptr, n_reads, word_nt, distance, method, cluster_id, keep,
+  return run_host(c, RUN_PLAIN, false, words, filtered, nullptr, nullptr, 1, nullptr, n_reads, word_nt, distance, method, cluster_id, keep,
                   summary);
 }
 
 int humid_dedup_run_grouped(humid_ctx *c, const uint64_t *words, const uint32_t *group, const uint8_t *filtered,
                             uint64_t n_reads, uint32_t word_nt, uint32_t n_groups, uint32_t distance, uint32_t method,
                             uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
-  return run_host(c, RUN_GROUPED, words, filtered, nullptr, group, n_groups, nullptr, n_reads, word_nt, distance, method,
+  return run_host(c, RUN_GROUPED, false, words, filtered, nullptr, group, n_groups, nullptr, n_reads, word_nt, distance, method,
                   cluster_id, keep, summary);
 }
 
 int humid_dedup_run_keyed(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
                           uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id,
                           uint8_t *keep, humid_summary *summary) {
-  return run_host(c, RUN_KEYED, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id, keep,
+  return run_host(c, RUN_KEYED, false, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id, keep,
                   summary);
 }
 
 int humid_dedup_run_keyed_corrected(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
                                     uint64_t n_reads, uint32_t word_nt, uint32_t distance, uint32_t method,
                                     uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
-  return run_host(c, RUN_CORRECTED, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id,
+  return run_host(c, RUN_CORRECTED, false, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id,
                   keep, summary);
 }
 
 int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
                           uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   if (n_reads && !bases) return fail(c, HUMID_E_INVALID, "null buffer");
-  return run_host(c, RUN_PLAIN, nullptr, nullptr, bases ? bases : (const uint8_t *)"", nullptr, 1, nullptr, n_reads, word_nt, distance,
+  return run_host(c, RUN_PLAIN, false, nullptr, nullptr, bases ? bases : (const uint8_t *)"", nullptr, 1, nullptr, n_reads, word_nt, distance,
                   method, cluster_id, keep, summary);
 }
 
@@ -434,9 +435,6 @@ static void gkey_split(const humid_ctx *c, const std::vector<u64> &iw, size_t U,
     HIPCHK(hipSetDevice(c->device));                                                          \
     TRY(expand_compact(c));                                                                   \
   } while (0)
-
-#define D2H(dst, src, bytes)                                                                  \
-  do { if ((dst) && (bytes)) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, c->stream)); } while (0)
 
 int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *first_read,
                      uint32_t *degree, uint32_t *cluster_id, uint8_t *is_max_leaf) {
@@ -557,7 +555,7 @@ int humid_whitelist_correct_device(humid_ctx *c, const uint64_t *d_key, const ui
                                    uint64_t *d_key_out, uint8_t *d_status, uint64_t counts[5]) {
   TRY(whitelist_correct_args(c, d_key, d_filtered, n_reads));
   HIPCHK(hipSetDevice(c->device));
-  ENSURE(c->wc_counts, 5 * sizeof(ull));
+  PASS_ENSURE(c->wc_counts, 5 * sizeof(ull));
   TRY(wl_correct_launch(c, d_key, d_filtered, (u32)n_reads, d_key_out, d_status, nullptr, c->wc_counts.as<ull>()));
   D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -568,23 +566,19 @@ int humid_whitelist_correct(humid_ctx *c, const uint64_t *key, const uint8_t *fi
                             uint64_t *key_out, uint8_t *status, uint64_t counts[5]) {
   TRY(whitelist_correct_args(c, key, filtered, n_reads));
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
   const size_t n = (size_t)n_reads;
-  ENSURE(c->wc_key, n * 8 + 16);
-  ENSURE(c->wc_filt, n + 16);
-  ENSURE(c->wc_out, n * 8 + 16);
-  ENSURE(c->wc_status, n + 16);
-  ENSURE(c->wc_counts, 5 * sizeof(ull));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->wc_key.p, key, n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->wc_filt.p, filtered, n, hipMemcpyHostToDevice, st));
-  }
-  TRY(wl_correct_launch(c, c->wc_key.as<u64>(), c->wc_filt.as<u8>(), (u32)n, c->wc_out.as<u64>(), c->wc_status.as<u8>(), nullptr,
-                        c->wc_counts.as<ull>()));
-  D2H(key_out, c->wc_out.p, n * 8);
-  D2H(status, c->wc_status.p, n);
+  u64 *d_key, *d_out;
+  u8 *d_filt, *d_status;
+  STAGE_IN(d_key, 0, key, n * 8);
+  STAGE_IN(d_filt, 1, filtered, n);
+  STAGE_OUT(d_out, 0, n * 8);
+  STAGE_OUT(d_status, 1, n);
+  PASS_ENSURE(c->wc_counts, 5 * sizeof(ull));
+  TRY(wl_correct_launch(c, d_key, d_filt, (u32)n, d_out, d_status, nullptr, c->wc_counts.as<ull>()));
+  D2H(key_out, d_out, n * 8);
+  D2H(status, d_status, n);
   D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 
@@ -783,22 +777,20 @@ int humid_paired_canonical(humid_ctx *c, const uint64_t *words, const uint8_t *f
   TRY(paired_canonical_args(c, words, filtered, n_reads, word_nt, words_out, strand_out));
   if (n_reads == 0) return HUMID_OK;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
   const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
-  ENSURE(c->pd_in_words, n * wbytes + 16);
-  ENSURE(c->pd_in_filt, n + 16);
-  ENSURE(c->pd_out_strand, n + 16);
-  HIPCHK(hipMemcpyAsync(c->pd_in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->pd_in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
+  u64 *d_words;
+  u8 *d_filt, *d_strand;
+  STAGE_IN(d_words, 0, words, n * wbytes);
+  STAGE_IN(d_filt, 1, filtered, n);
+  STAGE_OUT(d_strand, 0, n);
   TRY(with_word_type(word_nt, [&](auto *w) {
     typedef typename std::remove_const<typename std::remove_pointer<decltype(w)>::type>::type WT;
-    return pd_canonical_launch<WT>(c, c->pd_in_words.as<WT>(), c->pd_in_filt.as<u8>(), (u32)n, word_nt, c->pd_in_words.as<WT>(),
-                                   c->pd_out_strand.as<u8>());
+    return pd_canonical_launch<WT>(c, (const WT *)d_words, d_filt, (u32)n, word_nt, (WT *)d_words, d_strand);
   }));
   // (in place on the device: the staged copy of a filtered read's word comes back as it went in)
-  HIPCHK(hipMemcpyAsync(words_out, c->pd_in_words.p, n * wbytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(strand_out, c->pd_out_strand.p, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  D2H(words_out, d_words, n * wbytes);
+  D2H(strand_out, d_strand, n);
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 
@@ -815,37 +807,8 @@ int humid_dedup_run_paired_device(humid_ctx *c, const uint64_t *d_words, const u
 
 int humid_dedup_run_paired(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
                            uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
-  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  state_reset(c);
-  TRY(check_paired_args(c, word_nt));                        // (a refused shape moves nothing)
-  TRY(check_run_args(c, n_reads, word_nt, method, 64));
-  if (c->edit && distance >= 2)
-    return fail(c, HUMID_E_UNSUPPORTED, "edit distance %u against a mirrored word is not supported (option edit_distance)", distance);
-  if (n_reads && (!words || !filtered || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
-  ENSURE(c->in_words, n * wbytes + 16);
-  ENSURE(c->in_filt, n + 8);
-  ENSURE(c->out_cid, n * 4 + 8);
-  ENSURE(c->out_keep, n + 8);
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st));
-  }
-  humid_summary s;
-  memset(&s, 0, sizeof s);
-  TRY(with_word_type(word_nt, [&](auto *w) {
-    return run_paired_device(c, (decltype(w))c->in_words.p, c->in_filt.as<u8>(), n_reads, word_nt, distance, method,
-                             c->out_cid.as<u32>(), c->out_keep.as<u8>(), &s);
-  }));
-  hipError_t he = hipSuccess;
-  if (n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess) he = hipStreamSynchronize(st);
-  if (he != hipSuccess) { state_reset(c); return fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
-  if (summary) *summary = s;
-  return HUMID_OK;
+  return run_host(c, RUN_PLAIN, true, words, filtered, nullptr, nullptr, 1, nullptr, n_reads, word_nt, distance, method, cluster_id, keep,
+                  summary);
 }
 
 int humid_get_strands(humid_ctx *c, uint8_t *strand, uint64_t cap, uint32_t *top, uint32_t *bottom, humid_strand_summary *summary) {
@@ -882,41 +845,8 @@ int humid_select_best_device(humid_ctx *c, const uint64_t *d_words, const uint32
   TRY(select_best_args(c, d_words, d_cluster_id, d_keep, d_score, n_reads, word_nt, scope, d_keep_out));
   if (n_changed) *n_changed = 0;
   if (n_reads == 0) return HUMID_OK;
-  const bool wide = word_nt > 32, leaf = scope == HUMID_BEST_LEAF;
-  if (wide && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const u32 N = (u32)n_reads, C = (u32)c->C;
-  ENSURE(c->bs_rep, ((size_t)C + 1) * 4);
-  ENSURE(c->bs_best, ((size_t)C + 1) * 8);
-  ENSURE(c->bs_ctr, BEST_CTRS * 4);
-  u32 *rep = c->bs_rep.as<u32>(), *ctr = c->bs_ctr.as<u32>();
-  ull *best = c->bs_best.as<ull>();
-  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
-  HIPCHK(hipMemsetAsync(best, 0, ((size_t)C + 1) * 8, st));
-  HIPCHK(hipMemsetAsync(ctr, 0, BEST_CTRS * 4, st));
-  hipLaunchKernelGGL(k_best_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, N, C, rep, ctr);
-  const dim3 grid(blocks_for(N)), block(256);
-  if (wide && leaf)
-    hipLaunchKernelGGL((k_best_vote<W2, true>), grid, block, 0, st, (const W2 *)d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
-  else if (wide)
-    hipLaunchKernelGGL((k_best_vote<W2, false>), grid, block, 0, st, (const W2 *)d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
-  else if (leaf)
-    hipLaunchKernelGGL((k_best_vote<u64, true>), grid, block, 0, st, d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
-  else
-    hipLaunchKernelGGL((k_best_vote<u64, false>), grid, block, 0, st, d_words, d_cluster_id, d_score, N, C, (const u32 *)rep, (const u32 *)ctr, best);
-  hipLaunchKernelGGL(k_best_write, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, N, C, (const u32 *)rep, (const ull *)best,
-                     d_keep_out, d_rep_out, ctr);
-  HIPCHK(hipGetLastError());
-  u32 h[BEST_CTRS] = {0, 0, 0, 0};
-  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));                          // the pass's one host wait
-  if (h[BEST_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_select_best: a cluster id above the %u clusters of the last run", C);
-  if (h[BEST_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_select_best: a cluster has more than one read with keep == 1");
-  if (h[BEST_CLAIMS] != C)
-    return fail(c, HUMID_E_INVALID, "humid_select_best: %u reads with keep == 1 for the %u clusters of the last run", h[BEST_CLAIMS], C);
-  if (n_changed) *n_changed = h[BEST_CHANGED];
-  return HUMID_OK;
+  if (word_nt > 32 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  return best_pass(c, d_words, d_cluster_id, d_keep, d_score, n_reads, word_nt, scope, d_keep_out, d_rep_out, n_changed);
 }
 
 int humid_select_best(humid_ctx *c, const uint64_t *words, const uint32_t *cluster_id, const uint8_t *keep,
@@ -926,30 +856,24 @@ int humid_select_best(humid_ctx *c, const uint64_t *words, const uint32_t *clust
   if (n_changed) *n_changed = 0;
   if (n_reads == 0) return HUMID_OK;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t n = (size_t)n_reads, wbytes = word_nt > 32 ? 16 : 8;
-  ENSURE(c->bs_words, n * wbytes + 16);
-  ENSURE(c->bs_cid, n * 4 + 16);
-  ENSURE(c->bs_keep, n + 16);
-  ENSURE(c->bs_score, n * 4 + 16);
-  ENSURE(c->bs_keep_out, n + 16);
-  if (rep_out) ENSURE(c->bs_rep_out, n * 4 + 16);
-  HIPCHK(hipMemcpyAsync(c->bs_words.p, words, n * wbytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->bs_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->bs_keep.p, keep, n, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->bs_score.p, score, n * 4, hipMemcpyHostToDevice, st));
-  TRY(humid_select_best_device(c, c->bs_words.as<u64>(), c->bs_cid.as<u32>(), c->bs_keep.as<u8>(), c->bs_score.as<u32>(), n_reads,
-                               word_nt, scope, c->bs_keep_out.as<u8>(), rep_out ? c->bs_rep_out.as<u32>() : nullptr, n_changed));
-  D2H(keep_out, c->bs_keep_out.p, n);
-  D2H(rep_out, c->bs_rep_out.p, n * 4);
-  HIPCHK(hipStreamSynchronize(st));
+  const size_t n = (size_t)n_reads;
+  u64 *d_words;
+  u32 *d_cid, *d_score, *d_rep_out = nullptr;
+  u8 *d_keep, *d_keep_out;
+  STAGE_IN(d_words, 0, words, n * (word_nt > 32 ? 16 : 8));
+  STAGE_IN(d_cid, 1, cluster_id, n * 4);
+  STAGE_IN(d_keep, 2, keep, n);
+  STAGE_IN(d_score, 3, score, n * 4);
+  STAGE_OUT(d_keep_out, 0, n);
+  if (rep_out) STAGE_OUT(d_rep_out, 1, n * 4);
+  TRY(best_pass(c, d_words, d_cid, d_keep, d_score, n_reads, word_nt, scope, d_keep_out, d_rep_out, n_changed));
+  D2H(keep_out, d_keep_out, n);
+  D2H(rep_out, d_rep_out, n * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 
 // ---- consensus reads per cluster (kernels_consensus.hip.h) -------------------------------------------------------
-// (memory of the pass: plain allocations, never the slab a run carves its buffers from)
-#define CS_ENSURE(buf, bytes) HIPCHK((buf).ensure((bytes)))
-
 static int consensus_args(humid_ctx *c, const void *bases, const void *quals, const void *off, const void *cid, const void *keep,
                           uint64_t n_reads, uint32_t min_q, uint32_t cap_q) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
@@ -965,84 +889,7 @@ int humid_consensus_device(humid_ctx *c, const uint8_t *d_bases, const uint8_t *
                            const uint32_t *d_cluster_id, const uint8_t *d_keep, uint64_t n_reads, uint64_t n_clusters,
                            uint32_t min_q, uint32_t cap_q, humid_consensus_summary *summary) {
   TRY(consensus_args(c, d_bases, d_quals, d_off, d_cluster_id, d_keep, n_reads, min_q, cap_q));
-  if (summary) memset(summary, 0, sizeof *summary);
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  if (n_reads == 0 || n_clusters == 0) {                     // an empty result: out_off = {0}
-    CS_ENSURE(c->cs_ooff, 8);
-    HIPCHK(hipMemsetAsync(c->cs_ooff.p, 0, 8, st));
-    HIPCHK(hipStreamSynchronize(st));
-    c->cs_sum = humid_consensus_summary{};
-    c->cs_valid = true;
-    return HUMID_OK;
-  }
-  if (n_clusters > n_reads)                                  // (some cluster then has no read at all, so no kept one)
-    return fail(c, HUMID_E_INVALID, "humid_consensus: %llu clusters for %llu reads: a cluster without a read with keep == 1",
-                (ull)n_clusters, (ull)n_reads);
-  const u32 N = (u32)n_reads, C = (u32)n_clusters, min_q1 = min_q < 1 ? 1u : min_q;
-  const size_t max_big = (size_t)N / CONS_BIG + 2, max_piece = (size_t)N / CONS_PIECE + max_big + 2;
-  CS_ENSURE(c->cs_rep, ((size_t)C + 1) * 4);
-  CS_ENSURE(c->cs_cnt, ((size_t)C + 2) * 4);
-  CS_ENSURE(c->cs_moff, ((size_t)C + 1) * 4);
-  CS_ENSURE(c->cs_ctr, CONS_CTRS * 8);
-  CS_ENSURE(c->cs_ooff, ((size_t)C + 1) * 8);
-  CS_ENSURE(c->cs_big, max_big * sizeof(ConsBig));
-  CS_ENSURE(c->cs_piece, max_piece * sizeof(ConsPiece));
-  u32 *rep = c->cs_rep.as<u32>(), *cnt = c->cs_cnt.as<u32>(), *moff = c->cs_moff.as<u32>();
-  ull *ctr = c->cs_ctr.as<ull>();
-  u64 *ooff = c->cs_ooff.as<u64>();
-  ConsBig *big = c->cs_big.as<ConsBig>();
-  ConsPiece *piece = c->cs_piece.as<ConsPiece>();
-  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
-  HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)C + 2) * 4, st));
-  HIPCHK(hipMemsetAsync(ctr, 0, CONS_CTRS * 8, st));
-  hipLaunchKernelGGL(k_cons_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, d_off, N, (u64)n_bytes, C, rep, cnt, ctr);
-  TRY(exscan_in<u64>(c, ConsLenIn{rep, d_off, ctr, C}, ooff, (u64)C + 1));
-  TRY(exscan_in<u32>(c, PtrIn<u32>{cnt + 1}, moff, (u64)C + 1));
-  hipLaunchKernelGGL(k_cons_big_list, dim3(grid_stride_blocks(C)), dim3(256), 0, st, (const u32 *)cnt, (const u64 *)ooff, C, big, piece, ctr);
-  HIPCHK(hipGetLastError());
-  ull h[CONS_CTRS] = {};
-  u64 total = 0;
-  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&total, ooff + C, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));                          // the first host wait: is the input well formed, and the total that sizes the output
-  if (h[CONS_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_consensus: a cluster id above the %u clusters given", C);
-  if (h[CONS_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_consensus: a cluster has more than one read with keep == 1");
-  if (h[CONS_ERR] & 4u) return fail(c, HUMID_E_INVALID, "humid_consensus: off decreases");
-  if (h[CONS_ERR] & 8u) return fail(c, HUMID_E_INVALID, "humid_consensus: off[n_reads] lies beyond the %llu bytes given", (ull)n_bytes);
-  if (h[CONS_CLAIMS] != C)
-    return fail(c, HUMID_E_INVALID, "humid_consensus: %llu reads with keep == 1 for %u clusters", h[CONS_CLAIMS], C);
-  if (h[CONS_ERR] & 16u)
-    return fail(c, HUMID_E_OVERFLOW, "humid_consensus: a cluster of more than %u reads (32-bit sums)", CONS_MAX_DEPTH);
-  const u32 n_big = (u32)h[CONS_NBIG], n_pieces = (u32)h[CONS_NPIECES];
-  CS_ENSURE(c->cs_ob, (size_t)total + 16);
-  CS_ENSURE(c->cs_oq, (size_t)total + 16);
-  CS_ENSURE(c->cs_depth, (size_t)C * 4);
-  CS_ENSURE(c->cs_errors, (size_t)C * 8);
-  CS_ENSURE(c->cs_cur, ((size_t)C + 1) * 4);
-  CS_ENSURE(c->cs_mem, (size_t)N * 4);
-  HIPCHK(hipMemsetAsync(c->cs_cur.p, 0, ((size_t)C + 1) * 4, st));
-  hipLaunchKernelGGL(k_cons_scatter, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, N, (const u32 *)moff, c->cs_cur.as<u32>(), c->cs_mem.as<u32>());
-  hipLaunchKernelGGL(k_cons_small, dim3(blocks_for(C, 4)), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)rep, (const u32 *)moff,
-                     (const u32 *)c->cs_mem.p, (const u64 *)ooff, C, min_q1, cap_q, c->cs_ob.as<u8>(), c->cs_oq.as<u8>(),
-                     c->cs_depth.as<u32>(), c->cs_errors.as<u64>(), ctr);
-  if (n_big) {
-    const size_t tab_bytes = (size_t)h[CONS_TABCOLS] * 32;
-    CS_ENSURE(c->cs_tab, tab_bytes + 16);
-    HIPCHK(hipMemsetAsync(c->cs_tab.p, 0, tab_bytes, st));
-    hipLaunchKernelGGL(k_cons_piece, dim3(n_pieces), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)moff, (const u32 *)c->cs_mem.p,
-                       (const u64 *)ooff, (const ConsBig *)big, (const ConsPiece *)piece, min_q1, c->cs_tab.as<u32>());
-    hipLaunchKernelGGL(k_cons_final, dim3(n_big), dim3(256), 0, st, d_bases, d_quals, d_off, (const u32 *)rep, (const u32 *)moff,
-                       (const u64 *)ooff, (const ConsBig *)big, (const u32 *)c->cs_tab.p, cap_q, c->cs_ob.as<u8>(), c->cs_oq.as<u8>(),
-                       c->cs_depth.as<u32>(), c->cs_errors.as<u64>(), ctr);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));                          // the second host wait: the summary
-  c->cs_sum = humid_consensus_summary{(u64)C, total, (u64)h[CONS_MULTI], (u64)h[CONS_CHANGED], (u64)h[CONS_VOTES], (u64)h[CONS_ERRORS]};
-  c->cs_valid = true;
-  if (summary) *summary = c->cs_sum;
-  return HUMID_OK;
+  return consensus_pass(c, d_bases, d_quals, d_off, n_bytes, d_cluster_id, d_keep, n_reads, n_clusters, min_q, cap_q, summary);
 }
 
 int humid_consensus(humid_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t n_bytes,
@@ -1050,24 +897,18 @@ int humid_consensus(humid_ctx *c, const uint8_t *bases, const uint8_t *quals, co
                     uint32_t cap_q, humid_consensus_summary *summary) {
   TRY(consensus_args(c, bases, quals, off, cluster_id, keep, n_reads, min_q, cap_q));
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
   const size_t n = (size_t)n_reads, nb = (size_t)n_bytes;
-  if (n) {
-    CS_ENSURE(c->cs_in_bases, nb + 16);
-    CS_ENSURE(c->cs_in_quals, nb + 16);
-    CS_ENSURE(c->cs_in_off, (n + 1) * 8);
-    CS_ENSURE(c->cs_in_cid, n * 4 + 16);
-    CS_ENSURE(c->cs_in_keep, n + 16);
-    if (nb) {
-      HIPCHK(hipMemcpyAsync(c->cs_in_bases.p, bases, nb, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(c->cs_in_quals.p, quals, nb, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(hipMemcpyAsync(c->cs_in_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->cs_in_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->cs_in_keep.p, keep, n, hipMemcpyHostToDevice, st));
+  u8 *d_bases = nullptr, *d_quals = nullptr, *d_keep = nullptr;
+  u64 *d_off = nullptr;
+  u32 *d_cid = nullptr;
+  if (n) {                                                   // (no reads: every pointer may be null, and the pass reads none)
+    STAGE_IN(d_bases, 0, bases, nb);
+    STAGE_IN(d_quals, 1, quals, nb);
+    STAGE_IN(d_off, 2, off, (n + 1) * 8);
+    STAGE_IN(d_cid, 3, cluster_id, n * 4);
+    STAGE_IN(d_keep, 4, keep, n);
   }
-  return humid_consensus_device(c, c->cs_in_bases.as<u8>(), c->cs_in_quals.as<u8>(), c->cs_in_off.as<u64>(), n_bytes,
-                                c->cs_in_cid.as<u32>(), c->cs_in_keep.as<u8>(), n_reads, n_clusters, min_q, cap_q, summary);
+  return consensus_pass(c, d_bases, d_quals, d_off, n_bytes, d_cid, d_keep, n_reads, n_clusters, min_q, cap_q, summary);
 }
 
 int humid_get_consensus(humid_ctx *c, uint64_t cap_bytes, uint64_t *out_off, uint8_t *cons_bases, uint8_t *cons_quals,
@@ -1117,69 +958,8 @@ int humid_optical_duplicates_device(humid_ctx *c, const uint32_t *d_cluster_id, 
                                     uint32_t *d_per_cluster_out, humid_optical_summary *summary) {
   TRY(optical_args(c, d_cluster_id, d_keep, d_tile, d_x, d_y, n_reads, d_optical_out, summary));
   if (n_reads == 0) return HUMID_OK;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  if (n_clusters == 0) {                                     // no read is a member
-    HIPCHK(hipMemsetAsync(d_optical_out, 0, (size_t)n_reads, st));
-    if (d_origin_out) HIPCHK(hipMemsetAsync(d_origin_out, 0xff, (size_t)n_reads * 4, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return HUMID_OK;
-  }
-  if (n_clusters > n_reads)                                  // (some cluster then has no read at all, so no kept one)
-    return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: %llu clusters for %llu reads: a cluster without a read with keep == 1",
-                (ull)n_clusters, (ull)n_reads);
-  const u32 N = (u32)n_reads, C = (u32)n_clusters;
-  const size_t n = (size_t)N;
-  CS_ENSURE(c->op_rep, ((size_t)C + 1) * 4);
-  CS_ENSURE(c->op_bctr, BEST_CTRS * 4);
-  CS_ENSURE(c->op_ctr, OPT_CTRS * 8);
-  CS_ENSURE(c->op_k0, n * 4);
-  CS_ENSURE(c->op_v0, n * 4);
-  CS_ENSURE(c->op_v1, n * 4);
-  CS_ENSURE(c->op_ct, n * 8);
-  CS_ENSURE(c->op_xy, n * 8);
-  CS_ENSURE(c->op_vote, n * 8);
-  CS_ENSURE(c->op_parent, n * 4);
-  CS_ENSURE(c->op_root, n * 4);
-  CS_ENSURE(c->op_best, n * 8);
-  CS_ENSURE(c->op_gsize, n * 4);
-  u32 *rep = c->op_rep.as<u32>(), *bctr = c->op_bctr.as<u32>(), *k0 = c->op_k0.as<u32>(), *v0 = c->op_v0.as<u32>(), *v1 = c->op_v1.as<u32>();
-  u32 *parent = c->op_parent.as<u32>(), *root = c->op_root.as<u32>(), *gsize = c->op_gsize.as<u32>();
-  u64 *ct = c->op_ct.as<u64>(), *xy = c->op_xy.as<u64>(), *vote = c->op_vote.as<u64>();
-  ull *best = c->op_best.as<ull>(), *ctr = c->op_ctr.as<ull>();
-  HIPCHK(hipMemsetAsync(rep, 0xff, ((size_t)C + 1) * 4, st));
-  HIPCHK(hipMemsetAsync(bctr, 0, BEST_CTRS * 4, st));
-  HIPCHK(hipMemsetAsync(ctr, 0, OPT_CTRS * 8, st));
-  HIPCHK(hipMemsetAsync(best, 0xff, n * 8, st));
-  HIPCHK(hipMemsetAsync(gsize, 0, n * 4, st));
-  hipLaunchKernelGGL(k_best_rep, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_cluster_id, d_keep, N, C, rep, bctr);
-  // the read indices by (cluster_id, tile, x): three stable sorts, least significant key first.  The sorts follow no
-  // index of the input (an id above C only lands at the wrong place of an order nobody reads then).
-  TRY((sort_pairs_in<u32, u32>(c, OptKeyX{d_cluster_id, d_x}, k0, IotaIn{}, v0, N, 0, 32)));
-  TRY((sort_pairs_in<u32, u32>(c, OptKeyTile{d_cluster_id, d_tile, v0}, k0, PtrIn<u32>{v0}, v1, N, 0, 32)));
-  TRY((sort_pairs_in<u32, u32>(c, OptKeyCid{d_cluster_id, v1}, k0, PtrIn<u32>{v1}, v0, N, 0, bits_for((u64)C + 1))));
-  const dim3 grid(blocks_for(N)), block(256);
-  hipLaunchKernelGGL(k_opt_gather, dim3(grid_stride_blocks(N)), block, 0, st, (const u32 *)k0, (const u32 *)v0, d_keep, d_tile, d_x, d_y, N, C,
-                     (const u32 *)bctr, ct, xy, vote, parent, d_per_cluster_out);
-  hipLaunchKernelGGL(k_opt_walk, grid, block, 0, st, (const u64 *)ct, (const u64 *)xy, N, C, distance, c->op_walk, (const u32 *)bctr, parent);
-  hipLaunchKernelGGL(k_opt_root, grid, block, 0, st, (const u64 *)ct, (const u64 *)vote, N, C, (const u32 *)bctr, (const u32 *)parent, root,
-                     best, gsize);
-  hipLaunchKernelGGL(k_opt_write, dim3(grid_stride_blocks(N)), block, 0, st, (const u64 *)ct, (const u64 *)vote, (const u32 *)root,
-                     (const ull *)best, (const u32 *)gsize, N, C, (const u32 *)bctr, d_optical_out, d_origin_out, d_per_cluster_out, ctr);
-  HIPCHK(hipGetLastError());
-  u32 hb[BEST_CTRS] = {0, 0, 0, 0};
-  ull h[OPT_CTRS] = {};
-  HIPCHK(hipMemcpyAsync(hb, bctr, sizeof hb, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));                          // the pass's one host wait
-  if (hb[BEST_ERR] & 1u) return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: a cluster id above the %u clusters given", C);
-  if (hb[BEST_ERR] & 2u) return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: a cluster has more than one read with keep == 1");
-  if (hb[BEST_CLAIMS] != C)
-    return fail(c, HUMID_E_INVALID, "humid_optical_duplicates: %u reads with keep == 1 for %u clusters", hb[BEST_CLAIMS], C);
-  if (summary)
-    *summary = humid_optical_summary{(u64)C, (u64)h[OPT_MEMBERS], (u64)h[OPT_MEMBERS] - C, (u64)h[OPT_OPTICAL], (u64)h[OPT_GROUPS],
-                                     (u64)h[OPT_LARGEST]};
-  return HUMID_OK;
+  return optical_pass(c, d_cluster_id, d_keep, d_tile, d_x, d_y, n_reads, n_clusters, distance, d_optical_out, d_origin_out,
+                      d_per_cluster_out, summary);
 }
 
 int humid_optical_duplicates(humid_ctx *c, const uint32_t *cluster_id, const uint8_t *keep, const uint32_t *tile, const uint32_t *x,
@@ -1188,28 +968,22 @@ int humid_optical_duplicates(humid_ctx *c, const uint32_t *cluster_id, const uin
   TRY(optical_args(c, cluster_id, keep, tile, x, y, n_reads, optical_out, summary));
   if (n_reads == 0) return HUMID_OK;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t n = (size_t)n_reads, nc = n_clusters <= n_reads ? (size_t)n_clusters : 0;   // (more clusters than reads: refused below)
-  CS_ENSURE(c->op_cid, n * 4);
-  CS_ENSURE(c->op_keep, n);
-  CS_ENSURE(c->op_tile, n * 4);
-  CS_ENSURE(c->op_x, n * 4);
-  CS_ENSURE(c->op_y, n * 4);
-  CS_ENSURE(c->op_optical, n);
-  if (origin_out) CS_ENSURE(c->op_origin, n * 4);
-  if (per_cluster_out && nc) CS_ENSURE(c->op_pc, nc * 4);
-  HIPCHK(hipMemcpyAsync(c->op_cid.p, cluster_id, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->op_keep.p, keep, n, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->op_tile.p, tile, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->op_x.p, x, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->op_y.p, y, n * 4, hipMemcpyHostToDevice, st));
-  TRY(humid_optical_duplicates_device(c, c->op_cid.as<u32>(), c->op_keep.as<u8>(), c->op_tile.as<u32>(), c->op_x.as<u32>(), c->op_y.as<u32>(),
-                                      n_reads, n_clusters, distance, c->op_optical.as<u8>(), origin_out ? c->op_origin.as<u32>() : nullptr,
-                                      per_cluster_out && nc ? c->op_pc.as<u32>() : nullptr, summary));
-  D2H(optical_out, c->op_optical.p, n);
-  D2H(origin_out, c->op_origin.p, n * 4);
-  D2H(per_cluster_out, c->op_pc.p, nc * 4);
-  HIPCHK(hipStreamSynchronize(st));
+  const size_t n = (size_t)n_reads, nc = n_clusters <= n_reads ? (size_t)n_clusters : 0;   // (more clusters than reads: refused by the pass)
+  u32 *d_cid, *d_tile, *d_x, *d_y, *d_origin = nullptr, *d_pc = nullptr;
+  u8 *d_keep, *d_optical;
+  STAGE_IN(d_cid, 0, cluster_id, n * 4);
+  STAGE_IN(d_keep, 1, keep, n);
+  STAGE_IN(d_tile, 2, tile, n * 4);
+  STAGE_IN(d_x, 3, x, n * 4);
+  STAGE_IN(d_y, 4, y, n * 4);
+  STAGE_OUT(d_optical, 0, n);
+  if (origin_out) STAGE_OUT(d_origin, 1, n * 4);
+  if (per_cluster_out && nc) STAGE_OUT(d_pc, 2, nc * 4);
+  TRY(optical_pass(c, d_cid, d_keep, d_tile, d_x, d_y, n_reads, n_clusters, distance, d_optical, d_origin, d_pc, summary));
+  D2H(optical_out, d_optical, n);
+  D2H(origin_out, d_origin, n * 4);
+  D2H(per_cluster_out, d_pc, nc * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 

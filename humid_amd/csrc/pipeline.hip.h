@@ -134,7 +134,8 @@ struct humid_ctx {
   bool gf_padded = true;  // bucket orders of the compact graph stage through padded coarse bins (until one was full)
   bool no_chain = false;  // HUMID_NO_SCAN_CHAIN: scans without k_ps_scan_chain (experiment / cross-check)
   bool no_poll = false;   // HUMID_NO_POLL / a failed first try: blit copies + stream wait instead
-  DBuf in_words, in_filt, in_bases, out_cid, out_keep;       // host entry point staging
+  DBuf in_words, in_filt, in_bases, out_cid, out_keep;       // host entry point staging of a run (humid_get_packed_words reads it)
+  DBuf stage_in[5], stage_out[3];                            // host entry point staging of every post-run pass (STAGE_IN / STAGE_OUT)
   DBuf table, slot_out, slot_of_read, uniq_slot;             // table (cap+1) and per-read
   DBuf pk_keys, pk_vals, pbeg, ucount, pusable, ubase, pad_word, pad_cf, pslot;   // partitioned counts
   DBuf opos, own_packed, owner, owner_sorted, perm, small;                        // multi-GPU result return
@@ -221,7 +222,7 @@ struct humid_ctx {
   bool wl_coop = true;       // option "whitelist_coop": 0 = the lane-serial correction kernel (measurement / cross-check)
   u64 bc_N = 0;              // RUN_CORRECTED: bc_status / bc_counts are those of the run's bc_N reads
   DBuf bc_key, bc_filt, bc_status, bc_counts;            // corrected run: key_out, filtered', status, u64[5]
-  DBuf wc_key, wc_filt, wc_out, wc_status, wc_counts;    // humid_whitelist_correct*: staging and counts of its own
+  DBuf wc_counts;                                        // humid_whitelist_correct*: counts of its own
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
@@ -229,22 +230,18 @@ struct humid_ctx {
   DBuf gs_reads, gs_loff, gs_coff, gs_edges, gs_ps;   // reads u64[G], leaf / cluster offsets u32[G + 1], pairs u32[G]; scan of (count | degree << 32)
   // best-scoring read per cluster (humid_select_best*, kernels_best.hip.h): memory of its own, read by no accessor
   DBuf bs_rep, bs_best, bs_ctr;                              // u32[C + 1] representatives, u64[C + 1] votes, the pass's counters
-  DBuf bs_words, bs_cid, bs_keep, bs_score, bs_keep_out, bs_rep_out;   // host entry point staging
   // consensus reads (humid_consensus*, kernels_consensus.hip.h): results in memory of their own, kept until the next
   // humid_consensus* call; no run and no other accessor touches them
   DBuf cs_rep, cs_cnt, cs_moff, cs_cur, cs_mem, cs_ctr, cs_big, cs_piece, cs_tab;   // representatives, reads per cluster, member lists, large clusters
   DBuf cs_ooff, cs_ob, cs_oq, cs_depth, cs_errors;           // results: u64[C + 1], two byte blobs, u32[C], u64[C]
-  DBuf cs_in_bases, cs_in_quals, cs_in_off, cs_in_cid, cs_in_keep;   // host entry point staging
   bool cs_valid = false;     // a humid_consensus* call succeeded: cs_sum and the result buffers are its
   humid_consensus_summary cs_sum = {};
   // optical duplicates (humid_optical_duplicates*, kernels_optical.hip.h): memory of its own, read by no accessor
   DBuf op_rep, op_bctr, op_ctr, op_k0, op_v0, op_v1, op_ct, op_xy, op_vote, op_parent, op_root, op_best, op_gsize;
-  DBuf op_cid, op_keep, op_tile, op_x, op_y, op_optical, op_origin, op_pc;   // host entry point staging
   u32 op_walk = 64;          // option "optical_walk" (OPT_WALK_DEFAULT): followers a position walks before its wave takes over; 0 = no bound
   // strand-symmetric runs (humid_dedup_run_paired*, kernels_paired.hip.h): the pass runs over the canonical words
   bool pd_run = false;       // a paired pass is running: run_device takes its neighbour pairs from paired_edges
   DBuf pd_words, pd_strand, pd_mir, pd_top, pd_bottom, pd_ctr;   // canonical words, strands, mirrored leaves, tallies u32[C + 1], ull[PD_CTRS]
-  DBuf pd_in_words, pd_in_filt, pd_out_strand;   // humid_paired_canonical: staging of its own (the words in place)
   u64 pd_N = 0;              // state.paired: pd_strand holds the strands of the run's pd_N reads
   humid_strand_summary pd_sum = {};
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
@@ -284,7 +281,22 @@ static int fail(humid_ctx *c, int code, const char *fmt, ...) {
                   #expr, hipGetErrorString(_e), __FILE__, __LINE__);                        \
   } while (0)
 
+// Two memory rules.  A run's buffers and its own staging may be carved from the slab (ENSURE).  Every post-run pass
+// allocates plainly (PASS_ENSURE): the slab is sized for one run and takes nothing back.
 #define ENSURE(buf, bytes) HIPCHK((buf).ensure((bytes), &c->arena))
+#define PASS_ENSURE(buf, bytes) HIPCHK((buf).ensure((bytes)))
+#define D2H(dst, src, bytes)   /* null-tolerant: an output nobody asked for, or of no bytes, is not copied */ \
+  do { if ((dst) && (bytes)) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, c->stream)); } while (0)
+// The host-buffer forms of the post-run passes share ONE staging pool: they run on one stream and each synchronises
+// before it returns, so none overlap.  STAGE_OUT: d = room for `bytes` in output slot j.  STAGE_IN: d = input slot i
+// with `bytes` copied from the host pointer h (no bytes: room only, h may be null).
+#define STAGE_OUT(d, j, bytes) do { PASS_ENSURE(c->stage_out[j], (bytes) + 16); (d) = (decltype(d))c->stage_out[j].p; } while (0)
+#define STAGE_IN(d, i, h, bytes)                                                              \
+  do {                                                                                        \
+    PASS_ENSURE(c->stage_in[i], (bytes) + 16);                                                \
+    (d) = (decltype(d))c->stage_in[i].p;                                                      \
+    if (bytes) HIPCHK(hipMemcpyAsync((d), (h), (bytes), hipMemcpyHostToDevice, c->stream));   \
+  } while (0)
 
 static inline u32 blocks_for(u64 n, u32 bs = 256) { return (u32)((n + bs - 1) / bs); }
 static inline u32 grid_stride_blocks(u64 n, u32 bs = 256) {
@@ -2785,6 +2797,15 @@ static int check_paired_args(humid_ctx *c, u32 word_nt) {
   return HUMID_OK;
 }
 
+// what a paired run refuses before anything moves, buffers aside (both of its forms: run_host, run_paired_device)
+static int check_paired_run_args(humid_ctx *c, u64 n_reads, u32 word_nt, u32 distance, u32 method) {
+  TRY(check_paired_args(c, word_nt));
+  TRY(check_run_args(c, n_reads, word_nt, method, 64));
+  if (c->edit && distance >= 2)
+    return fail(c, HUMID_E_UNSUPPORTED, "edit distance %u against a mirrored word is not supported (option edit_distance)", distance);
+  return HUMID_OK;
+}
+
 // canonical words and strands of device arrays; nothing waits here
 template <class WT>
 static int pd_canonical_launch(humid_ctx *c, const WT *d_words, const u8 *d_filt, u32 N, u32 word_nt, WT *d_out, u8 *d_strand) {
@@ -2801,10 +2822,7 @@ static int run_paired_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, 
                              u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   state_reset(c);
-  TRY(check_paired_args(c, word_nt));
-  TRY(check_run_args(c, n_reads, word_nt, method, 64));
-  if (c->edit && distance >= 2)
-    return fail(c, HUMID_E_UNSUPPORTED, "edit distance %u against a mirrored word is not supported (option edit_distance)", distance);
+  TRY(check_paired_run_args(c, n_reads, word_nt, distance, method));
   if (n_reads && (!d_words || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (sizeof(WT) == 16 && ((uintptr_t)d_words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
   HIPCHK(hipSetDevice(c->device));

@@ -539,7 +539,8 @@ int humid_optical_duplicates_device(humid_ctx *ctx, const uint32_t *d_cluster_id
  * and humid_select_best* is valid after it when given the CANONICAL words.  Odd word_nt returns HUMID_E_INVALID,
  * word_nt > 64 HUMID_E_UNSUPPORTED, option "edit_distance" together with distance >= 2 HUMID_E_UNSUPPORTED.
  * n_reads == 0 and an all-filtered input return HUMID_OK with empty results.  Not available for grouped or keyed
- * runs or the multi-GPU pass.  The context stays usable whatever is returned.
+ * runs or the multi-GPU pass.  The context stays usable whatever is returned.  The host-buffer form goes the way of
+ * humid_dedup_run: its summary carries ms_h2d and ms_d2h, the copies in and out (the device form leaves them 0).
  * On the device (kernels_paired.hip.h): canonical words; the count stage over them; per combination of the pigeonhole
  * plan two sorted-key joins over the leaves, one against themselves and one against their mirrors, verified by
  * popcount; the pairs made unique and given to the graph stage; per-read outputs; strand tallies per cluster.
