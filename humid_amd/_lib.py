@@ -41,6 +41,15 @@ class HumidConsensusSummary(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class HumidDuplexSummary(C.Structure):
+    """humid_duplex_summary of include/humid_hip.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("n_clusters", "total_bytes", "multi_read", "bases_changed", "votes", "errors",
+                                          "duplex_clusters", "both_called", "agree", "disagree", "masked")]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class HumidOpticalSummary(C.Structure):
     """humid_optical_summary of include/humid_hip.h"""
     _fields_ = [(k, C.c_uint64) for k in ("n_clusters", "members", "duplicates", "optical", "groups", "largest_group")]
@@ -135,6 +144,12 @@ SYMBOLS = {
                                          C.POINTER(HumidConsensusSummary)]),
     "humid_get_consensus": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "humid_consensus_result_device": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "humid_duplex_consensus": (C.c_int, [C.c_void_p] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] * 2 + [C.c_void_p] * 3 +
+                               [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(HumidDuplexSummary)]),
+    "humid_duplex_consensus_device": (C.c_int, [C.c_void_p] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] * 2 +
+                                      [C.c_void_p] * 3 + [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                          C.POINTER(HumidDuplexSummary)]),
+    "humid_get_duplex_consensus": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(HumidDuplexSummary)]),
     "humid_optical_duplicates": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32] + [C.c_void_p] * 3 +
                                  [C.POINTER(HumidOpticalSummary)]),
     "humid_optical_duplicates_device": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32] +

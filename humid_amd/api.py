@@ -452,6 +452,69 @@ class Dedup(Context):
         self._check(self._lib.humid_consensus_result_device(self._h, *[C.byref(x) for x in p]))
         return dict(zip(("out_off", "bases", "quals", "depth", "errors"), [x.value or 0 for x in p]))
 
+    @staticmethod
+    def _layer(bases, quals, off, n, what):
+        """one layer as consensus() takes it: u8[N, L] matrices (off implied) or flat blobs with off u64[N + 1]"""
+        b = np.ascontiguousarray(bases, dtype=np.uint8)
+        q = np.ascontiguousarray(quals, dtype=np.uint8)
+        if b.shape != q.shape:
+            raise ValueError("bases_%s and quals_%s must have the same shape" % (what, what))
+        if off is None:
+            if b.ndim != 2 or b.shape[0] != n:
+                raise ValueError("without off_%s, bases_%s and quals_%s must be u8[N, L] matrices" % (what, what, what))
+            o = np.arange(n + 1, dtype=np.uint64) * np.uint64(b.shape[1])
+        else:
+            o = np.ascontiguousarray(off, dtype=np.uint64)
+            if b.ndim != 1 or o.shape != (n + 1,):
+                raise ValueError("with off_%s, bases_%s and quals_%s must be flat blobs and off_%s u64[N + 1]"
+                                 % (what, what, what, what))
+        return b, q, o
+
+    def duplex_consensus(self, bases_same, quals_same, bases_other, quals_other, cluster_id, keep, strand, off_same=None,
+                         off_other=None, n_clusters=None, min_q=10, strand_cap_q=40, cap_q=93):
+        """One duplex consensus record per cluster (include/humid_hip.h, humid_duplex_consensus): the members of the
+        representative's strand vote with their record of the SAME layer (the file the output belongs to), the
+        members of the other strand with their record of the OTHER layer; each class makes a call of its own with a
+        margin capped at strand_cap_q, and the two calls add when they agree and subtract when they differ.  Each
+        layer is given as u8[N, L] matrices or as flat blobs with off u64[N + 1], as in consensus(); cluster_id / keep
+        from run_paired (keep possibly from select_best), strand from strands().  One call per FastQ file, with the
+        layers exchanged.
+        Returns consensus()'s dict plus depth_same, depth_other, disagree (u32[C] each); summary has eleven fields."""
+        cid = np.ascontiguousarray(cluster_id, dtype=np.uint32)
+        n = len(cid)
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        st = np.ascontiguousarray(strand, dtype=np.uint8)
+        if cid.ndim != 1 or k.shape != (n,) or st.shape != (n,):
+            raise ValueError("cluster_id, keep and strand must have shape (N,)")
+        bs, qs, os_ = self._layer(bases_same, quals_same, off_same, n, "same")
+        bo, qo, oo = self._layer(bases_other, quals_other, off_other, n, "other")
+        if n_clusters is None:
+            n_clusters = int(cid.max()) if n else 0
+        sm = _lib.HumidDuplexSummary()
+        self._check(self._lib.humid_duplex_consensus(
+            self._h, _vp(bs), _vp(qs), _vp(os_), bs.size, _vp(bo), _vp(qo), _vp(oo), bo.size, _vp(cid), _vp(k), _vp(st), n,
+            int(n_clusters), int(min_q), int(strand_cap_q), int(cap_q), C.byref(sm)))
+        out = self._consensus_result(sm.asdict())
+        c = out["summary"]["n_clusters"]
+        for name in ("depth_same", "depth_other", "disagree"):
+            out[name] = np.zeros(c, np.uint32)
+        self._check(self._lib.humid_get_duplex_consensus(self._h, _vp(out["depth_same"]), _vp(out["depth_other"]),
+                                                         _vp(out["disagree"]), None))
+        return out
+
+    def duplex_consensus_device(self, d_bases_same, d_quals_same, d_off_same, n_bytes_same, d_bases_other, d_quals_other,
+                                d_off_other, n_bytes_other, d_cluster_id, d_keep, d_strand, n_reads, n_clusters, min_q=10,
+                                strand_cap_q=40, cap_q=93):
+        """duplex_consensus on device pointers (ints, e.g. tensor.data_ptr()); the results stay in HBM
+        (consensus_result_device).  Returns the summary dict."""
+        sm = _lib.HumidDuplexSummary()
+        self._check(self._lib.humid_duplex_consensus_device(
+            self._h, C.c_void_p(d_bases_same), C.c_void_p(d_quals_same), C.c_void_p(d_off_same), n_bytes_same,
+            C.c_void_p(d_bases_other), C.c_void_p(d_quals_other), C.c_void_p(d_off_other), n_bytes_other,
+            C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.c_void_p(d_strand), n_reads, n_clusters, int(min_q),
+            int(strand_cap_q), int(cap_q), C.byref(sm)))
+        return sm.asdict()
+
     def optical_duplicates(self, cluster_id, keep, tile, x, y, distance=100, n_clusters=None):
         """After a run: which duplicates of every cluster are optical ones (include/humid_hip.h,
         humid_optical_duplicates).  Two reads of a cluster are close when they lie on the same tile (NO_TILE: the read

@@ -66,11 +66,13 @@ struct Args {
   uint32_t optical_distance = 0;   // -O
   std::string dump_positions;  // --dump-positions (development: the -O positions of pass 1, then stop, no GPU)
   bool paired = false;         // -P (not in the reference): strand-symmetric words -- R1/R2 exchanged is the same molecule
+  bool duplex = false;         // -D (not in the reference; needs -P): every kept record carries the duplex consensus of its cluster
+  unsigned duplex_strand_cap = 40;   // --duplex-strand-cap
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] [-P] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -103,7 +105,13 @@ void usage(const char *argv0) {
                "      and -m allows its mismatches against either orientation.  One record pair per cluster is kept; -a\n"
                "      appends :<id>/A to a record read as given, :<id>/B to one read exchanged, :0 to an unusable one; a log\n"
                "      line, and with -s strands.dat: clusters with reads of both orientations (duplex) and of one only.\n"
-               "      Works with -x, -Q, -O, -a, -s; not with -b, -w, -g, -e, -C; one GPU\n",
+               "      Works with -x, -Q, -O, -D, -a, -s; not with -b, -w, -g, -e, -C (-D is the consensus of a -P run); one GPU\n"
+               "  -D  with -P: write duplex consensus reads.  The records of a cluster that were read in the orientation of its\n"
+               "      kept record vote with their read of the same file, the records read exchanged vote with their read of\n"
+               "      the other file; each orientation makes a call of its own, as -C does, with a quality of at most\n"
+               "      --duplex-strand-cap N (1..93, default 40); two calls of one base add their qualities, two calls of\n"
+               "      different bases subtract them (N and ! when nothing is left).  --consensus-min-q applies.  Only the _dedup\n"
+               "      files change; a log line, and with -s duplex.dat; inputs held in memory (no CRLF files); not with -C\n",
                argv0);
 }
 
@@ -126,6 +134,7 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "--dump-scores") { const char *v = need("--dump-scores"); if (!v) return false; a.dump_scores = v; }
     else if (t == "--dump-consensus-input") { const char *v = need("--dump-consensus-input"); if (!v) return false; a.dump_consensus = v; }
     else if (t == "--consensus-min-q") { const char *v = need("--consensus-min-q"); if (!v) return false; a.consensus_min_q = (unsigned)std::strtoul(v, nullptr, 10); }
+    else if (t == "--duplex-strand-cap") { const char *v = need("--duplex-strand-cap"); if (!v) return false; a.duplex_strand_cap = (unsigned)std::strtoul(v, nullptr, 10); }
     else if (t == "--dump-positions") { const char *v = need("--dump-positions"); if (!v) return false; a.dump_positions = v; }
     else if (t == "-O") {
       const char *v = need("-O");
@@ -137,6 +146,7 @@ bool parse(int argc, char **argv, Args &a) {
       a.optical_distance = (uint32_t)d;
     }
     else if (t == "-P") a.paired = !a.paired;
+    else if (t == "-D") a.duplex = !a.duplex;
     else if (t == "-Q") a.best = !a.best;
     else if (t == "-C") a.consensus = !a.consensus;
     else if (t == "-s") a.stats = !a.stats;
@@ -423,7 +433,14 @@ int main(int argc, char **argv) {
     else if (!a.whitelist.empty()) why = "-P does not work with -w";
     else if (sharded) why = "-P runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
     else if (a.edit) why = "-P does not work with -e (edit distance against an exchanged pair is not defined here)";
-    else if (a.consensus) why = "-P does not work with -C (a duplex consensus has to exchange the files of half of the reads)";
+    else if (a.consensus) why = "-P does not work with -C (the consensus of a -P run is -D: it takes half of the reads from the other file)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
+  if (a.duplex) {
+    const char *why = nullptr;
+    if (a.consensus) why = "-D does not work with -C (-C is the consensus of a plain run, -D that of a -P run)";
+    else if (!a.paired) why = "-D needs -P (the duplex consensus combines the two orientations of a strand-symmetric run)";
+    else if (a.duplex_strand_cap < 1 || a.duplex_strand_cap > 93) why = "--duplex-strand-cap takes 1 .. 93";
     if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
   }
   if (a.consensus_min_q > 93) {
@@ -431,7 +448,8 @@ int main(int argc, char **argv) {
     return 2;
   }
   const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty() || !a.dump_positions.empty();   // development: stop after pass 1, no GPU
-  const bool want_reads = a.consensus || !a.dump_consensus.empty();         // the reads themselves are gathered from the mappings
+  const bool cons_out = a.consensus || a.duplex;                            // pass 2 writes consensus bytes (put_consensus)
+  const bool want_reads = cons_out || !a.dump_consensus.empty();         // the reads themselves are gathered from the mappings
   const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
   const bool positions = a.optical || !a.dump_positions.empty();            // (nor without -O)
   std::vector<uint64_t> whitelist;
@@ -494,7 +512,7 @@ int main(int argc, char **argv) {
                      t_ctx, t_wait, t_pin, t_slab);
     });
   };
-  if (!dump_only && !sharded && !a.consensus) start_ctx();
+  if (!dump_only && !sharded && !cons_out) start_ctx();
   struct Release {                                      // every early return lets the thread go on
     std::atomic<long long> &n;
     ~Release() { long long e = -1; n.compare_exchange_strong(e, 0); }
@@ -545,11 +563,11 @@ int main(int argc, char **argv) {
 
   phase("files opened / indexed");
   if (want_reads && !fast) {
-    std::fprintf(stderr, "humid: -C needs the input files held in memory: not on the streaming input path (CRLF line ends, files over\n"
-                         "       HUMID_RETAIN_GB, HUMID_HOST_SLOW), where the reads are not retained\n");
+    std::fprintf(stderr, "humid: %s needs the input files held in memory: not on the streaming input path (CRLF line ends, files over\n"
+                         "       HUMID_RETAIN_GB, HUMID_HOST_SLOW), where the reads are not retained\n", a.duplex ? "-D" : "-C");
     return 1;
   }
-  if (!dump_only && a.consensus) start_ctx();
+  if (!dump_only && cons_out) start_ctx();
   // ---- pass 1: readData (src/humid.cc:89-100) ----
   t = start_message(log, "Reading data");
   const size_t wpr = a.word_length > 32 ? 2 : 1;   // uint64 per word (include/humid_hip.h)
@@ -637,7 +655,7 @@ int main(int argc, char **argv) {
   // returns the strands) and, for the dump, the strand of every read
   std::vector<uint64_t> cwords;
   std::vector<uint8_t> strand;
-  if (a.paired && (a.best || !a.dump_words.empty())) {
+  if (a.paired && (a.best || !a.dump_words.empty() || (a.duplex && !a.dump_consensus.empty()))) {
     cwords = words;
     strand.assign(N ? N : 1, HUMID_STRAND_NONE);
     parallel_ranges(N, threads, [&](size_t b, size_t e, unsigned) {
@@ -675,6 +693,7 @@ int main(int argc, char **argv) {
       out.write((const char *)lb.data(), (std::streamsize)lb.size());
       out.write((const char *)lq.data(), (std::streamsize)lq.size());
     }
+    if (a.paired && a.duplex) out.write((const char *)strand.data(), (std::streamsize)N);   // -P -D: then one strand byte per read
   }
   if (dump_only) return 0;
 
@@ -828,7 +847,7 @@ int main(int argc, char **argv) {
   }
   // -C: one consensus pass per input file, one after the other (a file's blobs are freed before the next is gathered);
   // what pass 2 needs stays on the host: per file the offsets and the two consensus blobs, in cluster-id order
-  std::vector<std::vector<uint64_t>> cons_off(a.consensus ? maps.size() : 0);
+  std::vector<std::vector<uint64_t>> cons_off(cons_out ? maps.size() : 0);
   std::vector<std::vector<uint8_t>> cons_b(cons_off.size()), cons_q(cons_off.size());
   if (a.consensus) {
     uint64_t changed = 0, disagree = 0, multi = 0;
@@ -862,6 +881,40 @@ int main(int argc, char **argv) {
     // (clusters and multi-read clusters are those of the run; bases changed and disagreeing votes add up over the files)
     log << "  consensus: " << sum.clusters << " clusters, " << multi << " multi-read, " << changed << " bases changed, "
         << disagree << " disagreeing votes\n";
+  }
+  // -D: both files' blobs are resident at once; output layer f takes file f as the same layer and the other file as
+  // the other layer.  The results come back through humid_get_consensus, so pass 2 is that of -C.
+  humid_duplex_summary dsum[2];
+  std::memset(dsum, 0, sizeof dsum);
+  if (a.duplex) {
+    std::vector<uint64_t> off[2];
+    std::vector<uint8_t> lb[2], lq[2];
+    for (size_t f = 0; f < 2; f++) gather_layer(maps[f], N, threads, off[f], lb[f], lq[f]);
+    for (size_t f = 0; f < 2; f++) {
+      const size_t g = 1 - f;
+      humid_duplex_summary &ds = dsum[f];
+      int crc = humid_duplex_consensus(ctx, lb[f].data(), lq[f].data(), off[f].data(), off[f][N], lb[g].data(), lq[g].data(), off[g].data(),
+                                       off[g][N], cluster_id, keep, strand.data(), N, sum.clusters, a.consensus_min_q, a.duplex_strand_cap,
+                                       93, &ds);
+      if (crc == HUMID_OK) {
+        cons_off[f].resize(ds.n_clusters + 1);
+        cons_b[f].resize(ds.total_bytes ? ds.total_bytes : 1);
+        cons_q[f].resize(ds.total_bytes ? ds.total_bytes : 1);
+        crc = humid_get_consensus(ctx, ds.total_bytes, cons_off[f].data(), cons_b[f].data(), cons_q[f].data(), nullptr, nullptr);
+      }
+      if (crc == HUMID_OK && ds.n_clusters != sum.clusters && N) crc = HUMID_E_STATE;   // (cannot happen: C was passed in)
+      if (crc != HUMID_OK) {
+        log << "failed.\n";
+        std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+        humid_ctx_destroy(ctx);
+        return 1;
+      }
+    }
+    // (clusters are those of the run; the columns add up over the two files)
+    log << "  duplex consensus: " << sum.clusters << " clusters, " << dsum[0].duplex_clusters << " duplex, "
+        << dsum[0].both_called + dsum[1].both_called << " columns called by both strands, " << dsum[0].agree + dsum[1].agree << " agree, "
+        << dsum[0].disagree + dsum[1].disagree << " disagree, " << dsum[0].masked + dsum[1].masked << " masked, "
+        << dsum[0].bases_changed + dsum[1].bases_changed << " bases changed\n";
   }
   // the kept record i of file f, copied to dst, takes the consensus of its cluster on its sequence and quality lines
   auto put_consensus = [&](size_t f, size_t i, char *dst) {
@@ -943,7 +996,7 @@ int main(int argc, char **argv) {
                 if (!keep[i]) return q;
                 const std::string_view rr = maps[f].raw(i);
                 memcpy(q, rr.data(), rr.size());
-                if (a.consensus) put_consensus(f, i, q);
+                if (cons_out) put_consensus(f, i, q);
                 return q + rr.size();
               });
           if (r > 0) done_dedup[f] = 1;
@@ -993,7 +1046,7 @@ int main(int argc, char **argv) {
                   if (keep[i]) {
                     std::string_view r = maps[f].raw(i);
                     o.append(r.data(), r.size());
-                    if (a.consensus) put_consensus(f, i, &o[o.size() - r.size()]);
+                    if (cons_out) put_consensus(f, i, &o[o.size() - r.size()]);
                   }
               } else if (re > rb) {
                 // annotated record = header + ':' + cluster id + the rest of the record verbatim
@@ -1098,6 +1151,19 @@ int main(int argc, char **argv) {
       out << "bottom_only: " << ssum.bottom_only << '\n';
       out << "top_reads: " << ssum.top_reads << '\n';
       out << "bottom_reads: " << ssum.bottom_reads << '\n';
+      out.close();
+      if (out.fail()) ok = -1;
+    }
+    if (ok == 1 && a.duplex) {                               // the summary of each file's call: file<k>.<field> value
+      std::ofstream out(a.dir_name + "/duplex.dat", std::ios::out | std::ios::binary);
+      for (size_t f = 0; f < 2; f++) {
+        const humid_duplex_summary &d = dsum[f];
+        const char *names[11] = {"n_clusters", "total_bytes", "multi_read", "bases_changed", "votes", "errors", "duplex_clusters",
+                                 "both_called", "agree", "disagree", "masked"};
+        const uint64_t vals[11] = {d.n_clusters, d.total_bytes, d.multi_read, d.bases_changed, d.votes, d.errors, d.duplex_clusters,
+                                   d.both_called, d.agree, d.disagree, d.masked};
+        for (int k = 0; k < 11; k++) out << "file" << f + 1 << '.' << names[k] << ' ' << vals[k] << '\n';
+      }
       out.close();
       if (out.fail()) ok = -1;
     }

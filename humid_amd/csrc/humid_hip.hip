@@ -877,7 +877,7 @@ int humid_select_best(humid_ctx *c, const uint64_t *words, const uint32_t *clust
 static int consensus_args(humid_ctx *c, const void *bases, const void *quals, const void *off, const void *cid, const void *keep,
                           uint64_t n_reads, uint32_t min_q, uint32_t cap_q) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  c->cs_valid = false;                                       // the last results end with the next call, whatever it returns
+  c->cs_valid = c->cs_duplex = false;                        // the last results end with the next call, whatever it returns
   if (min_q > 93) return fail(c, HUMID_E_INVALID, "humid_consensus: min_q must be 0 .. 93");
   if (cap_q < 1 || cap_q > 93) return fail(c, HUMID_E_INVALID, "humid_consensus: cap_q must be 1 .. 93");
   if (n_reads && (!bases || !quals || !off || !cid || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
@@ -938,6 +938,73 @@ int humid_consensus_result_device(humid_ctx *c, const uint64_t **d_out_off, cons
   if (d_quals) *d_quals = any ? c->cs_oq.as<u8>() : nullptr;
   if (d_depth) *d_depth = any ? c->cs_depth.as<u32>() : nullptr;
   if (d_errors) *d_errors = any ? c->cs_errors.as<u64>() : nullptr;
+  return HUMID_OK;
+}
+
+// ---- duplex consensus reads per cluster (kernels_dconsensus.hip.h) ------------------------------------------------
+static int duplex_consensus_args(humid_ctx *c, const void *bases_s, const void *quals_s, const void *off_s, const void *bases_o,
+                                 const void *quals_o, const void *off_o, const void *cid, const void *keep, const void *strand,
+                                 uint64_t n_reads, uint32_t min_q, uint32_t strand_cap_q, uint32_t cap_q) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  c->cs_valid = c->cs_duplex = false;                        // the last results end with the next call, whatever it returns
+  if (min_q > 93) return fail(c, HUMID_E_INVALID, "humid_duplex_consensus: min_q must be 0 .. 93");
+  if (strand_cap_q < 1 || strand_cap_q > 93) return fail(c, HUMID_E_INVALID, "humid_duplex_consensus: strand_cap_q must be 1 .. 93");
+  if (cap_q < 1 || cap_q > 93) return fail(c, HUMID_E_INVALID, "humid_duplex_consensus: cap_q must be 1 .. 93");
+  if (n_reads && (!bases_s || !quals_s || !off_s || !bases_o || !quals_o || !off_o || !cid || !keep || !strand))
+    return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads >= 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "humid_duplex_consensus: more than 2^32 - 2 reads");
+  return HUMID_OK;
+}
+
+int humid_duplex_consensus_device(humid_ctx *c, const uint8_t *d_bases_s, const uint8_t *d_quals_s, const uint64_t *d_off_s,
+                                  uint64_t n_bytes_s, const uint8_t *d_bases_o, const uint8_t *d_quals_o, const uint64_t *d_off_o,
+                                  uint64_t n_bytes_o, const uint32_t *d_cluster_id, const uint8_t *d_keep, const uint8_t *d_strand,
+                                  uint64_t n_reads, uint64_t n_clusters, uint32_t min_q, uint32_t strand_cap_q, uint32_t cap_q,
+                                  humid_duplex_summary *summary) {
+  TRY(duplex_consensus_args(c, d_bases_s, d_quals_s, d_off_s, d_bases_o, d_quals_o, d_off_o, d_cluster_id, d_keep, d_strand, n_reads, min_q,
+                            strand_cap_q, cap_q));
+  return duplex_consensus_pass(c, d_bases_s, d_quals_s, d_off_s, n_bytes_s, d_bases_o, d_quals_o, d_off_o, n_bytes_o, d_cluster_id, d_keep,
+                               d_strand, n_reads, n_clusters, min_q, strand_cap_q, cap_q, summary);
+}
+
+int humid_duplex_consensus(humid_ctx *c, const uint8_t *bases_s, const uint8_t *quals_s, const uint64_t *off_s, uint64_t n_bytes_s,
+                           const uint8_t *bases_o, const uint8_t *quals_o, const uint64_t *off_o, uint64_t n_bytes_o,
+                           const uint32_t *cluster_id, const uint8_t *keep, const uint8_t *strand, uint64_t n_reads, uint64_t n_clusters,
+                           uint32_t min_q, uint32_t strand_cap_q, uint32_t cap_q, humid_duplex_summary *summary) {
+  TRY(duplex_consensus_args(c, bases_s, quals_s, off_s, bases_o, quals_o, off_o, cluster_id, keep, strand, n_reads, min_q, strand_cap_q,
+                            cap_q));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads, nbs = (size_t)n_bytes_s, nbo = (size_t)n_bytes_o;
+  u8 *d_bs = nullptr, *d_qs = nullptr, *d_bo = nullptr, *d_qo = nullptr, *d_keep = nullptr, *d_strand = nullptr;
+  u64 *d_os = nullptr, *d_oo = nullptr;
+  u32 *d_cid = nullptr;
+  if (n) {                                                   // (no reads: every pointer may be null, and the pass reads none)
+    STAGE_IN(d_bs, 0, bases_s, nbs);
+    STAGE_IN(d_qs, 1, quals_s, nbs);
+    STAGE_IN(d_os, 2, off_s, (n + 1) * 8);
+    STAGE_IN(d_cid, 3, cluster_id, n * 4);
+    STAGE_IN(d_keep, 4, keep, n);
+    STAGE_IN(d_bo, 5, bases_o, nbo);
+    STAGE_IN(d_qo, 6, quals_o, nbo);
+    STAGE_IN(d_oo, 7, off_o, (n + 1) * 8);
+    STAGE_IN(d_strand, 8, strand, n);
+  }
+  return duplex_consensus_pass(c, d_bs, d_qs, d_os, n_bytes_s, d_bo, d_qo, d_oo, n_bytes_o, d_cid, d_keep, d_strand, n_reads, n_clusters,
+                               min_q, strand_cap_q, cap_q, summary);
+}
+
+int humid_get_duplex_consensus(humid_ctx *c, uint32_t *depth_same, uint32_t *depth_other, uint32_t *disagree,
+                               humid_duplex_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->cs_valid || !c->cs_duplex)
+    return fail(c, HUMID_E_STATE, "the last successful consensus call in this context was no humid_duplex_consensus* call");
+  const size_t C = (size_t)c->ds_sum.n_clusters;
+  HIPCHK(hipSetDevice(c->device));
+  D2H(depth_same, c->ds_same.p, C * 4);
+  D2H(depth_other, c->ds_other.p, C * 4);
+  D2H(disagree, c->ds_disagree.p, C * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (summary) *summary = c->ds_sum;
   return HUMID_OK;
 }
 

@@ -23,7 +23,7 @@
 #define CONS_MAX_DEPTH 46182444u   // 93 * this < 2^32: the u32 sums cannot wrap
 
 // the pass's u64 counters
-enum { CONS_ERR = 0 /* bit 0: an id above C; 1: two kept reads in a cluster; 2: off decreasing; 3: off[n] > n_bytes; 4: a cluster beyond CONS_MAX_DEPTH */,
+enum { CONS_ERR = 0 /* bit 0: an id above C; 1: two kept reads in a cluster; 2: off decreasing; 3: off[n] > n_bytes; 4: a cluster beyond CONS_MAX_DEPTH; 5: taken by the duplex pass, kernels_dconsensus.hip.h */,
        CONS_CLAIMS /* kept reads that claimed a cluster */, CONS_NBIG /* large clusters */, CONS_NPIECES /* their pieces */,
        CONS_TABCOLS /* columns of all their tables */, CONS_MULTI, CONS_CHANGED, CONS_VOTES, CONS_ERRORS, CONS_CTRS = 10 };
 

@@ -135,7 +135,7 @@ struct humid_ctx {
   bool no_chain = false;  // HUMID_NO_SCAN_CHAIN: scans without k_ps_scan_chain (experiment / cross-check)
   bool no_poll = false;   // HUMID_NO_POLL / a failed first try: blit copies + stream wait instead
   DBuf in_words, in_filt, in_bases, out_cid, out_keep;       // host entry point staging of a run (humid_get_packed_words reads it)
-  DBuf stage_in[5], stage_out[3];                            // host entry point staging of every post-run pass (STAGE_IN / STAGE_OUT)
+  DBuf stage_in[9], stage_out[3];                            // host entry point staging of every post-run pass (STAGE_IN / STAGE_OUT)
   DBuf table, slot_out, slot_of_read, uniq_slot;             // table (cap+1) and per-read
   DBuf pk_keys, pk_vals, pbeg, ucount, pusable, ubase, pad_word, pad_cf, pslot;   // partitioned counts
   DBuf opos, own_packed, owner, owner_sorted, perm, small;                        // multi-GPU result return
@@ -234,8 +234,12 @@ struct humid_ctx {
   // humid_consensus* call; no run and no other accessor touches them
   DBuf cs_rep, cs_cnt, cs_moff, cs_cur, cs_mem, cs_ctr, cs_big, cs_piece, cs_tab;   // representatives, reads per cluster, member lists, large clusters
   DBuf cs_ooff, cs_ob, cs_oq, cs_depth, cs_errors;           // results: u64[C + 1], two byte blobs, u32[C], u64[C]
-  bool cs_valid = false;     // a humid_consensus* call succeeded: cs_sum and the result buffers are its
+  bool cs_valid = false;     // a humid_consensus* or humid_duplex_consensus* call succeeded: cs_sum and the result buffers are its
   humid_consensus_summary cs_sum = {};
+  // duplex consensus reads (humid_duplex_consensus*, kernels_dconsensus.hip.h): the same scratch and result buffers, and
+  bool cs_duplex = false;    // cs_valid and that call was a duplex one: ds_* and ds_sum are its (humid_get_duplex_consensus)
+  DBuf ds_top, ds_same, ds_other, ds_disagree;               // TOP members u32[C + 2]; results: three u32[C]
+  humid_duplex_summary ds_sum = {};
   // optical duplicates (humid_optical_duplicates*, kernels_optical.hip.h): memory of its own, read by no accessor
   DBuf op_rep, op_bctr, op_ctr, op_k0, op_v0, op_v1, op_ct, op_xy, op_vote, op_parent, op_root, op_best, op_gsize;
   u32 op_walk = 64;          // option "optical_walk" (OPT_WALK_DEFAULT): followers a position walks before its wave takes over; 0 = no bound

@@ -446,8 +446,8 @@ int humid_select_best_device(humid_ctx *ctx, const uint64_t *d_words, const uint
  *   humid_get_consensus: host copies of the last successful call's results; any pointer may be NULL; cap_bytes is the
  *     room of cons_bases / cons_quals: cap_bytes < total_bytes with either given returns HUMID_E_INVALID.
  *   humid_consensus_result_device: the same arrays left in HBM (as humid_group_stats_device), owned by the context.
- * The results live in buffers of their own: they last until the next humid_consensus* call (successful or not) or
- * humid_ctx_destroy, and survive any run.  Both getters return HUMID_E_STATE before a successful call. */
+ * The results live in buffers of their own: they last until the next humid_consensus* or humid_duplex_consensus* call
+ * (successful or not) or humid_ctx_destroy, and survive any run.  Both getters return HUMID_E_STATE before a successful call. */
 typedef struct humid_consensus_summary {
   uint64_t n_clusters, total_bytes, multi_read, bases_changed, votes, errors;
 } humid_consensus_summary;
@@ -461,6 +461,83 @@ int humid_get_consensus(humid_ctx *ctx, uint64_t cap_bytes, uint64_t *out_off, u
                         uint8_t *cons_quals, uint32_t *depth, uint64_t *errors);
 int humid_consensus_result_device(humid_ctx *ctx, const uint64_t **d_out_off, const uint8_t **d_bases,
                                   const uint8_t **d_quals, const uint32_t **d_depth, const uint64_t **d_errors);
+
+/* ---- duplex consensus reads: the two strands of a cluster as two independent observations ------------------------
+ * (fgbio CallDuplexConsensusReads: a base seen on both strands is real, a base seen on one strand only is damage or
+ * a PCR error.)  After a strand-symmetric run a cluster holds the reads of both strands of a molecule.  Pooling their
+ * votes (humid_consensus) lets a strand of 50 reads outvote a strand of 2; here each strand makes a CAPPED call of its
+ * own and the two calls have to agree.  The definition is exact, in integers.  One call produces one output layer (one
+ * FastQ file of the pair) from two input layers: the SAME layer S, the file the output belongs to, and the OTHER layer
+ * O, the other file; a paired run calls it twice with S and O exchanged.
+ *   bases_s / quals_s / off_s[n_reads + 1], n_bytes_s and bases_o / quals_o / off_o, n_bytes_o: raw ASCII, Phred+33,
+ *       laid out as for humid_consensus; the lengths of the two layers are independent and may be 0.
+ *   cluster_id[n_reads], keep[n_reads]   from any run, keep possibly rewritten by humid_select_best.
+ *   strand[n_reads] (u8)                 as humid_get_strands / humid_paired_canonical give it.
+ *   n_clusters = C;  min_q in 0 .. 93, strand_cap_q in 1 .. 93, cap_q in 1 .. 93.
+ * A read with cluster_id == 0 is no member: none of its bytes and not its strand are read.  A member's strand must be
+ * HUMID_STRAND_TOP or HUMID_STRAND_BOTTOM.  r_c is the one member of cluster c with keep == 1.  The cluster's frame is
+ * its representative's: a member i with strand[i] == strand[r_c] is in class X and votes with its record of layer S;
+ * any other member is in class Y and votes with its record of layer O.  No reverse complement is involved (the other
+ * strand's R2 reads the same end in the same direction as this strand's R1), so flipping every strand value changes
+ * nothing.
+ * Votes are exactly those of humid_consensus: p = min(max(byte - 33, 0), 93), uppercase A C G T only, p >= max(min_q,
+ * 1), weight p.  Per column j < L = len_S(r_c) and per class s in {X, Y}: S_b^s the sum of the weights and n_b^s the
+ * number of the votes for base b (a member whose voting record is shorter than j + 1 casts nothing there); the class's
+ * call is b_s, the base with the largest sum (A before C before G before T among equals), with the margin
+ * m_s = min(first - second, strand_cap_q); m_s == 0 (no votes, or a tie) means the class makes no call.  Column j:
+ *   no vote in either class                          r_c's own bytes of layer S, verbatim;
+ *   m_X > 0, m_Y > 0, b_X == b_Y                     that base, 33 + min(m_X + m_Y, cap_q);
+ *   m_X > 0, m_Y > 0, bases differ, m_X != m_Y       the base of the larger margin, 33 + min(|m_X - m_Y|, cap_q);
+ *   m_X > 0, m_Y > 0, bases differ, m_X == m_Y       'N' and '!';
+ *   exactly one of m_X, m_Y > 0                      that class's base, 33 + min(m_s, cap_q);
+ *   votes were cast, neither class calls             'N' and '!'.
+ * When every member of every cluster has its representative's strand and strand_cap_q == 93, the outputs and the six
+ * shared summary fields are those of humid_consensus on layer S, bit for bit; no byte of layer O is then read.
+ * Per cluster (slot c - 1): depth = all its reads; depth_same / depth_other = the sizes of classes X / Y; errors (u64)
+ * = over the columns and the classes with m_s > 0 the class's votes minus n of its called base; disagree (u32) = the
+ * columns where both classes call different bases; out_off[C + 1] as in humid_consensus.
+ * humid_duplex_summary: the first six fields have the names and meanings of humid_consensus_summary (votes: of both
+ * classes); duplex_clusters = clusters where both classes are non-empty; both_called = columns where both classes
+ * call; agree / disagree = those with the same / with different bases; masked = columns where a vote was cast and 'N'
+ * is written.
+ * Refusals as in humid_consensus, found on the device and reported at the first host wait, nothing written and no
+ * unchecked index followed: HUMID_E_INVALID for an id above C, a cluster without a kept read or with two, off
+ * decreasing in either layer, off[n_reads] beyond the bytes given in either layer, a member with a strand above 1;
+ * parameters out of range and NULL buffers with n_reads > 0 are refused on the host (HUMID_E_INVALID).
+ * HUMID_E_OVERFLOW for a cluster of more than 46 182 444 reads.  n_reads == 0 or C == 0 returns HUMID_OK with an empty
+ * result.  The context stays usable and the last run's accessors valid, whatever is returned.  Two host waits.
+ * Not part of this pass (strand_cap_q = 40 is fgbio's post-UMI error rate, a convention, not a measurement):
+ *   - a minimum number of reads per strand;
+ *   - filtering to duplex-only clusters (callers have depth_same / depth_other);
+ *   - indel-aware alignment of the members;
+ *   - grouped, keyed and sharded runs (the strand-symmetric run has none).
+ * On the device (kernels_dconsensus.hip.h): the pass of humid_consensus with the member list of a cluster ordered TOP
+ * members first, BOTTOM members last, so that each class is one contiguous range read from one layer; two sets of
+ * sums per column; large clusters meet in a table of 16 u32 per column.
+ *   humid_duplex_consensus: host buffers.   humid_duplex_consensus_device: DEVICE pointers (summary stays a host
+ *     pointer; may be NULL); returns after the stream has drained.
+ *   The results go into the consensus result buffers: humid_get_consensus and humid_consensus_result_device answer for
+ *   the last successful call of either kind, and "until the next humid_consensus* call" includes the duplex calls and
+ *   vice versa.
+ *   humid_get_duplex_consensus: depth_same, depth_other, disagree (u32[C] each) and the summary of the last call; any
+ *     pointer may be NULL; HUMID_E_STATE unless the last successful consensus call on the context was a duplex one. */
+typedef struct humid_duplex_summary {
+  uint64_t n_clusters, total_bytes, multi_read, bases_changed, votes, errors;
+  uint64_t duplex_clusters, both_called, agree, disagree, masked;
+} humid_duplex_summary;
+int humid_duplex_consensus(humid_ctx *ctx, const uint8_t *bases_s, const uint8_t *quals_s, const uint64_t *off_s,
+                           uint64_t n_bytes_s, const uint8_t *bases_o, const uint8_t *quals_o, const uint64_t *off_o,
+                           uint64_t n_bytes_o, const uint32_t *cluster_id, const uint8_t *keep, const uint8_t *strand,
+                           uint64_t n_reads, uint64_t n_clusters, uint32_t min_q, uint32_t strand_cap_q, uint32_t cap_q,
+                           humid_duplex_summary *summary);
+int humid_duplex_consensus_device(humid_ctx *ctx, const uint8_t *d_bases_s, const uint8_t *d_quals_s,
+                                  const uint64_t *d_off_s, uint64_t n_bytes_s, const uint8_t *d_bases_o,
+                                  const uint8_t *d_quals_o, const uint64_t *d_off_o, uint64_t n_bytes_o,
+                                  const uint32_t *d_cluster_id, const uint8_t *d_keep, const uint8_t *d_strand,
+                                  uint64_t n_reads, uint64_t n_clusters, uint32_t min_q, uint32_t strand_cap_q,
+                                  uint32_t cap_q, humid_duplex_summary *summary);
+int humid_get_duplex_consensus(humid_ctx *ctx, uint32_t *depth_same, uint32_t *depth_other, uint32_t *disagree,
+                               humid_duplex_summary *summary);
 
 /* ---- optical duplicates: which duplicates of a cluster come from the instrument -------------------------------------
  * (Picard MarkDuplicates READ_PAIR_OPTICAL_DUPLICATES, clumpify dedupe optical: reads of the same tile within a few
