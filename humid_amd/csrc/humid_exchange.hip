@@ -447,13 +447,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
   u64 e_mine = 0;                                                    // 16-byte records in xr_eloc
   auto append_pairs = [&](const u64 *rec, u64 n_rec) -> int {
     if (!n_rec) return HUMID_OK;
-    if ((e_mine + n_rec) * 16 > c->xr_eloc.cap) {                    // grow, keeping what is there
-      DBuf bigger;
-      HIPCHK(bigger.ensure((e_mine + n_rec) * 32, nullptr));
-      if (e_mine) HIPCHK(hipMemcpyAsync(bigger.p, c->xr_eloc.p, e_mine * 16, hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-      c->xr_eloc = std::move(bigger);
-    }
+    HIPCHK(c->xr_eloc.grow_keeping(e_mine * 16, (e_mine + n_rec) * 16, st));
     HIPCHK(hipMemcpyAsync(c->xr_eloc.as<u8>() + e_mine * 16, rec, n_rec * 16, hipMemcpyDeviceToDevice, st));
     e_mine += n_rec;
     return HUMID_OK;
@@ -1313,11 +1307,9 @@ static int emit_orders(humid_ctx *c, const PairSearch<WT> &ps, const EmitOrder<W
     for (u32 k = 0; k < n_ord; k++) tiles_emit<WT>(c, ps, ord[k].w, d_runs[k], runs[k], mode, sink(ord[k]), ord[k].i_lo, ord[k].i_hi);
   };
   pairs(PM_EMIT_COUNT);
-  TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), T + 1));
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c, c->poff.as<u32>() + T));
-  const u64 E_near = c->h_ctr[CTR_N - 1] & 0xffffffffull, big_mask = c->h_ctr[CTR_BIGMASK];
-  u64 E_far = 0;
+  u64 E_near = 0, E_far = 0;
+  TRY(scan_total(c, c->pc.as<u32>(), c->poff.as<u32>(), T, &E_near));
+  const u64 big_mask = c->h_ctr[CTR_BIGMASK];
   if (big_mask) {
     HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SPECIAL], 0, sizeof(ull), st));
     for (u32 k = 0; k < n_ord; k++)
@@ -1466,15 +1458,7 @@ static int pairs_keyed_wide(humid_ctx *c, const void *d_items, u32 n, bool inter
     hipLaunchKernelGGL(k_split_items_w2, dim3(blocks_for(n)), dim3(256), 0, st, (const Item3 *)d_items, n, c->x_w.as<W2>(),
                        c->x_id.as<u32>(), c->x_cnt.as<u32>());
     const u32 kb = plan.key_bits ? plan.key_bits : 1;
-    if (kb <= 32) {
-      hipLaunchKernelGGL((k_combo_keys<u32, W2>), dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<W2>(), n, plan_fields(plan, combo),
-                         c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), c->seg_ks.as<u32>(), c->seg_v0.as<u32>(), c->seg_vs.as<u32>(), n, 0, kb));
-    } else {
-      hipLaunchKernelGGL((k_combo_keys<u64, W2>), dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<W2>(), n, plan_fields(plan, combo),
-                         c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->seg_ks.as<u64>(), c->seg_v0.as<u32>(), c->seg_vs.as<u32>(), n, 0, kb));
-    }
+    TRY(combo_keys_sorted<W2>(c, c->x_w.as<W2>(), n, plan_fields(plan, combo), kb, c->seg_ks.p, c->seg_vs.as<u32>()));
     hipLaunchKernelGGL(k_gather_bucket_words<W2>, dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<W2>(), c->seg_vs.as<u32>(), n,
                        c->seg_ws.as<W2>());
     TRY(emit_pairs<W2>(c, c->seg_ws.as<W2>(), c->seg_vs.as<u32>(), n, plan, combo, distance, &E));
@@ -1525,15 +1509,7 @@ int humid_stage_pairs_keyed(humid_ctx *c, const uint64_t *d_items, uint64_t n_it
     TRY((group_words_by_stretch<FieldsSrc, u64>(c, plan, combo, c->x_w.as<u64>(), n, c->seg_ws.as<u64>(), c->seg_vs.as<u32>(), &stretch)));
     if (!stretch) TRY(sort_words_by_stretch(c, plan, combo, c->x_w.as<u64>(), n, c->seg_ws.as<u64>(), c->seg_vs.as<u32>(), &stretch));
     if (!stretch) {
-      if (kb <= 32) {
-        hipLaunchKernelGGL((k_combo_keys<u32, u64>), dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<u64>(), n,
-                           plan_fields(plan, combo), c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
-        TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), c->seg_ks.as<u32>(), c->seg_v0.as<u32>(), c->seg_vs.as<u32>(), n, 0, kb));
-      } else {
-        hipLaunchKernelGGL((k_combo_keys<u64, u64>), dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<u64>(), n,
-                           plan_fields(plan, combo), c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
-        TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->seg_ks.as<u64>(), c->seg_v0.as<u32>(), c->seg_vs.as<u32>(), n, 0, kb));
-      }
+      TRY(combo_keys_sorted<u64>(c, c->x_w.as<u64>(), n, plan_fields(plan, combo), kb, c->seg_ks.p, c->seg_vs.as<u32>()));
       hipLaunchKernelGGL(k_gather_bucket_words<u64>, dim3(blocks_for(n)), dim3(256), 0, st, c->x_w.as<u64>(),
                          c->seg_vs.as<u32>(), n, c->seg_ws.as<u64>());
     }
@@ -1622,10 +1598,9 @@ static int compact_nodes_impl(humid_ctx *c, const uint64_t *d_edges, uint64_t n_
   TRY(sort_pairs<u32, u32>(c, c->x_ends.as<u32>(), c->x_ends_s.as<u32>(), c->x_slot.as<u32>(), c->x_slot_s.as<u32>(), n2, 0, 32));   // (global indices: all 32 bits may be in use)
   hipLaunchKernelGGL(k_heads_u32, dim3(blocks_for((u64)n2 + 1)), dim3(256), 0, st, c->x_ends_s.as<u32>(), n2,
                      c->x_head.as<u32>());
-  TRY(exscan_u32(c, c->x_head.as<u32>(), c->x_hpos.as<u32>(), (u64)n2 + 1));
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c, c->x_hpos.as<u32>() + n2));
-  const u32 M = (u32)(c->h_ctr[CTR_N - 1] & 0xffffffffull);
+  u64 n_distinct = 0;
+  TRY(scan_total(c, c->x_head.as<u32>(), c->x_hpos.as<u32>(), n2, &n_distinct));
+  const u32 M = (u32)n_distinct;
   ENSURE(c->x_nodes, ((size_t)M + 1) * 4);
   ENSURE(c->x_ncnt, ((size_t)M + 1) * 4);
   ENSURE(c->x_cedges, (size_t)E * 8);

@@ -80,6 +80,17 @@ struct DBuf {
     cap = want;
     return hipSuccess;
   }
+  // room for need_bytes with the first keep_bytes kept: a list that is appended to.  A new block of twice the need
+  // (never from the slab), one copy, one stream wait.
+  hipError_t grow_keeping(size_t keep_bytes, size_t need_bytes, hipStream_t stream) {
+    if (need_bytes <= cap) return hipSuccess;
+    DBuf bigger;
+    hipError_t e = bigger.ensure(need_bytes * 2);
+    if (e == hipSuccess && keep_bytes) e = hipMemcpyAsync(bigger.p, p, keep_bytes, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) *this = std::move(bigger);
+    return e;
+  }
   void release() { if (p && !in_arena) (void)hipFree(p); p = nullptr; cap = 0; in_arena = false; }
   template <class T> T *as() const { return (T *)p; }
 };
@@ -397,6 +408,16 @@ static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *
 }
 
 #define TRY(...) do { int _rc = (__VA_ARGS__); if (_rc != HUMID_OK) return _rc; } while (0)
+
+// exclusive scan of in[0 .. n] (n + 1 entries, the last a sentinel) and its total out[n], fetched with the counters:
+// one host wait.  h_ctr holds the counters of that moment afterwards.
+static int scan_total(humid_ctx *c, const u32 *in, u32 *out, u64 n, u64 *total) {
+  TRY(exscan_u32(c, in, out, n + 1));
+  HIPCHK(hipGetLastError());
+  TRY(read_counters(c, out + n));
+  *total = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+  return HUMID_OK;
+}
 
 // ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
 static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; }
@@ -1223,10 +1244,9 @@ static int stage_count_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u
   hipLaunchKernelGGL(k_wide_gather, dim3(grid), dim3(256), 0, st, d_words, v, N, hbits, c->w_sorted.as<W2>());
   hipLaunchKernelGGL(k_wide_heads, dim3(grid), dim3(256), 0, st, c->w_sorted.as<W2>(), N, c->d_ctr,
                      c->w_head.as<u32>());
-  TRY(exscan_u32(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), (u64)N + 1));
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c, c->w_hpos.as<u32>() + N));                               // h_ctr[CTR_N-1] = U
-  const u32 U = (u32)(c->h_ctr[CTR_N - 1] & 0xffffffffull);
+  u64 n_unique = 0;
+  TRY(scan_total(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), N, &n_unique));
+  const u32 U = (u32)n_unique;
   s.usable = c->usable = c->h_ctr[CTR_USABLE];
   s.unique = c->U = U;
   ENSURE(c->s_word, (size_t)(U + 1) * sizeof(W2));
@@ -1393,6 +1413,19 @@ static int sort_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, co
   return sort_pairs_in<u64, u32>(c, PtrIn<u64>{W}, ws, IotaIn{}, vs, n, bit_lo, bit_lo + bit_n);
 }
 
+// keys of the fields cf of src[0 .. n), sorted: kout = the keys ascending (u32 where key_bits <= 32, else u64),
+// vout = the index in src of each.  Scratch: seg_k0 / seg_v0.  The only place that launches k_combo_keys.
+template <class WT>
+static int combo_keys_sorted(humid_ctx *c, const WT *src, u32 n, const ComboFields &cf, u32 key_bits, void *kout, u32 *vout) {
+  auto go = [&](auto key) -> int {
+    using KT = decltype(key);
+    hipLaunchKernelGGL((k_combo_keys<KT, WT>), dim3(blocks_for(n)), dim3(256), 0, c->stream, src, n, cf, c->seg_k0.as<KT>(),
+                       c->seg_v0.as<u32>());
+    return sort_pairs<KT, u32>(c, c->seg_k0.as<KT>(), (KT *)kout, c->seg_v0.as<u32>(), vout, n, 0, key_bits);
+  };
+  return key_bits <= 32 ? go(u32{}) : go(u64{});
+}
+
 // words of the unique array in bucket order of combination `seg` (> 0): ws[i] = the word walked at
 // position i, vs[i] = its walk index.  Keys of <= 24 bits: two-level grouping; one stretch of the word:
 // the words themselves as sort keys; else keys + sort + gather.  Scratch: seg_k0 / seg_v0 / seg_ks.
@@ -1413,16 +1446,7 @@ static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *
     if (stretch) hipLaunchKernelGGL(k_gather_bucket_words<WT>, dim3(blocks_for(U)), dim3(256), 0, st, g_word, vs, U, ws, c->gf_valid);
   }
   if (stretch) return HUMID_OK;
-  const ComboFields cf = plan_fields(plan, seg);
-  if (kb <= 32) {
-    hipLaunchKernelGGL((k_combo_keys<u32, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, cf,
-                       c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
-    TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), c->seg_ks.as<u32>(), c->seg_v0.as<u32>(), vs, U, 0, kb));
-  } else {
-    hipLaunchKernelGGL((k_combo_keys<u64, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, cf,
-                       c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
-    TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->seg_ks.as<u64>(), c->seg_v0.as<u32>(), vs, U, 0, kb));
-  }
+  TRY(combo_keys_sorted<WT>(c, g_word, U, plan_fields(plan, seg), kb, c->seg_ks.p, vs));
   hipLaunchKernelGGL(k_gather_bucket_words<WT>, dim3(blocks_for(U)), dim3(256), 0, st, g_word, vs, U, ws);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
@@ -1652,6 +1676,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     if (c->h_ctr[CTR_EDGES] > 0xffffffffull)
       return fail(c, HUMID_E_OVERFLOW, "%llu neighbour pairs exceed the 32-bit adjacency offsets", (ull)(c->h_ctr[CTR_EDGES] / 2));
     big_mask = search ? c->h_ctr[CTR_BIGMASK] : 0;
+    u64 twoE = c->h_ctr[CTR_N - 1] & 0xffffffffull;
     if (big_mask) {
       // some bucket is longer than k_pairs walks: find those runs, count their remaining pairs as
       // tiles, and take the component statistics and the offsets again
@@ -1666,13 +1691,10 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
       HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_SMALLROOTS], 0, sizeof(ull), st));
       HIPCHK(hipMemsetAsync(c->csize.p, 0, (size_t)U * 4, st));
       comp_stats(c, U);
-      TRY(exscan_u32(c, c->deg.as<u32>(), c->nbr_off.as<u32>(), (u64)U + 1));
-      HIPCHK(hipGetLastError());
-      TRY(read_counters(c, c->nbr_off.as<u32>() + U));
+      TRY(scan_total(c, c->deg.as<u32>(), c->nbr_off.as<u32>(), U, &twoE));
       if (c->h_ctr[CTR_EDGES] > 0xffffffffull)
         return fail(c, HUMID_E_OVERFLOW, "%llu neighbour pairs exceed the 32-bit adjacency offsets", (ull)(c->h_ctr[CTR_EDGES] / 2));
     }
-    const u64 twoE = c->h_ctr[CTR_N - 1] & 0xffffffffull;
     E = twoE / 2;
     M = c->h_ctr[CTR_NONSINGLE];
     Mbig = c->h_ctr[CTR_MEMBERS];
@@ -2058,7 +2080,111 @@ static int expand_compact(humid_ctx *c) {
   return HUMID_OK;
 }
 
-static int unique_edges(humid_ctx *c, const u64 *d_edges, u64 raw, u32 U, u64 *n_edges_out);
+// sorted, duplicate-free copy of an edge list (smaller << 32 | larger) -> c->e_edges
+static int unique_edges(humid_ctx *c, const u64 *d_edges, u64 raw, u32 U, u64 *n_edges_out) {
+  hipStream_t st = c->stream;
+  *n_edges_out = 0;
+  if (raw == 0) return HUMID_OK;
+  if (raw >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many edges");
+  // ---- sort + unique ----
+  const u32 R = (u32)raw;
+  ENSURE(c->e_sorted, (size_t)R * 8);
+  ENSURE(c->e_head, ((size_t)R + 1) * 4);
+  ENSURE(c->e_hpos, ((size_t)R + 1) * 4);
+  TRY(sort_keys<u64>(c, d_edges, c->e_sorted.as<u64>(), R, 0, 32 + bits_for(U)));
+  hipLaunchKernelGGL(k_heads_u64, dim3(blocks_for((u64)R + 1)), dim3(256), 0, st, c->e_sorted.as<u64>(), R,
+                     c->e_head.as<u32>());
+  u64 E = 0;
+  TRY(scan_total(c, c->e_head.as<u32>(), c->e_hpos.as<u32>(), R, &E));
+  ENSURE(c->e_edges, (size_t)(E + 1) * 8);
+  hipLaunchKernelGGL(k_compact_heads_u64, dim3(blocks_for(R)), dim3(256), 0, st, c->e_sorted.as<u64>(),
+                     c->e_head.as<u32>(), c->e_hpos.as<u32>(), R, c->e_edges.as<u64>());
+  HIPCHK(hipGetLastError());
+  *n_edges_out = E;
+  return HUMID_OK;
+}
+
+// ---- one candidate join: the driver of the edit (-e) and the strand-symmetric (-P) search -------------------------
+// The two sides of a join, both sorted by key: entry t of X meets the run of entries of Y that hold its key.
+template <class KT>
+struct JoinKeys {
+  using key_type = KT;
+  const KT *kx; const u32 *vx;     // X: keys ascending, the word each came from
+  const KT *ky; const u32 *vy;     // Y: the same (X itself where a search joins its keys with themselves)
+  u32 U;                           // entries on either side
+};
+// The pairs of one join, appended to c->e_raw at raw; raw advances.  The protocol:
+//   clear the sentinel pc[U] and CTR_BIGMASK; COUNT, one lane per X entry; scan, and wait for the number of pairs;
+//   if the COUNT raised CTR_BIGMASK -- some run of equal keys in Y is longer than the c->walk_max candidates that one
+//   lane verifies --: every run in pieces of that many (k_edit_chunks), scan, wait for the number of pieces; COUNT,
+//   one lane per piece; scan, wait;
+//   nothing found: done.  Else room in e_raw (what it holds is kept) and FILL, over the entries or over the pieces.
+// Host waits: one per join, three where the runs are cut into pieces.
+// launch(fill, keys, n_pieces, pc, poff, out) holds the kernel launches of a search: fill is std::bool_constant<FILL>,
+// keys a JoinKeys<u32 | u64>; n_pieces == 0: the join over keys.U entries, else over the n_pieces pieces of e_runlo /
+// e_choff.  search: the search's name in the two overflow messages.
+template <class Launch>
+static int join_append(humid_ctx *c, const char *search, const void *kx, const u32 *vx, const void *ky, const u32 *vy, u32 U,
+                       bool k32, Launch launch, u64 &raw) {
+  auto run = [&](auto key) -> int {
+    using KT = decltype(key);
+    hipStream_t st = c->stream;
+    const JoinKeys<KT> k{(const KT *)kx, vx, (const KT *)ky, vy, U};
+    const std::false_type count{};
+    const std::true_type fill{};
+    HIPCHK(hipMemsetAsync(c->pc.as<u32>() + U, 0, 4, st));
+    HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
+    launch(count, k, (u64)0, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+    u64 found = 0, n_pieces = 0;                   // n_pieces > 0: this join goes through the pieces
+    TRY(scan_total(c, c->pc.as<u32>(), c->poff.as<u32>(), U, &found));
+    if (c->h_ctr[CTR_BIGMASK]) {
+      ENSURE(c->e_runlo, ((size_t)U + 1) * 4);
+      ENSURE(c->e_nch, ((size_t)U + 1) * 4);
+      ENSURE(c->e_choff, ((size_t)U + 1) * 4);
+      hipLaunchKernelGGL(k_edit_chunks<KT>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, k.kx, k.ky, U, c->walk_max,
+                         c->e_runlo.as<u32>(), c->e_nch.as<u32>());
+      TRY(scan_total(c, c->e_nch.as<u32>(), c->e_choff.as<u32>(), U, &n_pieces));
+      if (n_pieces >= 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pieces in the %s search", search);
+      ENSURE(c->e_pc2, ((size_t)n_pieces + 1) * 4);
+      ENSURE(c->e_poff2, ((size_t)n_pieces + 1) * 4);
+      HIPCHK(hipMemsetAsync(c->e_pc2.as<u32>() + n_pieces, 0, 4, st));
+      launch(count, k, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
+      TRY(scan_total(c, c->e_pc2.as<u32>(), c->e_poff2.as<u32>(), n_pieces, &found));
+    }
+    if (found == 0) return HUMID_OK;
+    if (raw + found >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pairs in the %s search", search);
+    HIPCHK(c->e_raw.grow_keeping((size_t)raw * 8, (size_t)(raw + found) * 8, st));
+    launch(fill, k, n_pieces, (u32 *)nullptr, (const u32 *)(n_pieces ? c->e_poff2 : c->poff).as<u32>(), c->e_raw.as<u64>() + raw);
+    raw += found;
+    return HUMID_OK;
+  };
+  return k32 ? run(u32{}) : run(u64{});
+}
+
+// edit_edges below: the offset vectors o[0 .. k) in [-D, D] of a combination of k members, walk cost <= 2 D, first
+// non-zero entry positive.  group_field: member 0 is the group field of a grouped run, which stays in place.
+static std::vector<std::vector<int>> edit_offset_patterns(u32 k, int D, bool group_field) {
+  std::vector<std::vector<int>> patterns;
+  std::vector<int> o(k, 0);
+  std::function<void(u32, int, bool)> rec = [&](u32 t, int cost, bool signed_yet) {
+    if (t == k) {
+      const int total = cost + (k ? (o[k - 1] < 0 ? -o[k - 1] : o[k - 1]) : 0);
+      if (total <= 2 * D) patterns.push_back(o);
+      return;
+    }
+    for (int v = -D; v <= D; v++) {
+      if (!signed_yet && v < 0) continue;                 // canonical sign
+      if (group_field && t == 0 && v != 0) continue;
+      const int prev = t ? o[t - 1] : 0;
+      const int step = v > prev ? v - prev : prev - v;
+      if (cost + step > 2 * D) continue;
+      o[t] = v;
+      rec(t + 1, cost + step, signed_yet || v != 0);
+    }
+  };
+  rec(0, 0, false);
+  return patterns;
+}
 
 // ---- edit distance (-e): neighbour pairs under Levenshtein distance 2 .. 5 --------------------------
 // (distance <= 1 is the Hamming search: equal lengths leave no room for a lone insertion.)
@@ -2093,7 +2219,6 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
   const u32 gnt = c->gk_nt, wn = word_nt - gnt;
   const ComboPlan plan = make_plan(wn, distance, U, c->force_segments, false, gnt);
   const u32 kb = plan.key_bits ? plan.key_bits : 1;
-  const bool k32 = kb <= 32;
   ENSURE(c->e_kx, (size_t)U * 8);
   ENSURE(c->e_vx, (size_t)U * 4);
   ENSURE(c->e_ky, (size_t)U * 8);
@@ -2102,144 +2227,45 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
   ENSURE(c->seg_v0, (size_t)U * 4);
   ENSURE(c->pc, ((size_t)U + 1) * 4);
   ENSURE(c->poff, ((size_t)U + 1) * 4);
+  const int D = (int)(distance / 2);             // the offsets' range; the band of the verification
+  auto launch = [&](auto fill, auto k, u64 n_pieces, u32 *pc, const u32 *poff, u64 *out) {
+    auto banded = [&](auto band) {
+      constexpr bool FILL = decltype(fill)::value;
+      constexpr u32 BAND = decltype(band)::value;
+      using KT = typename decltype(k)::key_type;
+      if (n_pieces)
+        hipLaunchKernelGGL((k_edit_join_chunks<FILL, KT, WT, BAND>), dim3(blocks_for(n_pieces)), dim3(256), 0, st, k.kx, k.vx, k.ky,
+                           k.vy, k.U, (const u32 *)c->e_runlo.as<u32>(), (const u32 *)c->e_choff.as<u32>(), (u32)n_pieces,
+                           c->walk_max, g_word, word_nt, distance, pc, poff, out);
+      else
+        hipLaunchKernelGGL((k_edit_join<FILL, KT, WT, BAND>), dim3(blocks_for(k.U)), dim3(256), 0, st, k.kx, k.vx, k.ky, k.vy, k.U,
+                           g_word, word_nt, distance, pc, poff, out, c->walk_max, &c->d_ctr[CTR_BIGMASK]);
+    };
+    if (D <= 1) banded(std::integral_constant<u32, 1>{});
+    else if (D == 2) banded(std::integral_constant<u32, 2>{});
+    else banded(std::integral_constant<u32, 0>{});
+  };
   u64 raw = 0;                                   // pairs collected so far (with duplicates)
   u32 join_no = 0;
-  auto sort_keys_of = [&](const ComboFields &cf, DBuf &kout, DBuf &vout) -> int {
-    if (k32) {
-      hipLaunchKernelGGL((k_combo_keys<u32, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, cf,
-                         c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), kout.as<u32>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
-    } else {
-      hipLaunchKernelGGL((k_combo_keys<u64, WT>), dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, cf,
-                         c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), kout.as<u64>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
-    }
-    return HUMID_OK;
-  };
   for (u32 cb = 0; cb < plan.ncombo; cb++) {
     const ComboFields cfx = plan_fields(plan, cb);
-    TRY(sort_keys_of(cfx, c->e_kx, c->e_vx));
-    const u32 k = cfx.nf;
-    // offset vectors o[0 .. k) in [-D, D], D = d / 2, walk cost <= 2 D, first non-zero entry positive
-    const int D = (int)(distance / 2);
-    std::vector<std::vector<int>> patterns;
-    {
-      std::vector<int> o(k, 0);
-      std::function<void(u32, int, bool)> rec = [&](u32 t, int cost, bool signed_yet) {
-        if (t == k) {
-          const int total = cost + (k ? (o[k - 1] < 0 ? -o[k - 1] : o[k - 1]) : 0);
-          if (total <= 2 * D) patterns.push_back(o);
-          return;
-        }
-        for (int v = -D; v <= D; v++) {
-          if (!signed_yet && v < 0) continue;                 // canonical sign
-          if (gnt && t == 0 && v != 0) continue;              // the group field stays in place
-          const int prev = t ? o[t - 1] : 0;
-          const int step = v > prev ? v - prev : prev - v;
-          if (cost + step > 2 * D) continue;
-          o[t] = v;
-          rec(t + 1, cost + step, signed_yet || v != 0);
-        }
-      };
-      rec(0, 0, false);
-    }
-    for (const std::vector<int> &o : patterns) {
-      {
-        ComboFields cfy = cfx;
-        bool valid = true, shifted = false;
-        for (u32 t = 0; t < k; t++) {
-          // offset +1 = one nucleotide towards the end of the word = a field shift lower by 2 bits
-          const int sh = (int)cfy.shift[t] - 2 * o[t];
-          if (sh < 0 || sh + (int)cfy.width[t] > (int)(2 * ((gnt && t == 0) ? word_nt : wn))) { valid = false; break; }   // off the word
-          cfy.shift[t] = (u8)sh;
-          shifted = shifted || o[t] != 0;
-        }
-        if (!valid) continue;
-        const u32 a = 0, b = shifted ? 1u : 0u;                // (a != b: Y keys differ from X keys)
-        if (join_no++ % part_world != part_rank) continue;     // another rank's join
-        const void *ky = c->e_kx.p;
-        const u32 *vy = c->e_vx.as<u32>();
-        if (a != b) {
-          TRY(sort_keys_of(cfy, c->e_ky, c->e_vy));
-          ky = c->e_ky.p;
-          vy = c->e_vy.as<u32>();
-        }
-        HIPCHK(hipMemsetAsync(c->pc.as<u32>() + U, 0, 4, st));
-        HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
-        const u32 jwalk = c->walk_max;                         // candidates one lane verifies for one entry (0: all)
-#define EDIT_JOIN(FILL, KT, BAND, PC, POFF, OUT)                                                              \
-  hipLaunchKernelGGL((k_edit_join<FILL, KT, WT, BAND>), dim3(blocks_for(U)), dim3(256), 0, st, c->e_kx.as<KT>(), \
-                     c->e_vx.as<u32>(), (const KT *)ky, vy, U, g_word, word_nt, distance, PC, POFF, OUT, jwalk, &c->d_ctr[CTR_BIGMASK])
-#define EDIT_CHUNKS(FILL, KT, BAND, NP, PC, POFF, OUT)                                                                    \
-  hipLaunchKernelGGL((k_edit_join_chunks<FILL, KT, WT, BAND>), dim3(blocks_for(NP)), dim3(256), 0, st, c->e_kx.as<KT>(),  \
-                     c->e_vx.as<u32>(), (const KT *)ky, vy, U, (const u32 *)c->e_runlo.as<u32>(), (const u32 *)c->e_choff.as<u32>(), \
-                     (u32)(NP), jwalk, g_word, word_nt, distance, PC, POFF, OUT)
-        if (k32) { if (D <= 1) EDIT_JOIN(false, u32, 1, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                   else if (D == 2) EDIT_JOIN(false, u32, 2, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                   else EDIT_JOIN(false, u32, 0, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr); }
-        else { if (D <= 1) EDIT_JOIN(false, u64, 1, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-               else if (D == 2) EDIT_JOIN(false, u64, 2, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-               else EDIT_JOIN(false, u64, 0, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr); }
-        TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), (u64)U + 1));
-        HIPCHK(hipGetLastError());
-        TRY(read_counters(c, c->poff.as<u32>() + U));
-        u64 found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-        u64 n_pieces = 0;                                       // > 0: this join goes through the pieces
-        if (c->h_ctr[CTR_BIGMASK]) {
-          // some run of equal keys is longer than one lane walks: every run in pieces of jwalk candidates
-          ENSURE(c->e_runlo, ((size_t)U + 1) * 4);
-          ENSURE(c->e_nch, ((size_t)U + 1) * 4);
-          ENSURE(c->e_choff, ((size_t)U + 1) * 4);
-          if (k32) hipLaunchKernelGGL(k_edit_chunks<u32>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u32>(), (const u32 *)ky, U,
-                                      jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
-          else hipLaunchKernelGGL(k_edit_chunks<u64>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u64>(), (const u64 *)ky, U,
-                                  jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
-          TRY(exscan_u32(c, c->e_nch.as<u32>(), c->e_choff.as<u32>(), (u64)U + 1));
-          HIPCHK(hipGetLastError());
-          TRY(read_counters(c, c->e_choff.as<u32>() + U));
-          n_pieces = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-          if (n_pieces >= 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pieces in the edit-distance search");
-          ENSURE(c->e_pc2, ((size_t)n_pieces + 1) * 4);
-          ENSURE(c->e_poff2, ((size_t)n_pieces + 1) * 4);
-          HIPCHK(hipMemsetAsync(c->e_pc2.as<u32>() + n_pieces, 0, 4, st));
-          if (k32) { if (D <= 1) EDIT_CHUNKS(false, u32, 1, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                     else if (D == 2) EDIT_CHUNKS(false, u32, 2, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                     else EDIT_CHUNKS(false, u32, 0, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr); }
-          else { if (D <= 1) EDIT_CHUNKS(false, u64, 1, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                 else if (D == 2) EDIT_CHUNKS(false, u64, 2, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-                 else EDIT_CHUNKS(false, u64, 0, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr); }
-          TRY(exscan_u32(c, c->e_pc2.as<u32>(), c->e_poff2.as<u32>(), n_pieces + 1));
-          HIPCHK(hipGetLastError());
-          TRY(read_counters(c, c->e_poff2.as<u32>() + n_pieces));
-          found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-        }
-        if (found == 0) continue;
-        if (raw + found >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pairs in the edit-distance search");
-        if ((raw + found) * 8 > c->e_raw.cap) {               // grow, keeping what is there
-          DBuf bigger;
-          HIPCHK(bigger.ensure((size_t)((raw + found) * 8 * 2)));
-          if (raw) HIPCHK(hipMemcpyAsync(bigger.p, c->e_raw.p, (size_t)raw * 8, hipMemcpyDeviceToDevice, st));
-          HIPCHK(hipStreamSynchronize(st));
-          c->e_raw = std::move(bigger);
-        }
-        if (n_pieces) {
-          if (k32) { if (D <= 1) EDIT_CHUNKS(true, u32, 1, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-                     else if (D == 2) EDIT_CHUNKS(true, u32, 2, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-                     else EDIT_CHUNKS(true, u32, 0, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw); }
-          else { if (D <= 1) EDIT_CHUNKS(true, u64, 1, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-                 else if (D == 2) EDIT_CHUNKS(true, u64, 2, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-                 else EDIT_CHUNKS(true, u64, 0, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw); }
-        } else
-        if (k32) { if (D <= 1) EDIT_JOIN(true, u32, 1, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-                   else if (D == 2) EDIT_JOIN(true, u32, 2, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-                   else EDIT_JOIN(true, u32, 0, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw); }
-        else { if (D <= 1) EDIT_JOIN(true, u64, 1, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-               else if (D == 2) EDIT_JOIN(true, u64, 2, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-               else EDIT_JOIN(true, u64, 0, (u32 *)nullptr, c->poff.as<u32>(), c->e_raw.as<u64>() + raw); }
-#undef EDIT_CHUNKS
-#undef EDIT_JOIN
-        raw += found;
+    TRY(combo_keys_sorted<WT>(c, g_word, U, cfx, kb, c->e_kx.p, c->e_vx.as<u32>()));
+    for (const std::vector<int> &o : edit_offset_patterns(cfx.nf, D, gnt != 0)) {
+      ComboFields cfy = cfx;
+      bool valid = true, shifted = false;
+      for (u32 t = 0; t < cfx.nf; t++) {
+        // offset +1 = one nucleotide towards the end of the word = a field shift lower by 2 bits
+        const int sh = (int)cfy.shift[t] - 2 * o[t];
+        if (sh < 0 || sh + (int)cfy.width[t] > (int)(2 * ((gnt && t == 0) ? word_nt : wn))) { valid = false; break; }   // off the word
+        cfy.shift[t] = (u8)sh;
+        shifted = shifted || o[t] != 0;
       }
+      if (!valid) continue;
+      if (join_no++ % part_world != part_rank) continue;     // another rank's join
+      // shifted: Y = the keys read at the shifted positions; else the X keys against themselves
+      if (shifted) TRY(combo_keys_sorted<WT>(c, g_word, U, cfy, kb, c->e_ky.p, c->e_vy.as<u32>()));
+      const DBuf &ky = shifted ? c->e_ky : c->e_kx, &vy = shifted ? c->e_vy : c->e_vx;
+      TRY(join_append(c, "edit-distance", c->e_kx.p, c->e_vx.as<u32>(), ky.p, vy.as<u32>(), U, kb <= 32, launch, raw));
     }
   }
   HIPCHK(hipGetLastError());
@@ -2249,38 +2275,11 @@ static int edit_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 di
   return HUMID_OK;
 }
 
-// sorted, duplicate-free copy of an edge list (smaller << 32 | larger) -> c->e_edges
-static int unique_edges(humid_ctx *c, const u64 *d_edges, u64 raw, u32 U, u64 *n_edges_out) {
-  hipStream_t st = c->stream;
-  *n_edges_out = 0;
-  if (raw == 0) return HUMID_OK;
-  if (raw >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many edges");
-  // ---- sort + unique ----
-  const u32 R = (u32)raw;
-  ENSURE(c->e_sorted, (size_t)R * 8);
-  ENSURE(c->e_head, ((size_t)R + 1) * 4);
-  ENSURE(c->e_hpos, ((size_t)R + 1) * 4);
-  TRY(sort_keys<u64>(c, d_edges, c->e_sorted.as<u64>(), R, 0, 32 + bits_for(U)));
-  hipLaunchKernelGGL(k_heads_u64, dim3(blocks_for((u64)R + 1)), dim3(256), 0, st, c->e_sorted.as<u64>(), R,
-                     c->e_head.as<u32>());
-  TRY(exscan_u32(c, c->e_head.as<u32>(), c->e_hpos.as<u32>(), (u64)R + 1));
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c, c->e_hpos.as<u32>() + R));
-  const u64 E = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-  ENSURE(c->e_edges, (size_t)(E + 1) * 8);
-  hipLaunchKernelGGL(k_compact_heads_u64, dim3(blocks_for(R)), dim3(256), 0, st, c->e_sorted.as<u64>(),
-                     c->e_head.as<u32>(), c->e_hpos.as<u32>(), R, c->e_edges.as<u64>());
-  HIPCHK(hipGetLastError());
-  *n_edges_out = E;
-  return HUMID_OK;
-}
-
 // ---- strand-symmetric neighbours (humid_dedup_run_paired*, kernels_paired.hip.h) ----------------------------------
 // Pairs of leaves u < v with min(ham(u, v), ham(u, m(v))) <= distance, as a duplicate-free ascending edge list in
 // c->e_edges.  g_word: the U canonical leaves, ascending.  For every combination of the pigeonhole plan two joins
 // over the leaves' keys X: against themselves (plain pairs) and against the keys of the mirrored leaves (mirror
-// pairs, verified against m(v)).  The host waits are those of edit_edges: one per join for the number of pairs, two
-// more where a run of equal keys is longer than one lane walks.
+// pairs, verified against m(v)).  The host waits are those of join_append.
 template <class WT>
 static int paired_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 distance, u64 *n_edges_out) {
   hipStream_t st = c->stream;
@@ -2291,7 +2290,6 @@ static int paired_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 
     return fail(c, HUMID_E_OVERFLOW, "distance %u over %u-nt words compares all pairs of %u unique words: too many neighbour pairs",
                 distance, word_nt, U);
   const u32 kb = plan.key_bits ? plan.key_bits : 1;
-  const bool k32 = kb <= 32;
   ENSURE(c->pd_mir, (size_t)U * sizeof(WT) + 16);
   ENSURE(c->e_kx, (size_t)U * 8);
   ENSURE(c->e_vx, (size_t)U * 4);
@@ -2303,85 +2301,26 @@ static int paired_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 
   ENSURE(c->poff, ((size_t)U + 1) * 4);
   const WT *mir = c->pd_mir.as<WT>();
   hipLaunchKernelGGL(k_pd_mirror<WT>, dim3(blocks_for(U)), dim3(256), 0, st, g_word, U, word_nt, c->pd_mir.as<WT>());
-  auto sort_keys_of = [&](const WT *src, const ComboFields &cf, DBuf &kout, DBuf &vout) -> int {
-    if (k32) {
-      hipLaunchKernelGGL((k_combo_keys<u32, WT>), dim3(blocks_for(U)), dim3(256), 0, st, src, U, cf,
-                         c->seg_k0.as<u32>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u32, u32>(c, c->seg_k0.as<u32>(), kout.as<u32>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
-    } else {
-      hipLaunchKernelGGL((k_combo_keys<u64, WT>), dim3(blocks_for(U)), dim3(256), 0, st, src, U, cf,
-                         c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
-      TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), kout.as<u64>(), c->seg_v0.as<u32>(), vout.as<u32>(), U, 0, kb));
-    }
-    return HUMID_OK;
-  };
   u64 raw = 0;                                   // pairs collected so far (with duplicates)
-  const u32 jwalk = c->walk_max;                 // candidates one lane verifies for one entry (0: all)
   for (u32 cb = 0; cb < plan.ncombo; cb++) {
     const ComboFields cf = plan_fields(plan, cb);
-    TRY(sort_keys_of(g_word, cf, c->e_kx, c->e_vx));
-    TRY(sort_keys_of(mir, cf, c->e_ky, c->e_vy));
+    TRY(combo_keys_sorted<WT>(c, g_word, U, cf, kb, c->e_kx.p, c->e_vx.as<u32>()));
+    TRY(combo_keys_sorted<WT>(c, mir, U, cf, kb, c->e_ky.p, c->e_vy.as<u32>()));
     for (u32 side = 0; side < 2; side++) {       // 0: the leaves themselves, 1: their mirrors
-      const void *ky = side ? c->e_ky.p : c->e_kx.p;
-      const u32 *vy = side ? c->e_vy.as<u32>() : c->e_vx.as<u32>();
       const WT *yw = side ? mir : g_word;
-      HIPCHK(hipMemsetAsync(c->pc.as<u32>() + U, 0, 4, st));
-      HIPCHK(hipMemsetAsync(&c->d_ctr[CTR_BIGMASK], 0, sizeof(ull), st));
-#define PD_JOIN(FILL, KT, PC, POFF, OUT)                                                                              \
-  hipLaunchKernelGGL((k_pd_join<FILL, KT, WT>), dim3(blocks_for(U)), dim3(256), 0, st, c->e_kx.as<KT>(), c->e_vx.as<u32>(), \
-                     (const KT *)ky, vy, U, g_word, yw, distance, PC, POFF, OUT, jwalk, &c->d_ctr[CTR_BIGMASK])
-#define PD_CHUNKS(FILL, KT, NP, PC, POFF, OUT)                                                                        \
-  hipLaunchKernelGGL((k_pd_join_chunks<FILL, KT, WT>), dim3(blocks_for(NP)), dim3(256), 0, st, c->e_kx.as<KT>(),     \
-                     c->e_vx.as<u32>(), (const KT *)ky, vy, U, (const u32 *)c->e_runlo.as<u32>(),                     \
-                     (const u32 *)c->e_choff.as<u32>(), (u32)(NP), jwalk, g_word, yw, distance, PC, POFF, OUT)
-      if (k32) PD_JOIN(false, u32, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-      else PD_JOIN(false, u64, c->pc.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-      TRY(exscan_u32(c, c->pc.as<u32>(), c->poff.as<u32>(), (u64)U + 1));
-      HIPCHK(hipGetLastError());
-      TRY(read_counters(c, c->poff.as<u32>() + U));
-      u64 found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-      u64 n_pieces = 0;                          // > 0: this join goes through the pieces
-      if (c->h_ctr[CTR_BIGMASK]) {
-        // some run of equal keys is longer than one lane walks: every run in pieces of jwalk candidates
-        ENSURE(c->e_runlo, ((size_t)U + 1) * 4);
-        ENSURE(c->e_nch, ((size_t)U + 1) * 4);
-        ENSURE(c->e_choff, ((size_t)U + 1) * 4);
-        if (k32) hipLaunchKernelGGL(k_edit_chunks<u32>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u32>(), (const u32 *)ky, U,
-                                    jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
-        else hipLaunchKernelGGL(k_edit_chunks<u64>, dim3(blocks_for((u64)U + 1)), dim3(256), 0, st, c->e_kx.as<u64>(), (const u64 *)ky, U,
-                                jwalk, c->e_runlo.as<u32>(), c->e_nch.as<u32>());
-        TRY(exscan_u32(c, c->e_nch.as<u32>(), c->e_choff.as<u32>(), (u64)U + 1));
-        HIPCHK(hipGetLastError());
-        TRY(read_counters(c, c->e_choff.as<u32>() + U));
-        n_pieces = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-        if (n_pieces >= 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pieces in the strand-symmetric search");
-        ENSURE(c->e_pc2, ((size_t)n_pieces + 1) * 4);
-        ENSURE(c->e_poff2, ((size_t)n_pieces + 1) * 4);
-        HIPCHK(hipMemsetAsync(c->e_pc2.as<u32>() + n_pieces, 0, 4, st));
-        if (k32) PD_CHUNKS(false, u32, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-        else PD_CHUNKS(false, u64, n_pieces, c->e_pc2.as<u32>(), (const u32 *)nullptr, (u64 *)nullptr);
-        TRY(exscan_u32(c, c->e_pc2.as<u32>(), c->e_poff2.as<u32>(), n_pieces + 1));
-        HIPCHK(hipGetLastError());
-        TRY(read_counters(c, c->e_poff2.as<u32>() + n_pieces));
-        found = c->h_ctr[CTR_N - 1] & 0xffffffffull;
-      }
-      if (found == 0) continue;
-      if (raw + found >= 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pairs in the strand-symmetric search");
-      if ((raw + found) * 8 > c->e_raw.cap) {                 // grow, keeping what is there
-        DBuf bigger;
-        HIPCHK(bigger.ensure((size_t)((raw + found) * 8 * 2)));
-        if (raw) HIPCHK(hipMemcpyAsync(bigger.p, c->e_raw.p, (size_t)raw * 8, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        c->e_raw = std::move(bigger);
-      }
-      if (n_pieces) {
-        if (k32) PD_CHUNKS(true, u32, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-        else PD_CHUNKS(true, u64, n_pieces, (u32 *)nullptr, (const u32 *)c->e_poff2.as<u32>(), c->e_raw.as<u64>() + raw);
-      } else if (k32) PD_JOIN(true, u32, (u32 *)nullptr, (const u32 *)c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-      else PD_JOIN(true, u64, (u32 *)nullptr, (const u32 *)c->poff.as<u32>(), c->e_raw.as<u64>() + raw);
-#undef PD_CHUNKS
-#undef PD_JOIN
-      raw += found;
+      auto launch = [&](auto fill, auto k, u64 n_pieces, u32 *pc, const u32 *poff, u64 *out) {
+        constexpr bool FILL = decltype(fill)::value;
+        using KT = typename decltype(k)::key_type;
+        if (n_pieces)
+          hipLaunchKernelGGL((k_pd_join_chunks<FILL, KT, WT>), dim3(blocks_for(n_pieces)), dim3(256), 0, st, k.kx, k.vx, k.ky, k.vy,
+                             k.U, (const u32 *)c->e_runlo.as<u32>(), (const u32 *)c->e_choff.as<u32>(), (u32)n_pieces, c->walk_max,
+                             g_word, yw, distance, pc, poff, out);
+        else
+          hipLaunchKernelGGL((k_pd_join<FILL, KT, WT>), dim3(blocks_for(k.U)), dim3(256), 0, st, k.kx, k.vx, k.ky, k.vy, k.U, g_word,
+                             yw, distance, pc, poff, out, c->walk_max, &c->d_ctr[CTR_BIGMASK]);
+      };
+      const DBuf &ky = side ? c->e_ky : c->e_kx, &vy = side ? c->e_vy : c->e_vx;
+      TRY(join_append(c, "strand-symmetric", c->e_kx.p, c->e_vx.as<u32>(), ky.p, vy.as<u32>(), U, kb <= 32, launch, raw));
     }
   }
   HIPCHK(hipGetLastError());

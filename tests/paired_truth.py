@@ -221,6 +221,30 @@ def long_run_words(seed, n=24, k=300):
     return from_ints(vals, n), np.zeros(len(vals), np.uint8)
 
 
+def shared_prefix_words(seed, n, share, k=300):
+    """k different words P.T: one prefix P of `share` nucleotides (more than half a word) in front of tails T, a third
+    of them random and each of the others one of those with one nucleotide changed, so pairs at distance 1 exist.  P
+    starts with 0 and holds 2 at position n / 2: every word is below its mirror, its own canonical word.  Every third
+    one is given as its mirror, a read of the other strand."""
+    rng = np.random.default_rng(seed)
+    h = n // 2
+    assert h < share < n
+    P = [0] + rng.integers(0, 4, size=share - 1).tolist()
+    P[h] = 2
+    tails = {}
+    while len(tails) < k:
+        if len(tails) % 3 == 0:
+            T = rng.integers(0, 4, size=n - share).tolist()
+        else:
+            T = list(list(tails)[int(rng.integers(0, len(tails)))])
+            T[int(rng.integers(0, len(T)))] = int(rng.integers(0, 4))
+        tails[tuple(T)] = True
+    vals = [pack(P + list(T)) for T in tails]
+    vals = [mirror(v, n) if j % 3 == 0 else v for j, v in enumerate(vals)]
+    vals = [vals[i] for i in rng.permutation(len(vals))]
+    return from_ints(vals, n), np.zeros(len(vals), np.uint8)
+
+
 def write_duplex_fastq(dirpath, seed, n_reads, n=24, read_len=30, gz=False, qual_of=None):
     """two FastQ files R1 / R2 without a UMI in the headers: molecules (a pair of random reads) sequenced several
     times, about half of the records from the other strand (R1 and R2 exchanged), with substitutions inside the first

@@ -2,11 +2,14 @@
 humid_get_strands) against tests/paired_truth.py, bit for bit: cluster ids, keep flags, the summary counts, leaves,
 adjacency, clusters, the three histograms, the strand of every read, the reads of each strand per cluster and the
 strand summary."""
+import collections
 import functools
+import itertools
 
 import numpy as np
 import pytest
 
+import edit_truth as et
 import humid_amd
 import paired_truth as pt
 from oracle import pyoracle as orc
@@ -108,21 +111,49 @@ def test_all_filtered_and_one_leaf(dd, n):
     assert_matches(dd, dd.run_paired(one, f1, word_nt=n, distance=1), t)
 
 
-def test_key_runs_longer_than_the_walk(dd):
-    """a few hundred leaves share one half: with bucket_walk 8 the joins take their long runs in pieces; the plain
-    and the mirror join both meet a run (X.R against X.R, and against the mirrors X.R' of the leaves R'.X)"""
-    words, filt = pt.long_run_words(7)
-    t = pt.run(words, filt, 24, 1)
-    assert t["summary"]["unique"] > 400 and t["summary"]["edges"] > 50
+def longest_key_run(t, n, d, s):
+    """(the longest run of equal join keys among the leaves' keys and among their mirrors' keys, the widest key in
+    bits): a key is a combination of s - d of the s segments of the plan"""
+    leaves = pt.to_ints(t["leaves"]["word"], n)
+    longest, bits = 0, 0
+    for combo in itertools.combinations(et.segments(n, s), s - d):
+        bits = max(bits, 2 * sum(ln for _, ln in combo))
+        for vals in (leaves, [pt.mirror(v, n) for v in leaves]):
+            keys = collections.Counter(tuple((v >> 2 * (n - at - ln)) & ((1 << 2 * ln) - 1) for at, ln in combo) for v in vals)
+            longest = max(longest, max(keys.values()))
+    assert bits <= 64                                   # (no key of these cases is cut)
+    return longest, bits
+
+
+# (n, d, plan_segments, segments of the plan, bits of a key): words of one or two u64 x keys of 32 or 64 bits.  Without
+# plan_segments the plan of a few hundred leaves is two halves at d = 1: the fewest segments whose key tells them apart.
+LONG_RUNS = [(24, 1, 0, 2, 24), (48, 2, 3, 3, 32), (64, 1, 0, 2, 64), (32, 1, 3, 3, 44)]
+
+
+@pytest.mark.parametrize("n,d,forced,s,key_bits", LONG_RUNS, ids=["n%d_d%d" % c[:2] for c in LONG_RUNS])
+def test_key_runs_longer_than_the_walk(dd, n, d, forced, s, key_bits):
+    """a few hundred leaves share one half (n = 32: the 22 nucleotides of the first two of three segments): with
+    bucket_walk 8 the joins take their long runs in pieces; where a half is shared the plain and the mirror join both
+    meet a run (X.R against X.R, and against the mirrors X.R' of the leaves R'.X)"""
+    words, filt = pt.shared_prefix_words(7, n, 22) if n == 32 else pt.long_run_words(7, n)
+    t = pt.run(words, filt, n, d)
+    assert t["summary"]["unique"] > (299 if n == 32 else 400) and t["summary"]["edges"] > 50
+    if n == 32:
+        assert t["strands"]["bottom_reads"] > 0
+    run, bits = longest_key_run(t, n, d, s)
+    assert run > 8 and bits == key_bits, (run, bits)
     dd.set_option("bucket_walk", 8)
+    dd.set_option("plan_segments", forced)
     try:
-        got = dd.run_paired(words, filt, word_nt=24, distance=1)
+        got = dd.run_paired(words, filt, word_nt=n, distance=d)
         assert_matches(dd, got, t)
-        t2 = pt.run(words, filt, 24, 2, 1)
-        assert_matches(dd, dd.run_paired(words, filt, word_nt=24, distance=2, method=1), t2)
+        if n == 24:
+            t2 = pt.run(words, filt, 24, 2, 1)
+            assert_matches(dd, dd.run_paired(words, filt, word_nt=24, distance=2, method=1), t2)
     finally:
         dd.set_option("bucket_walk", 1024)
-    assert_matches(dd, dd.run_paired(words, filt, word_nt=24, distance=1), t)
+        dd.set_option("plan_segments", 0)
+    assert_matches(dd, dd.run_paired(words, filt, word_nt=n, distance=d), t)
 
 
 @pytest.mark.parametrize("n", [8, 24, 48, 64])
