@@ -70,6 +70,14 @@ HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
 
+class HumidBcPosteriorSummary(C.Structure):
+    """humid_bc_posterior_summary of include/humid_hip.h"""
+    _fields_ = [("counts", C.c_uint64 * 5), ("multi", C.c_uint64), ("rescued", C.c_uint64)]
+
+    def asdict(self):
+        return dict(counts=[int(x) for x in self.counts], multi=int(self.multi), rescued=int(self.rescued))
+
+
 class HumidComm(C.Structure):
     """humid_comm of include/humid_hip.h: what moves bytes between ranks for humid_dedup_run_exchange"""
     _fields_ = [("user", C.c_void_p), ("rank", C.c_uint32), ("world", C.c_uint32),
@@ -130,6 +138,19 @@ SYMBOLS = {
                                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                          C.POINTER(HumidSummary)]),
     "humid_get_barcode_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "humid_whitelist_correct_posterior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(HumidBcPosteriorSummary)]),
+    "humid_whitelist_correct_posterior_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                           C.c_uint32, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(HumidBcPosteriorSummary)]),
+    "humid_dedup_run_keyed_posterior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(HumidSummary)]),
+    "humid_dedup_run_keyed_posterior_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                         C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
+    "humid_get_barcode_posterior": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "humid_whitelist_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "humid_get_group_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "humid_group_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 4),

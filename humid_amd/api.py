@@ -189,7 +189,24 @@ class Dedup(Context):
         self._wide = word_nt > 32
         return self.summary
 
-    def run_keyed(self, words, keys, filtered, word_nt=24, distance=1, method=DIRECTIONAL, edit=False, correct=False):
+    def _barcode_quals(self, quals, n):
+        """u8[N, K] Phred+33 bytes of the barcodes, K that of the whitelist now set"""
+        q = np.asarray(quals)
+        if q.dtype != np.uint8 or q.ndim != 2 or q.shape[0] != n:
+            raise ValueError("barcode qualities must be uint8 of shape (%d, K)" % n)
+        k = self.whitelist_info()["barcode_nt"]
+        if k and q.shape[1] != k:                               # (no whitelist: the library refuses the call)
+            raise ValueError("barcode qualities must be uint8 of shape %r" % ((n, k),))
+        return np.ascontiguousarray(q)
+
+    @staticmethod
+    def _min_odds(min_odds):
+        if not 1 <= int(min_odds) < 1 << 32:
+            raise ValueError("min_odds must be 1 .. 2**32 - 1")
+        return int(min_odds)
+
+    def run_keyed(self, words, keys, filtered, word_nt=24, distance=1, method=DIRECTIONAL, edit=False, correct=False,
+                  barcode_quals=None, min_odds=39):
         """Deduplicate within groups given by arbitrary 64-bit keys (include/humid_hip.h, humid_dedup_run_keyed):
         run_grouped with every usable read's group = the rank of its key among the distinct keys of the usable
         reads, ranked on the device.  keys: u64[N]; keys of filtered reads are not read.
@@ -197,7 +214,13 @@ class Dedup(Context):
         and "key", and group_keys() the sorted distinct keys.
         correct=True: the keys are corrected against the whitelist of set_whitelist() first and reads whose key is
         ambiguous or unmatched count as filtered (humid_dedup_run_keyed_corrected); barcode_status() then gives
-        every read's status."""
+        every read's status.
+        barcode_quals (u8[N, K] raw Phred+33 bytes of the barcode's nucleotides, with correct=True only): a key with
+        several whitelist barcodes one substitution away goes to the one whose weight (exact reads + 1) * error
+        probability of the differing base is at least min_odds times all the others' together, instead of being
+        ambiguous (humid_dedup_run_keyed_posterior); barcode_posterior() and whitelist_counts() answer afterwards."""
+        if barcode_quals is not None and not correct:
+            raise ValueError("barcode_quals needs correct=True")
         w = np.ascontiguousarray(words, dtype=np.uint64)
         f = np.ascontiguousarray(filtered, dtype=np.uint8)
         want = (len(f), 2) if word_nt > 32 else (len(f),)
@@ -210,11 +233,19 @@ class Dedup(Context):
             raise ValueError("keys must not be negative")
         k = np.ascontiguousarray(k, dtype=np.uint64)
         n = len(f)
+        if barcode_quals is not None:
+            mo = self._min_odds(min_odds)
+            q = self._barcode_quals(barcode_quals, n)
         self._wide = word_nt > 32
         self.set_option("edit_distance", int(bool(edit)))
         cid = np.zeros(n, dtype=np.uint32)
         keep = np.zeros(n, dtype=np.uint8)
         s = _lib.HumidSummary()
+        if barcode_quals is not None:
+            self._check(self._lib.humid_dedup_run_keyed_posterior(self._h, _vp(w), _vp(k), _vp(q), _vp(f), n, word_nt, distance,
+                                                                  method, mo, _vp(cid), _vp(keep), C.byref(s)))
+            self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
+            return cid, keep, self.summary
         fn = self._lib.humid_dedup_run_keyed_corrected if correct else self._lib.humid_dedup_run_keyed
         self._check(fn(self._h, _vp(w), _vp(k), _vp(f), n, word_nt, distance, method, _vp(cid), _vp(keep), C.byref(s)))
         self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
@@ -239,6 +270,18 @@ class Dedup(Context):
         self._check(self._lib.humid_dedup_run_keyed_corrected_device(
             self._h, C.c_void_p(d_words), C.c_void_p(d_keys), C.c_void_p(d_filtered), n_reads, word_nt, distance,
             method, C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
+        self._wide = word_nt > 32
+        return self.summary
+
+    def run_keyed_posterior_device(self, d_words, d_keys, d_quals, d_filtered, d_cluster_id, d_keep, n_reads, word_nt=24,
+                                   distance=1, method=DIRECTIONAL, min_odds=39):
+        """run_keyed(correct=True, barcode_quals=...) on device pointers (ints; d_keys u64[N], d_quals u8[N * K]);
+        results stay in HBM."""
+        s, mo = _lib.HumidSummary(), self._min_odds(min_odds)
+        self._check(self._lib.humid_dedup_run_keyed_posterior_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_keys), C.c_void_p(d_quals), C.c_void_p(d_filtered), n_reads, word_nt,
+            distance, method, mo, C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
         self.summary = self._grouped_summary = self._keyed_summary = s.asdict()
         self._wide = word_nt > 32
         return self.summary
@@ -327,16 +370,26 @@ class Dedup(Context):
         self._check(self._lib.humid_whitelist_info(self._h, C.byref(n), C.byref(k), C.byref(t)))
         return dict(n_distinct=n.value, barcode_nt=k.value, table_log2=t.value)
 
-    def correct_keys(self, keys, filtered):
+    def correct_keys(self, keys, filtered, quals=None, min_odds=39):
         """Correct keys against the whitelist without running anything else (humid_whitelist_correct): returns
         (keys_out u64[N], status u8[N] of BC_FILTERED .. BC_UNMATCHED, counts u64[5] indexed by status).  The
-        results of the last run stay untouched."""
+        results of the last run stay untouched.
+        quals (u8[N, K] raw Phred+33 bytes of the barcode's nucleotides): ambiguous keys are decided by quality and
+        abundance (humid_whitelist_correct_posterior, see run_keyed) and a fourth value is returned, dict(counts,
+        multi, rescued): the reads with two or more candidates and those of them that were corrected."""
         f = np.ascontiguousarray(filtered, dtype=np.uint8)
         if f.ndim != 1:
             raise ValueError("filtered must be one-dimensional")
         k = _keys_u64(keys, f.shape)
         n = len(f)
         out, status, counts = np.zeros(n, np.uint64), np.zeros(n, np.uint8), np.zeros(5, np.uint64)
+        if quals is not None:
+            mo = self._min_odds(min_odds)
+            q, sm = self._barcode_quals(quals, n), _lib.HumidBcPosteriorSummary()
+            self._check(self._lib.humid_whitelist_correct_posterior(self._h, _vp(k), _vp(q), _vp(f), n, mo,
+                                                                    _vp(out), _vp(status), C.byref(sm)))
+            d = sm.asdict()
+            return out, status, np.asarray(d["counts"], np.uint64), d
         self._check(self._lib.humid_whitelist_correct(self._h, _vp(k), _vp(f), n, _vp(out), _vp(status), _vp(counts)))
         return out, status, counts
 
@@ -347,6 +400,31 @@ class Dedup(Context):
             self._h, C.c_void_p(d_keys), C.c_void_p(d_filtered), n_reads, C.c_void_p(d_keys_out) if d_keys_out else None,
             C.c_void_p(d_status) if d_status else None, _vp(counts)))
         return counts
+
+    def correct_keys_posterior_device(self, d_keys, d_quals, d_filtered, d_keys_out, d_status, n_reads, min_odds=39):
+        """correct_keys(quals=...) on device pointers (ints; d_quals u8[N * K]; d_keys_out u64[N] and d_status u8[N]
+        may be 0); returns dict(counts, multi, rescued)"""
+        sm, mo = _lib.HumidBcPosteriorSummary(), self._min_odds(min_odds)
+        self._check(self._lib.humid_whitelist_correct_posterior_device(
+            self._h, C.c_void_p(d_keys), C.c_void_p(d_quals), C.c_void_p(d_filtered), n_reads, mo,
+            C.c_void_p(d_keys_out) if d_keys_out else None, C.c_void_p(d_status) if d_status else None, C.byref(sm)))
+        return sm.asdict()
+
+    def barcode_posterior(self):
+        """after run_keyed(correct=True, barcode_quals=...): dict(multi, rescued) of that run
+        (humid_get_barcode_posterior)"""
+        m, r = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.humid_get_barcode_posterior(self._h, C.byref(m), C.byref(r)))
+        return dict(multi=int(m.value), rescued=int(r.value))
+
+    def whitelist_counts(self, barcodes):
+        """u32[len(barcodes)]: the usable reads of the last posterior correction (call or run) whose key WAS each of
+        the given barcodes, before any correction; 0 for a value the whitelist does not hold
+        (humid_whitelist_counts)"""
+        b = _keys_u64(barcodes, None, "barcodes")
+        out = np.zeros(len(b), np.uint32)
+        self._check(self._lib.humid_whitelist_counts(self._h, _vp(b) if len(b) else None, len(b), _vp(out) if len(b) else None))
+        return out
 
     def barcode_status(self):
         """after run_keyed(correct=True): (status u8[N], counts u64[5]) of that run (humid_get_barcode_status)"""

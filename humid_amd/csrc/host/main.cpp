@@ -57,6 +57,9 @@ struct Args {
   bool keyed = false;          // -b given (not in the reference): the first `barcode` nucleotides of the word are matched exactly
   size_t barcode = 0;          // -b
   std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
+  bool posterior = false;      // --barcode-posterior (needs -w): barcodes with several listed neighbours are decided by base quality and abundance
+  unsigned long long min_odds = 39;   // --barcode-min-odds
+  std::string dump_bc_quals;   // --dump-barcode-quals (development: the barcode qualities of pass 1, then stop, no GPU)
   bool best = false;           // -Q (not in the reference): every cluster keeps its record with the best base qualities
   std::string dump_scores;     // --dump-scores (development: the -Q scores of pass 1, then stop, no GPU)
   bool consensus = false;      // -C (not in the reference): every kept record carries the consensus of its cluster's reads
@@ -72,7 +75,7 @@ struct Args {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE [--barcode-posterior]]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -86,6 +89,13 @@ void usage(const char *argv0) {
                "      starting with # are skipped).  A barcode that is not listed but has exactly one listed barcode one\n"
                "      substitution away becomes that barcode; reads whose barcode has several or none are left out like\n"
                "      reads with an N; with -s also barcodes.dat: exact / corrected / ambiguous / unmatched reads\n"
+               "  --barcode-posterior  with -w: a barcode with SEVERAL listed barcodes one substitution away is decided as Cell\n"
+               "      Ranger and STARsolo (1MM_multi) do: every candidate weighs (its exact reads in this input + 1) times the\n"
+               "      error probability of the differing base (its quality, the first K letters of the first file's quality\n"
+               "      line; at most Phred 40), and the heaviest wins when it weighs at least --barcode-min-odds N (default 39:\n"
+               "      a posterior of 0.975; N >= 1) times all the others together.  The barcode must come from the first\n"
+               "      file's read (no UMI in the headers, K nucleotides or more taken from it).  barcodes.dat gains the\n"
+               "      lines multi (reads with several candidates) and rescued (those of them corrected); a log line\n"
                "  -Q  keep the record with the best base qualities of every cluster instead of the first one: among the\n"
                "      records that carry the cluster's most abundant word, the one with the largest sum of Phred qualities\n"
                "      >= 15 over all input files (Picard's SUM_OF_BASE_QUALITIES; ties: the first; one GPU).  Only the\n"
@@ -130,6 +140,18 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-g") { const char *v = need("-g"); if (!v) return false; a.gpus = (unsigned)std::strtoul(v, nullptr, 10); }
     else if (t == "-b") { const char *v = need("-b"); if (!v) return false; a.keyed = true; a.barcode = std::strtoull(v, nullptr, 10); }
     else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelist = v; }
+    else if (t == "--barcode-posterior") a.posterior = !a.posterior;
+    else if (t == "--barcode-min-odds") {
+      const char *v = need("--barcode-min-odds");
+      if (!v) return false;
+      char *end = nullptr;
+      a.min_odds = std::strtoull(v, &end, 10);
+      if (*v < '0' || *v > '9' || *end != 0 || a.min_odds < 1 || a.min_odds > 0xffffffffull) {
+        std::fprintf(stderr, "humid: --barcode-min-odds takes odds of 1 .. 4294967295\n");
+        return false;
+      }
+    }
+    else if (t == "--dump-barcode-quals") { const char *v = need("--dump-barcode-quals"); if (!v) return false; a.dump_bc_quals = v; }
     else if (t == "--dump-words") { const char *v = need("--dump-words"); if (!v) return false; a.dump_words = v; }
     else if (t == "--dump-scores") { const char *v = need("--dump-scores"); if (!v) return false; a.dump_scores = v; }
     else if (t == "--dump-consensus-input") { const char *v = need("--dump-consensus-input"); if (!v) return false; a.dump_consensus = v; }
@@ -447,7 +469,8 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: --consensus-min-q takes 0 .. 93\n");
     return 2;
   }
-  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty() || !a.dump_positions.empty();   // development: stop after pass 1, no GPU
+  const bool dump_only = !a.dump_words.empty() || !a.dump_scores.empty() || !a.dump_consensus.empty() || !a.dump_positions.empty() ||
+                         !a.dump_bc_quals.empty();   // development: stop after pass 1, no GPU
   const bool cons_out = a.consensus || a.duplex;                            // pass 2 writes consensus bytes (put_consensus)
   const bool want_reads = cons_out || !a.dump_consensus.empty();         // the reads themselves are gathered from the mappings
   const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
@@ -465,6 +488,15 @@ int main(int argc, char **argv) {
     }
   }
   const bool corrected = !whitelist.empty();
+  if (a.posterior && !corrected) {
+    std::fprintf(stderr, "humid: --barcode-posterior needs -w FILE (it decides between the listed barcodes near a read's barcode)\n");
+    return 2;
+  }
+  const bool bc_quals = a.posterior || !a.dump_bc_quals.empty();            // pass 1 gathers the barcode's qualities
+  if (bc_quals && !a.keyed) {
+    std::fprintf(stderr, "humid: %s needs -b K (the qualities of the barcode's K nucleotides)\n", a.posterior ? "--barcode-posterior" : "--dump-barcode-quals");
+    return 2;
+  }
   std::ofstream log(a.log_name.c_str(), std::ios::out | std::ios::binary);
 
   // The HIP runtime and the context come up (a few hundred ms) while pass 1 parses the files.
@@ -537,6 +569,17 @@ int main(int argc, char **argv) {
     return 2;
   }
   WordPlan plan = make_plan(first_umi, a.files.size(), a.word_length);
+  if (bc_quals && (plan.header_umi != 0 || plan.take[0] < a.barcode)) {
+    // the barcode's qualities are the first K letters of the first file's quality line: the barcode must be its read's start
+    const char *flag = a.posterior ? "--barcode-posterior" : "--dump-barcode-quals";
+    if (plan.header_umi != 0)
+      std::fprintf(stderr, "humid: %s: the headers of %s carry a UMI, which starts the word: the barcode has no base qualities\n", flag,
+                   a.files.front().c_str());
+    else
+      std::fprintf(stderr, "humid: %s: only %zu nucleotides are taken from %s, fewer than the barcode's %zu (-b)\n", flag,
+                   (size_t)plan.take[0], a.files.front().c_str(), a.barcode);
+    return 2;
+  }
   time_t t = start_message(log, "Determing nucleotides to take");
   end_message(log, t);
   log << "  header: " << plan.header_umi;
@@ -582,6 +625,15 @@ int main(int argc, char **argv) {
   uint64_t n_records = 0;
   std::vector<uint32_t> scores;                    // -Q: one per record
   std::vector<uint32_t> pos_tile, pos_x, pos_y;    // -O: the position of every record (position.hpp)
+  // --barcode-posterior: K quality bytes per record, the first K letters of the first file's quality line ('!' where
+  // the line is shorter: such a read is filtered and its row never read)
+  std::vector<uint8_t> bcq;
+  const size_t K = a.barcode;
+  auto put_bc_quals = [&](uint8_t *row, const char *q, size_t len) {
+    const size_t have = len < K ? len : K;
+    std::memcpy(row, q, have);
+    std::memset(row + have, '!', K - have);
+  };
   if (fast) {
     size_t n = maps[0].records();
     for (auto &m : maps) n = m.records() < n ? m.records() : n;     // stop at the shortest file
@@ -605,6 +657,7 @@ int main(int argc, char **argv) {
     filtered.resize(n);
     if (scoring) scores.resize(n);
     if (positions) { pos_tile.resize(n); pos_x.resize(n); pos_y.resize(n); }
+    if (bc_quals) bcq.resize(n * K);
     parallel_ranges(n, threads, [&](size_t b, size_t e, unsigned) {
       std::string_view seqs[64], name0, nm, st, ql;
       for (size_t i = b; i < e; i++) {
@@ -613,6 +666,7 @@ int main(int argc, char **argv) {
           maps[f].lines(i, nm, seqs[f], st, ql);
           if (f == 0) name0 = nm;
           if (scoring) qsum += quality_sum(ql.data(), ql.size());
+          if (bc_quals && f == 0) put_bc_quals(&bcq[i * K], ql.data(), ql.size());
         }
         if (scoring) scores[i] = clamp_score(qsum);
         if (positions) { const Position ps = parse_position(name0); pos_tile[i] = ps.tile; pos_x[i] = ps.x; pos_y[i] = ps.y; }
@@ -641,6 +695,10 @@ int main(int argc, char **argv) {
         uint64_t qsum = 0;
         for (const FastqRecord &r : recs) qsum += quality_sum(r.quality.data(), r.quality.size());
         scores.push_back(clamp_score(qsum));
+      }
+      if (bc_quals) {
+        bcq.resize(bcq.size() + K);
+        put_bc_quals(&bcq[bcq.size() - K], recs[0].quality.data(), recs[0].quality.size());
       }
       if (positions) {
         const Position ps = parse_position(recs[0].name);
@@ -674,6 +732,11 @@ int main(int argc, char **argv) {
     std::ofstream out(a.dump_scores, std::ios::out | std::ios::binary);
     out.write((const char *)&N, 8);
     out.write((const char *)scores.data(), (std::streamsize)(N * 4));
+  }
+  if (!a.dump_bc_quals.empty()) {   // ... and the barcode qualities: a u64 count, then K bytes per read
+    std::ofstream out(a.dump_bc_quals, std::ios::out | std::ios::binary);
+    out.write((const char *)&N, 8);
+    out.write((const char *)bcq.data(), (std::streamsize)(N * K));
   }
   if (!a.dump_positions.empty()) {   // ... and the -O positions: a u64 count, then tile, x and y as three u32 arrays
     std::ofstream out(a.dump_positions, std::ios::out | std::ios::binary);
@@ -773,7 +836,10 @@ int main(int argc, char **argv) {
     if (rc == HUMID_OK && getenv("HUMID_TIMING"))
       std::fprintf(stderr, "[humid]   %u ranks, bulk data by %s: set-up %.1f ms, ranks %.1f ms\n", a.gpus,
                    shr.comm.c_str(), shr.ms_init, shr.ms_run);
-  } else if (corrected)
+  } else if (a.posterior)
+    rc = humid_dedup_run_keyed_posterior(ctx, run_words, keys.data(), bcq.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
+                                         method, (uint32_t)a.min_odds, cluster_id, keep, &sum);
+  else if (corrected)
     rc = humid_dedup_run_keyed_corrected(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
                                          method, cluster_id, keep, &sum);
   else if (a.paired)
@@ -796,6 +862,8 @@ int main(int argc, char **argv) {
   }
   uint64_t bc_counts[5] = {0, 0, 0, 0, 0};
   if (rc == HUMID_OK && corrected) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
+  uint64_t bc_multi = 0, bc_rescued = 0;
+  if (rc == HUMID_OK && a.posterior) rc = humid_get_barcode_posterior(ctx, &bc_multi, &bc_rescued);
   humid_strand_summary ssum;
   std::memset(&ssum, 0, sizeof ssum);
   if (rc == HUMID_OK && a.paired) {
@@ -824,6 +892,9 @@ int main(int argc, char **argv) {
   if (corrected)
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
+  if (a.posterior)
+    log << "  barcode posterior: " << bc_multi << " reads with several candidates, " << bc_rescued << " of them corrected (odds >= "
+        << a.min_odds << ")\n";
   if (a.paired)
     log << "  strands: " << ssum.n_clusters << " clusters, " << ssum.duplex << " duplex, " << ssum.top_only << " top only, "
         << ssum.bottom_only << " bottom only; " << ssum.top_reads << " top reads, " << ssum.bottom_reads << " bottom reads\n";
@@ -1140,6 +1211,10 @@ int main(int argc, char **argv) {
       out << "corrected: " << bc_counts[HUMID_BC_CORRECTED] << '\n';
       out << "ambiguous: " << bc_counts[HUMID_BC_AMBIGUOUS] << '\n';
       out << "unmatched: " << bc_counts[HUMID_BC_UNMATCHED] << '\n';
+      if (a.posterior) {
+        out << "multi: " << bc_multi << '\n';
+        out << "rescued: " << bc_rescued << '\n';
+      }
       out.close();
       if (out.fail()) ok = -1;
     }

@@ -274,17 +274,31 @@ int humid_dedup_run_keyed_corrected_device(humid_ctx *c, const uint64_t *d_words
   });
 }
 
+int humid_dedup_run_keyed_posterior_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_qual,
+                                           const uint8_t *d_filtered, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
+                                           uint32_t method, uint32_t min_odds, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                           humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  return with_word_type(word_nt, [&](auto *w) {
+    return run_keyed_corrected_device(c, (decltype(w))d_words, d_key, d_filtered, n_reads, word_nt, distance, method,
+                                      d_cluster_id, d_keep, summary, d_qual, min_odds, true);
+  });
+}
+
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
 // kind: what the run is (RUN_GROUPED: group may be null with n_groups = 1; RUN_KEYED on: key, null only without reads);
 // paired: the strand-symmetric run (RUN_PLAIN only; CtxState::paired).
 // Everything the kind refuses is refused here, before any copy: a refused shape moves nothing.
 static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *words, const uint8_t *filtered, const uint8_t *bases,
                     const uint32_t *group, uint32_t n_groups, const uint64_t *key, uint64_t n_reads, uint32_t word_nt,
-                    uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+                    uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary,
+                    const uint8_t *qual = nullptr, uint32_t min_odds = 0, bool posterior = false) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   state_reset(c);
   if (paired) TRY(check_paired_run_args(c, n_reads, word_nt, distance, method));
   if (kind == RUN_CORRECTED && !c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (posterior && min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
+  if (posterior && n_reads && !qual) return fail(c, HUMID_E_INVALID, "null buffer");
   if (kind >= RUN_KEYED) {
     TRY(check_run_args(c, n_reads, word_nt, method, 64));
     if (n_reads && !key) return fail(c, HUMID_E_INVALID, "null buffer");
@@ -333,6 +347,10 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
     ENSURE(c->kr_key_in, n * 8 + 8);
     HIPCHK(hipMemcpyAsync(c->kr_key_in.p, key, n * 8, hipMemcpyHostToDevice, st));
   }
+  if (n && posterior) {
+    ENSURE(c->bc_qual_in, n * c->wl_nt + 8);
+    HIPCHK(hipMemcpyAsync(c->bc_qual_in.p, qual, n * c->wl_nt, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipEventRecord(e1, st));
   int rc = with_word_type(word_nt, [&](auto *w) {
     auto *d_w = (decltype(w))c->in_words.p;
@@ -342,7 +360,8 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
     u8 *d_keep = c->out_keep.as<u8>();
     if (paired) return run_paired_device(c, d_w, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
     switch (kind) {
-      case RUN_CORRECTED: return run_keyed_corrected_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
+      case RUN_CORRECTED: return run_keyed_corrected_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s,
+                                                            posterior ? c->bc_qual_in.as<u8>() : nullptr, min_odds, posterior);
       case RUN_KEYED: return run_keyed_device(c, d_w, d_k, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
       case RUN_GROUPED: return run_grouped_device(c, d_w, group ? c->gk_group_in.as<u32>() : nullptr, d_f, n_reads, word_nt, n_groups,
                                                   distance, method, d_cid, d_keep, &s);
@@ -390,6 +409,13 @@ int humid_dedup_run_keyed_corrected(humid_ctx *c, const uint64_t *words, const u
                                     uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
   return run_host(c, RUN_CORRECTED, false, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id,
                   keep, summary);
+}
+
+int humid_dedup_run_keyed_posterior(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *qual,
+                                    const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
+                                    uint32_t method, uint32_t min_odds, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  return run_host(c, RUN_CORRECTED, false, words, filtered, nullptr, nullptr, 1, key, n_reads, word_nt, distance, method, cluster_id,
+                  keep, summary, qual, min_odds, true);
 }
 
 int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, uint32_t word_nt, uint32_t distance,
@@ -504,6 +530,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
     HIPCHK(hipStreamSynchronize(st));
     c->wl_table.release();
     c->wl_n = 0; c->wl_nt = 0; c->wl_log2 = 0;
+    c->wp_valid = false;
     return HUMID_OK;
   }
   if (barcode_nt < 1 || barcode_nt > 32) return fail(c, HUMID_E_INVALID, "barcode_nt must be 1 .. 32");
@@ -532,6 +559,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   HIPCHK(hipStreamSynchronize(st));
   c->wl_table = std::move(fresh);
   c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
+  c->wp_valid = false;                                       // (the reads per slot went with the table they index)
   return HUMID_OK;
 }
 
@@ -578,6 +606,87 @@ int humid_whitelist_correct(humid_ctx *c, const uint64_t *key, const uint8_t *fi
   D2H(key_out, d_out, n * 8);
   D2H(status, d_status, n);
   D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+// ---- correction by quality and abundance (kernels_wlpost.hip.h) ------------------------------------------------
+static int whitelist_posterior_args(humid_ctx *c, const void *key, const void *qual, const void *filtered, uint64_t n_reads,
+                                    uint32_t min_odds) {
+  TRY(whitelist_correct_args(c, key, filtered, n_reads));
+  if (min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
+  if (n_reads && !qual) return fail(c, HUMID_E_INVALID, "null buffer");
+  return HUMID_OK;
+}
+
+// the stand-alone call's one host wait: the seven counters -> the summary
+static int whitelist_posterior_finish(humid_ctx *c, humid_bc_posterior_summary *summary) {
+  ull h[WLP_CTRS] = {};
+  if (summary) HIPCHK(hipMemcpyAsync(h, c->wc_counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (summary) {
+    for (int i = 0; i < 5; i++) summary->counts[i] = h[i];
+    summary->multi = h[WLP_MULTI];
+    summary->rescued = h[WLP_RESCUED];
+  }
+  return HUMID_OK;
+}
+
+int humid_whitelist_correct_posterior_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_qual, const uint8_t *d_filtered,
+                                             uint64_t n_reads, uint32_t min_odds, uint64_t *d_key_out, uint8_t *d_status,
+                                             humid_bc_posterior_summary *summary) {
+  TRY(whitelist_posterior_args(c, d_key, d_qual, d_filtered, n_reads, min_odds));
+  HIPCHK(hipSetDevice(c->device));
+  PASS_ENSURE(c->wc_counts, WLP_CTRS * sizeof(ull));
+  TRY(wl_posterior_launch(c, d_key, d_filtered, d_qual, (u32)n_reads, min_odds, d_key_out, d_status, nullptr, c->wc_counts.as<ull>()));
+  return whitelist_posterior_finish(c, summary);
+}
+
+int humid_whitelist_correct_posterior(humid_ctx *c, const uint64_t *key, const uint8_t *qual, const uint8_t *filtered,
+                                      uint64_t n_reads, uint32_t min_odds, uint64_t *key_out, uint8_t *status,
+                                      humid_bc_posterior_summary *summary) {
+  TRY(whitelist_posterior_args(c, key, qual, filtered, n_reads, min_odds));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  u64 *d_key, *d_out;
+  u8 *d_filt, *d_qual, *d_status;
+  STAGE_IN(d_key, 0, key, n * 8);
+  STAGE_IN(d_filt, 1, filtered, n);
+  STAGE_IN(d_qual, 2, qual, n * c->wl_nt);
+  STAGE_OUT(d_out, 0, n * 8);
+  STAGE_OUT(d_status, 1, n);
+  PASS_ENSURE(c->wc_counts, WLP_CTRS * sizeof(ull));
+  TRY(wl_posterior_launch(c, d_key, d_filt, d_qual, (u32)n, min_odds, d_out, d_status, nullptr, c->wc_counts.as<ull>()));
+  D2H(key_out, d_out, n * 8);
+  D2H(status, d_status, n);
+  return whitelist_posterior_finish(c, summary);
+}
+
+int humid_get_barcode_posterior(humid_ctx *c, uint64_t *multi, uint64_t *rescued) {
+  NEED_LEAVES();
+  if (!state_run_is(c, RUN_CORRECTED) || !c->bc_posterior)
+    return fail(c, HUMID_E_STATE, "the last run was not a posterior corrected keyed run");
+  D2H(multi, c->bc_counts.as<ull>() + WLP_MULTI, sizeof(ull));
+  D2H(rescued, c->bc_counts.as<ull>() + WLP_RESCUED, sizeof(ull));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_whitelist_counts(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint32_t *counts_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->wl_n || !c->wp_valid) return fail(c, HUMID_E_STATE, "no posterior correction has run over the whitelist of this context");
+  if (n > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu barcodes exceed 2^31-1", (ull)n);
+  if (n && (!barcodes || !counts_out)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n == 0) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  u64 *d_bc;
+  u32 *d_out;
+  STAGE_IN(d_bc, 0, barcodes, (size_t)n * 8);
+  STAGE_OUT(d_out, 0, (size_t)n * 4);
+  hipLaunchKernelGGL(k_wlp_counts, dim3(grid_stride_blocks(n)), dim3(256), 0, c->stream, (const u64 *)d_bc, (u32)n,
+                     (const u64 *)c->wl_table.p, c->wl_log2, (const u32 *)c->wp_cnt.p, d_out);
+  HIPCHK(hipGetLastError());
+  D2H(counts_out, d_out, (size_t)n * 4);
   HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }

@@ -28,6 +28,21 @@ __device__ __forceinline__ bool wl_has(const u64 *__restrict__ tab, u32 cap_log2
   return false;
 }
 
+// wl_has that says WHERE: the slot of k in tab[0, cap], cap being the reserved slot, or NOSLOT (kernels_wlpost.hip.h
+// keeps a count per slot)
+__device__ __forceinline__ u32 wl_find(const u64 *__restrict__ tab, u32 cap_log2, u64 k) {
+  const u32 cap = 1u << cap_log2, mask = cap - 1u;
+  if (k == EMPTY_KEY) return tab[cap] == 0ull ? cap : NOSLOT;
+  u32 s = kr_home(k, cap_log2) & mask;
+  for (u32 probes = 0; probes < cap; probes++) {
+    const u64 t = tab[s];
+    if (t == k) return s;
+    if (t == EMPTY_KEY) return NOSLOT;
+    s = (s + 1u) & mask;
+  }
+  return NOSLOT;
+}
+
 static __global__ void __launch_bounds__(256)
 k_wl_insert(const u64 *__restrict__ bc, u32 n, u64 *tab, u32 cap_log2) {
   HUMID_GUARD_LAST_VGPR();

@@ -32,6 +32,7 @@
 #include "kernels_keyrank.hip.h"
 #include "kernels_gstats.hip.h"
 #include "kernels_whitelist.hip.h"
+#include "kernels_wlpost.hip.h"
 #include "kernels_paired.hip.h"
 
 // --------------------------------------------------------------------------------
@@ -112,8 +113,9 @@ static_assert(std::is_nothrow_move_constructible<DBuf>::value && std::is_nothrow
 //   (b) first_read of humid_get_leaves, humid_get_packed_words, humid_get_group_stats / humid_group_stats_device,
 //       humid_select_best* (which refuses with HUMID_E_INVALID)
 //   (c) humid_get_leaf_groups: RUN_GROUPED; humid_get_group_keys, humid_keyed_rank_info: RUN_KEYED;
-//       humid_get_barcode_status: RUN_CORRECTED.  The data of a kind (gk_word_nt, gk_leaf_nt, gk_groups; kr_n; bc_N)
-//       is valid exactly when the record says the run is of that kind.
+//       humid_get_barcode_status: RUN_CORRECTED; humid_get_barcode_posterior: RUN_CORRECTED with bc_posterior.  The
+//       data of a kind (gk_word_nt, gk_leaf_nt, gk_groups; kr_n; bc_N, bc_posterior) is valid exactly when the record
+//       says the run is of that kind.
 //   dense is orthogonal: humid_stage_map_dense and humid_stage_kernel_ms answer while it is set, whatever holds says.
 // The results of humid_consensus* are no part of this: they survive runs (cs_valid).
 enum RunKind : u8 { RUN_PLAIN, RUN_GROUPED, RUN_KEYED, RUN_CORRECTED };   // ordered: each kind is a case of the one before
@@ -234,6 +236,13 @@ struct humid_ctx {
   u64 bc_N = 0;              // RUN_CORRECTED: bc_status / bc_counts are those of the run's bc_N reads
   DBuf bc_key, bc_filt, bc_status, bc_counts;            // corrected run: key_out, filtered', status, u64[5]
   DBuf wc_counts;                                        // humid_whitelist_correct*: counts of its own
+  // correction by quality and abundance (humid_whitelist_correct_posterior*, humid_dedup_run_keyed_posterior*,
+  // kernels_wlpost.hip.h): bc_counts / wc_counts then hold WLP_CTRS counters; the reads per barcode belong to the last such
+  // call or run, whichever came later, and go with the whitelist they index (humid_whitelist_counts)
+  DBuf bc_qual_in;           // host entry point staging of a posterior run's qualities
+  DBuf wp_cnt, wp_slot;      // u32[cap + 1] reads per table slot; u32[n_reads] the slot of every read's key
+  bool wp_valid = false;     // wp_cnt holds the counts of a posterior call or run over the whitelist now set
+  bool bc_posterior = false; // RUN_CORRECTED: the correction was the posterior one (humid_get_barcode_posterior)
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
@@ -2708,14 +2717,45 @@ static int wl_correct_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u
   return HUMID_OK;
 }
 
+// The posterior correction over device arrays: zeroes d_counts (u64[WLP_CTRS]) and the reads per slot, then the prior
+// and the decision pass; nothing waits here.  The per-slot and per-read arrays are plain allocations of the context.
+static int wl_posterior_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, const u8 *d_qual, u32 N, u32 min_odds,
+                               u64 *d_key_out, u8 *d_status, u8 *d_filt_out, ull *d_counts) {
+  hipStream_t st = c->stream;
+  const size_t cap = (size_t)1 << c->wl_log2;
+  c->wp_valid = false;
+  PASS_ENSURE(c->wp_cnt, (cap + 1) * 4);
+  PASS_ENSURE(c->wp_slot, (size_t)N * 4 + 16);
+  HIPCHK(hipMemsetAsync(d_counts, 0, WLP_CTRS * sizeof(ull), st));
+  HIPCHK(hipMemsetAsync(c->wp_cnt.p, 0, (cap + 1) * 4, st));
+  if (N) {
+    const u64 *tab = (const u64 *)c->wl_table.p;
+    const dim3 grid(blocks_for(N)), block(256);
+    hipLaunchKernelGGL(k_wlp_prior, grid, block, 0, st, d_key, d_filt, N, tab, c->wl_log2, c->wp_cnt.as<u32>(), c->wp_slot.as<u32>());
+    if (c->wl_coop)
+      hipLaunchKernelGGL(k_wlp_decide<true>, grid, block, 0, st, d_key, d_filt, d_qual, N, (const u32 *)c->wp_slot.p, tab, c->wl_log2,
+                         (const u32 *)c->wp_cnt.p, c->wl_nt, min_odds, d_key_out, d_status, d_filt_out, d_counts);
+    else
+      hipLaunchKernelGGL(k_wlp_decide<false>, grid, block, 0, st, d_key, d_filt, d_qual, N, (const u32 *)c->wp_slot.p, tab, c->wl_log2,
+                         (const u32 *)c->wp_cnt.p, c->wl_nt, min_odds, d_key_out, d_status, d_filt_out, d_counts);
+    HIPCHK(hipGetLastError());
+  }
+  c->wp_valid = true;
+  return HUMID_OK;
+}
+
 // The corrected keyed pass: key_out and filtered' (filtered, ambiguous or unmatched) into context buffers, then the
 // keyed pass over them, unchanged.  The status counts are not waited for: humid_get_barcode_status reads them.
+// d_qual != null: the posterior correction (min_odds >= 1) in place of the plain one.
 template <class WI>
 static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads,
-                                      u32 word_nt, u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
+                                      u32 word_nt, u32 distance, u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum,
+                                      const u8 *d_qual = nullptr, u32 min_odds = 0, bool posterior = false) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   state_reset(c);
   if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (posterior && min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
+  if (posterior && n_reads && !d_qual) return fail(c, HUMID_E_INVALID, "null buffer");
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
   if (n_reads && (!d_words || !d_key || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
   HIPCHK(hipSetDevice(c->device));
@@ -2723,11 +2763,16 @@ static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64
   ENSURE(c->bc_key, (size_t)N * 8 + 16);
   ENSURE(c->bc_filt, (size_t)N + 16);
   ENSURE(c->bc_status, (size_t)N + 16);
-  ENSURE(c->bc_counts, 5 * sizeof(ull));
-  TRY(wl_correct_launch(c, d_key, d_filt, N, c->bc_key.as<u64>(), c->bc_status.as<u8>(), c->bc_filt.as<u8>(),
-                        c->bc_counts.as<ull>()));
+  ENSURE(c->bc_counts, WLP_CTRS * sizeof(ull));
+  if (posterior)
+    TRY(wl_posterior_launch(c, d_key, d_filt, d_qual, N, min_odds, c->bc_key.as<u64>(), c->bc_status.as<u8>(), c->bc_filt.as<u8>(),
+                            c->bc_counts.as<ull>()));
+  else
+    TRY(wl_correct_launch(c, d_key, d_filt, N, c->bc_key.as<u64>(), c->bc_status.as<u8>(), c->bc_filt.as<u8>(),
+                          c->bc_counts.as<ull>()));
   PassKind pass(c, RUN_CORRECTED);
   c->bc_N = n_reads;
+  c->bc_posterior = posterior;
   return run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method, d_cid,
                               d_keep, sum);
 }

@@ -257,7 +257,8 @@ int humid_keyed_rank_info(humid_ctx *ctx, uint64_t *n_keys, uint32_t *table_log2
  *   HUMID_BC_UNMATCHED     4    k not in W, no such w                                   k
  * So a key with bits set above 2K is unmatched, and a key that IS a whitelist barcode is exact even
  * when another barcode lies one nucleotide away.  Distance 2, insertions / deletions, base qualities
- * and barcodes with N (the caller marks such a read filtered) are not handled.
+ * (the next section decides ambiguous keys by them) and barcodes with N (the caller marks such a
+ * read filtered) are not handled.
  * A CORRECTED KEYED RUN is humid_dedup_run_keyed on key_out with
  *   filtered'[r] = filtered[r] || status[r] is AMBIGUOUS or UNMATCHED;
  * cluster_id / keep, the summary (usable counts filtered' == 0), humid_get_group_keys (now a subset
@@ -314,6 +315,83 @@ int humid_dedup_run_keyed_corrected_device(humid_ctx *ctx, const uint64_t *d_wor
                                            uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep,
                                            humid_summary *summary);
 int humid_get_barcode_status(humid_ctx *ctx, uint8_t *status, uint64_t cap, uint64_t counts[5]);
+
+/* ---- barcode whitelist: ambiguous keys decided by base quality and barcode abundance -------------
+ * (Cell Ranger, STARsolo 1MM_multi.)  W, K, key, filtered, the five statuses and key_out are those
+ * of the section above; a whitelist must be set.  Three inputs are new:
+ *   qual[n_reads * K]  u8, raw Phred+33 bytes: qual[r*K + j] belongs to barcode nucleotide j, j = 0
+ *                      the first nucleotide (bits 2(K-1-j) of the key).  Rows of filtered reads are
+ *                      never read.  p = min(max(byte - 33, 0), 93) as in humid_consensus, q = min(p, 40).
+ *   min_odds           u32 >= 1; 39 is a posterior of at least 0.975.
+ * The error weight of a base of quality q is E[q] = floor(2^24 * 10^(-q/10) + 0.5), q = 0 .. 40:
+ *   16777216 13326616 10585708 8408526 6679130 5305422 4214246 3347495 2659010 2112126 1677722
+ *   1332662 1058571 840853 667913 530542 421425 334749 265901 211213 167772 133266 105857 84085
+ *   66791 53054 42142 33475 26590 21121 16777 13327 10586 8409 6679 5305 4214 3347 2659 2112 1678
+ * Prior: for w in W, n_w = the usable reads of THIS call whose key equals w (its EXACT reads), and
+ * pi_w = n_w + 1.  Per usable read with key k:
+ *   k in W: EXACT, as above.
+ *   otherwise (a key with bits above 2K included) the candidates are the w in W that differ from k
+ *   in exactly one of the K nucleotides, j_w (so a key with bits above 2K has none);
+ *     weight(w) = pi_w * E[q of nucleotide j_w]          (< 2^55)
+ *     total     = the sum of the weights                 (< 2^62: at most 96 candidates)
+ *     best      = the candidate of the largest weight, ties to the smallest barcode value
+ *   no candidate: UNMATCHED, key_out = k;
+ *   weight(best) >= min_odds * (total - weight(best)), in exact integers: CORRECTED, key_out = best;
+ *   otherwise AMBIGUOUS, key_out = k.
+ * Consequences: a read with ONE candidate is corrected exactly as by humid_whitelist_correct; the
+ * statuses differ from the plain correction only on reads that are AMBIGUOUS there; with all quality
+ * bytes equal, no EXACT read and min_odds >= 2 the result equals humid_whitelist_correct bit for
+ * bit; the result is made of sums and a maximum over a total order and depends on no order of reads
+ * or atomics.  Not handled: barcodes with N (the caller marks such a read filtered), distance 2,
+ * insertions / deletions, caller-supplied priors, grouped or sharded runs.
+ * On the device: two launches.  The first looks every key up once (one lookup per run of equal keys
+ * inside a wave), keeps the slot per read and adds the run lengths into a count per table slot; the
+ * second probes only for the reads that missed: the lanes of the wave look the 3K variants of one
+ * read up side by side, a hit loads the one quality byte of its nucleotide, and a 64-bit sum and a
+ * maximum over the wave decide.  Option "whitelist_coop" 0 selects the lane-serial form.
+ *   humid_whitelist_correct_posterior: key, qual, filtered in; key_out, status, summary out; host
+ *     buffers; any output may be NULL.  summary.counts are the reads per status, multi the reads
+ *     with two or more candidates, rescued those of them that were CORRECTED.
+ *   humid_whitelist_correct_posterior_device: the same with DEVICE pointers for key, qual, filtered,
+ *     key_out and status.  Both: HUMID_E_STATE without a whitelist, HUMID_E_INVALID for min_odds == 0
+ *     or a NULL key / qual / filtered with n_reads > 0; n_reads == 0 is fine.  Like
+ *     humid_whitelist_correct they touch nothing of the last run.
+ *   humid_dedup_run_keyed_posterior(_device): humid_dedup_run_keyed_corrected(_device) with this
+ *     correction in front; a corrected keyed run for every accessor (humid_get_barcode_status
+ *     answers for it).  No host wait of its own: the counters are read by the getters.
+ *   humid_get_barcode_posterior: multi and rescued of the last run; either pointer may be NULL.
+ *     HUMID_E_STATE unless the last run was a posterior one.
+ *   humid_whitelist_counts: n_w of the last posterior call or run, whichever came later, for n
+ *     caller-given barcodes (a HOST array); 0 for a value that is no whitelist barcode.  The reads
+ *     per barcode BEFORE correction.  HUMID_E_STATE before such a call, or once the whitelist was
+ *     replaced or cleared after it. */
+typedef struct humid_bc_posterior_summary {
+    uint64_t counts[5];
+    uint64_t multi;
+    uint64_t rescued;
+} humid_bc_posterior_summary;
+int humid_whitelist_correct_posterior(humid_ctx *ctx, const uint64_t *key, const uint8_t *qual,
+                                      const uint8_t *filtered, uint64_t n_reads, uint32_t min_odds,
+                                      uint64_t *key_out, uint8_t *status,
+                                      humid_bc_posterior_summary *summary);
+int humid_whitelist_correct_posterior_device(humid_ctx *ctx, const uint64_t *d_key,
+                                             const uint8_t *d_qual, const uint8_t *d_filtered,
+                                             uint64_t n_reads, uint32_t min_odds, uint64_t *d_key_out,
+                                             uint8_t *d_status, humid_bc_posterior_summary *summary);
+int humid_dedup_run_keyed_posterior(humid_ctx *ctx, const uint64_t *words, const uint64_t *key,
+                                    const uint8_t *qual, const uint8_t *filtered, uint64_t n_reads,
+                                    uint32_t word_nt, uint32_t distance, uint32_t method,
+                                    uint32_t min_odds, uint32_t *cluster_id, uint8_t *keep,
+                                    humid_summary *summary);
+int humid_dedup_run_keyed_posterior_device(humid_ctx *ctx, const uint64_t *d_words,
+                                           const uint64_t *d_key, const uint8_t *d_qual,
+                                           const uint8_t *d_filtered, uint64_t n_reads,
+                                           uint32_t word_nt, uint32_t distance, uint32_t method,
+                                           uint32_t min_odds, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                           humid_summary *summary);
+int humid_get_barcode_posterior(humid_ctx *ctx, uint64_t *multi, uint64_t *rescued);
+int humid_whitelist_counts(humid_ctx *ctx, const uint64_t *barcodes, uint64_t n,
+                           uint32_t *counts_out);
 
 /* ---- per-group statistics: how many molecules every group holds ---------------------------------
  * (the UMI count per cell, or per (cell, gene): the count matrix.)  After a successful single-GPU run let G be
