@@ -78,6 +78,15 @@ class HumidBcPosteriorSummary(C.Structure):
         return dict(counts=[int(x) for x in self.counts], multi=int(self.multi), rescued=int(self.rescued))
 
 
+class HumidCellsSummary(C.Structure):
+    """humid_cells_summary of include/humid_hip.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("usable", "invalid_reads", "distinct", "selected", "merged", "cells",
+                                          "threshold_reads", "top_reads", "reads_in_cells")]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class HumidComm(C.Structure):
     """humid_comm of include/humid_hip.h: what moves bytes between ranks for humid_dedup_run_exchange"""
     _fields_ = [("user", C.c_void_p), ("rank", C.c_uint32), ("world", C.c_uint32),
@@ -151,6 +160,12 @@ SYMBOLS = {
                                                          C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
     "humid_get_barcode_posterior": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "humid_whitelist_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "humid_whitelist_discover": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_uint32, C.POINTER(HumidCellsSummary)]),
+    "humid_whitelist_discover_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_uint64, C.c_uint32, C.POINTER(HumidCellsSummary)]),
+    "humid_get_discovered_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "humid_get_barcode_count_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "humid_get_group_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "humid_group_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 4),

@@ -31,6 +31,9 @@ STRAND_TOP, STRAND_BOTTOM, STRAND_NONE = 0, 1, 2
 # per-read status of the barcode correction (include/humid_hip.h, HUMID_BC_*); also the index into its five counts
 BC_FILTERED, BC_EXACT, BC_CORRECTED, BC_AMBIGUOUS, BC_UNMATCHED = range(5)
 
+# how Dedup.discover_whitelist selects the cells (include/humid_hip.h, HUMID_CELLS_*)
+CELLS_TOP, CELLS_EXPECTED, CELLS_MIN_READS = 0, 1, 2
+
 
 class HumidError(RuntimeError):
     def __init__(self, code, msg):
@@ -425,6 +428,69 @@ class Dedup(Context):
         out = np.zeros(len(b), np.uint32)
         self._check(self._lib.humid_whitelist_counts(self._h, _vp(b) if len(b) else None, len(b), _vp(out) if len(b) else None))
         return out
+
+    def discover_whitelist(self, keys, filtered, barcode_nt=16, top=None, expected=None, min_reads=None, merge_ratio=0):
+        """The whitelist taken from the data (include/humid_hip.h, humid_whitelist_discover): the reads per barcode are
+        counted on the device, the abundant barcodes are the cells, and they become this object's whitelist as if by
+        set_whitelist.  Exactly one of top (the T most abundant), expected (every barcode with at least a tenth of the
+        reads of the barcode at rank (expected + 50) // 100) and min_reads (every barcode with that many reads) must be
+        given.  merge_ratio R >= 1 removes a selected barcode one substitution away from another with at least R
+        times its reads; 0 keeps all.  keys and filtered are numpy arrays, or both torch tensors on this object's device
+        (8-byte and 1-byte elements).  Returns the summary as a dict (usable, invalid_reads, distinct, selected, merged,
+        cells, threshold_reads, top_reads, reads_in_cells).  The results of the last run stay untouched."""
+        given = [(m, v) for m, v in ((CELLS_TOP, top), (CELLS_EXPECTED, expected), (CELLS_MIN_READS, min_reads)) if v is not None]
+        if len(given) != 1:
+            raise ValueError("exactly one of top, expected and min_reads must be given")
+        mode, param = given[0][0], int(given[0][1])
+        merge_ratio = int(merge_ratio)
+        if not 1 <= param < 2 ** 64:
+            raise ValueError("top, expected and min_reads must be in [1, 2**64)")
+        if not 0 <= merge_ratio < 2 ** 32:
+            raise ValueError("merge_ratio must be in [0, 2**32)")
+        if not 1 <= int(barcode_nt) <= 32:
+            raise ValueError("barcode_nt must be 1 .. 32")
+        sm = _lib.HumidCellsSummary()
+        if hasattr(keys, "data_ptr") and hasattr(filtered, "data_ptr"):
+            import torch
+            n = filtered.numel()
+            for a, size in ((keys, 8), (filtered, 1)):
+                if not a.is_cuda or not a.is_contiguous() or a.element_size() != size or a.numel() != n or a.dim() != 1:
+                    raise ValueError("device tensors must be contiguous, one-dimensional, of %d elements: keys of 8 bytes "
+                                     "each, filtered of 1" % n)
+            torch.cuda.synchronize(keys.device)
+            self._check(self._lib.humid_whitelist_discover_device(
+                self._h, C.c_void_p(keys.data_ptr()) if n else None, C.c_void_p(filtered.data_ptr()) if n else None, n,
+                int(barcode_nt), mode, param, merge_ratio, C.byref(sm)))
+            return sm.asdict()
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("filtered must be one-dimensional")
+        k = _keys_u64(keys, f.shape)
+        n = len(f)
+        self._check(self._lib.humid_whitelist_discover(self._h, _vp(k) if n else None, _vp(f) if n else None, n, int(barcode_nt),
+                                                       mode, param, merge_ratio, C.byref(sm)))
+        return sm.asdict()
+
+    def discovered_cells(self):
+        """after discover_whitelist: (barcodes u64[cells] ascending, reads u32[cells]), the cells and their reads
+        (humid_get_discovered_cells)"""
+        n = C.c_uint64()
+        self._check(self._lib.humid_get_discovered_cells(self._h, None, None, 0, C.byref(n)))
+        b, r = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        if n.value:
+            self._check(self._lib.humid_get_discovered_cells(self._h, _vp(b), _vp(r), n.value, C.byref(n)))
+        return b, r
+
+    def barcode_count_hist(self):
+        """after discover_whitelist: (reads u64[H] ascending, barcodes u64[H]): how many distinct barcodes have exactly
+        that many reads, over all barcodes of the call -- the data of a barcode-rank plot
+        (humid_get_barcode_count_hist)"""
+        n = C.c_uint64()
+        self._check(self._lib.humid_get_barcode_count_hist(self._h, None, None, 0, C.byref(n)))
+        r, b = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        if n.value:
+            self._check(self._lib.humid_get_barcode_count_hist(self._h, _vp(r), _vp(b), n.value, C.byref(n)))
+        return r, b
 
     def barcode_status(self):
         """after run_keyed(correct=True): (status u8[N], counts u64[5]) of that run (humid_get_barcode_status)"""

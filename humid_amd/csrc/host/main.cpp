@@ -59,6 +59,11 @@ struct Args {
   std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
   bool posterior = false;      // --barcode-posterior (needs -w): barcodes with several listed neighbours are decided by base quality and abundance
   unsigned long long min_odds = 39;   // --barcode-min-odds
+  int cells_mode = -1;         // --cells-top / --cells-expected / --cells-min-reads (not in the reference): HUMID_CELLS_*, the whitelist comes from the data
+  unsigned cells_modes_given = 0;     // how many of the three were given
+  unsigned long long cells_param = 0; // the mode's N
+  bool cells_ratio_given = false;     // --cells-merge-ratio was given
+  unsigned long long cells_ratio = 0; // --cells-merge-ratio (0: selected barcodes one substitution apart all stay)
   std::string dump_bc_quals;   // --dump-barcode-quals (development: the barcode qualities of pass 1, then stop, no GPU)
   bool best = false;           // -Q (not in the reference): every cluster keeps its record with the best base qualities
   std::string dump_scores;     // --dump-scores (development: the -Q scores of pass 1, then stop, no GPU)
@@ -75,7 +80,7 @@ struct Args {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE [--barcode-posterior]]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE | --cells-expected N] [--barcode-posterior]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -96,6 +101,15 @@ void usage(const char *argv0) {
                "      a posterior of 0.975; N >= 1) times all the others together.  The barcode must come from the first\n"
                "      file's read (no UMI in the headers, K nucleotides or more taken from it).  barcodes.dat gains the\n"
                "      lines multi (reads with several candidates) and rescued (those of them corrected); a log line\n"
+               "  --cells-top N | --cells-expected N | --cells-min-reads N  with -b and without -w: the whitelist is taken from\n"
+               "      the data.  The reads per barcode are counted and the cells are the N barcodes with the most reads (ties to\n"
+               "      the smaller barcode), or every barcode with at least a tenth of the reads of the barcode at rank\n"
+               "      (N + 50) / 100 (the order-of-magnitude rule of Cell Ranger 2 for N expected cells), or every barcode with\n"
+               "      at least N reads.  --cells-merge-ratio R (default 0: off) then drops a cell one substitution away from a\n"
+               "      cell with at least R times its reads.  Everything else is the -w path with the cells as the whitelist\n"
+               "      (--barcode-posterior included); no cell found: exit 1.  A log line; with -s also cells.dat, one line\n"
+               "      \"<barcode> <reads>\" per cell, and barcode_rank.dat, one line \"<reads> <barcodes>\" per number of reads.\n"
+               "      One GPU; not with -P or -g\n"
                "  -Q  keep the record with the best base qualities of every cluster instead of the first one: among the\n"
                "      records that carry the cluster's most abundant word, the one with the largest sum of Phred qualities\n"
                "      >= 15 over all input files (Picard's SUM_OF_BASE_QUALITIES; ties: the first; one GPU).  Only the\n"
@@ -149,6 +163,23 @@ bool parse(int argc, char **argv, Args &a) {
       if (*v < '0' || *v > '9' || *end != 0 || a.min_odds < 1 || a.min_odds > 0xffffffffull) {
         std::fprintf(stderr, "humid: --barcode-min-odds takes odds of 1 .. 4294967295\n");
         return false;
+      }
+    }
+    else if (t == "--cells-top" || t == "--cells-expected" || t == "--cells-min-reads" || t == "--cells-merge-ratio") {
+      const char *v = need(t.c_str());
+      if (!v) return false;
+      char *end = nullptr;
+      const unsigned long long x = std::strtoull(v, &end, 10);
+      const bool ratio = t == "--cells-merge-ratio";
+      if (*v < '0' || *v > '9' || *end != 0 || (ratio ? x > 0xffffffffull : x < 1)) {
+        std::fprintf(stderr, ratio ? "humid: %s takes a ratio of 0 .. 4294967295\n" : "humid: %s takes a number of 1 or more\n", t.c_str());
+        return false;
+      }
+      if (ratio) { a.cells_ratio_given = true; a.cells_ratio = x; }
+      else {
+        a.cells_mode = t == "--cells-top" ? (int)HUMID_CELLS_TOP : t == "--cells-expected" ? (int)HUMID_CELLS_EXPECTED : (int)HUMID_CELLS_MIN_READS;
+        a.cells_param = x;
+        a.cells_modes_given++;
       }
     }
     else if (t == "--dump-barcode-quals") { const char *v = need("--dump-barcode-quals"); if (!v) return false; a.dump_bc_quals = v; }
@@ -236,6 +267,32 @@ int write_groups(humid_ctx *ctx, size_t barcode_nt, const std::string &path) {
   }
   out.close();
   return out.fail() ? -1 : 1;
+}
+
+// --cells-* with -s: cells.dat, one line "<barcode> <reads>" per cell in ascending order, the barcode as its K letters, and
+// barcode_rank.dat, one line "<reads> <barcodes>" per number of reads a barcode has, ascending (humid_get_discovered_cells,
+// humid_get_barcode_count_hist).  Returns like write_hist.
+int write_cells(humid_ctx *ctx, size_t barcode_nt, const std::string &cells_path, const std::string &rank_path) {
+  uint64_t n = 0, h = 0;
+  if (humid_get_discovered_cells(ctx, nullptr, nullptr, 0, &n) != HUMID_OK) return 0;
+  std::vector<uint64_t> bc(n ? n : 1);
+  std::vector<uint32_t> reads(n ? n : 1);
+  if (n && humid_get_discovered_cells(ctx, bc.data(), reads.data(), n, &n) != HUMID_OK) return 0;
+  if (humid_get_barcode_count_hist(ctx, nullptr, nullptr, 0, &h) != HUMID_OK) return 0;
+  std::vector<uint64_t> hk(h ? h : 1), hv(h ? h : 1);
+  if (h && humid_get_barcode_count_hist(ctx, hk.data(), hv.data(), h, &h) != HUMID_OK) return 0;
+  std::ofstream out(cells_path, std::ios::out | std::ios::binary);
+  std::string letters(barcode_nt, 'A');
+  for (uint64_t g = 0; g < n; g++) {
+    for (size_t i = 0; i < barcode_nt; i++) letters[i] = "ACGT"[(bc[g] >> (2 * (barcode_nt - 1 - i))) & 3];
+    out << letters << ' ' << reads[g] << '\n';
+  }
+  out.close();
+  if (out.fail()) return -1;
+  std::ofstream rank(rank_path, std::ios::out | std::ios::binary);
+  for (uint64_t i = 0; i < h; i++) rank << hk[i] << ' ' << hv[i] << '\n';
+  rank.close();
+  return rank.fail() ? -1 : 1;
 }
 
 // -w FILE: one barcode of barcode_nt letters per line -> packed like the words (first letter most significant).
@@ -427,6 +484,17 @@ int main(int argc, char **argv) {
   }
   // HUMID_FORCE_SHARDED=1: the rank orchestration also for -g 1 (one rank; exercises the transport)
   const bool sharded = a.gpus > 1 || getenv("HUMID_FORCE_SHARDED") != nullptr;
+  const bool discover = a.cells_mode >= 0;                 // the whitelist comes from the data
+  if (discover || a.cells_ratio_given) {
+    const char *why = nullptr;
+    if (a.cells_modes_given > 1) why = "--cells-top, --cells-expected and --cells-min-reads exclude each other (one rule selects the cells)";
+    else if (!discover) why = "--cells-merge-ratio needs --cells-top, --cells-expected or --cells-min-reads (it merges the cells they select)";
+    else if (!a.whitelist.empty()) why = "--cells-top / --cells-expected / --cells-min-reads do not work with -w (the whitelist comes from FILE or from the data)";
+    else if (a.paired) why = "--cells-top / --cells-expected / --cells-min-reads do not work with -P";
+    else if (sharded) why = "--cells-top / --cells-expected / --cells-min-reads run on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+    else if (!a.keyed) why = "--cells-top / --cells-expected / --cells-min-reads need -b K (the cells are barcodes of K letters)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
   if (a.keyed && (a.barcode < 1 || a.barcode > 32 || a.barcode >= a.word_length)) {
     std::fprintf(stderr, "humid: -b takes a barcode length of 1 .. 32 nucleotides below the word length (-n %zu)\n", a.word_length);
     return 2;
@@ -487,7 +555,7 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
-  const bool corrected = !whitelist.empty();
+  const bool corrected = !whitelist.empty() || discover;
   if (a.posterior && !corrected) {
     std::fprintf(stderr, "humid: --barcode-posterior needs -w FILE (it decides between the listed barcodes near a read's barcode)\n");
     return 2;
@@ -818,10 +886,34 @@ int main(int argc, char **argv) {
   humid_summary sum;
   std::memset(&sum, 0, sizeof sum);
   if (a.edit) humid_ctx_set_option(ctx, "edit_distance", 1);
-  if (corrected && humid_whitelist_set(ctx, whitelist.data(), whitelist.size(), (uint32_t)a.barcode) != HUMID_OK) {
+  if (corrected && !discover && humid_whitelist_set(ctx, whitelist.data(), whitelist.size(), (uint32_t)a.barcode) != HUMID_OK) {
     std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
     humid_ctx_destroy(ctx);
     return 1;
+  }
+  humid_cells_summary csum;
+  std::memset(&csum, 0, sizeof csum);
+  auto cells_line = [&]() {
+    log << "  cells: " << csum.cells << " of " << csum.distinct << " barcodes (" << csum.selected << " selected at " << csum.threshold_reads
+        << " reads or more, " << csum.merged << " merged away), " << csum.reads_in_cells << " of " << csum.usable
+        << " usable reads in cells, largest barcode " << csum.top_reads << " reads, " << csum.invalid_reads << " reads with an invalid barcode\n";
+  };
+  if (discover) {
+    // the whitelist from the data: the barcodes of all usable reads are counted on the device, the cells become the
+    // context's whitelist, and what follows is the -w path
+    if (humid_whitelist_discover(ctx, keys.data(), run_filt, N, (uint32_t)a.barcode, (uint32_t)a.cells_mode, a.cells_param,
+                                 (uint32_t)a.cells_ratio, &csum) != HUMID_OK) {
+      std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
+      humid_ctx_destroy(ctx);
+      return 1;
+    }
+    if (csum.cells == 0) {
+      cells_line();
+      std::fprintf(stderr, "humid: no cell barcode was found among %llu barcodes of %llu usable reads\n", (unsigned long long)csum.distinct,
+                   (unsigned long long)csum.usable);
+      humid_ctx_destroy(ctx);
+      return 1;
+    }
   }
   t = start_message(log, a.edit ? "Calculating neighbours using Levenshtein distance"     // src/humid.cc:142
                                 : "Calculating neighbours using Hamming distance");
@@ -889,6 +981,7 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  if (discover) cells_line();
   if (corrected)
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
@@ -1218,6 +1311,7 @@ int main(int argc, char **argv) {
       out.close();
       if (out.fail()) ok = -1;
     }
+    if (ok == 1 && discover) ok = write_cells(ctx, a.barcode, a.dir_name + "/cells.dat", a.dir_name + "/barcode_rank.dat");
     if (ok == 1 && a.paired) {
       std::ofstream out(a.dir_name + "/strands.dat", std::ios::out | std::ios::binary);
       out << "clusters: " << ssum.n_clusters << '\n';

@@ -172,6 +172,11 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->kr_force_log2 = (u32)value;
     return HUMID_OK;
   }
+  if (strcmp(key, "cells_table_log2") == 0) {
+    if (value != 0 && (value < 4 || value > 32)) return fail(c, HUMID_E_INVALID, "cells_table_log2 must be 0 (automatic) or 4 .. 32");
+    c->cd_force_log2 = (u32)value;
+    return HUMID_OK;
+  }
   if (strcmp(key, "whitelist_coop") == 0) {
     c->wl_coop = value != 0;
     return HUMID_OK;
@@ -531,6 +536,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
     c->wl_table.release();
     c->wl_n = 0; c->wl_nt = 0; c->wl_log2 = 0;
     c->wp_valid = false;
+    c->cd_valid = false;
     return HUMID_OK;
   }
   if (barcode_nt < 1 || barcode_nt > 32) return fail(c, HUMID_E_INVALID, "barcode_nt must be 1 .. 32");
@@ -560,6 +566,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   c->wl_table = std::move(fresh);
   c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
   c->wp_valid = false;                                       // (the reads per slot went with the table they index)
+  c->cd_valid = false;                                       // (nor is this whitelist one a discover call installed)
   return HUMID_OK;
 }
 
@@ -607,6 +614,59 @@ int humid_whitelist_correct(humid_ctx *c, const uint64_t *key, const uint8_t *fi
   D2H(status, d_status, n);
   D2H(counts, c->wc_counts.p, 5 * sizeof(ull));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+// ---- whitelist from the data (kernels_cells.hip.h) -----------------------------------------------------------------
+int humid_whitelist_discover_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads,
+                                    uint32_t barcode_nt, uint32_t mode, uint64_t param, uint32_t merge_ratio,
+                                    humid_cells_summary *summary) {
+  TRY(cells_discover_args(c, d_key, d_filtered, n_reads, barcode_nt, mode, param));
+  return cells_discover_device(c, d_key, d_filtered, n_reads, barcode_nt, mode, param, merge_ratio, summary);
+}
+
+int humid_whitelist_discover(humid_ctx *c, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads, uint32_t barcode_nt,
+                             uint32_t mode, uint64_t param, uint32_t merge_ratio, humid_cells_summary *summary) {
+  TRY(cells_discover_args(c, key, filtered, n_reads, barcode_nt, mode, param));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  u64 *d_key;
+  u8 *d_filt;
+  STAGE_IN(d_key, 0, key, n * 8);
+  STAGE_IN(d_filt, 1, filtered, n);
+  return cells_discover_device(c, d_key, d_filt, n_reads, barcode_nt, mode, param, merge_ratio, summary);
+}
+
+int humid_get_discovered_cells(humid_ctx *c, uint64_t *barcodes, uint32_t *reads, uint64_t cap, uint64_t *n_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->cd_valid) return fail(c, HUMID_E_STATE, "the whitelist of this context was not installed by humid_whitelist_discover");
+  if (n_out) *n_out = c->cd_n_cells;
+  const u64 take = c->cd_n_cells < cap ? c->cd_n_cells : cap;
+  if (take && (barcodes || reads)) {
+    HIPCHK(hipSetDevice(c->device));
+    D2H(barcodes, c->cd_cells.p, (size_t)take * 8);
+    D2H(reads, c->cd_cellcnt.p, (size_t)take * 4);
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return HUMID_OK;
+}
+
+int humid_get_barcode_count_hist(humid_ctx *c, uint64_t *reads, uint64_t *barcodes, uint64_t cap, uint64_t *n_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->cd_valid) return fail(c, HUMID_E_STATE, "the whitelist of this context was not installed by humid_whitelist_discover");
+  if (!n_out) return fail(c, HUMID_E_INVALID, "null argument");
+  const u64 H = c->cd_n_hist;
+  *n_out = H;
+  const u64 take = H < cap ? H : cap;
+  if (take == 0 || (!reads && !barcodes)) return HUMID_OK;
+  HIPCHK(hipSetDevice(c->device));
+  // bin q starts at rank first[q] of the order by descending count; the bin below it (q - 1) is the run behind it
+  std::vector<u32> first((size_t)take);
+  D2H(reads, c->cd_hist_n.p, (size_t)take * 8);
+  D2H(first.data(), c->cd_hist_first.p, (size_t)take * 4);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (barcodes)
+    for (u64 q = 0; q < take; q++) barcodes[q] = (q == 0 ? c->cd_G : (u64)first[(size_t)q - 1]) - (u64)first[(size_t)q];
   return HUMID_OK;
 }
 

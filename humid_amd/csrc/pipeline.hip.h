@@ -33,6 +33,7 @@
 #include "kernels_gstats.hip.h"
 #include "kernels_whitelist.hip.h"
 #include "kernels_wlpost.hip.h"
+#include "kernels_cells.hip.h"
 #include "kernels_paired.hip.h"
 
 // --------------------------------------------------------------------------------
@@ -243,6 +244,14 @@ struct humid_ctx {
   DBuf wp_cnt, wp_slot;      // u32[cap + 1] reads per table slot; u32[n_reads] the slot of every read's key
   bool wp_valid = false;     // wp_cnt holds the counts of a posterior call or run over the whitelist now set
   bool bc_posterior = false; // RUN_CORRECTED: the correction was the posterior one (humid_get_barcode_posterior)
+  // whitelist from the data (humid_whitelist_discover*, kernels_cells.hip.h): buffers of its own, never the slab, never
+  // kr_table or anything else a run or an accessor reads; the results of the last successful call are kept for the getters
+  u32 cd_cap_log2 = 0;       // log2 of the counting table of the next call (0: 16); remembered from call to call, grown on demand
+  u32 cd_force_log2 = 0;     // option "cells_table_log2": every call starts with this table size (test hook)
+  DBuf cd_table, cd_cnt, cd_ctr, cd_k0, cd_c0, cd_kkey, cd_kccnt, cd_flag, cd_pos, cd_skey, cd_scnt, cd_tmp;   // table, counters, scratch lists
+  DBuf cd_cells, cd_cellcnt, cd_hist_n, cd_hist_first;   // results: cells ascending u64 / u32; histogram bins u64 / u32 (first rank)
+  bool cd_valid = false;     // the whitelist in place (or its absence: zero cells) was installed by a discover call
+  u64 cd_n_cells = 0, cd_n_hist = 0, cd_G = 0;           // entries of the result buffers; distinct barcodes of that call
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
@@ -2775,6 +2784,233 @@ static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64
   c->bc_posterior = posterior;
   return run_keyed_device<WI>(c, d_words, c->bc_key.as<u64>(), c->bc_filt.as<u8>(), n_reads, word_nt, distance, method, d_cid,
                               d_keep, sum);
+}
+
+// ---- whitelist from the data (humid_whitelist_discover*; kernels_cells.hip.h) ---------------------------------------
+// what both forms refuse before anything moves
+static int cells_discover_args(humid_ctx *c, const void *key, const void *filtered, u64 n_reads, u32 barcode_nt, u32 mode,
+                               u64 param) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (barcode_nt < 1 || barcode_nt > 32) return fail(c, HUMID_E_INVALID, "barcode_nt must be 1 .. 32");
+  if (mode > HUMID_CELLS_MIN_READS) return fail(c, HUMID_E_INVALID, "mode %u is none of HUMID_CELLS_TOP, _EXPECTED, _MIN_READS", mode);
+  if (param == 0) return fail(c, HUMID_E_INVALID, "the mode's parameter must be >= 1");
+  if (n_reads && (!key || !filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
+  return HUMID_OK;
+}
+
+// a host wait of the discovery: its counters, and (extra != null) one more device word
+static int cd_wait(humid_ctx *c, ull *h, const u32 *extra = nullptr, u32 *h_extra = nullptr) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, c->cd_ctr.p, CD_CTRS * sizeof(ull), hipMemcpyDeviceToHost, c->stream));
+  if (extra) HIPCHK(hipMemcpyAsync(h_extra, extra, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+template <class K, class V>
+static int cd_sort(humid_ctx *c, const K *kin, K *kout, const V *vin, V *vout, u64 n, u32 bits) {
+  PASS_ENSURE(c->cd_tmp, (rs_temp_bytes<K, V, true>(n)));
+  HIPCHK((rs_sort<K, V, true>(c->cd_tmp.p, PtrIn<K>{kin}, kout, PtrIn<V>{vin}, vout, n, 0, bits, c->stream)));
+  return HUMID_OK;
+}
+
+// pos[0 .. n] = the exclusive scan of flag[0 .. n] (n + 1 entries, the last a sentinel): pos[n] is the total
+static int cd_scan(humid_ctx *c, const u32 *flag, u32 *pos, u64 n) {
+  PASS_ENSURE(c->cd_tmp, ps_scan_scratch_items(n + 1) * 4 + 256);
+  HIPCHK((ps_exscan<u32>(PtrIn<u32>{flag}, pos, n + 1, (u32 *)c->cd_tmp.p, c->stream, c->no_chain ? nullptr : c->ps_chain, &c->ps_epoch)));
+  return HUMID_OK;
+}
+
+// Option "kernel_timing" (HUMID_KERNEL_TIMING): an event behind every stage of the discovery, and one line on stderr
+// with the milliseconds between them when the call ends (the host waits lie inside the stage they end)
+struct CdMarks {
+  bool on;
+  hipStream_t st;
+  std::vector<std::pair<const char *, hipEvent_t>> ev;
+  void mark(const char *name) {
+    hipEvent_t e;
+    if (!on || hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, st);
+    ev.push_back({name, e});
+  }
+  ~CdMarks() {
+    if (ev.size() > 1 && hipEventSynchronize(ev.back().second) == hipSuccess) {
+      fprintf(stderr, "[humid] whitelist discovery, ms:");
+      for (size_t i = 1; i < ev.size(); i++) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second);
+        fprintf(stderr, " %s %.3f", ev[i].first, ms);
+      }
+      fprintf(stderr, "\n");
+    }
+    for (auto &e : ev) (void)hipEventDestroy(e.second);
+  }
+};
+
+// The whole discovery over device arrays (arguments checked).  Four host waits at most: the distinct barcodes (again
+// after every table that was too small), the selection's size with the histogram's, the cells after the merge (only
+// with a merge), the installed table.  Nothing of the context changes before the last one succeeded.
+static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u64 n_reads, u32 K, u32 mode, u64 param,
+                                 u32 ratio, humid_cells_summary *sum) {
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const u32 N = (u32)n_reads;
+  const u64 lim = K < 32 ? (u64)1 << (2 * K) : 0ull;
+  ull h[CD_CTRS] = {};
+  PASS_ENSURE(c->cd_ctr, CD_CTRS * sizeof(ull));
+  ull *ctr = c->cd_ctr.as<ull>();
+  HIPCHK(hipMemsetAsync(ctr, 0, CD_CTRS * sizeof(ull), st));
+  CdMarks marks{c->kev_on, st, {}};
+  marks.mark("start");
+  u32 G = 0, cap_log2 = 0;
+  if (N) {
+    u32 full_log2 = 4;                                        // the size that cannot be too small: cap >= 2 N
+    while (full_log2 < 32 && ((u64)1 << full_log2) < 2 * (u64)N) full_log2++;
+    cap_log2 = c->cd_force_log2 ? c->cd_force_log2 : (c->cd_cap_log2 ? c->cd_cap_log2 : 16u);
+    cap_log2 = std::min(std::max(cap_log2, 4u), full_log2);
+    while (true) {
+      const u32 cap = 1u << cap_log2;
+      const u32 out_cap = std::min<u64>((u64)cap + 1, N);       // (every distinct barcode is some read's key)
+      PASS_ENSURE(c->cd_table, ((size_t)cap + 1) * 8);
+      PASS_ENSURE(c->cd_cnt, ((size_t)cap + 1) * 4);
+      PASS_ENSURE(c->cd_k0, (size_t)out_cap * 8 + 16);
+      PASS_ENSURE(c->cd_c0, (size_t)out_cap * 4 + 16);
+      HIPCHK(hipMemsetAsync(c->cd_table.p, 0xff, ((size_t)cap + 1) * 8, st));
+      HIPCHK(hipMemsetAsync(c->cd_cnt.p, 0, ((size_t)cap + 1) * 4, st));
+      HIPCHK(hipMemsetAsync(ctr, 0, CD_CTRS * sizeof(ull), st));
+      hipLaunchKernelGGL(k_cd_count, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_key, d_filt, N, c->cd_table.as<u64>(), c->cd_cnt.as<u32>(),
+                         cap_log2, cap_log2 == full_log2 ? cap : 128u, lim, ctr);
+      marks.mark("memset+k_cd_count");
+      hipLaunchKernelGGL(k_cd_compact, dim3(std::min<u32>(COMPACT_BLOCKS, blocks_for((u64)cap + 1))), dim3(256), 0, st,
+                         (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap, c->cd_k0.as<u64>(), c->cd_c0.as<u32>(), out_cap, ctr);
+      TRY(cd_wait(c, h));                                       // host wait 1
+      marks.mark("k_cd_compact+wait");
+      if (h[CD_OVERFULL] == 0 && h[CD_G] <= out_cap) break;
+      if (cap_log2 >= full_log2) return fail(c, HUMID_E_INVALID, "internal: the barcode table of 2^%u slots overflowed", cap_log2);
+      cap_log2 = std::min(cap_log2 + 4, full_log2);
+    }
+    G = (u32)h[CD_G];
+    // the next call starts with a table at most a third full for as many barcodes as this one saw
+    u32 next = 12;
+    while (next < full_log2 && ((u64)1 << next) < 3 * (u64)G) next++;
+    c->cd_cap_log2 = next;
+  }
+  humid_cells_summary s;
+  memset(&s, 0, sizeof s);
+  s.usable = h[CD_USABLE];
+  s.invalid_reads = h[CD_INVALID];
+  s.distinct = G;
+  // the results are built beside those of the last call, which stay in place until this one is complete
+  DBuf cells, cellcnt, hist_n, hist_first, fresh;
+  u64 n_cells = 0, n_hist = 0;
+  u32 wl_log2 = 0;
+  if (G) {
+    const u64 *k0 = c->cd_k0.as<u64>();
+    const u32 *c0 = c->cd_c0.as<u32>();
+    PASS_ENSURE(c->cd_kkey, (size_t)G * 8 + 16);
+    PASS_ENSURE(c->cd_kccnt, (size_t)G * 4 + 16);
+    PASS_ENSURE(c->cd_flag, ((size_t)G + 1) * 4 + 16);
+    PASS_ENSURE(c->cd_pos, ((size_t)G + 1) * 4 + 16);
+    // the ORDER: by key ascending, then stable by the complemented count (bits above the largest count's: all 1)
+    const u64 bits = h[CD_KEYBITS];
+    TRY((cd_sort<u64, u32>(c, k0, c->cd_kkey.as<u64>(), c0, c->cd_kccnt.as<u32>(), G, bits ? 64u - (u32)__builtin_clzll(bits) : 1u)));
+    u64 *okey = c->cd_k0.as<u64>();
+    u32 *occnt = c->cd_c0.as<u32>();
+    TRY((cd_sort<u32, u64>(c, c->cd_kccnt.as<u32>(), occnt, c->cd_kkey.as<u64>(), okey, G, 64u - (u32)__builtin_clzll(h[CD_MAXCNT] | 1ull))));
+    // a histogram bin per distinct count: H (H + 1) / 2 <= the reads
+    u64 hist_cap = 1;
+    while (hist_cap * (hist_cap + 1) / 2 <= (u64)N) hist_cap++;
+    hist_cap = std::min<u64>(hist_cap, G);
+    HIPCHK(hist_n.ensure((size_t)hist_cap * 8 + 16));
+    HIPCHK(hist_first.ensure((size_t)hist_cap * 4 + 16));
+    u32 *flag = c->cd_flag.as<u32>(), *pos = c->cd_pos.as<u32>();
+    marks.mark("two_sorts");
+    hipLaunchKernelGGL(k_cd_cut, dim3(1), dim3(64), 0, st, (const u64 *)okey, (const u32 *)occnt, G, mode, param, ctr);
+    hipLaunchKernelGGL(k_cd_heads, dim3(blocks_for((u64)G + 1)), dim3(256), 0, st, (const u32 *)occnt, G, flag);
+    TRY(cd_scan(c, flag, pos, G));
+    hipLaunchKernelGGL(k_cd_hist, dim3(blocks_for(G)), dim3(256), 0, st, (const u32 *)occnt, (const u32 *)flag, (const u32 *)pos, G,
+                       hist_n.as<u64>(), hist_first.as<u32>(), (u32)hist_cap, ctr);
+    hipLaunchKernelGGL(k_cd_members, dim3(blocks_for((u64)G + 1)), dim3(256), 0, st, (const u64 *)c->cd_kkey.p, (const u32 *)c->cd_kccnt.p,
+                       G, (const ull *)ctr, flag);
+    TRY(cd_scan(c, flag, pos, G));
+    TRY(cd_wait(c, h));                                         // host wait 2
+    marks.mark("cut+hist+members+wait");
+    const u64 sel = h[CD_SEL];
+    n_hist = h[CD_NHIST];
+    if (n_hist > hist_cap || sel > G) return fail(c, HUMID_E_INVALID, "internal: the selection or the histogram left its bounds");
+    s.selected = sel;
+    s.threshold_reads = h[CD_CUTCNT];
+    s.top_reads = h[CD_TOP];
+    if (sel && ratio == 0) {
+      if (sel > ((u64)1 << 30)) return fail(c, HUMID_E_OVERFLOW, "a whitelist of %llu barcodes exceeds 2^30", (ull)sel);
+      n_cells = sel;
+      HIPCHK(cells.ensure((size_t)sel * 8 + 16));
+      HIPCHK(cellcnt.ensure((size_t)sel * 4 + 16));
+      hipLaunchKernelGGL(k_cd_take, dim3(blocks_for(G)), dim3(256), 0, st, (const u64 *)c->cd_kkey.p, (const u32 *)c->cd_kccnt.p, NONE32,
+                         (const u32 *)flag, (const u32 *)pos, G, cells.as<u64>(), cellcnt.as<u32>(), (u32)sel, &ctr[CD_CELLREADS]);
+    } else if (sel) {
+      const u32 S = (u32)sel;
+      PASS_ENSURE(c->cd_skey, (size_t)S * 8 + 16);
+      PASS_ENSURE(c->cd_scnt, (size_t)S * 4 + 16);
+      hipLaunchKernelGGL(k_cd_take, dim3(blocks_for(G)), dim3(256), 0, st, (const u64 *)c->cd_kkey.p, (const u32 *)c->cd_kccnt.p, NONE32,
+                         (const u32 *)flag, (const u32 *)pos, G, c->cd_skey.as<u64>(), c->cd_scnt.as<u32>(), S, (ull *)nullptr);
+      // (flag and pos are free again: the decisions and their scan take them, S + 1 <= G + 1 entries)
+      if (c->wl_coop)
+        hipLaunchKernelGGL(k_cd_merge<true>, dim3(grid_stride_blocks((u64)S * 64)), dim3(256), 0, st, (const u64 *)c->cd_skey.p,
+                           (const u32 *)c->cd_scnt.p, S, (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap_log2, 3 * K, ratio, flag);
+      else
+        hipLaunchKernelGGL(k_cd_merge<false>, dim3(blocks_for(S)), dim3(256), 0, st, (const u64 *)c->cd_skey.p,
+                           (const u32 *)c->cd_scnt.p, S, (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap_log2, 3 * K, ratio, flag);
+      TRY(cd_scan(c, flag, pos, S));
+      u32 kept = 0;
+      TRY(cd_wait(c, h, pos + S, &kept));                       // host wait 3
+      marks.mark("take+k_cd_merge+wait");
+      if (kept > S) return fail(c, HUMID_E_INVALID, "internal: the merge kept more barcodes than it was given");
+      if (kept > (1u << 30)) return fail(c, HUMID_E_OVERFLOW, "a whitelist of %u barcodes exceeds 2^30", kept);
+      n_cells = kept;
+      if (kept) {
+        HIPCHK(cells.ensure((size_t)kept * 8 + 16));
+        HIPCHK(cellcnt.ensure((size_t)kept * 4 + 16));
+        hipLaunchKernelGGL(k_cd_take, dim3(blocks_for(S)), dim3(256), 0, st, (const u64 *)c->cd_skey.p, (const u32 *)c->cd_scnt.p, 0u,
+                           (const u32 *)flag, (const u32 *)pos, S, cells.as<u64>(), cellcnt.as<u32>(), kept, &ctr[CD_CELLREADS]);
+      }
+    }
+  }
+  u64 distinct = 0;
+  if (n_cells) {                                                 // the table, as humid_whitelist_set builds it
+    wl_log2 = 1;
+    while (((u64)1 << wl_log2) < 2 * n_cells) wl_log2++;
+    const size_t cap = (size_t)1 << wl_log2;
+    HIPCHK(fresh.ensure((cap + 2) * 8));
+    HIPCHK(hipMemsetAsync(fresh.p, 0xff, (cap + 1) * 8, st));
+    HIPCHK(hipMemsetAsync(fresh.as<u64>() + cap + 1, 0, 8, st));
+    hipLaunchKernelGGL(k_wl_insert, dim3(grid_stride_blocks(n_cells)), dim3(256), 0, st, (const u64 *)cells.p, (u32)n_cells, fresh.as<u64>(),
+                       wl_log2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&distinct, fresh.as<u64>() + cap + 1, 8, hipMemcpyDeviceToHost, st));
+  }
+  TRY(cd_wait(c, h));                                             // the last host wait
+  marks.mark("take+k_wl_insert+wait");
+  if (distinct != n_cells) return fail(c, HUMID_E_INVALID, "internal: %llu cells, %llu of them distinct", (ull)n_cells, (ull)distinct);
+  s.cells = n_cells;
+  s.merged = s.selected - n_cells;
+  s.reads_in_cells = h[CD_CELLREADS];
+  c->wl_table = std::move(fresh);                                 // (zero cells: an empty buffer, the whitelist is cleared)
+  c->wl_n = n_cells;
+  c->wl_nt = n_cells ? K : 0;
+  c->wl_log2 = wl_log2;
+  c->wp_valid = false;                                            // (the reads per slot went with the table they index)
+  c->cd_cells = std::move(cells);
+  c->cd_cellcnt = std::move(cellcnt);
+  c->cd_hist_n = std::move(hist_n);
+  c->cd_hist_first = std::move(hist_first);
+  c->cd_n_cells = n_cells;
+  c->cd_n_hist = n_hist;
+  c->cd_G = G;
+  c->cd_valid = true;
+  if (sum) *sum = s;
+  return HUMID_OK;
 }
 
 // ---- strand-symmetric runs (humid_dedup_run_paired*) ------------------------------------------------------------

@@ -393,6 +393,101 @@ int humid_get_barcode_posterior(humid_ctx *ctx, uint64_t *multi, uint64_t *rescu
 int humid_whitelist_counts(humid_ctx *ctx, const uint64_t *barcodes, uint64_t n,
                            uint32_t *counts_out);
 
+/* ---- barcode whitelist from the data: the abundant barcodes are the cells ------------------------
+ * (UMI-tools whitelist, Cell Ranger 2's cell calling, alevin's initial whitelist: for chemistries that
+ * ship no list of barcodes.)  Inputs: key[n_reads] (u64), filtered[n_reads] (u8), K = barcode_nt with
+ * 1 <= K <= 32, a mode with its param, and merge_ratio.  Keys of filtered reads are never read.  For
+ * K < 32 a usable read whose key is >= 4^K is an invalid-key read: it is counted in invalid_reads and
+ * takes no further part.  Everything below is exact integer arithmetic.
+ *   Counts     n_k = the usable, valid reads with key k; G = the number of distinct such keys.
+ *   ORDER      the distinct keys by (n_k descending, key value ascending), ranks 0 .. G-1: a total
+ *              order.  n(r) is the count at rank r.
+ *   Selection  HUMID_CELLS_TOP, param T >= 1: S = the ranks [0, min(T, G)); a tie at the cut goes to
+ *              the smaller barcode value.
+ *              HUMID_CELLS_EXPECTED, param X >= 1, after the order-of-magnitude rule of Cell Ranger 2
+ *              with rounding conventions of this library (it is NOT claimed to equal Cell Ranger's
+ *              result): b = min((X + 50) / 100, G - 1) in integer division, m = n(b); S = every key
+ *              with 10 n_k >= m (64-bit).
+ *              HUMID_CELLS_MIN_READS, param T >= 1: S = every key with n_k >= T.
+ *              G = 0: S is empty.
+ *   Merge      merge_ratio R >= 1 (0: no merge).  w in S is an error barcode when some v in S differs
+ *              from w in exactly one of the K nucleotides, ranks before w in the ORDER and has
+ *              n_v >= R n_w (64-bit product).  All error barcodes are removed.  The rule is evaluated
+ *              against S as selected, not iteratively: a barcode that is itself removed still removes
+ *              its neighbours, and the result depends on no order of evaluation.
+ *   Result     the cells = S minus the error barcodes.  They become the context's whitelist exactly
+ *              as if humid_whitelist_set(cells, K) had been called: it survives runs,
+ *              humid_whitelist_info answers for it, the reads per barcode of an earlier posterior
+ *              call are gone (humid_whitelist_counts: HUMID_E_STATE), and humid_whitelist_correct*,
+ *              humid_dedup_run_keyed_corrected* and the posterior forms follow unchanged.  Zero cells
+ *              clears the whitelist and returns HUMID_OK.  More than 2^30 cells returns
+ *              HUMID_E_OVERFLOW and the previous whitelist stays.
+ *   Summary    usable          usable reads
+ *              invalid_reads   usable reads with an invalid key
+ *              distinct        G
+ *              selected        |S| before the merge
+ *              merged          error barcodes removed
+ *              cells           cells after the merge
+ *              threshold_reads the smallest n_k in S, 0 when S is empty
+ *              top_reads       n(0), 0 when G = 0
+ *              reads_in_cells  the sum of n_k over the cells
+ * Refused on the host, before anything moves: HUMID_E_INVALID for K outside 1 .. 32, mode > 2, param 0,
+ * or a NULL key or filtered with n_reads > 0; HUMID_E_OVERFLOW for n_reads > 2^31 - 1.  After every
+ * refusal or failure the previous whitelist (and the result of an earlier discover call) stays and the
+ * context stays usable.  n_reads = 0 is legal: zero cells, the whitelist is cleared.
+ * Like humid_whitelist_correct the call touches nothing of the last run: it works in buffers of its
+ * own, not in the table humid_keyed_rank_info and the keyed accessors answer from, and every accessor
+ * still answers for the last run afterwards.
+ * Not handled: knee or density estimates of the number of cells, EmptyDrops-style tests against the
+ * ambient profile, distance 2, insertions / deletions, priors from outside, grouped or sharded runs.
+ * On the device (kernels_cells.hip.h): one pass over the reads counts them in an open-address table
+ * in HBM, the keys in one array and the reads per slot in another (one probe and one atomic add per
+ * run of equal keys inside a wave; the table is sized and grown as the key table of a keyed run is; option "cells_table_log2", 4 .. 32, 0 =
+ * automatic, sets the size it starts with and never changes a result); the occupied slots are
+ * compacted and sorted twice (by key, then stable by the complemented count: the ORDER); the cut is
+ * read off the ORDER on the device, and the runs of equal counts in it are the histogram; the members
+ * of S are taken in key order, one wave per member looks its 3K variants up in the counting table
+ * side by side (option "whitelist_coop" 0: one lane per member), and the survivors, ascending, are
+ * inserted into a table built beside the old one.  Work after the first pass is proportional to G;
+ * at most four host waits.
+ *   humid_whitelist_discover: key and filtered are HOST arrays; summary may be NULL.
+ *   humid_whitelist_discover_device: the same with DEVICE pointers for key and filtered (the summary
+ *     is written on the host).
+ *   humid_get_discovered_cells: the cells in ascending barcode value with their n_k.  *n_out = their
+ *     number (call with cap = 0 to size the buffers); writes min(cap, cells) entries.  Any pointer may
+ *     be NULL.
+ *   humid_get_barcode_count_hist: the pairs (n, number of distinct valid barcodes with exactly n
+ *     reads) in ascending n over all G barcodes -- the data of a barcode-rank ("knee") plot -- by the
+ *     protocol of humid_get_histogram.
+ *     Both getters return HUMID_E_STATE unless the whitelist in place (or, after a call that found no
+ *     cell, its absence) was installed by a discover call: humid_whitelist_set and a clear end that,
+ *     a discover call that failed or was refused changes nothing. */
+#define HUMID_CELLS_TOP       0u
+#define HUMID_CELLS_EXPECTED  1u
+#define HUMID_CELLS_MIN_READS 2u
+typedef struct humid_cells_summary {
+    uint64_t usable;
+    uint64_t invalid_reads;
+    uint64_t distinct;
+    uint64_t selected;
+    uint64_t merged;
+    uint64_t cells;
+    uint64_t threshold_reads;
+    uint64_t top_reads;
+    uint64_t reads_in_cells;
+} humid_cells_summary;
+int humid_whitelist_discover(humid_ctx *ctx, const uint64_t *key, const uint8_t *filtered,
+                             uint64_t n_reads, uint32_t barcode_nt, uint32_t mode, uint64_t param,
+                             uint32_t merge_ratio, humid_cells_summary *summary);
+int humid_whitelist_discover_device(humid_ctx *ctx, const uint64_t *d_key, const uint8_t *d_filtered,
+                                    uint64_t n_reads, uint32_t barcode_nt, uint32_t mode,
+                                    uint64_t param, uint32_t merge_ratio,
+                                    humid_cells_summary *summary);
+int humid_get_discovered_cells(humid_ctx *ctx, uint64_t *barcodes, uint32_t *reads, uint64_t cap,
+                               uint64_t *n_out);
+int humid_get_barcode_count_hist(humid_ctx *ctx, uint64_t *reads, uint64_t *barcodes, uint64_t cap,
+                                 uint64_t *n_out);
+
 /* ---- per-group statistics: how many molecules every group holds ---------------------------------
  * (the UMI count per cell, or per (cell, gene): the count matrix.)  After a successful single-GPU run let G be
  * its number of groups: n_groups as passed to humid_dedup_run_grouped*; after humid_dedup_run_keyed* the number
