@@ -147,6 +147,9 @@ SYMBOLS = {
                                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                          C.POINTER(HumidSummary)]),
     "humid_get_barcode_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "humid_whitelist_set_segments": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "humid_whitelist_segments_info": (C.c_int, [C.c_void_p, u32p, C.c_void_p, C.c_void_p, u32p]),
+    "humid_get_barcode_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_whitelist_correct_posterior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.POINTER(HumidBcPosteriorSummary)]),
     "humid_whitelist_correct_posterior_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

@@ -373,6 +373,50 @@ class Dedup(Context):
         self._check(self._lib.humid_whitelist_info(self._h, C.byref(n), C.byref(k), C.byref(t)))
         return dict(n_distinct=n.value, barcode_nt=k.value, table_log2=t.value)
 
+    def set_whitelist_segments(self, lists, seg_nt, max_inexact=None):
+        """A segmented whitelist (include/humid_hip.h, humid_whitelist_set_segments) for barcodes made of several short
+        segments, each with a list of its own (SPLiT-seq, inDrop, BD Rhapsody, sci-RNA-seq): lists[s] holds the known
+        values of segment s, integers below 4 ** seg_nt[s]; 1 .. 8 segments of 1 .. 10 nucleotides, 32 at the most
+        together.  Segment 0 is the first seg_nt[0] nucleotides of the key.  Every segment is corrected on its own,
+        one substitution at the most in each; a read with more than max_inexact (default: all) segments that are not
+        exact is unmatched.  It takes the place of the whitelist this object holds and stays until set_whitelist,
+        discover_whitelist or another call of this replaces it.  correct_keys and run_keyed(correct=True) then work
+        as with any whitelist (not with quals / barcode_quals); barcode_segments() gives the per-segment summary.
+        Split-pool data without a cell list composes from this: correct_keys with the segments, discover_whitelist on
+        its keys_out (with the reads it left ambiguous or unmatched marked filtered), then run_keyed(correct=True) on
+        keys_out against the cells found."""
+        nts = [int(x) for x in seg_nt]
+        if len(lists) != len(nts) or not 1 <= len(nts) <= 8:
+            raise ValueError("1 .. 8 segments, and one length per list")
+        ls = [_keys_u64(w, None, "barcodes") for w in lists]
+        if max_inexact is None:
+            max_inexact = len(nts)
+        if not 0 <= int(max_inexact) <= len(nts):
+            raise ValueError("max_inexact must be 0 .. the number of segments")
+        nt = np.asarray(nts, np.uint32)
+        n = np.asarray([len(w) for w in ls], np.uint64)
+        b = np.ascontiguousarray(np.concatenate(ls + [np.zeros(1, np.uint64)]))      # (never an empty buffer)
+        self._check(self._lib.humid_whitelist_set_segments(self._h, len(nts), _vp(nt), _vp(n), _vp(b), int(max_inexact)))
+
+    def whitelist_segments_info(self):
+        """dict(n_seg, seg_nt, seg_n, max_inexact) of the segmented whitelist: the nucleotides and the distinct values
+        of every segment (n_seg = 0: the whitelist is a plain one or none is set)"""
+        s, m = C.c_uint32(), C.c_uint32()
+        nt, n = np.zeros(8, np.uint32), np.zeros(8, np.uint64)
+        self._check(self._lib.humid_whitelist_segments_info(self._h, C.byref(s), _vp(nt), _vp(n), C.byref(m)))
+        return dict(n_seg=s.value, seg_nt=[int(x) for x in nt[:s.value]], seg_n=[int(x) for x in n[:s.value]],
+                    max_inexact=m.value)
+
+    def barcode_segments(self):
+        """after correct_keys or run_keyed(correct=True) over a segmented whitelist, whichever came later:
+        (seg_counts u64[S, 4], inexact_hist u64[S + 1]): per segment the usable reads whose segment was exact /
+        corrected / ambiguous / unmatched, and the reads by their number of segments that were not exact
+        (humid_get_barcode_segments)"""
+        s = self.whitelist_segments_info()["n_seg"]
+        sc, ih = np.zeros((8, 4), np.uint64), np.zeros(9, np.uint64)
+        self._check(self._lib.humid_get_barcode_segments(self._h, _vp(sc), _vp(ih)))
+        return sc[:s].copy(), ih[:s + 1].copy()
+
     def correct_keys(self, keys, filtered, quals=None, min_odds=39):
         """Correct keys against the whitelist without running anything else (humid_whitelist_correct): returns
         (keys_out u64[N], status u8[N] of BC_FILTERED .. BC_UNMATCHED, counts u64[5] indexed by status).  The

@@ -56,7 +56,10 @@ struct Args {
   unsigned gpus = 1;           // -g (not in the reference): ranks the read set is sharded over, one GPU each
   bool keyed = false;          // -b given (not in the reference): the first `barcode` nucleotides of the word are matched exactly
   size_t barcode = 0;          // -b
-  std::string whitelist;       // -w (not in the reference): file of known barcodes the -b barcodes are corrected against
+  std::vector<std::string> whitelists;   // -w (not in the reference): file of known barcodes the -b barcodes are corrected against; given several times: one file per segment of the barcode, in order
+  bool max_inexact_given = false;     // --barcode-max-inexact (several -w): segments of a read's barcode that may be other than exact
+  unsigned long long max_inexact = 0;
+  std::string word_pattern;    // --word-pattern (not in the reference): which letters of the first file's read make the word (C barcode, N UMI, X skipped)
   bool posterior = false;      // --barcode-posterior (needs -w): barcodes with several listed neighbours are decided by base quality and abundance
   unsigned long long min_odds = 39;   // --barcode-min-odds
   int cells_mode = -1;         // --cells-top / --cells-expected / --cells-min-reads (not in the reference): HUMID_CELLS_*, the whitelist comes from the data
@@ -80,7 +83,7 @@ struct Args {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE | --cells-expected N] [--barcode-posterior]] [-Q] [-C] [-O D] [-P [-D]] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -94,6 +97,18 @@ void usage(const char *argv0) {
                "      starting with # are skipped).  A barcode that is not listed but has exactly one listed barcode one\n"
                "      substitution away becomes that barcode; reads whose barcode has several or none are left out like\n"
                "      reads with an N; with -s also barcodes.dat: exact / corrected / ambiguous / unmatched reads\n"
+               "      -w A -w B -w C: a barcode of several segments (SPLiT-seq, inDrop, BD Rhapsody, sci-RNA-seq), one list per\n"
+               "      segment in order.  All lines of a file have one length, that of its segment (1..10 letters, 8 files at most),\n"
+               "      and the lengths add up to K.  Every segment is corrected on its own against its list, one substitution at the\n"
+               "      most in each; --barcode-max-inexact N (default: all segments) leaves out reads with more than N segments\n"
+               "      that are not exact.  barcodes.dat gains segment<s>.exact / .corrected / .ambiguous / .unmatched and\n"
+               "      inexact<m> (reads with m such segments); a log line.  Not with --barcode-posterior or --cells-*\n"
+               "  --word-pattern P  which letters of the FIRST file's read make the word, as UMI-tools' --bc-pattern: P is a\n"
+               "      string of C (barcode), N (UMI) and X (skipped), one letter per nucleotide of the read.  The C letters in\n"
+               "      order are the barcode and start the word (their number is K: -b may be left out), the N letters follow,\n"
+               "      and the remaining n - #C - #N nucleotides come from the other files (with one file n = #C + #N).  A read\n"
+               "      shorter than the pattern is left out like a read with an N.  Works with one -w, several or none; not with\n"
+               "      a UMI in the headers, -P, -g or --barcode-posterior\n"
                "  --barcode-posterior  with -w: a barcode with SEVERAL listed barcodes one substitution away is decided as Cell\n"
                "      Ranger and STARsolo (1MM_multi) do: every candidate weighs (its exact reads in this input + 1) times the\n"
                "      error probability of the differing base (its quality, the first K letters of the first file's quality\n"
@@ -153,7 +168,19 @@ bool parse(int argc, char **argv, Args &a) {
     else if (t == "-d") { const char *v = need("-d"); if (!v) return false; a.dir_name = v; }
     else if (t == "-g") { const char *v = need("-g"); if (!v) return false; a.gpus = (unsigned)std::strtoul(v, nullptr, 10); }
     else if (t == "-b") { const char *v = need("-b"); if (!v) return false; a.keyed = true; a.barcode = std::strtoull(v, nullptr, 10); }
-    else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelist = v; }
+    else if (t == "-w") { const char *v = need("-w"); if (!v) return false; a.whitelists.push_back(v); }
+    else if (t == "--word-pattern") { const char *v = need("--word-pattern"); if (!v) return false; a.word_pattern = v; }
+    else if (t == "--barcode-max-inexact") {
+      const char *v = need("--barcode-max-inexact");
+      if (!v) return false;
+      char *end = nullptr;
+      a.max_inexact = std::strtoull(v, &end, 10);
+      if (*v < '0' || *v > '9' || *end != 0 || a.max_inexact > 8) {
+        std::fprintf(stderr, "humid: --barcode-max-inexact takes a number of segments, 0 .. 8\n");
+        return false;
+      }
+      a.max_inexact_given = true;
+    }
     else if (t == "--barcode-posterior") a.posterior = !a.posterior;
     else if (t == "--barcode-min-odds") {
       const char *v = need("--barcode-min-odds");
@@ -298,7 +325,11 @@ int write_cells(humid_ctx *ctx, size_t barcode_nt, const std::string &cells_path
 // -w FILE: one barcode of barcode_nt letters per line -> packed like the words (first letter most significant).
 // Trailing whitespace and CR are dropped, then a trailing "-1" (10x style); empty lines and lines starting with '#'
 // are skipped; letters in either case.  false + a one-line message in err when the file cannot serve.
-bool read_whitelist(const std::string &path, size_t barcode_nt, std::vector<uint64_t> &out, std::string &err) {
+// barcode_nt = 0 (one file of several: a segment's list): the first barcode's length is taken, returned in barcode_nt,
+// and every other line must have it.
+bool read_whitelist(const std::string &path, size_t &barcode_nt, std::vector<uint64_t> &out, std::string &err) {
+  const bool infer = barcode_nt == 0;
+  const size_t before = out.size();
   if (path.size() >= 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
     err = "-w takes a plain text file, not " + path + " (decompress it first)";
     return false;
@@ -312,9 +343,14 @@ bool read_whitelist(const std::string &path, size_t barcode_nt, std::vector<uint
     while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
     if (line.empty() || line[0] == '#') continue;
     if (line.size() >= 2 && line.compare(line.size() - 2, 2, "-1") == 0) line.resize(line.size() - 2);
+    if (infer && barcode_nt == 0) barcode_nt = line.size();
     if (line.size() != barcode_nt) {
-      err = "-w: " + path + " line " + std::to_string(ln) + " has " + std::to_string(line.size()) + " letters, -b says " +
-            std::to_string(barcode_nt);
+      err = "-w: " + path + " line " + std::to_string(ln) + " has " + std::to_string(line.size()) + " letters, " +
+            (infer ? "the lines before it " : "-b says ") + std::to_string(barcode_nt);
+      return false;
+    }
+    if (infer && barcode_nt > 10) {
+      err = "-w: " + path + " holds barcodes of " + std::to_string(barcode_nt) + " letters: a segment of several -w has 1 .. 10";
       return false;
     }
     uint64_t v = 0;
@@ -334,7 +370,7 @@ bool read_whitelist(const std::string &path, size_t barcode_nt, std::vector<uint
     out.push_back(v);
   }
   if (in.bad()) { err = "-w: reading " + path + " failed"; return false; }
-  if (out.empty()) { err = "-w: " + path + " holds no barcode"; return false; }
+  if (out.size() == before) { err = "-w: " + path + " holds no barcode"; return false; }
   return true;
 }
 
@@ -485,11 +521,50 @@ int main(int argc, char **argv) {
   // HUMID_FORCE_SHARDED=1: the rank orchestration also for -g 1 (one rank; exercises the transport)
   const bool sharded = a.gpus > 1 || getenv("HUMID_FORCE_SHARDED") != nullptr;
   const bool discover = a.cells_mode >= 0;                 // the whitelist comes from the data
+  const bool segmented = a.whitelists.size() > 1;          // one -w per segment of the barcode
+  // what --word-pattern and several -w do not work with: one line each, before anything is opened
+  {
+    const char *why = nullptr;
+    if (!a.word_pattern.empty()) {
+      if (a.paired) why = "--word-pattern does not work with -P (a strand-symmetric word takes the same letters of both reads)";
+      else if (sharded) why = "--word-pattern runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+      else if (a.posterior) why = "--word-pattern does not work with --barcode-posterior (the barcode's qualities are taken from the start of the read)";
+    }
+    if (!why && segmented) {
+      if (a.posterior) why = "--barcode-posterior does not work with several -w (a segment of the barcode is corrected without qualities)";
+      else if (discover || a.cells_ratio_given) why = "--cells-top / --cells-expected / --cells-min-reads / --cells-merge-ratio do not work with several -w (the segments' lists are the whitelist)";
+      else if (a.whitelists.size() > 8) why = "-w: a barcode has 8 segments at the most";
+    }
+    if (!why && a.max_inexact_given && !segmented) why = "--barcode-max-inexact needs several -w (it counts the segments of a barcode)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 1; }
+  }
+  WordPlan pattern_plan;
+  if (!a.word_pattern.empty()) {
+    size_t n_c = 0;
+    std::string err;
+    if (!make_pattern_plan(a.word_pattern, a.files.size(), a.word_length, pattern_plan, n_c, err)) {
+      std::fprintf(stderr, "humid: %s\n", err.c_str());
+      return 1;
+    }
+    if (a.keyed && a.barcode != n_c) {
+      std::fprintf(stderr, "humid: --word-pattern has %zu C letters, -b says %zu\n", n_c, a.barcode);
+      return 1;
+    }
+    if (n_c) { a.keyed = true; a.barcode = n_c; }
+    // the word is made of the reads' letters alone: a UMI in the headers would start it
+    FastqReader peek(a.files.front());
+    if (!peek.ok()) { std::fprintf(stderr, "humid: cannot open %s\n", a.files.front().c_str()); return 1; }
+    FastqRecord r;
+    if (peek.read(r) && !header_umi(r.name).empty()) {
+      std::fprintf(stderr, "humid: --word-pattern takes the word from the reads alone: %s has a UMI in its headers\n", a.files.front().c_str());
+      return 1;
+    }
+  }
   if (discover || a.cells_ratio_given) {
     const char *why = nullptr;
     if (a.cells_modes_given > 1) why = "--cells-top, --cells-expected and --cells-min-reads exclude each other (one rule selects the cells)";
     else if (!discover) why = "--cells-merge-ratio needs --cells-top, --cells-expected or --cells-min-reads (it merges the cells they select)";
-    else if (!a.whitelist.empty()) why = "--cells-top / --cells-expected / --cells-min-reads do not work with -w (the whitelist comes from FILE or from the data)";
+    else if (!a.whitelists.empty()) why = "--cells-top / --cells-expected / --cells-min-reads do not work with -w (the whitelist comes from FILE or from the data)";
     else if (a.paired) why = "--cells-top / --cells-expected / --cells-min-reads do not work with -P";
     else if (sharded) why = "--cells-top / --cells-expected / --cells-min-reads run on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
     else if (!a.keyed) why = "--cells-top / --cells-expected / --cells-min-reads need -b K (the cells are barcodes of K letters)";
@@ -520,7 +595,7 @@ int main(int argc, char **argv) {
     if (a.files.size() != 2) why = "-P takes exactly two input files (R1 and R2)";
     else if (a.word_length % 2 != 0) why = "-P needs an even word length (-n): half of the word comes from each file";
     else if (a.keyed) why = "-P does not work with -b";
-    else if (!a.whitelist.empty()) why = "-P does not work with -w";
+    else if (!a.whitelists.empty()) why = "-P does not work with -w";
     else if (sharded) why = "-P runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
     else if (a.edit) why = "-P does not work with -e (edit distance against an exchanged pair is not defined here)";
     else if (a.consensus) why = "-P does not work with -C (the consensus of a -P run is -D: it takes half of the reads from the other file)";
@@ -544,14 +619,33 @@ int main(int argc, char **argv) {
   const bool scoring = a.best || !a.dump_scores.empty();                    // (without -Q pass 1 does no new work)
   const bool positions = a.optical || !a.dump_positions.empty();            // (nor without -O)
   std::vector<uint64_t> whitelist;
-  if (!a.whitelist.empty()) {
+  std::vector<uint32_t> seg_nt;                            // several -w: the letters and the entries of every file's list,
+  std::vector<uint64_t> seg_n;                             // the lists themselves one behind the other in whitelist
+  if (!a.whitelists.empty()) {
     if (!a.keyed) {
       std::fprintf(stderr, "humid: -w needs -b K (the whitelist holds barcodes of K letters)\n");
       return 2;
     }
     std::string err;
-    if (!read_whitelist(a.whitelist, a.barcode, whitelist, err)) {
-      std::fprintf(stderr, "humid: %s\n", err.c_str());
+    size_t total_nt = 0;
+    for (const std::string &file : a.whitelists) {
+      size_t nt = segmented ? 0 : a.barcode;
+      const size_t before = whitelist.size();
+      if (!read_whitelist(file, nt, whitelist, err)) {
+        std::fprintf(stderr, "humid: %s\n", err.c_str());
+        return 2;
+      }
+      seg_nt.push_back((uint32_t)nt);
+      seg_n.push_back(whitelist.size() - before);
+      total_nt += nt;
+    }
+    if (segmented && total_nt != a.barcode) {
+      std::fprintf(stderr, "humid: -w: the segments of the %zu files add up to %zu letters, the barcode has %zu\n", a.whitelists.size(), total_nt,
+                   a.barcode);
+      return 2;
+    }
+    if (segmented && a.max_inexact_given && a.max_inexact > a.whitelists.size()) {
+      std::fprintf(stderr, "humid: --barcode-max-inexact %llu exceeds the %zu segments\n", a.max_inexact, a.whitelists.size());
       return 2;
     }
   }
@@ -636,7 +730,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "humid: -P takes the word from the two reads alone: %s has a UMI in its headers\n", a.files.front().c_str());
     return 2;
   }
-  WordPlan plan = make_plan(first_umi, a.files.size(), a.word_length);
+  WordPlan plan = a.word_pattern.empty() ? make_plan(first_umi, a.files.size(), a.word_length) : pattern_plan;
   if (bc_quals && (plan.header_umi != 0 || plan.take[0] < a.barcode)) {
     // the barcode's qualities are the first K letters of the first file's quality line: the barcode must be its read's start
     const char *flag = a.posterior ? "--barcode-posterior" : "--dump-barcode-quals";
@@ -886,7 +980,10 @@ int main(int argc, char **argv) {
   humid_summary sum;
   std::memset(&sum, 0, sizeof sum);
   if (a.edit) humid_ctx_set_option(ctx, "edit_distance", 1);
-  if (corrected && !discover && humid_whitelist_set(ctx, whitelist.data(), whitelist.size(), (uint32_t)a.barcode) != HUMID_OK) {
+  const uint32_t max_inexact = a.max_inexact_given ? (uint32_t)a.max_inexact : (uint32_t)seg_nt.size();
+  if (corrected && !discover &&
+      (segmented ? humid_whitelist_set_segments(ctx, (uint32_t)seg_nt.size(), seg_nt.data(), seg_n.data(), whitelist.data(), max_inexact)
+                 : humid_whitelist_set(ctx, whitelist.data(), whitelist.size(), (uint32_t)a.barcode)) != HUMID_OK) {
     std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
     humid_ctx_destroy(ctx);
     return 1;
@@ -956,6 +1053,8 @@ int main(int argc, char **argv) {
   if (rc == HUMID_OK && corrected) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
   uint64_t bc_multi = 0, bc_rescued = 0;
   if (rc == HUMID_OK && a.posterior) rc = humid_get_barcode_posterior(ctx, &bc_multi, &bc_rescued);
+  uint64_t seg_counts[8 * 4] = {}, inexact_hist[9] = {};
+  if (rc == HUMID_OK && segmented) rc = humid_get_barcode_segments(ctx, seg_counts, inexact_hist);
   humid_strand_summary ssum;
   std::memset(&ssum, 0, sizeof ssum);
   if (rc == HUMID_OK && a.paired) {
@@ -985,6 +1084,14 @@ int main(int argc, char **argv) {
   if (corrected)
     log << "  barcodes: " << bc_counts[HUMID_BC_EXACT] << " exact, " << bc_counts[HUMID_BC_CORRECTED] << " corrected, "
         << bc_counts[HUMID_BC_AMBIGUOUS] << " ambiguous, " << bc_counts[HUMID_BC_UNMATCHED] << " unmatched\n";
+  if (segmented) {
+    log << "  barcode segments (exact/corrected/ambiguous/unmatched):";
+    for (size_t g = 0; g < seg_nt.size(); g++)
+      log << ' ' << seg_counts[4 * g] << '/' << seg_counts[4 * g + 1] << '/' << seg_counts[4 * g + 2] << '/' << seg_counts[4 * g + 3];
+    log << "; reads by segments not exact (at most " << max_inexact << "):";
+    for (size_t m = 0; m <= seg_nt.size(); m++) log << ' ' << inexact_hist[m];
+    log << '\n';
+  }
   if (a.posterior)
     log << "  barcode posterior: " << bc_multi << " reads with several candidates, " << bc_rescued << " of them corrected (odds >= "
         << a.min_odds << ")\n";
@@ -1307,6 +1414,12 @@ int main(int argc, char **argv) {
       if (a.posterior) {
         out << "multi: " << bc_multi << '\n';
         out << "rescued: " << bc_rescued << '\n';
+      }
+      if (segmented) {
+        const char *cls[4] = {"exact", "corrected", "ambiguous", "unmatched"};
+        for (size_t g = 0; g < seg_nt.size(); g++)
+          for (int k = 0; k < 4; k++) out << "segment" << g << '.' << cls[k] << ": " << seg_counts[4 * g + k] << '\n';
+        for (size_t m = 0; m <= seg_nt.size(); m++) out << "inexact" << m << ": " << inexact_hist[m] << '\n';
       }
       out.close();
       if (out.fail()) ok = -1;

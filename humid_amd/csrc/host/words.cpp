@@ -51,6 +51,42 @@ WordPlan make_plan(size_t first_header_umi, size_t n_files, size_t word_nt) {
   return p;
 }
 
+bool make_pattern_plan(const std::string &pattern, size_t n_files, size_t word_nt, WordPlan &plan, size_t &n_barcode,
+                       std::string &err) {
+  std::vector<WordPlan::Range> bc, umi;
+  size_t n_c = 0, n_n = 0;
+  for (size_t i = 0; i < pattern.size(); i++) {
+    const char ch = pattern[i];
+    if (ch != 'C' && ch != 'N' && ch != 'X') { err = "--word-pattern takes the letters C (barcode), N (UMI) and X (skipped)"; return false; }
+    if (ch == 'X') continue;
+    std::vector<WordPlan::Range> &to = ch == 'C' ? bc : umi;
+    (ch == 'C' ? n_c : n_n)++;
+    if (!to.empty() && to.back().off + to.back().len == i) to.back().len++;
+    else to.push_back({i, 1});
+  }
+  if (pattern.empty()) { err = "--word-pattern takes a pattern of one letter or more"; return false; }
+  if (n_c + n_n > word_nt || (n_files == 1 && n_c + n_n != word_nt)) {
+    err = "--word-pattern: the pattern's " + std::to_string(n_c) + " C and " + std::to_string(n_n) + " N letters " +
+          (n_files == 1 ? "must add up to" : "exceed") + " the word length (-n " + std::to_string(word_nt) + ")";
+    return false;
+  }
+  plan = WordPlan();
+  plan.word_nt = word_nt;
+  plan.header_umi = 0;
+  plan.take = nt_from_file(n_files - 1, word_nt - n_c - n_n);
+  plan.take.insert(plan.take.begin(), n_c + n_n);
+  plan.patterned = true;
+  plan.first = bc;
+  plan.first.insert(plan.first.end(), umi.begin(), umi.end());
+  n_barcode = n_c;
+  return true;
+}
+
+// the letters of range r that the read has (the rest is padding)
+static inline std::string_view cut(std::string_view s, const WordPlan::Range &r) {
+  return r.off < s.size() ? s.substr(r.off, r.len) : std::string_view();
+}
+
 // appends `want` symbols of `s` (cut or padded with a non-ACGT symbol) to the packed word
 template <class Acc>
 static inline void push_symbols(std::string_view s, size_t want, Acc &w, bool &filtered) {
@@ -71,7 +107,11 @@ bool make_word(std::string_view first_header, const std::string_view *seqs, size
   uint64_t w = 0;
   bool filtered = false;
   if (plan.header_umi > 0) push_symbols(header_umi(first_header), plan.header_umi, w, filtered);
-  for (size_t f = 0; f < n_files; f++) push_symbols(seqs[f], plan.take[f], w, filtered);
+  for (size_t f = 0; f < n_files; f++) {
+    if (f == 0 && plan.patterned)
+      for (const WordPlan::Range &r : plan.first) push_symbols(cut(seqs[0], r), r.len, w, filtered);
+    else push_symbols(seqs[f], plan.take[f], w, filtered);
+  }
   word = w;
   return filtered;
 }
@@ -86,7 +126,11 @@ static inline uint8_t *copy_padded(std::string_view s, size_t want, uint8_t *out
 void gather_bases(std::string_view first_header, const std::string_view *seqs, size_t n_files,
                   const WordPlan &plan, uint8_t *out) {
   if (plan.header_umi > 0) out = copy_padded(header_umi(first_header), plan.header_umi, out);
-  for (size_t f = 0; f < n_files; f++) out = copy_padded(seqs[f], plan.take[f], out);
+  for (size_t f = 0; f < n_files; f++) {
+    if (f == 0 && plan.patterned)
+      for (const WordPlan::Range &r : plan.first) out = copy_padded(cut(seqs[0], r), r.len, out);
+    else out = copy_padded(seqs[f], plan.take[f], out);
+  }
 }
 
 bool make_word_wide(std::string_view first_header, const std::string_view *seqs, size_t n_files,
@@ -94,7 +138,11 @@ bool make_word_wide(std::string_view first_header, const std::string_view *seqs,
   unsigned __int128 w = 0;
   bool filtered = false;
   if (plan.header_umi > 0) push_symbols(header_umi(first_header), plan.header_umi, w, filtered);
-  for (size_t f = 0; f < n_files; f++) push_symbols(seqs[f], plan.take[f], w, filtered);
+  for (size_t f = 0; f < n_files; f++) {
+    if (f == 0 && plan.patterned)
+      for (const WordPlan::Range &r : plan.first) push_symbols(cut(seqs[0], r), r.len, w, filtered);
+    else push_symbols(seqs[f], plan.take[f], w, filtered);
+  }
   word[0] = (uint64_t)(w >> 64);     // the first word_nt - 32 symbols
   word[1] = (uint64_t)w;             // the last 32
   return filtered;

@@ -26,9 +26,21 @@ struct WordPlan {
   size_t word_nt = 24;
   size_t header_umi = 0;           // symbols taken from the first file's header UMI
   std::vector<size_t> take;        // symbols taken from each file's read
+  // --word-pattern: the first file's read contributes these letters instead of its first take[0] ones, range after
+  // range: the barcode's (the pattern's C) in read order, then the UMI's (its N); take[0] is their total
+  struct Range { size_t off, len; };
+  bool patterned = false;
+  std::vector<Range> first;
 };
 // first_header_umi: UMI length found in the first record of the first file (peekUMI)
 WordPlan make_plan(size_t first_header_umi, size_t n_files, size_t word_nt);
+
+// --word-pattern P (letters C, N, X as in UMI-tools' --bc-pattern, applied to the first file's read): the C letters in
+// order are the barcode and start the word, the N letters follow, X letters are skipped; the remaining
+// word_nt - #C - #N symbols come from the other files (nt_from_file over them).  No header UMI.  n_barcode = #C.
+// false + a one-line message in err when the pattern cannot serve.
+bool make_pattern_plan(const std::string &pattern, size_t n_files, size_t word_nt, WordPlan &plan, size_t &n_barcode,
+                       std::string &err);
 
 // One record set -> packed word (first symbol most significant).  Returns true when the word is
 // filtered (a symbol outside ACGT, including 'N' padding of short UMIs/reads; coded as 'G').
@@ -58,7 +70,8 @@ inline bool canonical_word(uint64_t *w, size_t wpr, size_t word_nt) {
 
 // getNucleotides (src/fastq.cc:116-144) as raw bytes, for the device-side packing of
 // humid_dedup_run_bases: out[plan.word_nt] = the header UMI cut or padded with 'N' to plan.header_umi
-// symbols, then the first plan.take[f] bytes of every file's read, 'N' where a read is short.  The
+// symbols, then the first plan.take[f] bytes of every file's read (the first file's ranges with --word-pattern), 'N'
+// where a read is short.  The
 // bytes are copied as they stand in the FastQ; the device maps and validates them.
 void gather_bases(std::string_view first_header, const std::string_view *seqs, size_t n_files,
                   const WordPlan &plan, uint8_t *out);

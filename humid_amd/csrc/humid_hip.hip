@@ -302,6 +302,7 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
   state_reset(c);
   if (paired) TRY(check_paired_run_args(c, n_reads, word_nt, distance, method));
   if (kind == RUN_CORRECTED && !c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (posterior && c->sg.n_seg) return fail(c, HUMID_E_UNSUPPORTED, SEG_NO_POSTERIOR);
   if (posterior && min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
   if (posterior && n_reads && !qual) return fail(c, HUMID_E_INVALID, "null buffer");
   if (kind >= RUN_KEYED) {
@@ -534,6 +535,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   if (n == 0) {                                              // clear
     HIPCHK(hipStreamSynchronize(st));
     c->wl_table.release();
+    seg_drop(c);
     c->wl_n = 0; c->wl_nt = 0; c->wl_log2 = 0;
     c->wp_valid = false;
     c->cd_valid = false;
@@ -564,9 +566,100 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   HIPCHK(hipMemcpyAsync(&distinct, fresh.as<u64>() + cap + 1, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->wl_table = std::move(fresh);
+  seg_drop(c);
   c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
   c->wp_valid = false;                                       // (the reads per slot went with the table they index)
   c->cd_valid = false;                                       // (nor is this whitelist one a discover call installed)
+  return HUMID_OK;
+}
+
+// ---- segmented whitelist (kernels_segments.hip.h) ------------------------------------------------------------------
+int humid_whitelist_set_segments(humid_ctx *c, uint32_t n_seg, const uint32_t *seg_nt, const uint64_t *seg_n, const uint64_t *barcodes,
+                                 uint32_t max_inexact) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (n_seg < 1 || n_seg > SEG_MAX) return fail(c, HUMID_E_INVALID, "a segmented whitelist has 1 .. %u segments", SEG_MAX);
+  if (!seg_nt || !seg_n || !barcodes) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (max_inexact > n_seg) return fail(c, HUMID_E_INVALID, "max_inexact %u exceeds the %u segments", max_inexact, n_seg);
+  SegPlan plan = {};
+  plan.n_seg = n_seg;
+  plan.max_inexact = max_inexact;
+  u64 total = 0, entries = 0;
+  for (u32 s = 0; s < n_seg; s++) {
+    if (seg_nt[s] < 1 || seg_nt[s] > SEG_MAX_NT) return fail(c, HUMID_E_INVALID, "segment %u: a segment has 1 .. %u nucleotides", s, SEG_MAX_NT);
+    if (seg_n[s] == 0) return fail(c, HUMID_E_INVALID, "segment %u: the list is empty", s);
+    if (seg_n[s] > ((u64)1 << 30)) return fail(c, HUMID_E_OVERFLOW, "segment %u: a list of %llu barcodes exceeds 2^30", s, (ull)seg_n[s]);
+    plan.key_nt += seg_nt[s];
+    plan.mask[s] = (1u << (2 * seg_nt[s])) - 1u;
+    plan.off[s] = (u32)entries;
+    entries += (u64)plan.mask[s] + 1;
+    for (u64 i = 0; i < seg_n[s]; i++)
+      if (barcodes[total + i] > plan.mask[s])
+        return fail(c, HUMID_E_INVALID, "segment %u: barcode %llu = 0x%llx is not a %u-nucleotide word", s, (ull)i, (ull)barcodes[total + i],
+                    seg_nt[s]);
+    total += seg_n[s];
+  }
+  if (plan.key_nt > 32) return fail(c, HUMID_E_INVALID, "the segments add up to %u nucleotides, more than 32", plan.key_nt);
+  for (u32 s = 0, below = plan.key_nt; s < n_seg; s++) {           // segment 0 is the most significant
+    below -= seg_nt[s];
+    plan.shift[s] = 2 * below;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  // the new tables are built beside the whitelist in place, which stays until they are complete
+  DBuf fresh, work, stage, ndist;                            // (all free themselves on every early return)
+  HIPCHK(fresh.ensure((size_t)entries * 4));
+  HIPCHK(work.ensure((size_t)entries * 4));
+  HIPCHK(stage.ensure((size_t)total * 8));
+  HIPCHK(ndist.ensure(SEG_MAX * sizeof(ull)));
+  HIPCHK(hipMemsetAsync(fresh.p, 0xff, (size_t)entries * 4, st));
+  HIPCHK(hipMemsetAsync(work.p, 0, (size_t)entries * 4, st));
+  HIPCHK(hipMemsetAsync(ndist.p, 0, SEG_MAX * sizeof(ull), st));
+  HIPCHK(hipMemcpyAsync(stage.p, barcodes, (size_t)total * 8, hipMemcpyHostToDevice, st));
+  for (u64 s = 0, at = 0; s < n_seg; at += seg_n[s], s++) {      // (a table's entries are indexed by the subkey: one pair of launches per segment)
+    hipLaunchKernelGGL(k_seg_mark, dim3(grid_stride_blocks(seg_n[s])), dim3(256), 0, st, (const u64 *)stage.p + at, (u32)seg_n[s], seg_nt[s],
+                       fresh.as<u32>() + plan.off[s], work.as<u32>() + plan.off[s], ndist.as<ull>() + s);
+    hipLaunchKernelGGL(k_seg_finish, dim3(grid_stride_blocks((u64)plan.mask[s] + 1)), dim3(256), 0, st, fresh.as<u32>() + plan.off[s],
+                       (const u32 *)work.p + plan.off[s], plan.mask[s] + 1u);
+  }
+  HIPCHK(hipGetLastError());
+  ull distinct[SEG_MAX] = {};
+  HIPCHK(hipMemcpyAsync(distinct, ndist.p, sizeof distinct, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  unsigned __int128 product = 1;
+  for (u32 s = 0; s < n_seg; s++) product *= distinct[s];
+  c->wl_table.release();
+  c->sg_table = std::move(fresh);
+  c->sg = plan;
+  for (u32 s = 0; s < SEG_MAX; s++) c->sg_distinct[s] = distinct[s];
+  c->sg_sum_valid = false;
+  c->wl_n = product > (unsigned __int128)~0ull ? ~0ull : (u64)product;   // (all 4^32 keys of K = 32: one more than a u64 holds)
+  c->wl_nt = plan.key_nt; c->wl_log2 = 0;
+  c->wp_valid = false;
+  c->cd_valid = false;
+  return HUMID_OK;
+}
+
+int humid_whitelist_segments_info(humid_ctx *c, uint32_t *n_seg, uint32_t seg_nt[8], uint64_t seg_n[8], uint32_t *max_inexact) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (n_seg) *n_seg = c->sg.n_seg;
+  if (max_inexact) *max_inexact = c->sg.max_inexact;
+  for (u32 s = 0; s < SEG_MAX; s++) {
+    u32 nt = 0;
+    for (u32 m = s < c->sg.n_seg ? c->sg.mask[s] : 0u; m; m >>= 2) nt++;
+    if (seg_nt) seg_nt[s] = nt;
+    if (seg_n) seg_n[s] = s < c->sg.n_seg ? c->sg_distinct[s] : 0;
+  }
+  return HUMID_OK;
+}
+
+int humid_get_barcode_segments(humid_ctx *c, uint64_t seg_counts[32], uint64_t inexact_hist[9]) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->sg.n_seg || !c->sg_sum_valid)
+    return fail(c, HUMID_E_STATE, "no correction has run over a segmented whitelist of this context (humid_whitelist_set_segments)");
+  HIPCHK(hipSetDevice(c->device));
+  D2H(seg_counts, c->sg_sum.p, SEG_SUM_HIST * sizeof(ull));
+  D2H(inexact_hist, c->sg_sum.as<ull>() + SEG_SUM_HIST, (SEG_MAX + 1) * sizeof(ull));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
 
@@ -674,6 +767,7 @@ int humid_get_barcode_count_hist(humid_ctx *c, uint64_t *reads, uint64_t *barcod
 static int whitelist_posterior_args(humid_ctx *c, const void *key, const void *qual, const void *filtered, uint64_t n_reads,
                                     uint32_t min_odds) {
   TRY(whitelist_correct_args(c, key, filtered, n_reads));
+  if (c->sg.n_seg) return fail(c, HUMID_E_UNSUPPORTED, SEG_NO_POSTERIOR);
   if (min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
   if (n_reads && !qual) return fail(c, HUMID_E_INVALID, "null buffer");
   return HUMID_OK;

@@ -33,6 +33,7 @@
 #include "kernels_gstats.hip.h"
 #include "kernels_whitelist.hip.h"
 #include "kernels_wlpost.hip.h"
+#include "kernels_segments.hip.h"
 #include "kernels_cells.hip.h"
 #include "kernels_paired.hip.h"
 
@@ -244,6 +245,13 @@ struct humid_ctx {
   DBuf wp_cnt, wp_slot;      // u32[cap + 1] reads per table slot; u32[n_reads] the slot of every read's key
   bool wp_valid = false;     // wp_cnt holds the counts of a posterior call or run over the whitelist now set
   bool bc_posterior = false; // RUN_CORRECTED: the correction was the posterior one (humid_get_barcode_posterior)
+  // segmented whitelist (humid_whitelist_set_segments, kernels_segments.hip.h): in place of wl_table; wl_n is then the
+  // product of the lists' distinct entries (saturating), wl_nt the sum of the segments, wl_log2 0
+  SegPlan sg = {};           // sg.n_seg = 0: the whitelist in place is plain or absent
+  u64 sg_distinct[SEG_MAX] = {};   // distinct entries of every list
+  DBuf sg_table;             // u32[sum of 4^L_s]: the resolution tables, one behind the other
+  DBuf sg_sum;               // u64[SEG_SUM_N]: the per-segment summary of the last segmented correct call or corrected run
+  bool sg_sum_valid = false; // ... which ran over the segmented whitelist now set (humid_get_barcode_segments)
   // whitelist from the data (humid_whitelist_discover*, kernels_cells.hip.h): buffers of its own, never the slab, never
   // kr_table or anything else a run or an accessor reads; the results of the last successful call are kept for the getters
   u32 cd_cap_log2 = 0;       // log2 of the counting table of the next call (0: 16); remembered from call to call, grown on demand
@@ -2710,11 +2718,31 @@ static int run_keyed_device(humid_ctx *c, const WI *d_words, const u64 *d_key, c
 }
 
 // ---- barcode whitelist (humid_whitelist_*, humid_dedup_run_keyed_corrected*; kernels_whitelist.hip.h) -----------
+#define SEG_NO_POSTERIOR "the correction by quality and abundance does not work with a segmented whitelist (humid_whitelist_set_segments)"
+// the whitelist in place stops being a segmented one (it is replaced by a plain one, or cleared)
+static void seg_drop(humid_ctx *c) {
+  c->sg_table.release();
+  c->sg = SegPlan{};
+  c->sg_sum_valid = false;
+}
+
 // The correction pass over device arrays: zeroes d_counts (u64[5]) and launches the kernel; nothing waits here.
 static int wl_correct_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N, u64 *d_key_out, u8 *d_status,
                              u8 *d_filt_out, ull *d_counts) {
   hipStream_t st = c->stream;
   HIPCHK(hipMemsetAsync(d_counts, 0, 5 * sizeof(ull), st));
+  if (c->sg.n_seg) {                                                // a segmented whitelist: S table reads per read, no probing
+    c->sg_sum_valid = false;
+    PASS_ENSURE(c->sg_sum, SEG_SUM_N * sizeof(ull));
+    HIPCHK(hipMemsetAsync(c->sg_sum.p, 0, SEG_SUM_N * sizeof(ull), st));
+    if (N) {
+      hipLaunchKernelGGL(k_seg_resolve, dim3(blocks_for(N)), dim3(256), 0, st, d_key, d_filt, N, (const u32 *)c->sg_table.p, c->sg,
+                         d_key_out, d_status, d_filt_out, d_counts, c->sg_sum.as<ull>());
+      HIPCHK(hipGetLastError());
+    }
+    c->sg_sum_valid = true;
+    return HUMID_OK;
+  }
   if (N == 0) return HUMID_OK;
   if (c->wl_coop)
     hipLaunchKernelGGL(k_wl_correct<true>, dim3(blocks_for(N)), dim3(256), 0, st, d_key, d_filt, N, (const u64 *)c->wl_table.p,
@@ -2763,6 +2791,7 @@ static int run_keyed_corrected_device(humid_ctx *c, const WI *d_words, const u64
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   state_reset(c);
   if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (posterior && c->sg.n_seg) return fail(c, HUMID_E_UNSUPPORTED, SEG_NO_POSTERIOR);
   if (posterior && min_odds == 0) return fail(c, HUMID_E_INVALID, "min_odds must be >= 1");
   if (posterior && n_reads && !d_qual) return fail(c, HUMID_E_INVALID, "null buffer");
   TRY(check_run_args(c, n_reads, word_nt, method, 64));
@@ -2997,6 +3026,7 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
   s.merged = s.selected - n_cells;
   s.reads_in_cells = h[CD_CELLREADS];
   c->wl_table = std::move(fresh);                                 // (zero cells: an empty buffer, the whitelist is cleared)
+  seg_drop(c);
   c->wl_n = n_cells;
   c->wl_nt = n_cells ? K : 0;
   c->wl_log2 = wl_log2;

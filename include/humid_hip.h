@@ -316,6 +316,62 @@ int humid_dedup_run_keyed_corrected_device(humid_ctx *ctx, const uint64_t *d_wor
                                            humid_summary *summary);
 int humid_get_barcode_status(humid_ctx *ctx, uint8_t *status, uint64_t cap, uint64_t counts[5]);
 
+/* ---- segmented barcode whitelist: one list per segment, every segment corrected on its own -------
+ * (STARsolo CB_UMI_Complex with several --soloCBwhitelist, UMI-tools --bc-pattern, the split-pool
+ * pipelines: SPLiT-seq, inDrop, BD Rhapsody, sci-RNA-seq.)  A segmented whitelist has S segments,
+ * 1 <= S <= 8; segment s has L_s nucleotides, 1 <= L_s <= 10, and a set W_s of distinct packed
+ * L_s-mers; K = sum of L_s <= 32.  Segment 0 is the first L_0 nucleotides of the K-nucleotide key
+ * (its most significant bits), segment s follows segment s - 1.  For a usable read with key
+ * k < 4^K and subkeys k_s, the class c_s of segment s is the correction of the section above of k_s
+ * against W_s over L_s nucleotides:
+ *   EXACT      k_s in W_s
+ *   CORRECTED  exactly one w in W_s at Hamming distance 1: it replaces k_s
+ *   AMBIGUOUS  two or more such w
+ *   UNMATCHED  none
+ * Let m be the number of segments whose class is not EXACT.  With max_inexact (0 .. S) the status is
+ *   HUMID_BC_FILTERED   filtered[r] != 0; the key is not read, key_out[r] = 0
+ *   HUMID_BC_UNMATCHED  k >= 4^K or m > max_inexact
+ *   otherwise the worst class of its segments, UNMATCHED > AMBIGUOUS > CORRECTED > EXACT.
+ * key_out[r] is the corrected segments one behind the other for an EXACT or CORRECTED read, k for an
+ * AMBIGUOUS or UNMATCHED one.  So S = 1 is humid_whitelist_correct with that one list, and
+ * max_inexact = 1 is humid_whitelist_correct against the product list W_0 x ... x W_(S-1), both bit for
+ * bit; max_inexact = S allows one substitution in EVERY segment, which no product list expresses.
+ * Beside counts[5] a correction leaves a per-segment summary over the usable reads with k < 4^K,
+ * whatever max_inexact is: seg_counts[s][c] the reads whose segment s is EXACT / CORRECTED /
+ * AMBIGUOUS / UNMATCHED (c = 0 .. 3), inexact_hist[m] the reads by m.
+ * On the device: a segment has at most 4^10 values, so humid_whitelist_set_segments works out the
+ * answer for EVERY value once, on the device, into one direct-index table per segment (32-bit
+ * entries, class << 30 | subkey, at most 4 MB a segment, in HBM and for the usual chemistries in L2):
+ * every list entry marks itself exact, adds itself to the hit count of its 3 L_s variants and offers
+ * itself as their winner by an atomic minimum, and a second kernel turns the counts into classes.
+ * A read is then S independent table reads and no probing, in one pass in front of the unchanged
+ * keyed pass, with no host wait of its own.
+ *   humid_whitelist_set_segments: seg_nt[n_seg], seg_n[n_seg] and barcodes (the lists one behind the
+ *     other, seg_n[s] entries of segment s) are HOST arrays; duplicates in a list collapse.  It
+ *     installs the segmented whitelist in place of whatever whitelist the context holds and survives
+ *     runs as that of humid_whitelist_set does; humid_whitelist_set, humid_whitelist_discover and a
+ *     clear replace it.  HUMID_E_INVALID for n_seg outside 1 .. 8, a segment outside 1 .. 10
+ *     nucleotides, K > 32, an empty list, an entry >= 4^L_s or max_inexact > n_seg (HUMID_E_OVERFLOW
+ *     for a list of more than 2^30 entries): the previous whitelist stays and the context usable.
+ *   humid_whitelist_segments_info: n_seg (0: the whitelist in place is plain or absent), the
+ *     nucleotides and the distinct entries of every segment (0 behind the last), max_inexact.  Any
+ *     pointer may be NULL.  humid_whitelist_info answers K for a segmented whitelist, the product of
+ *     the distinct entries as n_distinct (at most 2^64 - 1) and table_log2 = 0.
+ *   With a segmented whitelist in place humid_whitelist_correct(_device) and
+ *   humid_dedup_run_keyed_corrected(_device) follow the definition above, and humid_get_barcode_status
+ *   answers as for any corrected run; the posterior calls and runs of the next section return
+ *   HUMID_E_UNSUPPORTED and humid_whitelist_counts HUMID_E_STATE.
+ *   humid_get_barcode_segments: seg_counts (8 rows of 4, rows behind the last segment zero) and
+ *     inexact_hist (9 bins) of the last correct call or corrected run over the segmented whitelist in
+ *     place, whichever came later.  Either pointer may be NULL.  HUMID_E_STATE before such a call or
+ *     once the whitelist was replaced. */
+int humid_whitelist_set_segments(humid_ctx *ctx, uint32_t n_seg, const uint32_t *seg_nt,
+                                 const uint64_t *seg_n, const uint64_t *barcodes,
+                                 uint32_t max_inexact);
+int humid_whitelist_segments_info(humid_ctx *ctx, uint32_t *n_seg, uint32_t seg_nt[8],
+                                  uint64_t seg_n[8], uint32_t *max_inexact);
+int humid_get_barcode_segments(humid_ctx *ctx, uint64_t seg_counts[32], uint64_t inexact_hist[9]);
+
 /* ---- barcode whitelist: ambiguous keys decided by base quality and barcode abundance -------------
  * (Cell Ranger, STARsolo 1MM_multi.)  W, K, key, filtered, the five statuses and key_out are those
  * of the section above; a whitelist must be set.  Three inputs are new:
