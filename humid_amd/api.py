@@ -848,6 +848,98 @@ class Dedup(Context):
                     stats=dict(total=int(s["total"]), usable=int(s["usable"]),
                                unique=int(s["unique"]), clusters=int(s["clusters"])))
 
+    def accumulator(self, word_nt=24):
+        """A read set fed in chunks (include/humid_hip.h, humid_accum_*): empties any earlier accumulator of this
+        object and returns the new one."""
+        return Accumulator(self, word_nt)
+
+
+class Accumulator:
+    """One read set deduplicated in chunks: add() every chunk, finish(), then map() every chunk.
+
+    The results are those of Dedup.run over all added reads sorted by global index (base + position in the chunk),
+    whatever the order of the chunks.  The accumulator lives in the Dedup object's context: after finish(),
+    dd.adjacency(), dd.clusters() and dd.histogram() answer for the accumulated set (until the first map())."""
+
+    def __init__(self, dd: Dedup, word_nt: int):
+        self._dd = dd
+        self._lib = dd._lib
+        dd._check(self._lib.humid_accum_begin(dd._h, int(word_nt)))
+        self.word_nt = int(word_nt)
+        self._next = 0
+
+    def _chunk(self, words, filtered):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        want = (len(f), 2) if self.word_nt > 32 else (len(f),)
+        if f.ndim != 1 or w.shape != want:
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % (want, self.word_nt, f.shape))
+        return w, f
+
+    def add(self, words, filtered, base=None):
+        """adds a chunk whose first read has global index `base` (default: the reads added so far); returns the base used"""
+        w, f = self._chunk(words, filtered)
+        base = self._next if base is None else int(base)
+        self._dd._check(self._lib.humid_accum_add(self._dd._h, _vp(w), _vp(f), len(f), base))
+        self._next = max(self._next, base + len(f))
+        return base
+
+    def add_device(self, d_words, d_filtered, n_reads, base):
+        """the same with integer device pointers"""
+        self._dd._check(self._lib.humid_accum_add_device(self._dd._h, C.c_void_p(d_words), C.c_void_p(d_filtered), n_reads, int(base)))
+        self._next = max(self._next, int(base) + n_reads)
+        return int(base)
+
+    def finish(self, distance=1, method=DIRECTIONAL, edit=False):
+        """clusters the accumulated words; returns the summary dict of Dedup.run over all added reads"""
+        dd = self._dd
+        dd.set_option("edit_distance", int(bool(edit)))
+        s = _lib.HumidSummary()
+        dd._check(self._lib.humid_accum_finish(dd._h, distance, method, C.byref(s)))
+        dd.summary = s.asdict()
+        dd._wide = self.word_nt > 32
+        return dd.summary
+
+    def map(self, words, filtered, base):
+        """(cluster_id u32[N], keep u8[N], n_unknown) of a chunk whose first read has global index `base`"""
+        w, f = self._chunk(words, filtered)
+        cid = np.zeros(len(f), dtype=np.uint32)
+        keep = np.zeros(len(f), dtype=np.uint8)
+        unknown = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_map(self._dd._h, _vp(w), _vp(f), len(f), int(base), _vp(cid), _vp(keep),
+                                                  C.byref(unknown)))
+        return cid, keep, unknown.value
+
+    def map_device(self, d_words, d_filtered, n_reads, base, d_cluster_id, d_keep):
+        """the same with integer device pointers; the results stay in HBM.  Returns n_unknown."""
+        unknown = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_map_device(self._dd._h, C.c_void_p(d_words), C.c_void_p(d_filtered), n_reads,
+                                                         int(base), C.c_void_p(d_cluster_id), C.c_void_p(d_keep),
+                                                         C.byref(unknown)))
+        return unknown.value
+
+    def leaves(self):
+        """dict(word u64[U] or u64[U, 2], count u32[U], first u64[U]) of the accumulated list, ascending"""
+        n = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_get_leaves(self._dd._h, None, None, None, 0, C.byref(n)))
+        u = n.value
+        out = dict(word=np.zeros((u, 2) if self.word_nt > 32 else u, np.uint64), count=np.zeros(u, np.uint32),
+                   first=np.zeros(u, np.uint64))
+        self._dd._check(self._lib.humid_accum_get_leaves(self._dd._h, _vp(out["word"]), _vp(out["count"]), _vp(out["first"]),
+                                                         u, C.byref(n)))
+        return out
+
+    def info(self):
+        """dict(word_nt, chunks, total, usable, unique, finished)"""
+        nt, fin = C.c_uint32(), C.c_uint32()
+        v = [C.c_uint64() for _ in range(4)]
+        self._dd._check(self._lib.humid_accum_info(self._dd._h, C.byref(nt), *[C.byref(x) for x in v], C.byref(fin)))
+        return dict(word_nt=nt.value, chunks=v[0].value, total=v[1].value, usable=v[2].value, unique=v[3].value,
+                    finished=bool(fin.value))
+
+    def clear(self):
+        self._dd._check(self._lib.humid_accum_clear(self._dd._h))
+
 
 class ClusterGraph(Context):
     """NLeaf graphs built by hand, as tests/test_cluster.cc:11-14 does with link()."""

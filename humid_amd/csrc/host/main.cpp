@@ -79,11 +79,13 @@ struct Args {
   bool paired = false;         // -P (not in the reference): strand-symmetric words -- R1/R2 exchanged is the same molecule
   bool duplex = false;         // -D (not in the reference; needs -P): every kept record carries the duplex consensus of its cluster
   unsigned duplex_strand_cap = 40;   // --duplex-strand-cap
+  bool chunked = false;        // --chunk-reads given (not in the reference): the device part runs as an accumulated run over chunks
+  unsigned long long chunk_reads = 0;   // --chunk-reads: records per chunk
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] [--chunk-reads N] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -150,7 +152,12 @@ void usage(const char *argv0) {
                "      the other file; each orientation makes a call of its own, as -C does, with a quality of at most\n"
                "      --duplex-strand-cap N (1..93, default 40); two calls of one base add their qualities, two calls of\n"
                "      different bases subtract them (N and ! when nothing is left).  --consensus-min-q applies.  Only the _dedup\n"
-               "      files change; a log line, and with -s duplex.dat; inputs held in memory (no CRLF files); not with -C\n",
+               "      files change; a log line, and with -s duplex.dat; inputs held in memory (no CRLF files); not with -C\n"
+               "  --chunk-reads N  the GPU sees the records N at a time (N >= 1): every chunk's words are counted and merged into one\n"
+               "      accumulated list, the list is clustered once, and every chunk is then given its results.  All outputs are\n"
+               "      those of the run without the flag; the device holds one chunk and the distinct words, not the whole read\n"
+               "      set.  Works with -n, -m, -e, -x, -s, -a, -q; one GPU; not with -g, -b, -w, --cells-*, --word-pattern, -P, -Q,\n"
+               "      -C, -D or -O.  The host still holds all words at once: its limit of 2^31 - 1 records stays\n",
                argv0);
 }
 
@@ -225,6 +232,14 @@ bool parse(int argc, char **argv, Args &a) {
       a.optical = true;
       a.optical_distance = (uint32_t)d;
     }
+    else if (t == "--chunk-reads") {
+      const char *v = need("--chunk-reads");
+      if (!v) return false;
+      char *end = nullptr;
+      a.chunk_reads = std::strtoull(v, &end, 10);
+      if (*v < '0' || *v > '9' || *end != 0) { std::fprintf(stderr, "humid: --chunk-reads takes a number of records, 1 or more\n"); return false; }
+      a.chunked = true;
+    }
     else if (t == "-P") a.paired = !a.paired;
     else if (t == "-D") a.duplex = !a.duplex;
     else if (t == "-Q") a.best = !a.best;
@@ -253,6 +268,17 @@ void end_message(std::ofstream &log, time_t start) {
   log.flush();
 }
 
+// histogram `which` of the context as (key, value) pairs; HUMID_OK or the library's code
+int fetch_hist(humid_ctx *ctx, uint32_t which, std::vector<std::pair<uint64_t, uint64_t>> &out) {
+  uint64_t n = 0;
+  int rc = humid_get_histogram(ctx, which, nullptr, nullptr, 0, &n);
+  std::vector<uint64_t> k(n ? n : 1), v(n ? n : 1);
+  if (rc == HUMID_OK && n) rc = humid_get_histogram(ctx, which, k.data(), v.data(), n, &n);
+  out.clear();
+  for (uint64_t i = 0; rc == HUMID_OK && i < n; i++) out.emplace_back(k[i], v[i]);
+  return rc;
+}
+
 void make_dirs(const std::string &path) {   // std::filesystem::create_directories
   std::string cur;
   for (size_t i = 0; i <= path.size(); i++) {
@@ -265,12 +291,10 @@ void make_dirs(const std::string &path) {   // std::filesystem::create_directori
 
 // 1 = written, 0 = the library failed (humid_last_error says why), -1 = the file could not be written
 int write_hist(humid_ctx *ctx, uint32_t which, const std::string &path) {
-  uint64_t n = 0;
-  if (humid_get_histogram(ctx, which, nullptr, nullptr, 0, &n) != HUMID_OK) return 0;
-  std::vector<uint64_t> k(n ? n : 1), v(n ? n : 1);
-  if (n && humid_get_histogram(ctx, which, k.data(), v.data(), n, &n) != HUMID_OK) return 0;
+  std::vector<std::pair<uint64_t, uint64_t>> h;
+  if (fetch_hist(ctx, which, h) != HUMID_OK) return 0;
   std::ofstream out(path, std::ios::out | std::ios::binary);
-  for (uint64_t i = 0; i < n; i++) out << k[i] << ' ' << v[i] << '\n';   // src/humid.cc:333-349
+  for (const auto &kv : h) out << kv.first << ' ' << kv.second << '\n';   // src/humid.cc:333-349
   out.close();
   return out.fail() ? -1 : 1;
 }
@@ -521,6 +545,22 @@ int main(int argc, char **argv) {
   // HUMID_FORCE_SHARDED=1: the rank orchestration also for -g 1 (one rank; exercises the transport)
   const bool sharded = a.gpus > 1 || getenv("HUMID_FORCE_SHARDED") != nullptr;
   const bool discover = a.cells_mode >= 0;                 // the whitelist comes from the data
+  if (a.chunked) {
+    // what an accumulated run does not do: one line, before anything is opened and before any GPU use
+    const char *why = nullptr;
+    if (a.chunk_reads == 0) why = "--chunk-reads takes a number of records, 1 or more";
+    else if (sharded) why = "--chunk-reads runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+    else if (a.keyed) why = "--chunk-reads does not work with -b";
+    else if (!a.whitelists.empty()) why = "--chunk-reads does not work with -w";
+    else if (discover || a.cells_ratio_given) why = "--chunk-reads does not work with --cells-top / --cells-expected / --cells-min-reads / --cells-merge-ratio";
+    else if (!a.word_pattern.empty()) why = "--chunk-reads does not work with --word-pattern";
+    else if (a.paired) why = "--chunk-reads does not work with -P";
+    else if (a.best) why = "--chunk-reads does not work with -Q (the post-run passes need a complete run)";
+    else if (a.consensus) why = "--chunk-reads does not work with -C (the post-run passes need a complete run)";
+    else if (a.duplex) why = "--chunk-reads does not work with -D";
+    else if (a.optical) why = "--chunk-reads does not work with -O (the post-run passes need a complete run)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
   const bool segmented = a.whitelists.size() > 1;          // one -w per segment of the barcode
   // what --word-pattern and several -w do not work with: one line each, before anything is opened
   {
@@ -697,7 +737,8 @@ int main(int argc, char **argv) {
         if (getenv("HUMID_NO_PINNED") == nullptr && !a.keyed)   // (-b: keys and shorter words, from ordinary memory)
           pin_thread = std::thread([&] { pinned = (uint8_t *)humid_host_alloc(pin_bytes); t_pin = since(); });
         if (getenv("HUMID_NO_SLAB") == nullptr)
-          humid_ctx_reserve(ctx, (uint64_t)n, (uint32_t)a.word_length);   // one slab + the code object loaded
+          humid_ctx_reserve(ctx, a.chunked ? std::min<uint64_t>((uint64_t)n, a.chunk_reads) : (uint64_t)n,
+                            (uint32_t)a.word_length);   // one slab (--chunk-reads: for one chunk) + the code object loaded
         t_slab = since();
         if (pin_thread.joinable()) pin_thread.join();
       }
@@ -783,7 +824,7 @@ int main(int argc, char **argv) {
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
   // (-Q: the selection compares the packed words, so the host packs them)
-  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && !a.paired && getenv("HUMID_DEVICE_PACK") != nullptr;
+  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && !a.paired && !a.chunked && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
   std::vector<uint32_t> scores;                    // -Q: one per record
   std::vector<uint32_t> pos_tile, pos_x, pos_y;    // -O: the position of every record (position.hpp)
@@ -1025,6 +1066,17 @@ int main(int argc, char **argv) {
     if (rc == HUMID_OK && getenv("HUMID_TIMING"))
       std::fprintf(stderr, "[humid]   %u ranks, bulk data by %s: set-up %.1f ms, ranks %.1f ms\n", a.gpus,
                    shr.comm.c_str(), shr.ms_init, shr.ms_run);
+  } else if (a.chunked) {
+    // an accumulated run (include/humid_hip.h): every chunk added with the index of its first record as its base, the
+    // list clustered, the histograms fetched at once (the first map ends the record finish published), every chunk mapped
+    rc = humid_accum_begin(ctx, (uint32_t)a.word_length);
+    for (uint64_t b = 0; rc == HUMID_OK && b < N; b += a.chunk_reads)
+      rc = humid_accum_add(ctx, run_words + b * wpr, run_filt + b, std::min<uint64_t>(a.chunk_reads, N - b), b);
+    if (rc == HUMID_OK) rc = humid_accum_finish(ctx, (uint32_t)a.distance, method, &sum);
+    for (uint32_t which = 0; rc == HUMID_OK && a.stats && which < 3; which++) rc = fetch_hist(ctx, which, shr.hist[which]);
+    for (uint64_t b = 0; rc == HUMID_OK && b < N; b += a.chunk_reads)
+      rc = humid_accum_map(ctx, run_words + b * wpr, run_filt + b, std::min<uint64_t>(a.chunk_reads, N - b), b, cluster_id + b, keep + b,
+                           nullptr);
   } else if (a.posterior)
     rc = humid_dedup_run_keyed_posterior(ctx, run_words, keys.data(), bcq.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
                                          method, (uint32_t)a.min_odds, cluster_id, keep, &sum);
@@ -1398,8 +1450,8 @@ int main(int argc, char **argv) {
     const char *names[3] = {"/counts.dat", "/neigh.dat", "/clusters.dat"};
     int ok = 1;
     for (uint32_t which = 0; which < 3 && ok == 1; which++) {
-      if (!sharded) { ok = write_hist(ctx, which, a.dir_name + names[which]); continue; }
-      std::ofstream out(a.dir_name + names[which], std::ios::out | std::ios::binary);   // gathered by the ranks
+      if (!sharded && !a.chunked) { ok = write_hist(ctx, which, a.dir_name + names[which]); continue; }
+      std::ofstream out(a.dir_name + names[which], std::ios::out | std::ios::binary);   // gathered by the ranks, or fetched after the finish of an accumulated run
       for (auto &kv : shr.hist[which]) out << kv.first << ' ' << kv.second << '\n';
       out.close();
       if (out.fail()) ok = -1;

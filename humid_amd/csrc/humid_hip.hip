@@ -236,6 +236,11 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->force_segments = (u32)value;
     return HUMID_OK;
   }
+  if (strcmp(key, "accum_tile") == 0) {
+    if (value < 64 || value > ACC_TILE || (value & (value - 1))) return fail(c, HUMID_E_INVALID, "accum_tile must be a power of two, 64 .. %u", ACC_TILE);
+    c->ac_tile = (u32)value;
+    return HUMID_OK;
+  }
   return fail(c, HUMID_E_INVALID, "unknown option '%s'", key);
 }
 
@@ -1395,6 +1400,170 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
   if (n_clusters) *n_clusters = (u32)C;
   TRY(export_clusters(c, U, C, cl_size, cl_max_count, cl_max_leaf));
   return state_publish(c, CtxState::HAND_GRAPH);
+}
+
+// ---- accumulated runs: a read set fed in chunks (pipeline.hip.h, kernels_accum.hip.h) -------------------------
+// the record of a finish points at the accumulator's arrays: it ends with them
+// (free_memory false: humid_accum_begin keeps the blocks for the next accumulator, humid_accum_clear returns them)
+static void accum_release(humid_ctx *c, bool free_memory) {
+  if (state_has_leaves(c) && c->gU && c->g_word == c->ac_word[c->ac_cur].p) state_reset(c);
+  if (free_memory) {
+    for (int k = 0; k < 2; k++) { c->ac_word[k].release(); c->ac_cnt[k].release(); c->ac_first[k].release(); }
+    c->ac_cid.release(); c->ac_ismax.release(); c->ac_lcid.release(); c->ac_lismax.release();
+    c->ac_split.release(); c->ac_tcnt.release(); c->ac_toff.release(); c->ac_flag.release();
+  }
+  c->ac_on = c->ac_finished = false;
+  c->ac_nt = c->ac_cur = 0;
+  c->ac_U = c->ac_chunks = c->ac_total = c->ac_usable = 0;
+}
+
+int humid_accum_begin(humid_ctx *c, uint32_t word_nt) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  TRY(check_run_args(c, 0, word_nt, 0, 64));
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  accum_release(c, false);
+  c->ac_on = true;
+  c->ac_nt = word_nt;
+  return HUMID_OK;
+}
+
+int humid_accum_clear(humid_ctx *c) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  accum_release(c, true);
+  return HUMID_OK;
+}
+
+// what add and map refuse before anything moves
+static int accum_chunk_args(humid_ctx *c, const void *words, const void *filtered, uint64_t n_reads, bool device) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "a chunk of %llu reads exceeds 2^31-1", (ull)n_reads);
+  if (n_reads && (!words || !filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (device && c->ac_nt > 32 && ((uintptr_t)words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
+  return HUMID_OK;
+}
+
+int humid_accum_add_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads, uint64_t base_index) {
+  TRY(accum_chunk_args(c, d_words, d_filtered, n_reads, true));
+  state_reset(c);
+  HIPCHK(hipSetDevice(c->device));
+  TRY(with_word_type(c->ac_nt, [&](auto *w) {
+    TRY(accum_count_chunk(c, (decltype(w))d_words, d_filtered, n_reads));
+    if (c->U) TRY(accum_merge<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, base_index));
+    return (int)HUMID_OK;
+  }));
+  HIPCHK(hipStreamSynchronize(c->stream));                     // (the caller's arrays are free again)
+  c->ac_chunks++;
+  c->ac_total += n_reads;
+  c->ac_usable += c->usable;
+  c->ac_finished = false;
+  return state_publish_count(c, false);
+}
+
+int humid_accum_add(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index) {
+  TRY(accum_chunk_args(c, words, filtered, n_reads, false));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads, wbytes = c->ac_nt > 32 ? 16 : 8;
+  ENSURE(c->in_words, n * wbytes + 16);
+  ENSURE(c->in_filt, n + 8);
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, c->stream));
+  }
+  return humid_accum_add_device(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, base_index);
+}
+
+int humid_accum_finish(humid_ctx *c, uint32_t distance, uint32_t method, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+  TRY(check_run_args(c, c->ac_U, c->ac_nt, method, 64));
+  state_reset(c);
+  HIPCHK(hipSetDevice(c->device));
+  humid_summary s;
+  memset(&s, 0, sizeof s);
+  s.total = c->ac_total;
+  s.usable = c->ac_usable;
+  s.unique = c->ac_U;
+  c->ac_finished = false;
+  c->word_nt = c->ac_nt; c->distance = distance; c->method = method;
+  c->gU = 0; c->E = c->M = c->C = 0;
+  TRY(with_word_type(c->ac_nt, [&](auto *w) {
+    return accum_finish<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, distance, method, s);
+  }));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->ac_finished = true;
+  if (summary) *summary = s;
+  return state_publish(c, CtxState::STAGE_GRAPH);
+}
+
+int humid_accum_map_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads, uint64_t base_index,
+                           uint32_t *d_cluster_id, uint8_t *d_keep, uint64_t *n_unknown) {
+  TRY(accum_chunk_args(c, d_words, d_filtered, n_reads, true));
+  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
+  if (n_reads && (!d_cluster_id || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  state_reset(c);                                              // (the record finish published ends here: the chunk is counted in the context's buffers)
+  HIPCHK(hipSetDevice(c->device));
+  u64 unknown = 0;
+  TRY(with_word_type(c->ac_nt, [&](auto *w) {
+    TRY(accum_count_chunk(c, (decltype(w))d_words, d_filtered, n_reads));
+    return accum_map<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, base_index, d_cluster_id, d_keep, &unknown);
+  }));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (n_unknown) *n_unknown = unknown;
+  return state_publish_count(c, false);
+}
+
+int humid_accum_map(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index,
+                    uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown) {
+  TRY(accum_chunk_args(c, words, filtered, n_reads, false));
+  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
+  if (n_reads && (!cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads, wbytes = c->ac_nt > 32 ? 16 : 8;
+  ENSURE(c->in_words, n * wbytes + 16);
+  ENSURE(c->in_filt, n + 8);
+  ENSURE(c->out_cid, n * 4 + 8);
+  ENSURE(c->out_keep, n + 8);
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, c->stream));
+  }
+  TRY(humid_accum_map_device(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, base_index, c->out_cid.as<u32>(),
+                             c->out_keep.as<u8>(), n_unknown));
+  D2H(cluster_id, c->out_cid.p, n * 4);
+  D2H(keep, c->out_keep.p, n);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_accum_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint64_t *first_index, uint64_t cap, uint64_t *n_out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+  HIPCHK(hipSetDevice(c->device));
+  if (n_out) *n_out = c->ac_U;
+  const size_t n = (size_t)std::min<u64>(cap, c->ac_U), wbytes = c->ac_nt > 32 ? 16 : 8;
+  const u32 cur = c->ac_cur;
+  D2H(word, c->ac_word[cur].p, n * wbytes);
+  D2H(count, c->ac_cnt[cur].p, n * 4);
+  D2H(first_index, c->ac_first[cur].p, n * 8);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_accum_info(humid_ctx *c, uint32_t *word_nt, uint64_t *chunks, uint64_t *total, uint64_t *usable, uint64_t *unique,
+                     uint32_t *finished) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+  if (word_nt) *word_nt = c->ac_nt;
+  if (chunks) *chunks = c->ac_chunks;
+  if (total) *total = c->ac_total;
+  if (usable) *usable = c->ac_usable;
+  if (unique) *unique = c->ac_U;
+  if (finished) *finished = c->ac_finished ? 1u : 0u;
+  return HUMID_OK;
 }
 
 }  // extern "C"

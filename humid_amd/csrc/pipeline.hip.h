@@ -36,6 +36,7 @@
 #include "kernels_segments.hip.h"
 #include "kernels_cells.hip.h"
 #include "kernels_paired.hip.h"
+#include "kernels_accum.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -285,6 +286,18 @@ struct humid_ctx {
   DBuf pd_words, pd_strand, pd_mir, pd_top, pd_bottom, pd_ctr;   // canonical words, strands, mirrored leaves, tallies u32[C + 1], ull[PD_CTRS]
   u64 pd_N = 0;              // state.paired: pd_strand holds the strands of the run's pd_N reads
   humid_strand_summary pd_sum = {};
+  // accumulated runs (humid_accum_*, kernels_accum.hip.h): a read set fed in chunks.  The list -- distinct words ascending,
+  // reads per word, smallest global read index per word -- lives in TWO buffer sets of its own (never the slab): a merge
+  // reads set ac_cur and writes the other, and the sets swap only when it succeeded.  Kept until humid_accum_begin,
+  // humid_accum_clear or the end of the context; no run and no other accessor touches it.
+  bool ac_on = false;        // humid_accum_begin was called
+  bool ac_finished = false;  // humid_accum_finish succeeded after the last add: ac_cid / ac_ismax are those of the list
+  u32 ac_nt = 0, ac_cur = 0; // word length; the set that holds the list
+  u32 ac_tile = ACC_TILE;    // option "accum_tile": merge positions per tile
+  u64 ac_U = 0, ac_chunks = 0, ac_total = 0, ac_usable = 0;   // words in the list; chunks, reads and usable reads added
+  DBuf ac_word[2], ac_cnt[2], ac_first[2];                    // WT[U], u32[U], u64[U]
+  DBuf ac_split, ac_tcnt, ac_toff, ac_flag;                   // the merge: tile splits, new words per tile, their scan; overflow flag + unknown reads
+  DBuf ac_cid, ac_ismax, ac_lcid, ac_lismax;                  // finish's copy of cid / ismax per word; a mapped chunk's per-leaf results
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -2574,6 +2587,122 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   }
   if (sum) *sum = s;
   return state_publish(c, CtxState::RUN);
+}
+
+// ---- accumulated runs (humid_accum_*): a read set fed in chunks (kernels_accum.hip.h) --------------------------
+// add = the count stage over the chunk + accum_merge; finish = the graph stage over the accumulated list + a copy of
+// its cid / ismax; map = the count stage over the chunk + accum_lookup + the unchanged stage_map.  Per-read work stays
+// in the count and un-permute kernels; what is new is proportional to unique words.
+// the count stage over one chunk, leaving the context as humid_stage_count does
+template <class WT>
+static int accum_count_chunk(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_reads) {
+  humid_summary s;
+  memset(&s, 0, sizeof s);
+  c->last_unperm_tiled = false;
+  c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
+  c->word_nt = c->ac_nt;
+  c->gU = 0;
+  if (n_reads == 0) return HUMID_OK;
+  if constexpr (sizeof(WT) == 16) return stage_count_wide(c, d_words, d_filt, (u32)n_reads, c->ac_nt, s);
+  else return stage_count(c, d_words, d_filt, (u32)n_reads, c->ac_nt, 0ull, ~0ull, 0, s);
+}
+
+// The list of set ac_cur merged with the chunk just counted (s_word / s_cnt / s_first of c->U words, first read
+// = base + s_first) into the other set; the sets swap at the end.  ONE host wait: the new number of words sizes
+// the buffers the fill pass writes (the same wait brings the overflow flag).  Every failure leaves ac_cur and
+// ac_U as they were.
+template <class WT>
+static int accum_merge(humid_ctx *c, u64 base) {
+  hipStream_t st = c->stream;
+  const u32 nA = (u32)c->ac_U, nB = (u32)c->U, T = c->ac_tile;
+  const u64 P = (u64)nA + nB;                                  // (both below 2^31)
+  const u32 n_tiles = (u32)((P + T - 1) / T);
+  const u32 cur = c->ac_cur, nxt = cur ^ 1u;
+  PASS_ENSURE(c->ac_split, ((size_t)n_tiles + 1) * 4);
+  PASS_ENSURE(c->ac_tcnt, ((size_t)n_tiles + 1) * 4);
+  PASS_ENSURE(c->ac_toff, ((size_t)n_tiles + 1) * 4);
+  PASS_ENSURE(c->ac_flag, 16);
+  HIPCHK(hipMemsetAsync(c->ac_flag.p, 0, 16, st));
+  HIPCHK(hipMemsetAsync(c->ac_tcnt.as<u32>() + n_tiles, 0, 4, st));      // (the scan's sentinel)
+  const WT *a_word = c->ac_word[cur].as<WT>(), *b_word = c->s_word.as<WT>();
+  const u32 *a_cnt = c->ac_cnt[cur].as<u32>(), *b_cnt = c->s_cnt.as<u32>(), *b_first = c->s_first.as<u32>();
+  const u64 *a_first = c->ac_first[cur].as<u64>();
+  const size_t lds = ((size_t)T + 2) * sizeof(WT);
+  hipLaunchKernelGGL((k_accum_partition<WT>), dim3(blocks_for((u64)n_tiles + 1)), dim3(256), 0, st, a_word, nA, b_word, nB, T, n_tiles,
+                     c->ac_split.as<u32>());
+  hipLaunchKernelGGL((k_accum_tile<WT, 0>), dim3(n_tiles), dim3(ACC_THREADS), lds, st, a_word, a_cnt, a_first, nA, b_word, b_cnt, b_first,
+                     nB, base, T, (const u32 *)c->ac_split.as<u32>(), c->ac_tcnt.as<u32>(), (const u32 *)nullptr, (WT *)nullptr,
+                     (u32 *)nullptr, (u64 *)nullptr, c->ac_flag.as<u32>());
+  TRY(exscan_u32(c, c->ac_tcnt.as<u32>(), c->ac_toff.as<u32>(), (u64)n_tiles + 1));
+  HIPCHK(hipGetLastError());
+  TRY(read_counters(c, c->ac_toff.as<u32>() + n_tiles, c->ac_flag.as<u32>()));
+  const u64 nU = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+  if (c->h_ctr[CTR_N - 2] & 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "the reads of one word exceed 2^32-1");
+  if (nU > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu accumulated unique words exceed 2^31-1", (ull)nU);
+  // (a set that must grow doubles: an allocation and the release of the old block cost more than a merge)
+  auto room = [](const DBuf &b, size_t bytes) { return bytes <= b.cap ? bytes : std::max(bytes, 2 * b.cap); };
+  PASS_ENSURE(c->ac_word[nxt], room(c->ac_word[nxt], (size_t)nU * sizeof(WT) + 16));
+  PASS_ENSURE(c->ac_cnt[nxt], room(c->ac_cnt[nxt], (size_t)nU * 4 + 16));
+  PASS_ENSURE(c->ac_first[nxt], room(c->ac_first[nxt], (size_t)nU * 8 + 16));
+  hipLaunchKernelGGL((k_accum_tile<WT, 1>), dim3(n_tiles), dim3(ACC_THREADS), lds, st, a_word, a_cnt, a_first, nA, b_word, b_cnt, b_first,
+                     nB, base, T, (const u32 *)c->ac_split.as<u32>(), (u32 *)nullptr, (const u32 *)c->ac_toff.as<u32>(),
+                     c->ac_word[nxt].as<WT>(), c->ac_cnt[nxt].as<u32>(), c->ac_first[nxt].as<u64>(), (u32 *)nullptr);
+  HIPCHK(hipGetLastError());
+  c->ac_cur = nxt;
+  c->ac_U = nU;
+  return HUMID_OK;
+}
+
+// The graph stage over the accumulated list (not the context's own unique words: stage_graph's `own` is false), the
+// cluster count, and the copy of cid / ismax a later map reads -- map counts its chunk in the context's buffers.
+template <class WT>
+static int accum_finish(humid_ctx *c, u32 distance, u32 method, humid_summary &s) {
+  const u32 U = (u32)c->ac_U, cur = c->ac_cur;
+  if (U == 0) return HUMID_OK;
+  const WT *g_word = c->ac_word[cur].as<WT>();
+  const u32 *g_cnt = c->ac_cnt[cur].as<u32>();
+  u32 nps = 0;
+  if (c->edit && distance >= 2) {
+    u64 E = 0;
+    TRY(edit_edges<WT>(c, g_word, U, c->ac_nt, distance, &E));
+    static const u64 no_edges = 0;
+    TRY(stage_graph<WT>(c, g_word, g_cnt, U, c->ac_nt, distance, method, s, nps, E ? c->e_edges.as<u64>() : &no_edges, E));
+  } else
+    TRY(stage_graph<WT>(c, g_word, g_cnt, U, c->ac_nt, distance, method, s, nps));
+  TRY(n_clusters_from_scan(c, U, &c->C));
+  s.clusters = c->C;
+  PASS_ENSURE(c->ac_cid, (size_t)U * 4 + 16);
+  PASS_ENSURE(c->ac_ismax, (size_t)U + 16);
+  HIPCHK(hipMemcpyAsync(c->ac_cid.p, c->cid.p, (size_t)U * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->ac_ismax.p, c->ismax.p, (size_t)U, hipMemcpyDeviceToDevice, c->stream));
+  return HUMID_OK;
+}
+
+// Per-read results of the chunk just counted: its leaves looked up in the accumulated list, then stage_map.
+// *h_unknown: usable reads whose word the accumulator never saw (they get 0 / 0).
+template <class WT>
+static int accum_map(humid_ctx *c, u64 base, u32 *d_cid, u8 *d_keep, u64 *h_unknown) {
+  hipStream_t st = c->stream;
+  const u32 N = (u32)c->N, nB = (u32)c->U, nA = (u32)c->ac_U, cur = c->ac_cur;
+  *h_unknown = 0;
+  if (N == 0) return HUMID_OK;
+  if (nB == 0) {                                               // everything filtered
+    HIPCHK(hipMemsetAsync(d_cid, 0, (size_t)N * 4, st));
+    HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)N, st));
+    return HUMID_OK;
+  }
+  PASS_ENSURE(c->ac_lcid, (size_t)nB * 4 + 16);
+  PASS_ENSURE(c->ac_lismax, (size_t)nB + 16);
+  PASS_ENSURE(c->ac_flag, 16);
+  HIPCHK(hipMemsetAsync(c->ac_flag.p, 0, 16, st));
+  ull *unknown = c->ac_flag.as<ull>() + 1;
+  hipLaunchKernelGGL((k_accum_lookup<WT>), dim3(grid_stride_blocks(nB)), dim3(256), 0, st, c->ac_word[cur].as<WT>(),
+                     c->ac_first[cur].as<u64>(), c->ac_cid.as<u32>(), c->ac_ismax.as<u8>(), nA, c->s_word.as<WT>(), c->s_cnt.as<u32>(),
+                     c->s_first.as<u32>(), nB, base, c->ac_lcid.as<u32>(), c->ac_lismax.as<u8>(), unknown);
+  HIPCHK(hipGetLastError());
+  TRY(stage_map(c, c->ac_lcid.as<u32>(), c->ac_lismax.as<u8>(), N, d_cid, d_keep));
+  HIPCHK(hipMemcpyAsync(h_unknown, unknown, 8, hipMemcpyDeviceToHost, st));
+  return HUMID_OK;
 }
 
 // ---- grouped runs (humid_dedup_run_grouped*): one pass over many groups ------------------------------------

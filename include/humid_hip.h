@@ -125,7 +125,10 @@ const char *humid_last_error(const humid_ctx *ctx);   /* ctx may be NULL */
  * "optical_walk": how many following reads of its window (same cluster and tile, x no more than the distance ahead)
  * a sorted position of humid_optical_duplicates* is compared with by its own lane (default 64); the rest of a longer
  * window is compared by the 64 lanes of the position's wave side by side.  0 = no bound (quadratic per lane on a
- * cluster of 10^5 reads on one spot).  Results do not depend on it. */
+ * cluster of 10^5 reads on one spot).  Results do not depend on it.
+ * "accum_tile": merge positions per workgroup of humid_accum_add*'s merge, a power of two from 64 to 2048 (default
+ * 2048: the staged tile takes 16 KB of LDS for one-word words, 32 KB for two-word words).  Results do not depend on it;
+ * small values make small inputs cross many tile boundaries (tests). */
 int  humid_ctx_set_option(humid_ctx *ctx, const char *key, int64_t value);
 /* Optional: one slab of device memory for a run over about n_reads reads, so that the first run does
  * not pay ~35 separate allocations (the `humid` host calls it while pass 1 still parses).  Never
@@ -872,6 +875,63 @@ int humid_dedup_run_paired_device(humid_ctx *ctx, const uint64_t *d_words, const
                                   uint8_t *d_keep, humid_summary *summary);
 int humid_get_strands(humid_ctx *ctx, uint8_t *strand, uint64_t cap, uint32_t *top, uint32_t *bottom,
                       humid_strand_summary *summary);
+
+/* ---- accumulated runs: one read set fed in chunks ---------------------------------------------------
+ * For a read set that does not fit one call: more than 2^31 - 1 reads, more than the device holds at once, or reads
+ * that arrive in pieces (a second lane, a top-up run).  An accumulator belongs to a context and has a fixed word_nt
+ * (1 .. 64, word layout as everywhere).  Chunks are added; each carries base_index, the GLOBAL index of its first
+ * read: read i of the chunk has global index base_index + i.  The index ranges of different chunks must be disjoint;
+ * this is not checked (with overlapping ranges keep is unspecified, nothing faults).  The accumulator holds, per
+ * distinct usable word, ascending (Trie::walk() order): word, count (summed over all chunks), first_index (u64: the
+ * smallest global index of a usable read with that word).  count is a sum and first_index a minimum, so nothing below
+ * depends on the order in which the chunks were added.
+ * Results.  Let R be all added reads sorted by global index.
+ *   humid_accum_finish  the summary (total, usable, unique, clusters, edges, nonsingle; times are 0) of humid_dedup_run
+ *                       over R, and that run's leaves, adjacency, clusters and histograms: the context is left as
+ *                       humid_stage_graph leaves it, so humid_get_leaves (without first_read: use
+ *                       humid_accum_get_leaves), humid_get_adjacency, humid_get_clusters and humid_get_histogram answer
+ *                       for the accumulated set, and everything that needs a complete single-GPU run returns
+ *                       HUMID_E_STATE.  Option "edit_distance" applies here as in humid_dedup_run.
+ *   humid_accum_map     per read of the chunk given: cluster_id = the id that run gives to its word; keep = 1 iff the
+ *                       read is usable, its word is its cluster's maxLeaf and its global index equals that leaf's
+ *                       first_index.  Filtered reads get 0 / 0.  A usable read whose word the accumulator never saw
+ *                       gets 0 / 0 and is counted in *n_unknown (may be NULL); the call still returns HUMID_OK.  The
+ *                       chunk need not be one that was added.  The first map after a finish ends the record finish
+ *                       published (the chunk is counted in the context's buffers; map reads the accumulator's own
+ *                       copy of the per-leaf results).
+ * States.  add, finish, map, get_leaves and info return HUMID_E_STATE before humid_accum_begin; map also unless
+ * finish succeeded after the last add.  An add after finish is legal: it re-opens the accumulator, and finish must be
+ * called again.  get_leaves and info work in every state after begin.  A chunk of 0 reads and a chunk of filtered
+ * reads only are legal.  add leaves the context's record as humid_stage_count does.  The accumulator lives in device
+ * memory of its own and survives every other call on the context until humid_accum_begin (which empties any earlier
+ * accumulator and keeps its memory for the new one), humid_accum_clear (which returns the memory) or humid_ctx_destroy.
+ * Limits.  A chunk holds at most 2^31 - 1 reads, the accumulated list at most 2^31 - 1 words, a count at most
+ * 2^32 - 1: HUMID_E_OVERFLOW otherwise.  The total number of reads is a u64 with no limit of its own.  word_nt == 0
+ * returns HUMID_E_INVALID, word_nt > 64 HUMID_E_UNSUPPORTED, method > 1 HUMID_E_INVALID.  Any failing call leaves the
+ * accumulator as it was and the context usable: the merge writes into the second of two buffer sets, and the sets
+ * swap only on success.
+ * On the device (kernels_accum.hip.h): add = the count stage over the chunk + a merge-path merge of its unique list
+ * into the accumulated one (equal words combined; one host wait, for the new number of words); finish = the graph stage
+ * over the accumulated list; map = the count stage over the chunk + one binary search per unique word of the chunk +
+ * the un-permute of humid_dedup_run.  Every add rewrites the accumulated list.
+ * Grouped, keyed, corrected, paired and multi-GPU forms, and the post-run passes, are not available for accumulated runs.
+ * humid_accum_get_leaves: the first min(cap, unique) entries; *n_out = unique; any pointer may be NULL.
+ * humid_accum_info: word_nt, chunks added, reads and usable reads added, unique words, finished (0 / 1).
+ *   *_device: DEVICE pointers for the per-read arrays; n_unknown stays a host pointer. */
+int humid_accum_begin(humid_ctx *ctx, uint32_t word_nt);
+int humid_accum_add(humid_ctx *ctx, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index);
+int humid_accum_add_device(humid_ctx *ctx, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                           uint64_t base_index);
+int humid_accum_finish(humid_ctx *ctx, uint32_t distance, uint32_t method, humid_summary *summary);
+int humid_accum_map(humid_ctx *ctx, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index,
+                    uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown);
+int humid_accum_map_device(humid_ctx *ctx, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                           uint64_t base_index, uint32_t *d_cluster_id, uint8_t *d_keep, uint64_t *n_unknown);
+int humid_accum_get_leaves(humid_ctx *ctx, uint64_t *word, uint32_t *count, uint64_t *first_index, uint64_t cap,
+                           uint64_t *n_out);
+int humid_accum_info(humid_ctx *ctx, uint32_t *word_nt, uint64_t *chunks, uint64_t *total, uint64_t *usable,
+                     uint64_t *unique, uint32_t *finished);
+int humid_accum_clear(humid_ctx *ctx);
 
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
