@@ -817,6 +817,12 @@ class Dedup(Context):
             out["key"] = self.group_keys()[out["group"]] if u else np.zeros(0, np.uint64)
         return out
 
+    def graph_split_info(self):
+        """dict(pairs_direct, pairs_graph, full_graph_built) of the last run (humid_graph_split_info)"""
+        a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self._lib.humid_graph_split_info(self._h, C.byref(a), C.byref(b), C.byref(f)))
+        return dict(pairs_direct=a.value, pairs_graph=b.value, full_graph_built=f.value)
+
     def adjacency(self):
         u = int(self.summary["unique"])
         e2 = 2 * int(self.summary["edges"])

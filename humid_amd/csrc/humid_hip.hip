@@ -213,6 +213,10 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->fused_search = value != 0;
     return HUMID_OK;
   }
+  if (strcmp(key, "pair_split") == 0) {
+    c->pair_split = value != 0;
+    return HUMID_OK;
+  }
   if (strcmp(key, "padded_partition") == 0) {
     c->pt_padded = value != 0;
     return HUMID_OK;
@@ -472,6 +476,16 @@ static void gkey_split(const humid_ctx *c, const std::vector<u64> &iw, size_t U,
     HIPCHK(hipSetDevice(c->device));                                                          \
     TRY(expand_compact(c));                                                                   \
   } while (0)
+
+int humid_graph_split_info(humid_ctx *c, uint64_t *pairs_direct, uint64_t *pairs_graph, uint32_t *full_graph_built) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!state_has_leaves(c)) return fail(c, HUMID_E_STATE, "no completed dedup run / graph stage in this context");
+  const bool split = c->cg_valid && c->cg_split;
+  if (pairs_direct) *pairs_direct = split ? c->cg_iso : 0;
+  if (pairs_graph) *pairs_graph = split ? c->cg_R : c->E;
+  if (full_graph_built) *full_graph_built = (!split || c->cg_full) ? 1u : 0u;
+  return HUMID_OK;
+}
 
 int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *first_read,
                      uint32_t *degree, uint32_t *cluster_id, uint8_t *is_max_leaf) {

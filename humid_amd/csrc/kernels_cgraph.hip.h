@@ -64,6 +64,17 @@ __device__ __forceinline__ u32 br_rank(const BitRank &br, u32 u) {
   return r;
 }
 
+// an end of a pair marked in `bits`.  MULTI: the bit was set already, so the leaf has at least two pairs (no pair is
+// found twice: the first-combination rule) and is marked in `multi` too.  A template argument, not a null pointer: with
+// both forms in one kernel the compiler makes every atomic a returning one, and the search that wants no `multi` pays
+// for it (4 us per search kernel of the metric pass)
+template <bool MULTI>
+__device__ __forceinline__ void mark_end(u32 *bits, u32 *multi, u32 u) {
+  const u32 m = 1u << (u & 31);
+  if constexpr (MULTI) { if (atomicOr(&bits[u >> 5], m) & m) atomicOr(&multi[u >> 5], m); }
+  else atomicOr(&bits[u >> 5], m);
+}
+
 // the same as the input of a scan (prims.hip.h): item b = set bits of block b, item n_blk = 0 -- the rank
 // blocks come out of ONE launch, without the array of counts in between
 struct BitsBlockIn {
@@ -171,10 +182,10 @@ __device__ __forceinline__ void pa_walk(const ACC &word, WT wi, WT w1, u32 i, u3
 // found[q] pairs, the first at first_off[q].  Room for the workgroup's pairs comes from ONE atomic on the cursor of
 // region blockIdx.x % ER_REGIONS; a region that is full keeps counting and sets *overflow.  A single pair is written
 // from first_off, several walk again.  lds: NW + 1 words.
-template <u32 NP, u32 NW, class WT, class ACC, class IDX>
+template <u32 NP, u32 NW, bool MULTI, class WT, class ACC, class IDX>
 __device__ __forceinline__ void pa_emit(const ACC &word, const IDX &idx, u32 i0, u32 stride, u32 n, const u32 (&found)[NP],
-                                        const u32 (&first_off)[NP], const PairRule<WT> &r, const EdgeRegs &er, u32 *bits, u32 *overflow,
-                                        u32 *lds) {
+                                        const u32 (&first_off)[NP], const PairRule<WT> &r, const EdgeRegs &er, u32 *bits, u32 *multi,
+                                        u32 *overflow, u32 *lds) {
   u32 total_found = 0;
 #pragma unroll
   for (u32 q = 0; q < NP; q++) total_found += found[q];
@@ -203,9 +214,22 @@ __device__ __forceinline__ void pa_emit(const ACC &word, const IDX &idx, u32 i0,
       if (at >= er.cap_r) return;
       const u32 rj = idx(j);
       out[at++] = ri < rj ? (((u64)ri << 32) | rj) : (((u64)rj << 32) | ri);
-      atomicOr(&bits[rj >> 5], 1u << (rj & 31));
+      mark_end<MULTI>(bits, multi, rj);
     };
-    atomicOr(&bits[ri >> 5], 1u << (ri & 31));
+    if (MULTI && found[q] == 1) {
+      // both ends' old words requested before either is looked at
+      const u32 rj = idx(i + first_off[q]);
+      if (at < er.cap_r) {
+        out[at++] = ri < rj ? (((u64)ri << 32) | rj) : (((u64)rj << 32) | ri);
+        const u32 mi = 1u << (ri & 31), mj = 1u << (rj & 31);
+        const u32 oi = atomicOr(&bits[ri >> 5], mi), oj = atomicOr(&bits[rj >> 5], mj);
+        if (oi & mi) atomicOr(&multi[ri >> 5], mi);
+        if (oj & mj) atomicOr(&multi[rj >> 5], mj);
+      } else atomicOr(&bits[ri >> 5], 1u << (ri & 31));    // (the region is full: this attempt is thrown away)
+      continue;
+    }
+    mark_end<MULTI>(bits, multi, ri);
+    if (MULTI && found[q] > 1) atomicOr(&multi[ri >> 5], 1u << (ri & 31));     // (marked once for all its pairs)
     if (found[q] == 1) { emit(i + first_off[q]); continue; }
     const WT wi = word(i);
     const u32 jend = pa_jend(i, n, r.walk_max);
@@ -217,10 +241,10 @@ __device__ __forceinline__ void pa_emit(const ACC &word, const IDX &idx, u32 i0,
   }
 }
 
-template <bool PASS0, class WT>
+template <bool PASS0, class WT, bool MULTI = false>
 __global__ void __launch_bounds__(256)
-k_pairs_append(const WT *__restrict__ W, const u32 *__restrict__ V, u32 n, PairRule<WT> rule, EdgeRegs er, u32 *bits, ull *big, u32 *overflow,
-               const u32 *__restrict__ n_valid = nullptr) {
+k_pairs_append(const WT *__restrict__ W, const u32 *__restrict__ V, u32 n, PairRule<WT> rule, EdgeRegs er, u32 *bits, u32 *multi, ull *big,
+               u32 *overflow, const u32 *__restrict__ n_valid = nullptr) {
   HUMID_GUARD_LAST_VGPR();
   __shared__ u32 lds[5];
   PH_DECL;
@@ -247,8 +271,8 @@ k_pairs_append(const WT *__restrict__ W, const u32 *__restrict__ V, u32 n, PairR
     if (i < n) pa_walk(word, wi[q], w1[q], i, n, rule, big, found[q], first_off[q]);
   }
   PH(1);
-  if (PASS0) pa_emit<PA_PPT, 4>(word, IdxSelf{}, i0, 256u, n, found, first_off, rule, er, bits, overflow, lds);
-  else pa_emit<PA_PPT, 4>(word, IdxGlobal{V}, i0, 256u, n, found, first_off, rule, er, bits, overflow, lds);
+  if (PASS0) pa_emit<PA_PPT, 4, MULTI>(word, IdxSelf{}, i0, 256u, n, found, first_off, rule, er, bits, multi, overflow, lds);
+  else pa_emit<PA_PPT, 4, MULTI>(word, IdxGlobal{V}, i0, 256u, n, found, first_off, rule, er, bits, multi, overflow, lds);
   PH(2); PH(3); PH(4);
   PH_END(5, 4, (blockIdx.x & 15u) == 5u);              // 1 walks | 2 block scan, region cursor, writes | (3, 4 -)
 }
@@ -268,11 +292,13 @@ struct IdxGrouped {
   const u32 *v_in;
   __device__ __forceinline__ u32 operator()(u32 j) const { return v_in[inv[j]]; }
 };
-struct PairSearchDev {
+template <bool MULTI>
+struct PairSearchDevT {
   static constexpr bool on = true;
   PairRule<u64> rule;
   EdgeRegs er;
   u32 *bits;
+  u32 *multi;                    // leaves with at least two pairs (mark_end<MULTI>); null without MULTI
   ull *big;
   u32 *overflow;
   // k_group_fine: the n grouped words of ONE coarse bin at sw (output order; a bucket never leaves its bin, so the
@@ -287,22 +313,113 @@ struct PairSearchDev {
       found[q] = 0; first_off[q] = 0;
       if (i < n) pa_walk(word, sw[i], sw[i + 1 < n ? i + 1 : i], i, n, rule, big, found[q], first_off[q]);
     }
-    pa_emit<NP, T / 64u>(word, IdxGrouped{inv, v_in}, threadIdx.x, T, n, found, first_off, rule, er, bits, overflow, scratch);
+    pa_emit<NP, T / 64u, MULTI>(word, IdxGrouped{inv, v_in}, threadIdx.x, T, n, found, first_off, rule, er, bits, multi, overflow, scratch);
   }
 };
+
+using PairSearchDev = PairSearchDevT<false>;      // (also what the host hands on: group_fine_with_search picks the kernel by `multi`)
 
 // both ends of a plain pair list marked in the bitmap (pairs that were not found by k_pairs_append: the
 // large-bucket tiles, the edit-distance joins)
 static __global__ void __launch_bounds__(256)
-k_mark_pairs(const u64 *__restrict__ pairs, u32 n_pairs, u32 n_leaves, u32 *bits, u32 *bad) {
+k_mark_pairs(const u64 *__restrict__ pairs, u32 n_pairs, u32 n_leaves, u32 *bits, u32 *bad, u32 *multi = nullptr) {
   HUMID_GUARD_LAST_VGPR();
   const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n_pairs) return;
   const u64 e = pairs[k];
   const u32 a = (u32)(e >> 32), b = (u32)e;
   if (a >= n_leaves || b >= n_leaves || a == b) { *bad = 1; return; }
-  atomicOr(&bits[a >> 5], 1u << (a & 31));
-  atomicOr(&bits[b >> 5], 1u << (b & 31));
+  if (multi) { mark_end<true>(bits, multi, a); mark_end<true>(bits, multi, b); }
+  else { mark_end<false>(bits, multi, a); mark_end<false>(bits, multi, b); }
+}
+
+// ---- isolated pairs settled without a graph ------------------------------------------------------------
+// One launch behind the searches (bits / multi complete).  A pair whose two ends have no other pair IS its component:
+// its clusters follow from the two counts (the two-node branch of k_cg_trivial), written per end as
+// pair_res[u] = walk index of the creator | (u is the cluster's maxLeaf) << 31, with the later end marked in the
+// non-creator bitmap when it joins the earlier one's cluster.  Every other pair goes, unchanged, to the dense list
+// `rest` with both ends marked in rest_bits: the compact graph is built over those alone.  The pairs are only read.
+// A thread takes SPLIT_PPT pairs (all loads of a step requested together; ONE atomic per workgroup and round on
+// out[SPLIT_REST]: with one per 256 pairs the launch was bound by ~10^3 atomics on one address).
+// out[SPLIT_RMAX]: the fullest region's cursor (for the host: what the search wanted of one region); out[SPLIT_ALL]:
+// all pairs in the regions and the far list (isolated pairs = all - rest).
+// grid: x over the positions of a region (SPLIT_PPT x 256 per workgroup), y = region (ER_REGIONS + 1 of them)
+enum { SPLIT_RMAX = 0, SPLIT_ALL, SPLIT_REST, SPLIT_WORDS = 4 };
+#define SPLIT_PPT 4u
+template <bool MAXIMUM>
+__global__ void __launch_bounds__(256)
+k_pairs_split(EdgeRegs er, const u32 *__restrict__ multi, const u32 *__restrict__ cnt, u32 *__restrict__ pair_res, u32 *nbits,
+              u32 *rest_bits, u64 *__restrict__ rest, u32 rest_cap, u32 n_leaves, u32 *out) {
+  HUMID_GUARD_LAST_VGPR();
+  __shared__ u32 lds[8];
+  const u32 r = blockIdx.y;
+  if (blockIdx.x == 0 && r == 0 && threadIdx.x < 64) {
+    const u32 c = er.cur[threadIdx.x * ER_STRIDE];
+    u32 mx = c, sum = c < er.cap_r ? c : er.cap_r;
+#pragma unroll
+    for (u32 d = 32; d >= 1; d >>= 1) { const u32 y = __shfl_xor(mx, d); mx = y > mx ? y : mx; sum += __shfl_xor(sum, d); }
+    if (threadIdx.x == 0) { out[SPLIT_RMAX] = mx; out[SPLIT_ALL] = sum + er.n_far; }
+  }
+  const u32 n_r = er_count(er, r);
+  const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (u32 k0 = blockIdx.x * (SPLIT_PPT * 256u); k0 < n_r; k0 += gridDim.x * (SPLIT_PPT * 256u)) {   // (uniform: the workgroup stays together)
+    u64 e[SPLIT_PPT];
+    u32 ma[SPLIT_PPT], mb[SPLIT_PPT], ca[SPLIT_PPT], cb[SPLIT_PPT];
+    bool ok[SPLIT_PPT];
+#pragma unroll
+    for (u32 q = 0; q < SPLIT_PPT; q++) {
+      const u32 k = k0 + q * 256u + threadIdx.x;
+      e[q] = k < n_r ? *er_at(er, r, k) : 0ull;
+    }
+#pragma unroll
+    for (u32 q = 0; q < SPLIT_PPT; q++) {
+      const u32 a = (u32)(e[q] >> 32), b = (u32)e[q];
+      ok[q] = a < n_leaves && b < n_leaves && a != b;          // (beyond the region's end; a malformed given pair: reported by k_mark_pairs, dropped here)
+      ma[q] = mb[q] = ca[q] = cb[q] = 0;
+      if (ok[q]) { ma[q] = multi[a >> 5]; mb[q] = multi[b >> 5]; ca[q] = cnt[a]; cb[q] = cnt[b]; }
+    }
+    u32 mine = 0;
+#pragma unroll
+    for (u32 q = 0; q < SPLIT_PPT; q++) {
+      if (!ok[q]) continue;
+      const u32 a = (u32)(e[q] >> 32), b = (u32)e[q];
+      if (((ma[q] >> (a & 31)) | (mb[q] >> (b & 31))) & 1u) { mine++; continue; }
+      ok[q] = false;                                           // (settled here: ok[q] from now on = goes to the rest)
+      bool joined = true, b_max;
+      if (MAXIMUM) b_max = cb[q] > ca[q];
+      else if (at_least_double((u64)cb[q], (u64)ca[q])) b_max = true;      // a climbs to b, b floods back to a
+      else if (at_least_double((u64)ca[q], (u64)cb[q])) b_max = false;     // a stays, absorbs b
+      else { joined = false; b_max = false; }                             // two clusters
+      if (joined) {
+        pair_res[a] = a | (b_max ? 0u : 0x80000000u);
+        pair_res[b] = a | (b_max ? 0x80000000u : 0u);
+        atomicOr(&nbits[b >> 5], 1u << (b & 31));
+      } else {
+        pair_res[a] = a | 0x80000000u;
+        pair_res[b] = b | 0x80000000u;
+      }
+    }
+    const u32 incl = wave_incl_scan(mine);
+    if (lane == 63) lds[wv] = incl;
+    __syncthreads();
+    const u32 w0 = lds[0], w1 = lds[1], w2 = lds[2], w3 = lds[3];
+    const u32 total = w0 + w1 + w2 + w3;
+    if (total) {                                               // (uniform)
+      if (threadIdx.x == 0) lds[4] = atomicAdd(&out[SPLIT_REST], total);
+      __syncthreads();
+      u32 at = lds[4] + (wv > 0 ? w0 : 0u) + (wv > 1 ? w1 : 0u) + (wv > 2 ? w2 : 0u) + incl - mine;
+#pragma unroll
+      for (u32 q = 0; q < SPLIT_PPT; q++) {
+        if (!ok[q]) continue;
+        const u32 a = (u32)(e[q] >> 32), b = (u32)e[q];
+        if (at < rest_cap) rest[at] = e[q];
+        at++;
+        atomicOr(&rest_bits[a >> 5], 1u << (a & 31));
+        atomicOr(&rest_bits[b >> 5], 1u << (b & 31));
+      }
+    }
+    __syncthreads();
+  }
 }
 
 // ---- compact nodes -----------------------------------------------------------------------------------
@@ -337,11 +454,11 @@ struct DegIn {
 };
 
 // pairs in walk indices -> pairs in compact indices (in place), degrees, component forest
-// grid: x over the positions of a region, y = region (ER_REGIONS + 1 of them)
+// grid: x over the positions of a region, y = region (ER_REGIONS + 1 - r_first of them)
 static __global__ void __launch_bounds__(256)
-k_pairs_relabel(EdgeRegs er, BitRank br, const u32 *__restrict__ ncnt, u32 *deg, u32 *parent, bool join_by_count) {
+k_pairs_relabel(EdgeRegs er, BitRank br, const u32 *__restrict__ ncnt, u32 *deg, u32 *parent, bool join_by_count, u32 r_first) {
   HUMID_GUARD_LAST_VGPR();
-  const u32 r = blockIdx.y;
+  const u32 r = r_first + blockIdx.y;                  // (r_first: as in k_fill_and_stats)
   const u32 n_r = er_count(er, r);
   for (u32 k = blockIdx.x * blockDim.x + threadIdx.x; k < n_r; k += gridDim.x * blockDim.x) {
     u64 *slot = er_at(er, r, k);
@@ -532,9 +649,10 @@ k_cg_trivial(const u32 *__restrict__ P, const u32 *__restrict__ csize, const u32
 // ---- results -------------------------------------------------------------------------------------------
 // nodes that did not create a cluster, as a bitmap over walk indices
 static __global__ void __launch_bounds__(256)
-k_noncreator_bits(const u32 *__restrict__ cl_of, const u32 *__restrict__ nodes, u32 m, u32 *bits) {
+k_noncreator_bits(const u32 *__restrict__ cl_of, const u32 *__restrict__ nodes, u32 m, u32 *bits, const u32 *__restrict__ m_dev = nullptr) {
   HUMID_GUARD_LAST_VGPR();
   const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m_dev && *m_dev < m) m = *m_dev;                 // (the launch is sized by a bound)
   if (c >= m || cl_of[c] == c + 1) return;
   const u32 u = nodes[c];
   atomicOr(&bits[u >> 5], 1u << (u & 31));
@@ -543,20 +661,30 @@ k_noncreator_bits(const u32 *__restrict__ cl_of, const u32 *__restrict__ nodes, 
 // per unique word: (read to keep, cluster id) at the slot of its word.  Cluster ids follow
 // src/humid.cc:177-180: 1 + the number of cluster-creating leaves before the creator in the walk =
 // 1 + creator - (nodes before it that created nothing).
+// pair_res != null (the graph stage split its pairs, k_pairs_split): the compact graph holds the leaves of `in_graph`
+// only (rest_bits and its rank blocks); a leaf of any_pair that is not among them is an end of an isolated pair, with its
+// creator and maxLeaf flag in pair_res.  pair_res == null: in_graph is the bitmap of all leaves with a pair.
 static __global__ void __launch_bounds__(256)
 k_finalize_leaves(BitRank in_graph, BitRank noncreator, const u32 *__restrict__ nodes, const u32 *__restrict__ cl_of,
                   const u32 *__restrict__ maxleaf, u32 n, const u32 *__restrict__ s_first, const u32 *__restrict__ s_slot,
-                  u64 *__restrict__ slot_out, u32 *__restrict__ cid_out, u8 *__restrict__ ismax_out) {
+                  u64 *__restrict__ slot_out, u32 *__restrict__ cid_out, u8 *__restrict__ ismax_out,
+                  const u32 *__restrict__ any_pair = nullptr, const u32 *__restrict__ pair_res = nullptr) {
   HUMID_GUARD_LAST_VGPR();
   const u32 u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= n) return;
   u32 g = u;
   bool mx = true;
-  if (br_test(in_graph, u)) {
+  if (pair_res && !((any_pair[u >> 5] >> (u & 31)) & 1u)) {
+    // (no pair at all: most leaves -- one bitmap read, as without the split)
+  } else if (br_test(in_graph, u)) {
     const u32 c = br_rank(in_graph, u);
     const u32 cc = cl_of[c] - 1u;                      // compact index of the creator
     g = nodes[cc];
     mx = maxleaf[cc] == c;
+  } else if (pair_res) {
+    const u32 p = pair_res[u];
+    g = p & 0x7fffffffu;
+    mx = (p >> 31) != 0;
   }
   const u32 id = 1u + g - br_rank(noncreator, g);
   if (slot_out) slot_out[s_slot ? s_slot[u] : u] = ((u64)(mx ? s_first[u] : NONE32) << 32) | id;

@@ -177,6 +177,20 @@ struct humid_ctx {
   bool cg_valid = false;            // the last graph stage left its results in the cg_* arrays ...
   bool cg_expanded = false;         // ... and the per-unique-word view of them has been built (accessors)
   u32 cg_M = 0, cg_nblocks = 0;
+  // the pairs of a graph stage split (k_pairs_split): isolated pairs are settled from the pair list, the compact graph
+  // holds the rest.  cg_multi: leaves with >= 2 pairs; cg_rbits: ends of the rest pairs; cg_rest: those pairs;
+  // cg_pres: creator | maxLeaf flag of the ends of isolated pairs
+  DBuf cg_multi, cg_rbits, cg_rest, cg_pres;
+  bool pair_split = true;           // option "pair_split": 0 = every pair goes through the compact graph
+  bool cg_split = false;            // the last graph stage split its pairs: cg_* hold the REST graph until cg_ensure_full
+  bool cg_full = false;             // ... and the graph over all pairs has been built since (accessors; once per run)
+  bool cg_broken = false;           // ... and building that graph failed halfway (the pair list is relabelled in place: no second try)
+  bool cg_m_late = false;           // ... and the rest graph's node count comes with the pass's last wait (n_clusters_compact)
+  u64 cg_iso = 0, cg_R = 0;         // isolated pairs, rest pairs of that stage
+  EdgeRegs cg_er = {};              // its pair list (regions + far), untouched by the split
+  u64 cg_pairs_bound = 0;
+  u32 cg_method = 0;
+  const u32 *ctr_x[3] = {nullptr, nullptr, nullptr};   // read_counters_begin without the mapped mirror: what _end copies
   // owner-local clustering of the exchange pass (kernels_xchg.hip.h): records by destination, interior / crossing /
   // flagged-interior records, the forest over own leaves, crossing-creator bitmap and ids, own results
   DBuf xo_gw, xo_gc;                // the edit-distance road: unique words / counts of all ranks
@@ -398,7 +412,8 @@ static int exscan_u32(humid_ctx *c, const u32 *in, u32 *out, u64 n) { return exs
 // in h_ctr[CTR_N - 1].
 // One tiny kernel stores the counters (and the extra value) straight into the page-locked mirror and then
 // a sequence number; the host watches that word.  Two blit copies + hipStreamSynchronize cost ~30 us of idle
-// GPU per host wait, this ~10 (three waits per single-GPU pass, eight in the multi-GPU pass).
+// GPU per host wait, this ~10 (three waits per single-GPU pass, eight in the multi-GPU pass; with pair_split a fourth
+// that the GPU works through: read_counters_begin / _end below).
 static __global__ void k_publish_counters(const ull *__restrict__ ctr, const u32 *__restrict__ extra32, const u32 *__restrict__ extra32b,
                                    volatile ull *host, ull seq, const u32 *__restrict__ extra32c = nullptr) {
   HUMID_GUARD_LAST_VGPR();
@@ -414,12 +429,23 @@ static __global__ void k_publish_counters(const ull *__restrict__ ctr, const u32
   if (threadIdx.x == 0) { host[CTR_N] = seq; __threadfence_system(); }
 }
 // extra32 -> h_ctr[CTR_N - 1] (low half), extra32b -> h_ctr[CTR_N - 2], extra32c -> h_ctr[CTR_N - 3]
-static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr) {
+// The wait in two halves: _begin puts the publishing kernel into the stream, _end waits for it.  Kernels launched in
+// between run while the host waits and decides (their results are not in the counters the host sees): a wait that
+// costs the GPU no idle time.  read_counters is the two back to back.
+static int read_counters_begin(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr) {
+  c->ctr_x[0] = extra32; c->ctr_x[1] = extra32b; c->ctr_x[2] = extra32c;
   if (c->h_ctr_dev && !c->no_poll) {
     const ull seq = ++c->ctr_seq;
     hipLaunchKernelGGL(k_publish_counters, dim3(1), dim3(64), 0, c->stream, (const ull *)c->d_ctr, extra32, extra32b,
                        (volatile ull *)c->h_ctr_dev, seq, extra32c);
     HIPCHK(hipGetLastError());
+  }
+  return HUMID_OK;
+}
+static int read_counters_end(humid_ctx *c) {
+  const u32 *extra32 = c->ctr_x[0], *extra32b = c->ctr_x[1], *extra32c = c->ctr_x[2];
+  if (c->h_ctr_dev && !c->no_poll) {
+    const ull seq = c->ctr_seq;
     volatile ull *flag = (volatile ull *)&c->h_ctr[CTR_N];
     const auto t0 = std::chrono::steady_clock::now();
     u32 spins = 0;
@@ -444,6 +470,10 @@ static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
+}
+static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr) {
+  const int rc = read_counters_begin(c, extra32, extra32b, extra32c);
+  return rc != HUMID_OK ? rc : read_counters_end(c);
 }
 
 #define TRY(...) do { int _rc = (__VA_ARGS__); if (_rc != HUMID_OK) return _rc; } while (0)
@@ -601,8 +631,11 @@ static GraphArrays legacy_arrays(humid_ctx *c) {
 // Mbig = those in components larger than SMALL_COMP; small_roots listed by k_comp_count.
 // Leaves cl_of (creator + 1) / maxleaf / cl_size (at the creators) in `g`.
 // trivial_done: the components of one and two nodes are done and the roots listed (k_cg_trivial)
+// late_m (with trivial_done): U and M are bounds and Mbig is not known yet -- the device's node count (*late_m) and
+// CTR_MEMBERS are fetched while k_cluster_small_lds runs (read_counters_begin / _end), before the kernels that need them
+// exact; *late_m_out = the node count
 static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt, u32 U, u64 M, u64 Mbig, u32 method,
-                           bool trivial_done = false) {
+                           bool trivial_done = false, const u32 *late_m = nullptr, u64 *late_m_out = nullptr) {
   hipStream_t st = c->stream;
   if (!trivial_done && c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));
   if (trivial_done) {
@@ -614,12 +647,20 @@ static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt,
                        g.idx, g.cl_of, g.maxleaf, g.cl_size);
   if (M > 0) {
     const u64 small_cap = M / 3 + 1;                  // listed roots: components of >= 3 of the M leaves with neighbours
+    if (late_m) TRY(read_counters_begin(c, nullptr, nullptr, late_m));
     if (method == HUMID_METHOD_MAXIMUM)
       hipLaunchKernelGGL(k_cluster_small_lds<true>, dim3(blocks_for(small_cap, 64)), dim3(64), 0, st, c->small_roots.as<u32>(),
                          (const ull *)c->d_ctr, g.parent, g.csize, U, g_cnt, g.off, g.idx, g.cl_of, g.maxleaf, g.cl_size);
     else
       hipLaunchKernelGGL(k_cluster_small_lds<false>, dim3(blocks_for(small_cap, 64)), dim3(64), 0, st, c->small_roots.as<u32>(),
                          (const ull *)c->d_ctr, g.parent, g.csize, U, g_cnt, g.off, g.idx, g.cl_of, g.maxleaf, g.cl_size);
+    if (late_m) {
+      TRY(read_counters_end(c));
+      Mbig = c->h_ctr[CTR_MEMBERS];
+      M = c->h_ctr[CTR_N - 3] & 0xffffffffull;
+      U = (u32)M;
+      if (late_m_out) *late_m_out = M;
+    }
     if (Mbig > 0) {
       ENSURE(c->mk0, (size_t)Mbig * 8);
       ENSURE(c->mk1, (size_t)Mbig * 8);
@@ -1599,24 +1640,33 @@ static void tiles_emit(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &
 }
 // k_pairs_append over a whole order; n_valid: the words a padded grouping holds (bucket_order with may_pad)
 template <class WT>
-static void pairs_append(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const EdgeRegs &er, u32 *bits, ull *big, u32 *overflow,
-                         const u32 *n_valid) {
+static void pairs_append(humid_ctx *c, const PairSearch<WT> &s, const Walked<WT> &w, const EdgeRegs &er, u32 *bits, u32 *multi, ull *big,
+                         u32 *overflow, const u32 *n_valid) {
   const dim3 grid(blocks_for(w.n, PA_PPT * 256)), blk(256);
   const PairRule<WT> rule{w.mask, s.em, w.cb, s.distance, s.walk_max};
-  if (w.V)
-    hipLaunchKernelGGL((k_pairs_append<false, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, big, overflow, n_valid);
+  if (w.V && multi)
+    hipLaunchKernelGGL((k_pairs_append<false, WT, true>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, multi, big, overflow, n_valid);
+  else if (w.V)
+    hipLaunchKernelGGL((k_pairs_append<false, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, multi, big, overflow, n_valid);
+  else if (multi)
+    hipLaunchKernelGGL((k_pairs_append<true, WT, true>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, multi, big, overflow, n_valid);
   else
-    hipLaunchKernelGGL((k_pairs_append<true, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, big, overflow, n_valid);
+    hipLaunchKernelGGL((k_pairs_append<true, WT>), grid, blk, 0, c->stream, w.W, w.V, w.n, rule, er, bits, multi, big, overflow, n_valid);
 }
 // the same search as an argument of the kernel that holds the combination's words while it groups them (GroupRide)
-static PairSearchDev pairs_append_dev(const PairSearch<u64> &s, u64 mask, u32 cb, const EdgeRegs &er, u32 *bits, ull *big, u32 *overflow) {
-  return PairSearchDev{PairRule<u64>{mask, s.em, cb, s.distance, s.walk_max}, er, bits, big, overflow};
+static PairSearchDev pairs_append_dev(const PairSearch<u64> &s, u64 mask, u32 cb, const EdgeRegs &er, u32 *bits, u32 *multi, ull *big,
+                                      u32 *overflow) {
+  return PairSearchDev{PairRule<u64>{mask, s.em, cb, s.distance, s.walk_max}, er, bits, multi, big, overflow};
 }
 // level 2 of a grouping whose coarse bins all hold at most GF_SMALL words, with the grouped combination's search in it
 static void group_fine_with_search(humid_ctx *c, const FieldsSrc &src, const u64 *k0, const u32 *v0, const u32 *cbase, u32 d1, u32 d2, u64 *ws,
                                    u32 *vs, u32 cap1, const PairSearchDev &s) {
-  hipLaunchKernelGGL((k_group_fine<FieldsSrc, 0, PairSearchDev>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, k0, v0, cbase, d1, d2, ws,
-                     vs, cap1, s);
+  if (s.multi)
+    hipLaunchKernelGGL((k_group_fine<FieldsSrc, 0, PairSearchDevT<true>>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, k0, v0, cbase, d1, d2,
+                       ws, vs, cap1, PairSearchDevT<true>{s.rule, s.er, s.bits, s.multi, s.big, s.overflow});
+  else
+    hipLaunchKernelGGL((k_group_fine<FieldsSrc, 0, PairSearchDev>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, k0, v0, cbase, d1, d2, ws,
+                       vs, cap1, s);
 }
 // component sizes and what is read from them (M, Mbig, 2E, the roots of the small components) for deg / parent over U nodes
 static void comp_stats(humid_ctx *c, u32 U) {
@@ -1780,6 +1830,9 @@ struct CgSource {
   const u32 *cnt_by_id;        // counts by id (with plain pairs)
   u32 n_ids;                   // id space = bits of the bitmap c->cg_bits (zeroed, then marked, by the caller)
   u64 pairs_bound;             // no more pairs than this can be in the source
+  u32 *bits = nullptr;         // the bitmap of the marked ids if not c->cg_bits (the rest of a split stage: c->cg_rbits)
+  bool no_wait = false;        // no host wait: the caller knows the pairs (er.e == null, a dense list of pairs_bound pairs),
+                               // regions_max is not wanted and CgStatus is left alone
 };
 struct CgStatus {
   bool overflow = false;       // an append region was full: `wanted` says how much room the search wants in all
@@ -1794,6 +1847,7 @@ static GraphArrays cg_arrays(humid_ctx *c) {
 // components; ONE host wait at the end (every launch before it is sized by bounds: nodes <= 2 x pairs).
 static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
   hipStream_t st = c->stream;
+  u32 *bits = src.bits ? src.bits : c->cg_bits.as<u32>();
   const u32 n_words = (((src.n_ids + 31) / 32) + 7) & ~7u, n_blk = n_words / 8;
   const u64 pb = std::max<u64>(src.pairs_bound, 1);
   if (2 * pb + 2 > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
@@ -1812,10 +1866,11 @@ static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
   ENSURE(c->cg_cl_size, ((size_t)Mb + 1) * 8);
   ENSURE(c->small_roots, ((size_t)Mb / 3 + 2) * 4);
   ENSURE(c->small, 64);
-  TRY(exscan_in<u32>(c, BitsBlockIn{c->cg_bits.as<u32>(), n_blk}, c->cg_blk.as<u32>(), (u64)n_blk + 1));
-  const BitRank br{c->cg_bits.as<u32>(), c->cg_blk.as<u32>()};
+  TRY(exscan_in<u32>(c, BitsBlockIn{bits, n_blk}, c->cg_blk.as<u32>(), (u64)n_blk + 1));
+  const BitRank br{bits, c->cg_blk.as<u32>()};
   const u32 *m_dev = c->cg_blk.as<u32>() + n_blk;
   const GraphArrays g = cg_arrays(c);
+  const u32 r_first = src.er.e ? 0u : ER_REGIONS;        // no regions (one dense pair list): the `far` region alone
   hipLaunchKernelGGL(k_nodes_init, dim3(blocks_for(n_words)), dim3(256), 0, st, br, n_words, src.cnt_by_id, c->cg_nodes.as<u32>(),
                      c->cg_ncnt.as<u32>(), g.deg, g.parent, g.csize, c->cg_curs.as<u32>(), n_blk);
   const bool by_count = (method & 1) == 0;
@@ -1837,16 +1892,15 @@ static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
     src.er.n_far = src.n_recs;
   } else {
     const u32 gx = (u32)std::min<u64>(std::max<u64>(blocks_for(std::max<u64>(src.er.cap_r, src.er.n_far)), 1), 4096);
-    hipLaunchKernelGGL(k_pairs_relabel, dim3(gx, ER_REGIONS + 1), dim3(256), 0, st, src.er, br, (const u32 *)c->cg_ncnt.as<u32>(),
-                       g.deg, g.parent, by_count);
+    hipLaunchKernelGGL(k_pairs_relabel, dim3(gx, ER_REGIONS + 1 - r_first), dim3(256), 0, st, src.er, br, (const u32 *)c->cg_ncnt.as<u32>(),
+                       g.deg, g.parent, by_count, r_first);
   }
   TRY(exscan_in<u32>(c, DegIn{g.deg, m_dev}, g.off, (u64)Mb + 1));
   {
     // CSR rows and component sizes side by side (one launch: kernels_cgraph.hip.h)
     const u32 gx = (u32)std::min<u64>(std::max<u64>(blocks_for(std::max<u64>(src.er.cap_r, src.er.n_far)), 1), 4096);
-    const u32 r_first = src.er.e ? 0u : ER_REGIONS;      // no regions (one dense pair list): the `far` region alone
     hipLaunchKernelGGL(k_fill_and_stats, dim3(gx * (ER_REGIONS + 1 - r_first) + blocks_for(Mb)), dim3(256), 0, st, src.er, (const u32 *)g.off,
-                       c->cg_curs.as<u32>(), g.idx, c->small.as<u32>(), gx, (const u32 *)g.deg, g.parent, Mb, g.csize, m_dev, r_first);
+                       c->cg_curs.as<u32>(), g.idx, src.no_wait ? (u32 *)nullptr : c->small.as<u32>(), gx, (const u32 *)g.deg, g.parent, Mb, g.csize, m_dev, r_first);
   }
   hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(Mb)), dim3(256), 0, st, (const u32 *)g.off, Mb, g.idx);
   if (c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));
@@ -1860,6 +1914,7 @@ static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
                        (const u32 *)c->cg_ncnt.as<u32>(), (const u32 *)g.off, (const u32 *)g.idx, g.cl_of, g.maxleaf, g.cl_size, c->d_ctr,
                        c->small_roots.as<u32>());
   HIPCHK(hipGetLastError());
+  if (src.no_wait) return HUMID_OK;
   TRY(read_counters(c, g.off + Mb, c->small.as<u32>(), m_dev));              // 2E, pairs the fullest region wanted, M
   out.wanted = (c->h_ctr[CTR_N - 2] & 0xffffffffull) * ER_REGIONS;            // (as a total: every region has the same room)
   out.overflow = (c->h_ctr[CTR_EOVER] & 0xffffffffull) != 0;
@@ -1872,16 +1927,18 @@ static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
 }
 // the components of 3 and more nodes, then the nodes that created no cluster as a bitmap over the ids with
 // its rank structure (c->cg_nbits zeroed by the caller; cg_nblk)
-static int cg_cluster_rest(humid_ctx *c, u32 n_ids, u64 M, u64 Mbig, u32 method) {
+// late_m: M is a bound, Mbig unknown (cluster_kernels); *late_m_out = the node count if the cluster kernels fetched it
+static int cg_cluster_rest(humid_ctx *c, u32 n_ids, u64 M, u64 Mbig, u32 method, const u32 *late_m = nullptr, bool fetch = false,
+                           u64 *late_m_out = nullptr) {
   hipStream_t st = c->stream;
   const u32 n_words = (((n_ids + 31) / 32) + 7) & ~7u, n_blk = n_words / 8;
   const GraphArrays g = cg_arrays(c);
   ENSURE(c->cg_nblk, ((size_t)n_blk + 1) * 4);
-  if (M > 0) TRY(cluster_kernels(c, g, c->cg_ncnt.as<u32>(), (u32)M, M, Mbig, method, true));
+  if (M > 0) TRY(cluster_kernels(c, g, c->cg_ncnt.as<u32>(), (u32)M, M, Mbig, method, true, fetch ? late_m : (const u32 *)nullptr, late_m_out));
   else if (c->kev_on) HIPCHK(hipEventRecord(c->kev[3], st));
   if (M > 0)
     hipLaunchKernelGGL(k_noncreator_bits, dim3(blocks_for(M)), dim3(256), 0, st, (const u32 *)g.cl_of, c->cg_nodes.as<u32>(), (u32)M,
-                       c->cg_nbits.as<u32>());
+                       c->cg_nbits.as<u32>(), late_m);
   TRY(exscan_in<u32>(c, BitsBlockIn{c->cg_nbits.as<u32>(), n_blk}, c->cg_nblk.as<u32>(), (u64)n_blk + 1));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
@@ -1894,6 +1951,9 @@ static int cg_cluster_rest(humid_ctx *c, u32 n_ids, u64 M, u64 Mbig, u32 method)
 // it (expand_compact).  Leaves: slot_out (own = the graph is over this context's unique words) or
 // cid / ismax (own = false), c->cg_* and the cluster count on the device (n_clusters_compact).
 // ext_edges != nullptr: the pairs are GIVEN as (smaller << 32 | larger) walk indices (edit distance).
+// Option pair_split (the default): a pair whose two ends have no other pair is settled by k_pairs_split right behind
+// the searches, and cg_build only sees the rest (a dense list, its ends in cg_rbits); the attempt's host wait stands
+// behind k_pairs_split, the rest build has none.  The cg_* arrays then hold the rest graph: cg_ensure_full.
 template <class WT>
 static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, u32 word_nt,
                                u32 distance, u32 method, humid_summary &s, u32 &n_pair_segs_out,
@@ -1905,6 +1965,9 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->gU = U;
   c->cg_valid = false;
   c->cg_expanded = false;
+  c->cg_split = c->cg_full = c->cg_m_late = c->cg_broken = false;
+  c->cg_iso = c->cg_R = 0;
+  const bool split = c->pair_split;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
   const PairSearch<WT> ps = pair_search<WT>(c, plan, distance);
   const bool given = ext_edges != nullptr;
@@ -1923,6 +1986,13 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   ENSURE(c->cg_cur, (size_t)(ER_REGIONS * ER_STRIDE + 8) * 4);
   ENSURE(c->small_roots, ((size_t)U / 3 + 2) * 4);
   ENSURE(c->small, 64);
+  if (split) {
+    ENSURE(c->cg_multi, (size_t)n_words * 4);
+    ENSURE(c->cg_rbits, (size_t)n_words * 4);
+    ENSURE(c->cg_pres, (size_t)U * 4 + 4);
+  }
+  u32 *multi = split ? c->cg_multi.as<u32>() : (u32 *)nullptr;
+  u64 n_iso = 0, R = 0;
   TRY(ensure_seg_scratch<WT>(c, nseg, U));
   u32 *bad = c->cg_cur.as<u32>() + ER_REGIONS * ER_STRIDE;       // malformed given pair
   const u64 *far = given ? ext_edges : nullptr;
@@ -1953,12 +2023,17 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       z.p[1] = c->cg_nbits.as<u32>(); z.n[1] = n_words;
       z.p[2] = c->cg_cur.as<u32>(); z.n[2] = ER_REGIONS * ER_STRIDE + 8;
       z.p[3] = (u32 *)&c->d_ctr[CTR_EDGES]; z.n[3] = 2 * (CTR_GOVER - CTR_EDGES + 1);
+      if (split) {
+        z.p[4] = multi; z.n[4] = n_words;
+        z.p[5] = c->cg_rbits.as<u32>(); z.n[5] = n_words;
+        z.p[6] = c->small.as<u32>(); z.n[6] = SPLIT_WORDS;
+      }
       hipLaunchKernelGGL(k_zero_many, dim3(64), dim3(256), 0, st, z);
     }
     // a launch of k_pairs_append over the order of combination seg, between its two events
     auto search_alone = [&](u32 seg) -> int {
       if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
-      pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK],
+      pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK],
                        (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
       if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
       return HUMID_OK;
@@ -1977,7 +2052,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
           GroupRide ride;
           if constexpr (std::is_same<WT, u64>::value) {
             if (ride_on) {
-              ride.group = pairs_append_dev(ps, w_from<u64>(plan.mask[seg]), seg, er, c->cg_bits.as<u32>(), &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
+              ride.group = pairs_append_dev(ps, w_from<u64>(plan.mask[seg]), seg, er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
               if (seg < 8 && c->kev_on) { ride.ev_group[0] = c->kev[20 + 2 * seg]; ride.ev_group[1] = c->kev[21 + 2 * seg]; }
             }
           }
@@ -1990,12 +2065,36 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       if (!searched) TRY(search_alone(seg));
     }
     if (n_far)
-      hipLaunchKernelGGL(k_mark_pairs, dim3(blocks_for(n_far)), dim3(256), 0, st, far, (u32)n_far, U, c->cg_bits.as<u32>(), bad);
-    CgSource src;
-    src.er = er; src.recs = nullptr; src.n_recs = 0; src.cnt_by_id = g_cnt; src.n_ids = U;
-    src.pairs_bound = ecap + n_far;
-    TRY(cg_build(c, src, method, cgs));
-    er = src.er;
+      hipLaunchKernelGGL(k_mark_pairs, dim3(blocks_for(n_far)), dim3(256), 0, st, far, (u32)n_far, U, c->cg_bits.as<u32>(), bad, multi);
+    if (split) {
+      // the isolated pairs are settled here, the others listed; the attempt's ONE host wait follows at once (a retry has
+      // built no graph)
+      const u64 rest_cap = (u64)ER_REGIONS * er.cap_r + n_far;
+      if (rest_cap > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
+      ENSURE(c->cg_rest, (size_t)(rest_cap + 1) * 8);
+      const u32 gx = (u32)std::min<u64>(std::max<u64>(blocks_for(std::max<u64>(er.cap_r, er.n_far), SPLIT_PPT * 256), 1), 4096);
+      u32 *sp = c->small.as<u32>();
+      if (method == HUMID_METHOD_MAXIMUM)
+        hipLaunchKernelGGL(k_pairs_split<true>, dim3(gx, ER_REGIONS + 1), dim3(256), 0, st, er, (const u32 *)multi, g_cnt, c->cg_pres.as<u32>(),
+                           c->cg_nbits.as<u32>(), c->cg_rbits.as<u32>(), c->cg_rest.as<u64>(), (u32)rest_cap, U, sp);
+      else
+        hipLaunchKernelGGL(k_pairs_split<false>, dim3(gx, ER_REGIONS + 1), dim3(256), 0, st, er, (const u32 *)multi, g_cnt, c->cg_pres.as<u32>(),
+                           c->cg_nbits.as<u32>(), c->cg_rbits.as<u32>(), c->cg_rest.as<u64>(), (u32)rest_cap, U, sp);
+      HIPCHK(hipGetLastError());
+      TRY(read_counters(c, sp + SPLIT_REST, sp + SPLIT_RMAX, sp + SPLIT_ALL));
+      cgs.wanted = (c->h_ctr[CTR_N - 2] & 0xffffffffull) * ER_REGIONS;
+      cgs.overflow = (c->h_ctr[CTR_EOVER] & 0xffffffffull) != 0;
+      cgs.group_over = c->h_ctr[CTR_GOVER] != 0;
+      cgs.big_mask = c->h_ctr[CTR_BIGMASK];
+      R = c->h_ctr[CTR_N - 1] & 0xffffffffull;
+      n_iso = (c->h_ctr[CTR_N - 3] & 0xffffffffull) - std::min<u64>(R, c->h_ctr[CTR_N - 3] & 0xffffffffull);
+    } else {
+      CgSource src;
+      src.er = er; src.recs = nullptr; src.n_recs = 0; src.cnt_by_id = g_cnt; src.n_ids = U;
+      src.pairs_bound = ecap + n_far;
+      TRY(cg_build(c, src, method, cgs));
+      er = src.er;
+    }
     if (cgs.group_over) {                                // a padded coarse bin of a grouping was full: words are missing
       c->gf_padded = false;                              // from a bucket order -- all of it again with exact bins
       for (u32 q = 0; q < MAX_COMBOS; q++) ordered_seg[q] = false;
@@ -2005,8 +2104,9 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     if (cgs.overflow) {                                  // a region was full: more room, once more
       c->cg_ecap = cgs.wanted + cgs.wanted / 2 + ER_REGIONS * 64;
-      // cg_build has relabelled the pairs of the tiles IN PLACE (k_pairs_relabel): that list cannot be used again,
-      // the tiles make it once more behind the next search.  (A search that rode in the groupings spreads its pairs
+      // Without pair_split cg_build has relabelled the pairs of the tiles IN PLACE (k_pairs_relabel): that list cannot be
+      // used again, the tiles make it once more behind the next search.  With pair_split no graph has been built and the
+      // list is intact; it is dropped all the same, so that both paths take the same attempts.  (A search that rode in the groupings spreads its pairs
       // over one region per coarse bin, k_pairs_append over one per 1024 positions: the search behind the tiles can
       // fill a region where the one in front of them did not.)
       if (!given) { far = nullptr; n_far = 0; }
@@ -2050,24 +2150,57 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       n_far = got;
       if (n_far) continue;                              // (nothing beyond the walk after all: the list stands)
     }
-    E = cgs.E; M = cgs.M; Mbig = cgs.Mbig;
+    if (split) {
+      c->cg_er = er;
+      c->cg_pairs_bound = ecap + n_far;
+    } else { E = cgs.E; M = cgs.M; Mbig = cgs.Mbig; }
     // far too roomy for this input: the next pass gets what this one wanted + a quarter (launches are sized by it)
     if (search && 2 * (cgs.wanted + cgs.wanted / 4 + ER_REGIONS * 64) < c->cg_ecap) c->cg_ecap = cgs.wanted + cgs.wanted / 4 + ER_REGIONS * 64;
     break;
   }
+  const u32 *late_m = nullptr;
+  bool fetch = false;
+  if (split) {
+    // the compact graph over the R rest pairs (a dense list) and their ends (cg_rbits), sized by R; no wait of its own
+    c->cg_split = true;
+    c->cg_method = method;
+    c->cg_iso = n_iso; c->cg_R = R;
+    E = n_iso + R;
+    if (R > 0) {
+      CgSource src;
+      src.er.e = nullptr; src.er.cap_r = 0; src.er.cur = c->cg_cur.as<u32>(); src.er.far = c->cg_rest.as<u64>(); src.er.n_far = (u32)R;
+      src.recs = nullptr; src.n_recs = 0; src.cnt_by_id = g_cnt; src.n_ids = U;
+      src.pairs_bound = R;
+      src.bits = c->cg_rbits.as<u32>();
+      src.no_wait = true;
+      TRY(cg_build(c, src, method, cgs));
+      late_m = c->cg_blk.as<u32>() + n_blk;
+      // a component of more than SMALL_COMP nodes has at least SMALL_COMP pairs: with fewer, Mbig = 0 and the node
+      // count can wait for the pass's last wait; else both come while k_cluster_small_lds runs
+      fetch = R >= SMALL_COMP;
+      c->cg_m_late = !fetch;
+      M = std::min<u64>(U, 2 * R);                       // (a bound)
+      Mbig = 0;
+    } else if (c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));   // (no rest pair, no cg_build: the cluster kernels' first event is its)
+  }
   s.edges = c->E = E;
-  s.nonsingle = c->M = M;
-  c->cg_M = (u32)M;
   if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[2], st));
-  TRY(cg_cluster_rest(c, U, M, Mbig, method));
+  u64 M_rest = 0;
+  TRY(cg_cluster_rest(c, U, M, Mbig, method, late_m, fetch, &M_rest));
+  if (split) M = 2 * n_iso + (fetch ? M_rest : 0);       // (cg_m_late: n_clusters_compact adds the rest graph's nodes)
+  s.nonsingle = c->M = M;
+  c->cg_M = split ? 0u : (u32)M;
   const GraphArrays g = cg_arrays(c);
   const bool own = ((const void *)g_word == c->s_word.p) && U == (u32)c->U;
   if (!own) { ENSURE(c->cid, (size_t)U * 4); ENSURE(c->ismax, (size_t)U); }
-  hipLaunchKernelGGL(k_finalize_leaves, dim3(blocks_for(U)), dim3(256), 0, st, BitRank{c->cg_bits.as<u32>(), c->cg_blk.as<u32>()},
+  hipLaunchKernelGGL(k_finalize_leaves, dim3(blocks_for(U)), dim3(256), 0, st,
+                     BitRank{split ? c->cg_rbits.as<u32>() : c->cg_bits.as<u32>(), c->cg_blk.as<u32>()},
                      BitRank{c->cg_nbits.as<u32>(), c->cg_nblk.as<u32>()}, c->cg_nodes.as<u32>(), (const u32 *)g.cl_of,
                      (const u32 *)g.maxleaf, U, own ? c->s_first.as<u32>() : (const u32 *)nullptr,
                      own ? c->s_slot.as<u32>() : (const u32 *)nullptr, own ? c->slot_out.as<u64>() : (u64 *)nullptr,
-                     own ? (u32 *)nullptr : c->cid.as<u32>(), own ? (u8 *)nullptr : c->ismax.as<u8>());
+                     own ? (u32 *)nullptr : c->cid.as<u32>(), own ? (u8 *)nullptr : c->ismax.as<u8>(),
+                     split ? (const u32 *)c->cg_bits.as<u32>() : (const u32 *)nullptr,
+                     split ? (const u32 *)c->cg_pres.as<u32>() : (const u32 *)nullptr);
   c->slots_done = own;
   c->cg_valid = true;
   HIPCHK(hipGetLastError());
@@ -2077,15 +2210,55 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
 
 // clusters = unique words - graph nodes that created no cluster (the pass's last host wait)
 static int n_clusters_compact(humid_ctx *c, u32 U, u64 *out) {
-  TRY(read_counters(c, c->cg_nblk.as<u32>() + c->cg_nblocks));
+  TRY(read_counters(c, c->cg_nblk.as<u32>() + c->cg_nblocks, c->cg_m_late ? c->cg_blk.as<u32>() + c->cg_nblocks : (const u32 *)nullptr));
   *out = (u64)U - (c->h_ctr[CTR_N - 1] & 0xffffffffull);
+  if (c->cg_m_late) { c->M += c->h_ctr[CTR_N - 2] & 0xffffffffull; c->cg_m_late = false; }   // (the rest graph's nodes)
   return HUMID_OK;
 }
 
 // The per-unique-word view of a compact graph stage, for the accessors (humid_get_leaves / _adjacency /
 // _clusters / _histogram): degrees, CSR rows in walk indices, cluster arrays, creator prefix sum, ids.
+// The gate in front of every reader of c->cg_* outside the graph stage.  A stage that split its pairs left the REST
+// graph there; the accessors want the graph over all pairs.  The regions and the far list are as the searches left them
+// (k_pairs_split only reads), so the unsplit build and the cluster kernels run over them once, with cg_bits as the node
+// bitmap.  Nothing the run delivered is touched: not slot_out, not cid / keep, not the summary (cg_nbits / cg_nblk, which
+// the ids came from, stay as they are too).
+// It runs after the pass: the pass's per-kernel events (kev[2], kev[3]) are not recorded again, and d_ctr / h_ctr /
+// c->small, which it overwrites, are read by nothing once a pass has returned.  The build relabels the pair list in
+// place, so a failure halfway leaves nothing to build from: cg_broken, and the accessors fail from then on.
+static int cg_build_full(humid_ctx *c) {
+  hipStream_t st = c->stream;
+  struct NoKernelEvents { humid_ctx *c; bool on; ~NoKernelEvents() { c->kev_on = on; } } quiet{c, c->kev_on};
+  c->kev_on = false;
+  {
+    ZeroList z;
+    memset(&z, 0, sizeof z);
+    z.p[0] = (u32 *)&c->d_ctr[CTR_EDGES]; z.n[0] = 2 * (CTR_GOVER - CTR_EDGES + 1);
+    hipLaunchKernelGGL(k_zero_many, dim3(1), dim3(256), 0, st, z);
+  }
+  CgSource src;
+  src.er = c->cg_er; src.recs = nullptr; src.n_recs = 0; src.cnt_by_id = c->g_cnt; src.n_ids = c->gU;
+  src.pairs_bound = c->cg_pairs_bound;
+  CgStatus cgs;
+  TRY(cg_build(c, src, c->cg_method, cgs));
+  if (cgs.E != c->E) return fail(c, HUMID_E_INVALID, "internal: the full graph has %llu pairs, the run found %llu", (ull)cgs.E, (ull)c->E);
+  if (cgs.M > 0) TRY(cluster_kernels(c, cg_arrays(c), c->cg_ncnt.as<u32>(), (u32)cgs.M, cgs.M, cgs.Mbig, c->cg_method, true));
+  HIPCHK(hipStreamSynchronize(st));
+  c->cg_M = (u32)cgs.M;
+  c->cg_full = true;
+  return HUMID_OK;
+}
+static int cg_ensure_full(humid_ctx *c) {
+  if (!c->cg_valid || !c->cg_split || c->cg_full) return HUMID_OK;
+  if (c->cg_broken) return fail(c, HUMID_E_STATE, "the graph of this run could not be built when it was first asked for; run again");
+  const int rc = cg_build_full(c);
+  if (rc != HUMID_OK) c->cg_broken = true;
+  return rc;
+}
+
 static int expand_compact(humid_ctx *c) {
   if (!c->cg_valid || c->cg_expanded) return HUMID_OK;
+  TRY(cg_ensure_full(c));
   hipStream_t st = c->stream;
   const u32 U = c->gU, M = c->cg_M;
   const u64 E = c->E;
@@ -2554,6 +2727,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   if (c->cg_valid) TRY(n_clusters_compact(c, U, &c->C));
   else TRY(n_clusters_from_scan(c, U, &c->C));
   s.clusters = c->C;
+  s.nonsingle = c->M;
   const u64 E = c->E, M = c->M;
   // (the last host wait watches a mapped flag, not the stream: the runtime may not have seen the last
   // event's signal yet -- "device not ready" from hipEventElapsedTime once in ~10^3 runs)

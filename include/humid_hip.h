@@ -1103,6 +1103,12 @@ int humid_stage_scatter(humid_ctx *ctx, const uint32_t *d_perm, const uint32_t *
  * humid_stage_count_dense accepts d_filtered = NULL: every read is usable and lies in
  * [range_lo, range_hi] (checked); the array is counted as it stands and the range only shapes the
  * word-ordered LDS buckets. */
+/* Which road the pairs of the last run / graph stage took (option "pair_split", default 1): a pair whose two ends have
+ * no other pair is settled straight from the pair list (*pairs_direct), the others go through the compact graph
+ * (*pairs_graph); pairs_direct + pairs_graph = the summary's edges.  *full_graph_built: the graph over ALL pairs exists
+ * in the context -- 1 after a run that did not split, else 0 until an accessor (humid_get_leaves / _adjacency /
+ * _clusters / _histogram) has asked for it; the run's results never depend on it.  Any pointer may be NULL. */
+int humid_graph_split_info(humid_ctx *ctx, uint64_t *pairs_direct, uint64_t *pairs_graph, uint32_t *full_graph_built);
 /* HIP-event durations of the dominant kernels of the last humid_stage_count_dense /
  * humid_stage_map_dense pair (k_dedup_lds or k_hash_insert; k_read_map_bucket, k_read_map_part or k_read_map_packed) */
 int humid_stage_kernel_ms(humid_ctx *ctx, float *ms_k_insert, float *ms_k_map, uint32_t *count_mode_used);
