@@ -318,6 +318,30 @@ def test_tiles_make_a_far_list(split, whole, umi_words):
     assert infos[0]["pairs_direct"] > 0 and infos[0]["pairs_graph"] > 0
 
 
+def test_padded_coarse_bin_full_on_the_first_run():
+    """6 000 distinct 24-nt words at d = 1 whose last twelve nucleotides are all the same.  The plan has two
+    combinations of one 12-nt segment each (4^12 >= 6 000 keys apiece); the second one's key is nucleotides 12 .. 23,
+    24 bits, grouped into 2^9 coarse bins (group_words_by_stretch).  Every word has the same key, so all 6 000 land in ONE bin,
+    whose padded room is 6000 / 512 + 6000 / 512 / 4 + 1024 = 11 + 2 + 1024 = 1 037 words: the bin is full, the first
+    run of a new context throws its attempt away and makes every order again with exact bins (and that one bucket of
+    6 000 words, longer than the walk of 1 024, goes on in the tiles).  The padding stays off for the context, hence two
+    fresh ones.  The first twelve nucleotides are 6 000 of the 4^9 values of nine of them: about 0.6 neighbours a word,
+    isolated pairs and rest pairs both."""
+    rng = np.random.default_rng(512)
+    hi = rng.choice(4 ** 9, size=6000, replace=False).astype(U64)
+    u = (hi << U64(24)) | U64(0x5A3C96)
+    words = np.repeat(u, rng.integers(1, 6, size=len(u)))
+    words = np.ascontiguousarray(words[rng.permutation(len(words))])
+    a, b = humid_amd.Dedup(), humid_amd.Dedup()
+    try:
+        b.set_option("pair_split", 0)
+        infos = split_and_whole(a, b, words, np.zeros(len(words), np.uint8))
+        assert infos[0]["pairs_direct"] > 0 and infos[0]["pairs_graph"] > 0
+    finally:
+        a.close()
+        b.close()
+
+
 def test_six_combinations(split, whole):
     words, filt = synth_words(20_000, 6, 12, p_sub=8e-3, p_n=1e-3)
     """d = 2 over 12 nt: six combinations, five of them searched inside their grouping"""
