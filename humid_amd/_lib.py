@@ -66,6 +66,21 @@ class HumidStrandSummary(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+# HUMID_ROAD_* of include/humid_hip.h: the event codes of humid_get_run_roads, by name
+ROADS = {1: "PART_PADDED_REDO", 2: "ORDERS_REDONE", 3: "REGIONS_REGROWN", 4: "FAR_TILES", 5: "CSR_TILES", 6: "JOIN_PIECES"}
+ROADS_MAX = 32
+
+
+class HumidRunRoads(C.Structure):
+    """humid_run_roads of include/humid_hip.h"""
+    _fields_ = [("n_events", C.c_uint32), ("graph_attempts", C.c_uint32), ("events", C.c_uint8 * ROADS_MAX)]
+
+    def asdict(self):
+        n = int(self.n_events)
+        return dict(events=[ROADS[int(e)] for e in self.events[:min(n, ROADS_MAX)]], n_events=n,
+                    graph_attempts=int(self.graph_attempts))
+
+
 HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
@@ -238,6 +253,7 @@ SYMBOLS = {
     "humid_stage_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), u64p]),
     "humid_graph_split_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
+    "humid_get_run_roads": (C.c_int, [C.c_void_p, C.POINTER(HumidRunRoads)]),
     "humid_stage_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), u32p]),
     "humid_stage_route_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "humid_stage_route": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32, u64p,

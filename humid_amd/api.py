@@ -823,6 +823,14 @@ class Dedup(Context):
         self._check(self._lib.humid_graph_split_info(self._h, C.byref(a), C.byref(b), C.byref(f)))
         return dict(pairs_direct=a.value, pairs_graph=b.value, full_graph_built=f.value)
 
+    def run_roads(self):
+        """what the last mutating call retried (humid_get_run_roads): dict(events, n_events, graph_attempts).  events:
+        the names of the first 32 events in order, of PART_PADDED_REDO, ORDERS_REDONE, REGIONS_REGROWN, FAR_TILES,
+        CSR_TILES, JOIN_PIECES; graph_attempts: passes through the compact graph stage's retry loop (0: it did not run)"""
+        r = _lib.HumidRunRoads()
+        self._check(self._lib.humid_get_run_roads(self._h, C.byref(r)))
+        return r.asdict()
+
     def adjacency(self):
         u = int(self.summary["unique"])
         e2 = 2 * int(self.summary["edges"])

@@ -487,6 +487,14 @@ int humid_graph_split_info(humid_ctx *c, uint64_t *pairs_direct, uint64_t *pairs
   return HUMID_OK;
 }
 
+int humid_get_run_roads(humid_ctx *c, humid_run_roads *out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!out) return fail(c, HUMID_E_INVALID, "null argument");
+  if (c->state.holds == CtxState::NOTHING) return fail(c, HUMID_E_STATE, "no completed run or stage call in this context");
+  *out = c->roads;
+  return HUMID_OK;
+}
+
 int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *first_read,
                      uint32_t *degree, uint32_t *cluster_id, uint8_t *is_max_leaf) {
   NEED_LEAVES();

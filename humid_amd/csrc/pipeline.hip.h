@@ -133,6 +133,7 @@ struct CtxState {
 struct humid_ctx {
   int device = 0;
   CtxState state;
+  humid_run_roads roads = {};      // what the last mutating call retried (humid_get_run_roads): cleared with the record, host stores only
   RunKind pass_kind = RUN_PLAIN;   // the kind of the pass now running (PassKind below); RUN_PLAIN between calls
   Arena arena;               // humid_ctx_reserve
   hipStream_t stream = nullptr;
@@ -489,7 +490,12 @@ static int scan_total(humid_ctx *c, const u32 *in, u32 *out, u64 n, u64 *total) 
 }
 
 // ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
-static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; }
+static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; c->roads = humid_run_roads{}; }
+// one retry of the call now running (HUMID_ROAD_*): behind the host wait that showed it, a store on the host
+static inline void road_taken(humid_ctx *c, u8 road) {
+  if (c->roads.n_events < HUMID_ROADS_MAX) c->roads.events[c->roads.n_events] = road;
+  c->roads.n_events++;
+}
 static inline void state_begin_graph(humid_ctx *c) { const bool dense = c->state.dense; state_reset(c); c->state.dense = dense; }
 // the last statement of a mutating entry point that succeeded (a RUN is of the kind of the pass that ran it)
 static inline int state_publish(humid_ctx *c, CtxState::Holds holds) {
@@ -942,6 +948,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   TRY(read_counters(c));
   if (used_padded && c->h_ctr[CTR_SPECIAL]) {          // a coarse bin outgrew its padded room: once more, with the histogram pass
     c->pt_padded = false;
+    road_taken(c, HUMID_ROAD_PART_PADDED_REDO);
     return stage_count_lds(c, d_words, d_filt, N, word_nt, range_lo, range_hi, km, ordered, s, overflowed, wide);
   }
   if (c->h_ctr[CTR_OVERFULL]) { *overflowed = true; return HUMID_OK; }
@@ -1068,7 +1075,7 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   if (getenv("HUMID_TRACE_COUNT"))
     fprintf(stderr, "[rec count] N %u pb %u kbits %u ibits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits,
             ibits, cap1, (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
-  if (c->h_ctr[CTR_SPECIAL]) { c->pt_padded = false; return HUMID_OK; }     // a bin outgrew its room: the exact kernels from now on
+  if (c->h_ctr[CTR_SPECIAL]) { c->pt_padded = false; road_taken(c, HUMID_ROAD_PART_PADDED_REDO); return HUMID_OK; }     // a bin outgrew its room: the exact kernels from now on
   if (c->h_ctr[CTR_OVERFULL]) return HUMID_OK;
   c->last_count_lds = true;
   c->last_count_sorted = false;
@@ -1767,6 +1774,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     big_mask = search ? c->h_ctr[CTR_BIGMASK] : 0;
     u64 twoE = c->h_ctr[CTR_N - 1] & 0xffffffffull;
     if (big_mask) {
+      road_taken(c, HUMID_ROAD_CSR_TILES);
       // some bucket is longer than k_pairs walks: find those runs, count their remaining pairs as
       // tiles, and take the component statistics and the offsets again
       for (u32 seg = 0; seg < plan.ncombo; seg++)
@@ -2007,6 +2015,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   const u32 *seg_valid[MAX_COMBOS] = {nullptr};
   for (int attempt = 0;; attempt++) {
     if (attempt > 5) return fail(c, HUMID_E_INVALID, "internal: the pair list does not settle");
+    c->roads.graph_attempts = (u32)attempt + 1;
     if (search && c->cg_ecap == 0) c->cg_ecap = std::max<u64>((u64)U / 4, 4096);
     const u64 ecap = search ? c->cg_ecap : ER_REGIONS;
     if (ecap / ER_REGIONS + 1 > 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
@@ -2097,6 +2106,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     if (cgs.group_over) {                                // a padded coarse bin of a grouping was full: words are missing
       c->gf_padded = false;                              // from a bucket order -- all of it again with exact bins
+      road_taken(c, HUMID_ROAD_ORDERS_REDONE);
       for (u32 q = 0; q < MAX_COMBOS; q++) ordered_seg[q] = false;
       far = given ? ext_edges : nullptr;
       n_far = given ? n_ext_edges : 0;
@@ -2104,6 +2114,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     if (cgs.overflow) {                                  // a region was full: more room, once more
       c->cg_ecap = cgs.wanted + cgs.wanted / 2 + ER_REGIONS * 64;
+      road_taken(c, HUMID_ROAD_REGIONS_REGROWN);
       // Without pair_split cg_build has relabelled the pairs of the tiles IN PLACE (k_pairs_relabel): that list cannot be
       // used again, the tiles make it once more behind the next search.  With pair_split no graph has been built and the
       // list is intact; it is dropped all the same, so that both paths take the same attempts.  (A search that rode in the groupings spreads its pairs
@@ -2148,7 +2159,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       }
       far = c->cg_far.as<u64>();
       n_far = got;
-      if (n_far) continue;                              // (nothing beyond the walk after all: the list stands)
+      if (n_far) { road_taken(c, HUMID_ROAD_FAR_TILES); continue; }   // (else nothing beyond the walk after all: the list stands)
     }
     if (split) {
       c->cg_er = er;
@@ -2357,6 +2368,7 @@ static int join_append(humid_ctx *c, const char *search, const void *kx, const u
                          c->e_runlo.as<u32>(), c->e_nch.as<u32>());
       TRY(scan_total(c, c->e_nch.as<u32>(), c->e_choff.as<u32>(), U, &n_pieces));
       if (n_pieces >= 0xfffffff0ull) return fail(c, HUMID_E_OVERFLOW, "too many candidate pieces in the %s search", search);
+      if (n_pieces) road_taken(c, HUMID_ROAD_JOIN_PIECES);
       ENSURE(c->e_pc2, ((size_t)n_pieces + 1) * 4);
       ENSURE(c->e_poff2, ((size_t)n_pieces + 1) * 4);
       HIPCHK(hipMemsetAsync(c->e_pc2.as<u32>() + n_pieces, 0, 4, st));

@@ -1109,6 +1109,38 @@ int humid_stage_scatter(humid_ctx *ctx, const uint32_t *d_perm, const uint32_t *
  * in the context -- 1 after a run that did not split, else 0 until an accessor (humid_get_leaves / _adjacency /
  * _clusters / _histogram) has asked for it; the run's results never depend on it.  Any pointer may be NULL. */
 int humid_graph_split_info(humid_ctx *ctx, uint64_t *pairs_direct, uint64_t *pairs_graph, uint32_t *full_graph_built);
+/* Which attempts the last mutating call (a run, humid_accum_add / _finish / _map, a humid_stage_* call that counts or
+ * builds a graph) threw away and took again, in the order they happened.  A record the host keeps while it decides:
+ * it costs the GPU nothing and changes no result.  One event per occurrence:
+ *   HUMID_ROAD_PART_PADDED_REDO  count stage: a padded coarse bin of the partition outgrew its room; the exact
+ *                                partition from then on
+ *   HUMID_ROAD_ORDERS_REDONE     compact graph stage: a padded coarse bin of a bucket order was full; every order
+ *                                is made again with exact bins, from then on
+ *   HUMID_ROAD_REGIONS_REGROWN   compact graph stage: an append region of the pair list was full; more room
+ *   HUMID_ROAD_FAR_TILES         compact graph stage: a bucket is longer than the bounded walk; the tiles made the
+ *                                list of its far pairs and the search was taken again behind them
+ *   HUMID_ROAD_CSR_TILES         per-unique-word graph (option compact_graph 0, humid_accum_finish, humid_stage_graph):
+ *                                the tiles completed the buckets beyond the walk
+ *   HUMID_ROAD_JOIN_PIECES       a candidate join of the edit-distance or strand-symmetric search cut its runs of
+ *                                equal keys into pieces (one event per such join)
+ * n_events counts all of them; events[] holds the first HUMID_ROADS_MAX.  graph_attempts: passes through the retry
+ * loop of the compact graph stage (1 = nothing was retried; 0 = that stage did not run).  The lazy full graph of the
+ * accessors records nothing, and no accessor changes the record.  A stage call that leaves the context's state as it
+ * is (humid_stage_pairs_edit) adds its events to the record of the call before it.  HUMID_E_STATE before the first
+ * successful mutating call and after a failed one. */
+#define HUMID_ROAD_PART_PADDED_REDO 1
+#define HUMID_ROAD_ORDERS_REDONE    2
+#define HUMID_ROAD_REGIONS_REGROWN  3
+#define HUMID_ROAD_FAR_TILES        4
+#define HUMID_ROAD_CSR_TILES        5
+#define HUMID_ROAD_JOIN_PIECES      6
+#define HUMID_ROADS_MAX 32
+typedef struct humid_run_roads {
+  uint32_t n_events;                 /* events of the call, also those beyond HUMID_ROADS_MAX     */
+  uint32_t graph_attempts;
+  uint8_t events[HUMID_ROADS_MAX];   /* HUMID_ROAD_*, in order; 0 behind the last                 */
+} humid_run_roads;
+int humid_get_run_roads(humid_ctx *ctx, humid_run_roads *out);
 /* HIP-event durations of the dominant kernels of the last humid_stage_count_dense /
  * humid_stage_map_dense pair (k_dedup_lds or k_hash_insert; k_read_map_bucket, k_read_map_part or k_read_map_packed) */
 int humid_stage_kernel_ms(humid_ctx *ctx, float *ms_k_insert, float *ms_k_map, uint32_t *count_mode_used);

@@ -19,8 +19,13 @@ def dd():
     d.close()
 
 
-def check_edit(dd, words, filt, n, d, maximum, deep=True):
+def check_edit(dd, words, filt, n, d, maximum, deep=True, roads=None):
+    """roads: a list that receives what this run retried (Dedup.run_roads), read before the accessors"""
     cid, keep, s = dd.run(words, filt, word_nt=n, distance=d, method=int(maximum), edit=True)
+    taken = dd.run_roads()
+    if roads is not None:
+        print("roads", taken)
+        roads.append(taken)
     p = orc.Pipeline(n)
     p.read_data(words, filt)
     p.find_edit_neighbours(d)
@@ -39,6 +44,7 @@ def check_edit(dd, words, filt, n, d, maximum, deep=True):
         assert np.array_equal(off.astype(np.uint64), ooff) and np.array_equal(idx, oidx)
         cl, ocl = dd.clusters(), p.clusters()
         assert np.array_equal(cl["size"], ocl["size"]) and np.array_equal(cl["max_leaf"], ocl["max_leaf"])
+        assert dd.run_roads() == taken
     return s
 
 
@@ -222,9 +228,12 @@ def test_edit_joins_cut_long_runs_into_pieces(dd):
     filt = np.concatenate([np.zeros(len(words) - len(extra), np.uint8), ef])
     perm = rng.permutation(len(words))
     words, filt = words[perm], filt[perm]
-    check_edit(dd, words, filt, 24, 2, False, deep=True)
+    roads = []
+    check_edit(dd, words, filt, 24, 2, False, deep=True, roads=roads)
     dd.set_option("bucket_walk", 37)                     # nearly every run in pieces
     try:
-        check_edit(dd, words[:20_000], filt[:20_000], 24, 3, True, deep=False)
+        check_edit(dd, words[:20_000], filt[:20_000], 24, 3, True, deep=False, roads=roads)
     finally:
         dd.set_option("bucket_walk", 1024)
+    for r in roads:                                      # (given pairs: one attempt of the graph stage, nothing of its own to retry)
+        assert r["n_events"] >= 1 and set(r["events"]) == {"JOIN_PIECES"} and r["graph_attempts"] == 1, r

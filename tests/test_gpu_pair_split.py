@@ -119,9 +119,11 @@ class Builder:
 def snapshot(dd, words, filt, n, d, maximum, **kw):
     cid, keep, s = dd.run(words, filt, word_nt=n, distance=d, method=int(maximum), **kw)
     before = dd.graph_split_info()
+    taken = dd.run_roads()
     off, idx = dd.adjacency()
     return dict(cid=cid, keep=keep, summary={k: s[k] for k in ("total", "usable", "unique", "clusters", "edges", "nonsingle")},
-                leaves=dd.leaves(), off=off, idx=idx, clusters=dd.clusters(), info=before, info_after=dd.graph_split_info())
+                leaves=dd.leaves(), off=off, idx=idx, clusters=dd.clusters(), info=before, info_after=dd.graph_split_info(),
+                roads=taken, roads_after=dd.run_roads())
 
 
 def assert_same_arrays(a, b):
@@ -134,18 +136,27 @@ def assert_same_arrays(a, b):
             assert np.array_equal(a[part][k], b[part][k]), (part, k)
 
 
-def split_and_whole(split, whole, words, filt, n=24, d=1, methods=(False, True), options=()):
-    """both contexts against the oracle and against each other; returns the split context's info per method"""
+def split_and_whole(split, whole, words, filt, n=24, d=1, methods=(False, True), options=(), roads=None):
+    """both contexts against the oracle and against each other; returns the split context's info per method.
+    roads: a list that receives, per method, what the runs retried (Dedup.run_roads): dict(split, whole) of the two
+    runs against the oracle -- the FIRST runs of the input on fresh contexts -- and dict(split, whole) of the two runs
+    of the same input behind them"""
     infos = []
     try:
         for key, value, _ in options:
             split.set_option(key, value)
             whole.set_option(key, value)
         for maximum in methods:
-            s1 = check_against_oracle(split, words, filt, n, d, maximum)
-            s2 = check_against_oracle(whole, words, filt, n, d, maximum)
+            first = []
+            s1 = check_against_oracle(split, words, filt, n, d, maximum, roads=first)
+            s2 = check_against_oracle(whole, words, filt, n, d, maximum, roads=first)
             a = snapshot(split, words, filt, n, d, maximum)
             b = snapshot(whole, words, filt, n, d, maximum)
+            print("roads of the second runs", a["roads"], b["roads"])
+            assert a["roads_after"] == a["roads"] and b["roads_after"] == b["roads"]      # (the accessors record nothing)
+            if roads is not None:
+                roads.append(dict(split=first[0], whole=first[1]))
+                roads.append(dict(split=a["roads"], whole=b["roads"]))
             for k in ("unique", "clusters", "edges", "nonsingle"):
                 assert s1[k] == s2[k] == a["summary"][k], k
             assert_same_arrays(a, b)
@@ -296,9 +307,15 @@ def test_region_full_on_the_first_run(umi_words):
     a, b = humid_amd.Dedup(), humid_amd.Dedup()
     try:
         b.set_option("pair_split", 0)
-        infos = split_and_whole(a, b, words, filt)
+        roads = []
+        infos = split_and_whole(a, b, words, filt, roads=roads)
         assert infos[0]["pairs_direct"] + infos[0]["pairs_graph"] == 5743
         assert infos[0]["pairs_direct"] > 0 and infos[0]["pairs_graph"] > 0
+        for dd in ("split", "whole"):
+            assert roads[0][dd]["events"].count("REGIONS_REGROWN") >= 1, roads[0]
+            assert roads[0][dd]["graph_attempts"] == 1 + roads[0][dd]["n_events"]
+            for later in roads[1:]:                         # (the context remembers the room)
+                assert later[dd] == dict(events=[], n_events=0, graph_attempts=1), later
     finally:
         a.close()
         b.close()
@@ -314,8 +331,11 @@ def test_tiles_make_a_far_list(split, whole, umi_words):
     """bucket_walk = 1: nearly every bucket of two words and more goes on in the tiles, whose pairs are marked by
     k_mark_pairs"""
     words, filt = umi_words
-    infos = split_and_whole(split, whole, words, filt, options=[("bucket_walk", 1, 1024)])
+    roads = []
+    infos = split_and_whole(split, whole, words, filt, options=[("bucket_walk", 1, 1024)], roads=roads)
     assert infos[0]["pairs_direct"] > 0 and infos[0]["pairs_graph"] > 0
+    for r in roads:
+        assert "FAR_TILES" in r["split"]["events"] and "FAR_TILES" in r["whole"]["events"], r
 
 
 def test_padded_coarse_bin_full_on_the_first_run():
@@ -335,8 +355,14 @@ def test_padded_coarse_bin_full_on_the_first_run():
     a, b = humid_amd.Dedup(), humid_amd.Dedup()
     try:
         b.set_option("pair_split", 0)
-        infos = split_and_whole(a, b, words, np.zeros(len(words), np.uint8))
+        roads = []
+        infos = split_and_whole(a, b, words, np.zeros(len(words), np.uint8), roads=roads)
         assert infos[0]["pairs_direct"] > 0 and infos[0]["pairs_graph"] > 0
+        for dd in ("split", "whole"):
+            ev = roads[0][dd]["events"]
+            assert "ORDERS_REDONE" in ev and "FAR_TILES" in ev[ev.index("ORDERS_REDONE"):], roads[0]
+            for later in roads[1:]:                         # (the padding stays off: the tiles alone)
+                assert later[dd] == dict(events=["FAR_TILES"], n_events=1, graph_attempts=2), later
     finally:
         a.close()
         b.close()

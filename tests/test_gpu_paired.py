@@ -146,14 +146,24 @@ def test_key_runs_longer_than_the_walk(dd, n, d, forced, s, key_bits):
     dd.set_option("plan_segments", forced)
     try:
         got = dd.run_paired(words, filt, word_nt=n, distance=d)
+        pieces = [dd.run_roads()]
         assert_matches(dd, got, t)
+        assert dd.run_roads() == pieces[0]
         if n == 24:
             t2 = pt.run(words, filt, 24, 2, 1)
-            assert_matches(dd, dd.run_paired(words, filt, word_nt=24, distance=2, method=1), t2)
+            got = dd.run_paired(words, filt, word_nt=24, distance=2, method=1)
+            pieces.append(dd.run_roads())
+            assert_matches(dd, got, t2)
     finally:
         dd.set_option("bucket_walk", 1024)
         dd.set_option("plan_segments", 0)
-    assert_matches(dd, dd.run_paired(words, filt, word_nt=n, distance=d), t)
+    got = dd.run_paired(words, filt, word_nt=n, distance=d)
+    whole_runs = dd.run_roads()
+    assert_matches(dd, got, t)
+    print("roads", pieces, whole_runs)
+    for r in pieces:                                     # (the pairs are given to the graph stage: one attempt)
+        assert r["n_events"] >= 1 and set(r["events"]) == {"JOIN_PIECES"} and r["graph_attempts"] == 1, r
+    assert run <= 1024 and whole_runs == dict(events=[], n_events=0, graph_attempts=1), (run, whole_runs)
 
 
 @pytest.mark.parametrize("n", [8, 24, 48, 64])

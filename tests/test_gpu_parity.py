@@ -24,6 +24,7 @@ def dd(request):
     d.set_option("tile_partition", request.param[2])
     d.count_mode = request.param[0]
     d.count_order = request.param[1]
+    d.tile_partition = request.param[2]
     yield d
     d.close()
 
@@ -37,8 +38,14 @@ def oracle_full(words, filt, n, d, maximum):
     return p, cid, keep
 
 
-def check_against_oracle(dd, words, filt, n, d, maximum, deep=True):
+def check_against_oracle(dd, words, filt, n, d, maximum, deep=True, roads=None):
+    """roads: a list that receives what this run retried (Dedup.run_roads), read right behind the run -- before the
+    accessors, which must leave the record alone (the lazy full graph build included)"""
     cid, keep, s = dd.run(words, filt, word_nt=n, distance=d, method=int(maximum))
+    taken = dd.run_roads()
+    if roads is not None:
+        print("roads", taken)
+        roads.append(taken)
     p, ocid, okeep = oracle_full(words, filt, n, d, maximum)
     os_ = p.summary()
     for k in ("total", "usable", "unique", "clusters", "edges"):
@@ -61,6 +68,7 @@ def check_against_oracle(dd, words, filt, n, d, maximum, deep=True):
         assert np.array_equal(cl["max_count"].astype(np.uint64), ocl["max_count"])
         assert np.array_equal(cl["max_leaf"], ocl["max_leaf"])
         assert dd.histograms() == orc.histograms(p)
+        assert dd.run_roads() == taken
     return s
 
 
@@ -432,25 +440,38 @@ def test_large_bucket(dd):
     check_against_oracle(dd, words, np.zeros(n_reads, np.uint8), 24, 1, True)
 
 
+# The longest bucket of any combination of the plan (2 halves of 12 nt; 15 combinations of four 2-nt segments; 10 of two
+# segments of 3 or 4 nt; 3 of one third of 40 nt) in the read sets of the two tests below, per walk -- every walk has a seed
+# of its own.  Counted with numpy from the unique words.  Only a bucket LONGER than the walk is left to the tiles.
+LONGEST_BUCKET = {(120_000, 24, 1): {1: 8, 7: 7, 300: 7}, (60_000, 12, 2): {1: 8, 7: 7, 300: 7},
+                  (40_000, 16, 3): {1: 18, 7: 16, 300: 18}, (20_000, 40, 2): {1: 9, 7: 13, 300: 9}}
+
+
 @pytest.mark.parametrize("walk", [1, 7, 300])
 @pytest.mark.parametrize("cfg", [(120_000, 24, 1), (60_000, 12, 2), (40_000, 16, 3), (20_000, 40, 2)])
 def test_tiles_take_over_beyond_the_bucket_walk(dd1, walk, cfg):
     """k_pairs bounded to `walk` followers: every bucket longer than that is completed by k_big_runs +
     k_pairs_tiles (squares of the upper triangle, the partly-near squares filtered pair by pair).  With a
-    tiny walk nearly every bucket of every combination takes that road: all arrays against the oracle."""
+    walk of 1 nearly every bucket of every combination takes that road: all arrays against the oracle.
+    The record of the run says whether it was taken (FAR_TILES): with a walk of 1 in every case, with 7 where words
+    are 16 and 40 nt -- the buckets of the 24-nt and 12-nt cases are 7 words at most --, with 300 in none: those six
+    cases compare a search that never leaves the walk."""
     n_reads, n, d = cfg
+    roads = []
     dd1.set_option("bucket_walk", walk)
     try:
         if n <= 32:
             words, filt = synth_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
-            check_against_oracle(dd1, words, filt, n, d, False)
-            check_against_oracle(dd1, words, filt, n, d, True, deep=False)
+            check_against_oracle(dd1, words, filt, n, d, False, roads=roads)
+            check_against_oracle(dd1, words, filt, n, d, True, deep=False, roads=roads)
         else:
             from humid_amd.synth import synth_wide_words
             words, filt = synth_wide_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
-            check_against_oracle(dd1, words, filt, n, d, False)
+            check_against_oracle(dd1, words, filt, n, d, False, roads=roads)
     finally:
         dd1.set_option("bucket_walk", 1024)
+    for r in roads:
+        assert ("FAR_TILES" in r["events"]) == (LONGEST_BUCKET[cfg][walk] > walk), r
 
 
 @pytest.mark.parametrize("walk", [1, 7])
@@ -459,22 +480,27 @@ def test_per_unique_word_graph_with_a_small_walk(dd1, walk, cfg):
     """compact_graph 0: the search fills the CSR rows per unique word (k_pairs PM_COUNT / PM_FILL), the form the
     multi-GPU all-gather mode builds on.  With a tiny walk the buckets of three words and more of every
     combination are completed by the CSR modes of k_pairs_tiles, for one-word and two-word words: all arrays
-    against the oracle (the shapes of test_tiles_take_over_beyond_the_bucket_walk, there on the compact graph)."""
+    against the oracle (the shapes of test_tiles_take_over_beyond_the_bucket_walk, there on the compact graph).
+    The record says CSR_TILES for three of the four cases: the 12-nt words' buckets are 7 words at most, so a walk
+    of 7 leaves the tiles nothing (LONGEST_BUCKET)."""
     n_reads, n, d = cfg
+    roads = []
     dd1.set_option("compact_graph", 0)
     dd1.set_option("bucket_walk", walk)
     try:
         if n <= 32:
             words, filt = synth_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
-            check_against_oracle(dd1, words, filt, n, d, False)
-            check_against_oracle(dd1, words, filt, n, d, True)
+            check_against_oracle(dd1, words, filt, n, d, False, roads=roads)
+            check_against_oracle(dd1, words, filt, n, d, True, roads=roads)
         else:
             from humid_amd.synth import synth_wide_words
             words, filt = synth_wide_words(n_reads, 5 + walk, n, p_sub=8e-3, p_n=1e-3)
-            check_against_oracle(dd1, words, filt, n, d, False)
+            check_against_oracle(dd1, words, filt, n, d, False, roads=roads)
     finally:
         dd1.set_option("bucket_walk", 1024)
         dd1.set_option("compact_graph", 1)
+    for r in roads:                                          # (the per-unique-word graph has no retry loop: no attempts)
+        assert r["events"] == (["CSR_TILES"] if LONGEST_BUCKET[cfg][walk] > walk else []) and r["graph_attempts"] == 0, r
 
 
 def test_stage_graph_with_a_small_walk():
@@ -533,13 +559,16 @@ def test_multi_square_run_on_the_per_unique_word_graph(dd1, d):
     filt = np.zeros(len(words), np.uint8)
     dd1.set_option("compact_graph", 0)
     dd1.set_option("bucket_walk", 300)
+    roads = []
     try:
-        s = check_against_oracle(dd1, words, filt, 24, d, False)
+        s = check_against_oracle(dd1, words, filt, 24, d, False, roads=roads)
         assert s["unique"] == 5000 and s["edges"] > 0
-        check_against_oracle(dd1, words, filt, 24, d, True, deep=False)
+        check_against_oracle(dd1, words, filt, 24, d, True, deep=False, roads=roads)
     finally:
         dd1.set_option("bucket_walk", 1024)
         dd1.set_option("compact_graph", 1)
+    for r in roads:
+        assert r["events"] == ["CSR_TILES"] and r["graph_attempts"] == 0, r
 
 
 @pytest.mark.parametrize("d", [1, 2])
@@ -561,7 +590,13 @@ def test_grouping_of_a_huge_key_bucket(dd1, block_words):
     """bucket order of the second-half combination comes from a two-level grouping (k_group_fine); 20 000 /
     60 000 distinct words with the SAME last 12 nucleotides put that many words into one coarse bin -- the
     roads for bins of 8161 .. 32768 words and beyond -- and into one key bucket (tiles); plus ordinary
-    words around them"""
+    words around them.
+    What the runs retry (Dedup.run_roads): every one of them goes through the tiles (FAR_TILES), and every event is one
+    discarded attempt.  On the MI355X, this test alone: [ORDERS_REDONE, REGIONS_REGROWN, FAR_TILES] at d = 1,
+    [REGIONS_REGROWN, FAR_TILES] at d = 2, [FAR_TILES] behind the library sort for 20 000 words, and the same without
+    ORDERS_REDONE for 60 000.  A context meets the full padded bin once and groups with exact bins from then on (the
+    bin roads named above are taken by every later run), and other tests share this context: ORDERS_REDONE is only
+    asserted to be absent behind the first run of the test."""
     rng = np.random.default_rng(5)
     heads = rng.choice(1 << 24, size=block_words, replace=False).astype(np.uint64)
     block = (heads << np.uint64(24)) | np.uint64(0x6b1e57)
@@ -570,11 +605,16 @@ def test_grouping_of_a_huge_key_bucket(dd1, block_words):
     filt = np.concatenate([filt, np.zeros(len(words) - len(filt), np.uint8)])
     perm = rng.permutation(len(words))
     words, filt = words[perm], filt[perm]
+    roads = []
     for d in (1, 2):
-        check_against_oracle(dd1, words, filt, 24, d, False, deep=(d == 1))
+        check_against_oracle(dd1, words, filt, 24, d, False, deep=(d == 1), roads=roads)
     dd1.set_option("group_buckets", 0)                      # and the library sort gives the same
-    check_against_oracle(dd1, words, filt, 24, 1, False, deep=False)
+    check_against_oracle(dd1, words, filt, 24, 1, False, deep=False, roads=roads)
     dd1.set_option("group_buckets", 1)
+    for k, r in enumerate(roads):
+        assert "FAR_TILES" in r["events"] and set(r["events"]) <= {"ORDERS_REDONE", "REGIONS_REGROWN", "FAR_TILES"}, r
+        assert r["graph_attempts"] == 1 + r["n_events"], r
+        assert k == 0 or "ORDERS_REDONE" not in r["events"], r
 
 
 def test_padded_partition_outgrown_by_duplicated_words(dd):
@@ -587,13 +627,21 @@ def test_padded_partition_outgrown_by_duplicated_words(dd):
     hot = rng.random(len(words)) < 0.35
     words = words.copy()
     words[hot] = np.uint64(0x0123456789ab)
+    roads = []
     dd.set_option("padded_partition", 1)
-    for rep in range(2):
-        s = check_against_oracle(dd, words, filt, 24, 1, False, deep=(rep == 0))
-        assert s["unique"] > 100_000
-    words2, filt2 = synth_words(200_000, 10, 24, p_sub=3e-3)
-    check_against_oracle(dd, words2, filt2, 24, 1, False, deep=False)
-    dd.set_option("padded_partition", 1)
+    try:
+        for rep in range(2):
+            s = check_against_oracle(dd, words, filt, 24, 1, False, deep=(rep == 0), roads=roads)
+            assert s["unique"] > 100_000
+        words2, filt2 = synth_words(200_000, 10, 24, p_sub=3e-3)
+        check_against_oracle(dd, words2, filt2, 24, 1, False, deep=False, roads=roads)
+    finally:
+        # the run above turned the padding off inside the context; every context of the fixture is created with the
+        # default, 1 (the fixture sets count_mode, count_order and tile_partition only): the tests behind this one get it back
+        dd.set_option("padded_partition", 1)
+    redo = [r["events"].count("PART_PADDED_REDO") for r in roads]
+    # only the tile partition has padded bins: the global table does not partition, the library radix passes have no bins
+    assert redo == ([1, 0, 0] if dd.count_mode == 0 and dd.tile_partition == 1 else [0, 0, 0]), roads
 
 
 @pytest.mark.parametrize("top30,n_special,expect_records", [(0x15555555, 40, True), (0x2aaaaaaa, 200, True), (0x3fffffff, 40, True),
