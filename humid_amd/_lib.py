@@ -228,6 +228,15 @@ SYMBOLS = {
     "humid_accum_get_leaves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "humid_accum_info": (C.c_int, [C.c_void_p, u32p, u64p, u64p, u64p, u64p, u32p]),
     "humid_accum_clear": (C.c_int, [C.c_void_p]),
+    "humid_accum_begin_keyed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "humid_accum_add_keyed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "humid_accum_add_keyed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "humid_accum_map_keyed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, u64p]),
+    "humid_accum_map_keyed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                               C.c_void_p, C.c_void_p, u64p]),
+    "humid_accum_get_leaves_keyed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "humid_accum_keyed_info": (C.c_int, [C.c_void_p, u32p, u32p, u64p]),
     "humid_get_leaves": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "humid_get_adjacency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "humid_get_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

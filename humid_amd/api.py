@@ -867,6 +867,11 @@ class Dedup(Context):
         object and returns the new one."""
         return Accumulator(self, word_nt)
 
+    def keyed_accumulator(self, word_nt=12, key_nt=0):
+        """A read set with 64-bit keys fed in chunks (include/humid_hip.h, humid_accum_*_keyed): empties any earlier
+        accumulator of this object, of either kind, and returns the new one."""
+        return KeyedAccumulator(self, word_nt, key_nt)
+
 
 class Accumulator:
     """One read set deduplicated in chunks: add() every chunk, finish(), then map() every chunk.
@@ -950,6 +955,99 @@ class Accumulator:
         self._dd._check(self._lib.humid_accum_info(self._dd._h, C.byref(nt), *[C.byref(x) for x in v], C.byref(fin)))
         return dict(word_nt=nt.value, chunks=v[0].value, total=v[1].value, usable=v[2].value, unique=v[3].value,
                     finished=bool(fin.value))
+
+    def clear(self):
+        self._dd._check(self._lib.humid_accum_clear(self._dd._h))
+
+
+class KeyedAccumulator:
+    """One read set deduplicated per key in chunks (include/humid_hip.h, humid_accum_*_keyed): add() every chunk with
+    its keys, finish(), then map() every chunk.
+
+    The results are those of Dedup.run_keyed over all added reads sorted by global index.  word_nt is 1 .. 32; key_nt = 0
+    takes any 64-bit key, key_nt = 1 .. 32 promises keys < 4**key_nt (a 16-nt barcode and a 12-nt UMI then share one
+    uint64 on the device).  After finish(), dd.group_keys(), dd.group_stats(), dd.adjacency(), dd.clusters() and
+    dd.histogram() answer for the accumulated set (until the first map()); dd.leaves() does not (it asks for first_read,
+    which only a complete run has: leaves() of this object gives the list with its global first indices).
+    Whitelist correction composes per chunk: keys_out, status, _ = dd.correct_keys(keys, filtered), then add or map
+    keys_out with filtered | (status >= BC_AMBIGUOUS)."""
+
+    def __init__(self, dd: Dedup, word_nt: int, key_nt: int):
+        self._dd = dd
+        self._lib = dd._lib
+        dd._check(self._lib.humid_accum_begin_keyed(dd._h, int(word_nt), int(key_nt)))
+        self.word_nt, self.key_nt = int(word_nt), int(key_nt)
+        self._next = 0
+
+    @staticmethod
+    def _chunk(words, keys, filtered):
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("filtered must be one-dimensional")
+        return _keys_u64(words, f.shape, "words"), _keys_u64(keys, f.shape), f
+
+    def add(self, words, keys, filtered, base=None):
+        """adds a chunk whose first read has global index `base` (default: the reads added so far); returns the base used"""
+        w, k, f = self._chunk(words, keys, filtered)
+        base = self._next if base is None else int(base)
+        self._dd._check(self._lib.humid_accum_add_keyed(self._dd._h, _vp(w), _vp(k), _vp(f), len(f), base))
+        self._next = max(self._next, base + len(f))
+        return base
+
+    def add_device(self, d_words, d_keys, d_filtered, n_reads, base):
+        """the same with integer device pointers"""
+        self._dd._check(self._lib.humid_accum_add_keyed_device(self._dd._h, C.c_void_p(d_words), C.c_void_p(d_keys),
+                                                               C.c_void_p(d_filtered), n_reads, int(base)))
+        self._next = max(self._next, int(base) + n_reads)
+        return int(base)
+
+    def finish(self, distance=1, method=DIRECTIONAL, edit=False):
+        """clusters the accumulated entries; returns the summary dict of Dedup.run_keyed over all added reads"""
+        dd = self._dd
+        dd.set_option("edit_distance", int(bool(edit)))
+        s = _lib.HumidSummary()
+        dd._check(self._lib.humid_accum_finish(dd._h, distance, method, C.byref(s)))
+        dd.summary = dd._grouped_summary = dd._keyed_summary = s.asdict()
+        dd._wide = False
+        return dd.summary
+
+    def map(self, words, keys, filtered, base):
+        """(cluster_id u32[N], keep u8[N], n_unknown) of a chunk whose first read has global index `base`"""
+        w, k, f = self._chunk(words, keys, filtered)
+        cid = np.zeros(len(f), dtype=np.uint32)
+        keep = np.zeros(len(f), dtype=np.uint8)
+        unknown = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_map_keyed(self._dd._h, _vp(w), _vp(k), _vp(f), len(f), int(base), _vp(cid),
+                                                        _vp(keep), C.byref(unknown)))
+        return cid, keep, unknown.value
+
+    def map_device(self, d_words, d_keys, d_filtered, n_reads, base, d_cluster_id, d_keep):
+        """the same with integer device pointers; the results stay in HBM.  Returns n_unknown."""
+        unknown = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_map_keyed_device(self._dd._h, C.c_void_p(d_words), C.c_void_p(d_keys),
+                                                               C.c_void_p(d_filtered), n_reads, int(base),
+                                                               C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(unknown)))
+        return unknown.value
+
+    def leaves(self):
+        """dict(key u64[U], word u64[U], count u32[U], first u64[U]) of the accumulated list, ascending by (key, word)"""
+        n = C.c_uint64()
+        self._dd._check(self._lib.humid_accum_get_leaves_keyed(self._dd._h, None, None, None, None, 0, C.byref(n)))
+        u = n.value
+        out = dict(key=np.zeros(u, np.uint64), word=np.zeros(u, np.uint64), count=np.zeros(u, np.uint32),
+                   first=np.zeros(u, np.uint64))
+        self._dd._check(self._lib.humid_accum_get_leaves_keyed(self._dd._h, _vp(out["key"]), _vp(out["word"]),
+                                                               _vp(out["count"]), _vp(out["first"]), u, C.byref(n)))
+        return out
+
+    def info(self):
+        """dict(word_nt, key_nt, entry_words, n_keys, chunks, total, usable, unique, finished)"""
+        nt, fin, knt, ew, nk = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        v = [C.c_uint64() for _ in range(4)]
+        self._dd._check(self._lib.humid_accum_info(self._dd._h, C.byref(nt), *[C.byref(x) for x in v], C.byref(fin)))
+        self._dd._check(self._lib.humid_accum_keyed_info(self._dd._h, C.byref(knt), C.byref(ew), C.byref(nk)))
+        return dict(word_nt=nt.value, key_nt=knt.value, entry_words=ew.value, n_keys=nk.value, chunks=v[0].value,
+                    total=v[1].value, usable=v[2].value, unique=v[3].value, finished=bool(fin.value))
 
     def clear(self):
         self._dd._check(self._lib.humid_accum_clear(self._dd._h))

@@ -502,7 +502,7 @@ int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *fi
   if (U == 0) return HUMID_OK;
   if (first_read && !state_has_run(c))
     return fail(c, HUMID_E_STATE, "first_read is only available after a single-GPU humid_dedup_run*");
-  if (word && state_run_is(c, RUN_GROUPED) && (c->gk_leaf_nt || c->g_wpr != (c->gk_word_nt > 32 ? 2u : 1u))) {
+  if (word && state_groups_are(c, RUN_GROUPED) && (c->gk_leaf_nt || c->g_wpr != (c->gk_word_nt > 32 ? 2u : 1u))) {
     // grouped internal words -> the caller's words (the group goes to humid_get_leaf_groups)
     std::vector<u64> iw(U * c->g_wpr);
     HIPCHK(hipMemcpyAsync(iw.data(), c->g_word, U * 8 * c->g_wpr, hipMemcpyDeviceToHost, c->stream));
@@ -521,7 +521,7 @@ int humid_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint32_t *fi
 
 int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
   NEED_LEAVES();
-  if (!state_run_is(c, RUN_GROUPED)) return fail(c, HUMID_E_STATE, "the last run was not a grouped run");
+  if (!state_groups_are(c, RUN_GROUPED)) return fail(c, HUMID_E_STATE, "the last run was not a grouped run");
   size_t U = (size_t)c->gU;
   if (U == 0 || !group) return HUMID_OK;
   if (!c->gk_leaf_nt) { memset(group, 0, U * 4); return HUMID_OK; }
@@ -534,12 +534,12 @@ int humid_get_leaf_groups(humid_ctx *c, uint32_t *group) {
 
 int humid_get_group_keys(humid_ctx *c, uint64_t *keys, uint64_t cap, uint64_t *n_out) {
   NEED_LEAVES();
-  if (!state_run_is(c, RUN_KEYED)) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
+  if (!state_groups_are(c, RUN_KEYED)) return fail(c, HUMID_E_STATE, "the last run was not a keyed run");
   if (!n_out) return fail(c, HUMID_E_INVALID, "null argument");
   *n_out = c->kr_n;
   const u64 take = c->kr_n < cap ? c->kr_n : cap;
   if (take && keys) {
-    D2H(keys, c->kr_keys.p, take * 8);
+    D2H(keys, state_keyed_graph(c) ? c->ac_keys.p : c->kr_keys.p, take * 8);
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return HUMID_OK;
@@ -975,11 +975,15 @@ int humid_get_histogram(humid_ctx *c, uint32_t which, uint64_t *keys, uint64_t *
 // the leaves, one lower-bound search per group boundary, one difference per group.  Runs on the first call after a
 // run; every later call finds the record's stats_current.  Nothing of g_word is copied to the host.
 static int group_stats(humid_ctx *c) {
-  if (!state_has_run(c)) return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
+  if (!state_has_run(c) && !state_keyed_graph(c))
+    return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
   if (c->state.stats_current) return HUMID_OK;
+  // (the scan below carries the reads in 32 bits: a run holds fewer, the reads of a keyed accumulator need not)
+  if (c->usable > 0xffffffffull)
+    return fail(c, HUMID_E_UNSUPPORTED, "group statistics over %llu accumulated reads (more than 2^32-1)", (ull)c->usable);
   hipStream_t st = c->stream;
   const u32 U = c->gU;
-  const u32 G = state_run_is(c, RUN_KEYED) ? c->kr_n : state_run_is(c, RUN_GROUPED) ? c->gk_groups : 1u;
+  const u32 G = state_groups_are(c, RUN_KEYED) ? c->kr_n : state_run_is(c, RUN_GROUPED) ? c->gk_groups : 1u;
   const size_t off_bytes = ((size_t)G + 1) * 4;
   ENSURE(c->gs_loff, off_bytes);
   ENSURE(c->gs_coff, off_bytes);
@@ -993,7 +997,7 @@ static int group_stats(humid_ctx *c) {
   } else {
     ENSURE(c->gs_ps, (size_t)U * 8);
     TRY(exscan_in<u64>(c, GsPairIn{c->g_cnt, c->deg.as<u32>()}, c->gs_ps.as<u64>(), U));
-    const u32 gnt = state_run_is(c, RUN_GROUPED) ? c->gk_leaf_nt : 0u, wb = 2 * c->gk_word_nt;
+    const u32 gnt = state_groups_are(c, RUN_GROUPED) ? c->gk_leaf_nt : 0u, wb = 2 * c->gk_word_nt;
     const u32 nb = grid_stride_blocks((u64)G + 1);
     if (c->g_wpr == 2)
       hipLaunchKernelGGL(k_gs_offsets<W2>, dim3(nb), dim3(256), 0, st, (const W2 *)c->g_word, c->pos.as<u32>(), U, (u32)c->C, wb,
@@ -1428,15 +1432,16 @@ int humid_cluster_graph(humid_ctx *c, const uint32_t *count, const uint32_t *nbr
 // the record of a finish points at the accumulator's arrays: it ends with them
 // (free_memory false: humid_accum_begin keeps the blocks for the next accumulator, humid_accum_clear returns them)
 static void accum_release(humid_ctx *c, bool free_memory) {
-  if (state_has_leaves(c) && c->gU && c->g_word == c->ac_word[c->ac_cur].p) state_reset(c);
+  if (state_has_leaves(c) && c->gU && (c->g_word == c->ac_word[c->ac_cur].p || c->g_word == c->ac_iword.p)) state_reset(c);
   if (free_memory) {
     for (int k = 0; k < 2; k++) { c->ac_word[k].release(); c->ac_cnt[k].release(); c->ac_first[k].release(); }
     c->ac_cid.release(); c->ac_ismax.release(); c->ac_lcid.release(); c->ac_lismax.release();
     c->ac_split.release(); c->ac_tcnt.release(); c->ac_toff.release(); c->ac_flag.release();
+    c->ac_head.release(); c->ac_hpos.release(); c->ac_keys.release(); c->ac_iword.release();
   }
-  c->ac_on = c->ac_finished = false;
-  c->ac_nt = c->ac_cur = 0;
-  c->ac_U = c->ac_chunks = c->ac_total = c->ac_usable = 0;
+  c->ac_on = c->ac_finished = c->ac_keyed = false;
+  c->ac_nt = c->ac_cur = c->ac_key_nt = c->ac_ent_nt = 0;
+  c->ac_U = c->ac_chunks = c->ac_total = c->ac_usable = c->ac_G = 0;
 }
 
 int humid_accum_begin(humid_ctx *c, uint32_t word_nt) {
@@ -1450,6 +1455,21 @@ int humid_accum_begin(humid_ctx *c, uint32_t word_nt) {
   return HUMID_OK;
 }
 
+int humid_accum_begin_keyed(humid_ctx *c, uint32_t word_nt, uint32_t key_nt) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  TRY(check_run_args(c, 0, word_nt, 0, 32));
+  if (key_nt > 32) return fail(c, HUMID_E_INVALID, "key_nt must be 0 (any 64-bit key) or 1 .. 32");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  accum_release(c, false);
+  c->ac_on = c->ac_keyed = true;
+  c->ac_nt = word_nt;
+  c->ac_key_nt = key_nt;
+  // one uint64 `key << 2 * word_nt | word` while it holds both; else {key, word}, a word of 32 + key_nt nucleotides
+  c->ac_ent_nt = (key_nt && key_nt + word_nt <= 32) ? key_nt + word_nt : 32 + (key_nt ? key_nt : 32);
+  return HUMID_OK;
+}
+
 int humid_accum_clear(humid_ctx *c) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   HIPCHK(hipSetDevice(c->device));
@@ -1458,22 +1478,30 @@ int humid_accum_clear(humid_ctx *c) {
   return HUMID_OK;
 }
 
-// what add and map refuse before anything moves
-static int accum_chunk_args(humid_ctx *c, const void *words, const void *filtered, uint64_t n_reads, bool device) {
-  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+#define ACCUM_NEED(keyed)                                                                                        \
+  do {                                                                                                           \
+    if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");                                                \
+    if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");          \
+    if (c->ac_keyed != (keyed))                                                                                  \
+      return fail(c, HUMID_E_STATE, (keyed) ? "the accumulator of this context is a plain one (humid_accum_begin_keyed)" \
+                                            : "the accumulator of this context is a keyed one: use the humid_accum_*_keyed calls"); \
+  } while (0)
+
+// what add and map refuse before anything moves (key: of the keyed calls)
+static int accum_chunk_args(humid_ctx *c, bool keyed, const void *words, const void *key, const void *filtered, uint64_t n_reads,
+                            bool device) {
+  ACCUM_NEED(keyed);
   if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "a chunk of %llu reads exceeds 2^31-1", (ull)n_reads);
-  if (n_reads && (!words || !filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads && (!words || !filtered || (keyed && !key))) return fail(c, HUMID_E_INVALID, "null buffer");
   if (device && c->ac_nt > 32 && ((uintptr_t)words & 15)) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
   return HUMID_OK;
 }
 
-int humid_accum_add_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads, uint64_t base_index) {
-  TRY(accum_chunk_args(c, d_words, d_filtered, n_reads, true));
+// add and map over device arrays, arguments checked (d_key: null for a plain accumulator)
+static int accum_add_device(humid_ctx *c, const u64 *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads, u64 base_index) {
   state_reset(c);
   HIPCHK(hipSetDevice(c->device));
-  TRY(with_word_type(c->ac_nt, [&](auto *w) {
-    TRY(accum_count_chunk(c, (decltype(w))d_words, d_filtered, n_reads));
+  TRY(accum_counted(c, d_words, d_key, d_filt, n_reads, [&](auto *w) {
     if (c->U) TRY(accum_merge<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, base_index));
     return (int)HUMID_OK;
   }));
@@ -1485,17 +1513,78 @@ int humid_accum_add_device(humid_ctx *c, const uint64_t *d_words, const uint8_t 
   return state_publish_count(c, false);
 }
 
-int humid_accum_add(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index) {
-  TRY(accum_chunk_args(c, words, filtered, n_reads, false));
+static int accum_map_device(humid_ctx *c, const u64 *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads, u64 base_index,
+                            u32 *d_cluster_id, u8 *d_keep, u64 *n_unknown) {
+  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
+  if (n_reads && (!d_cluster_id || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  state_reset(c);                                              // (the record finish published ends here: the chunk is counted in the context's buffers)
   HIPCHK(hipSetDevice(c->device));
-  const size_t n = (size_t)n_reads, wbytes = c->ac_nt > 32 ? 16 : 8;
+  u64 unknown = 0;
+  TRY(accum_counted(c, d_words, d_key, d_filt, n_reads, [&](auto *w) {
+    return accum_map<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, base_index, d_cluster_id, d_keep, &unknown);
+  }));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (n_unknown) *n_unknown = unknown;
+  return state_publish_count(c, false);
+}
+
+// the host forms: the chunk staged (key: null for a plain accumulator), the device form, the results copied back
+static int accum_stage_chunk(humid_ctx *c, const u64 *words, const u64 *key, const u8 *filtered, size_t n) {
+  const size_t wbytes = c->ac_nt > 32 ? 16 : 8;
   ENSURE(c->in_words, n * wbytes + 16);
   ENSURE(c->in_filt, n + 8);
+  if (key) ENSURE(c->kr_key_in, n * 8 + 16);
   if (n) {
     HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, c->stream));
+    if (key) HIPCHK(hipMemcpyAsync(c->kr_key_in.p, key, n * 8, hipMemcpyHostToDevice, c->stream));
   }
-  return humid_accum_add_device(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, base_index);
+  return HUMID_OK;
+}
+
+static int accum_add_host(humid_ctx *c, const u64 *words, const u64 *key, const u8 *filtered, u64 n_reads, u64 base_index) {
+  HIPCHK(hipSetDevice(c->device));
+  TRY(accum_stage_chunk(c, words, key, filtered, (size_t)n_reads));
+  return accum_add_device(c, c->in_words.as<u64>(), key ? c->kr_key_in.as<u64>() : nullptr, c->in_filt.as<u8>(), n_reads, base_index);
+}
+
+static int accum_map_host(humid_ctx *c, const u64 *words, const u64 *key, const u8 *filtered, u64 n_reads, u64 base_index,
+                          uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown) {
+  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
+  if (n_reads && (!cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  TRY(accum_stage_chunk(c, words, key, filtered, n));
+  ENSURE(c->out_cid, n * 4 + 8);
+  ENSURE(c->out_keep, n + 8);
+  TRY(accum_map_device(c, c->in_words.as<u64>(), key ? c->kr_key_in.as<u64>() : nullptr, c->in_filt.as<u8>(), n_reads, base_index,
+                       c->out_cid.as<u32>(), c->out_keep.as<u8>(), n_unknown));
+  D2H(cluster_id, c->out_cid.p, n * 4);
+  D2H(keep, c->out_keep.p, n);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_accum_add_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads, uint64_t base_index) {
+  TRY(accum_chunk_args(c, false, d_words, nullptr, d_filtered, n_reads, true));
+  return accum_add_device(c, d_words, nullptr, d_filtered, n_reads, base_index);
+}
+
+int humid_accum_add(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index) {
+  TRY(accum_chunk_args(c, false, words, nullptr, filtered, n_reads, false));
+  return accum_add_host(c, words, nullptr, filtered, n_reads, base_index);
+}
+
+int humid_accum_add_keyed_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint64_t base_index) {
+  TRY(accum_chunk_args(c, true, d_words, d_key, d_filtered, n_reads, true));
+  return accum_add_device(c, d_words, d_key, d_filtered, n_reads, base_index);
+}
+
+int humid_accum_add_keyed(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads,
+                          uint64_t base_index) {
+  TRY(accum_chunk_args(c, true, words, key, filtered, n_reads, false));
+  return accum_add_host(c, words, key, filtered, n_reads, base_index);
 }
 
 int humid_accum_finish(humid_ctx *c, uint32_t distance, uint32_t method, humid_summary *summary) {
@@ -1512,58 +1601,52 @@ int humid_accum_finish(humid_ctx *c, uint32_t distance, uint32_t method, humid_s
   c->ac_finished = false;
   c->word_nt = c->ac_nt; c->distance = distance; c->method = method;
   c->gU = 0; c->E = c->M = c->C = 0;
-  TRY(with_word_type(c->ac_nt, [&](auto *w) {
-    return accum_finish<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, distance, method, s);
-  }));
+  c->cg_valid = false;                                         // (an empty list runs no graph stage: nothing of an earlier run's is left to expand)
+  if (c->ac_keyed) {
+    c->ac_G = 0;
+    c->kr_n = 0;
+    c->gk_word_nt = c->ac_nt; c->gk_leaf_nt = 0; c->gk_groups = 1;
+    c->usable = c->ac_usable;                                  // (what the group statistics close the last group with)
+    if (c->ac_U)
+      TRY(with_word_type(c->ac_ent_nt, [&](auto *w) {
+        return accum_finish_keyed_any<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, distance, method, s);
+      }));
+  } else
+    TRY(with_word_type(c->ac_nt, [&](auto *w) {
+      return accum_finish<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, distance, method, s);
+    }));
   HIPCHK(hipStreamSynchronize(c->stream));
   c->ac_finished = true;
   if (summary) *summary = s;
-  return state_publish(c, CtxState::STAGE_GRAPH);
+  return c->ac_keyed ? state_publish_keyed_graph(c) : state_publish(c, CtxState::STAGE_GRAPH);
 }
 
 int humid_accum_map_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads, uint64_t base_index,
                            uint32_t *d_cluster_id, uint8_t *d_keep, uint64_t *n_unknown) {
-  TRY(accum_chunk_args(c, d_words, d_filtered, n_reads, true));
-  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
-  if (n_reads && (!d_cluster_id || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
-  state_reset(c);                                              // (the record finish published ends here: the chunk is counted in the context's buffers)
-  HIPCHK(hipSetDevice(c->device));
-  u64 unknown = 0;
-  TRY(with_word_type(c->ac_nt, [&](auto *w) {
-    TRY(accum_count_chunk(c, (decltype(w))d_words, d_filtered, n_reads));
-    return accum_map<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, base_index, d_cluster_id, d_keep, &unknown);
-  }));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (n_unknown) *n_unknown = unknown;
-  return state_publish_count(c, false);
+  TRY(accum_chunk_args(c, false, d_words, nullptr, d_filtered, n_reads, true));
+  return accum_map_device(c, d_words, nullptr, d_filtered, n_reads, base_index, d_cluster_id, d_keep, n_unknown);
 }
 
 int humid_accum_map(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint64_t base_index,
                     uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown) {
-  TRY(accum_chunk_args(c, words, filtered, n_reads, false));
-  if (!c->ac_finished) return fail(c, HUMID_E_STATE, "no humid_accum_finish since the last humid_accum_add");
-  if (n_reads && (!cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
-  HIPCHK(hipSetDevice(c->device));
-  const size_t n = (size_t)n_reads, wbytes = c->ac_nt > 32 ? 16 : 8;
-  ENSURE(c->in_words, n * wbytes + 16);
-  ENSURE(c->in_filt, n + 8);
-  ENSURE(c->out_cid, n * 4 + 8);
-  ENSURE(c->out_keep, n + 8);
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, c->stream));
-  }
-  TRY(humid_accum_map_device(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, base_index, c->out_cid.as<u32>(),
-                             c->out_keep.as<u8>(), n_unknown));
-  D2H(cluster_id, c->out_cid.p, n * 4);
-  D2H(keep, c->out_keep.p, n);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return HUMID_OK;
+  TRY(accum_chunk_args(c, false, words, nullptr, filtered, n_reads, false));
+  return accum_map_host(c, words, nullptr, filtered, n_reads, base_index, cluster_id, keep, n_unknown);
+}
+
+int humid_accum_map_keyed_device(humid_ctx *c, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint64_t base_index, uint32_t *d_cluster_id, uint8_t *d_keep, uint64_t *n_unknown) {
+  TRY(accum_chunk_args(c, true, d_words, d_key, d_filtered, n_reads, true));
+  return accum_map_device(c, d_words, d_key, d_filtered, n_reads, base_index, d_cluster_id, d_keep, n_unknown);
+}
+
+int humid_accum_map_keyed(humid_ctx *c, const uint64_t *words, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads,
+                          uint64_t base_index, uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown) {
+  TRY(accum_chunk_args(c, true, words, key, filtered, n_reads, false));
+  return accum_map_host(c, words, key, filtered, n_reads, base_index, cluster_id, keep, n_unknown);
 }
 
 int humid_accum_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint64_t *first_index, uint64_t cap, uint64_t *n_out) {
-  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->ac_on) return fail(c, HUMID_E_STATE, "no accumulator in this context (humid_accum_begin)");
+  ACCUM_NEED(false);
   HIPCHK(hipSetDevice(c->device));
   if (n_out) *n_out = c->ac_U;
   const size_t n = (size_t)std::min<u64>(cap, c->ac_U), wbytes = c->ac_nt > 32 ? 16 : 8;
@@ -1572,6 +1655,33 @@ int humid_accum_get_leaves(humid_ctx *c, uint64_t *word, uint32_t *count, uint64
   D2H(count, c->ac_cnt[cur].p, n * 4);
   D2H(first_index, c->ac_first[cur].p, n * 8);
   HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+int humid_accum_get_leaves_keyed(humid_ctx *c, uint64_t *key, uint64_t *word, uint32_t *count, uint64_t *first_index, uint64_t cap,
+                                 uint64_t *n_out) {
+  ACCUM_NEED(true);
+  HIPCHK(hipSetDevice(c->device));
+  if (n_out) *n_out = c->ac_U;
+  const size_t n = (size_t)std::min<u64>(cap, c->ac_U), epr = c->ac_ent_nt > 32 ? 2 : 1;
+  const u32 cur = c->ac_cur, wb = 2 * c->ac_nt;
+  std::vector<u64> ent((key || word) ? n * epr : 0);
+  D2H(ent.data(), c->ac_word[cur].p, ent.size() * 8);
+  D2H(count, c->ac_cnt[cur].p, n * 4);
+  D2H(first_index, c->ac_first[cur].p, n * 8);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n && !ent.empty(); i++) {             // (a one-word entry: wb <= 62)
+    if (key) key[i] = epr == 2 ? ent[2 * i] : ent[i] >> wb;
+    if (word) word[i] = epr == 2 ? ent[2 * i + 1] : ent[i] & ((1ull << wb) - 1ull);
+  }
+  return HUMID_OK;
+}
+
+int humid_accum_keyed_info(humid_ctx *c, uint32_t *key_nt, uint32_t *entry_words, uint64_t *n_keys) {
+  ACCUM_NEED(true);
+  if (key_nt) *key_nt = c->ac_key_nt;
+  if (entry_words) *entry_words = c->ac_ent_nt > 32 ? 2u : 1u;
+  if (n_keys) *n_keys = c->ac_finished ? c->ac_G : 0;
   return HUMID_OK;
 }
 

@@ -13,11 +13,13 @@
 //   it and the B part with the entry BEHIND it, which is all a pair cut by a tile boundary needs.
 //   LDS: (T + 2) words, 16 KB (u64) or 32 KB (W2) at the default T = ACC_TILE = 2048: several workgroups per CU.
 //   the LOOKUP of a chunk's unique words in the accumulated list (k_accum_lookup): one binary search per chunk leaf.
+// A keyed accumulator (humid_accum_*_keyed) runs the same code over entries (key, word): the second half of this file.
 // Integers only.  The only atomics are the overflow flag and the unknown-read counter: results do not depend on the schedule.
 #ifndef HUMID_KERNELS_ACCUM_HIP_H
 #define HUMID_KERNELS_ACCUM_HIP_H
 
 #include "common.hip.h"
+#include "kernels_gkey.hip.h"
 
 #define ACC_TILE 2048u       // default merge positions per tile (option "accum_tile": a power of two, 64 .. ACC_TILE)
 #define ACC_THREADS 256u
@@ -145,6 +147,69 @@ __global__ void k_accum_lookup(const WT *__restrict__ a_word, const u64 *__restr
     l_cid[u] = found ? a_cid[lo] : 0u;
     l_ismax[u] = (found && a_ismax[lo] && a_first[lo] == base + b_first[u]) ? (u8)1 : (u8)0;
     if (!found) atomicAdd(unknown, (ull)b_cnt[u]);
+  }
+}
+
+// ---- keyed accumulators (humid_accum_*_keyed): an entry is the pair (key, word) in (key, word) order -------------------
+// ET, the entry type: u64 `key << 2 * word_nt | word` when key_nt >= 1 and key_nt + word_nt <= 32, W2 {hi = key, lo = word}
+// otherwise.  Either orders as (key, word) does, so the count stage, the merge and the lookup above run over entries as
+// they do over words.  Three kernels of their own:
+//   k_acck_pack    per read of a chunk: its entry (a filtered read's is 0: its key is not read); a usable key that does
+//                  not fit key_nt stores `epoch` into *bad, as k_gkey_words does for a group, and is cut to the field
+//   k_acck_heads   per entry of the accumulated list: 1 where the key differs from the entry before (finish; one
+//                  exclusive scan over the flags ranks the keys, its total is the number of distinct keys)
+//   k_acck_ranks   per entry: the internal word `rank << 2 * word_nt | word` of a keyed pass (IT: u64, or W2 beyond 32
+//                  nucleotides), and at every head the key itself into keys[rank]
+__device__ __forceinline__ u64 acck_key(u64 e, u32 wb) { return e >> wb; }             // (one-word entries: wb <= 62)
+__device__ __forceinline__ u64 acck_key(W2 e, u32) { return e.hi; }
+__device__ __forceinline__ u64 acck_word(u64 e, u32 wb) { return e & ((1ull << wb) - 1ull); }
+__device__ __forceinline__ u64 acck_word(W2 e, u32) { return e.lo; }
+__device__ __forceinline__ void acck_put(u64 *out, u64 key, u64 word, u32 wb) { *out = (key << wb) | word; }
+__device__ __forceinline__ void acck_put(W2 *out, u64 key, u64 word, u32) { *out = W2{key, word}; }
+
+template <class ET>
+__global__ void k_acck_pack(const u64 *__restrict__ words, const u64 *__restrict__ key, const u8 *__restrict__ filt, u32 n,
+                            u32 word_nt, u32 key_nt, ET *__restrict__ out, u32 *bad, u32 epoch) {
+  HUMID_GUARD_LAST_VGPR();
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool wrong = false;
+  if (i < n) {
+    u64 k = 0, w = 0;
+    if (filt[i] == 0) {
+      const u64 kmask = (key_nt == 0 || key_nt >= 32) ? ~0ull : (1ull << (2 * key_nt)) - 1ull;
+      const u64 wmask = word_nt >= 32 ? ~0ull : (1ull << (2 * word_nt)) - 1ull;
+      k = key[i];
+      wrong = (k & ~kmask) != 0;
+      k &= kmask;
+      w = words[i] & wmask;
+    }
+    acck_put(&out[i], k, w, 2 * word_nt);
+  }
+  const u64 lanes = __ballot(wrong);
+  if (lanes && (threadIdx.x & 63u) == (u32)(__ffsll((long long)lanes) - 1)) {
+    __hip_atomic_store(bad, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+  }
+}
+
+// head[i] for i in [0, U]: entry i starts a key; head[U] = 0 is the scan's sentinel
+template <class ET>
+__global__ void k_acck_heads(const ET *__restrict__ ent, u32 U, u32 wb, u32 *__restrict__ head) {
+  HUMID_GUARD_LAST_VGPR();
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i <= U; i += (u64)gridDim.x * blockDim.x)
+    head[i] = (i < U && (i == 0 || acck_key(ent[i], wb) != acck_key(ent[i - 1], wb))) ? 1u : 0u;
+}
+
+// hpos: the exclusive scan of head.  The rank of entry i's key is the number of heads up to and including i, less one.
+template <class ET, class IT>
+__global__ void k_acck_ranks(const ET *__restrict__ ent, const u32 *__restrict__ head, const u32 *__restrict__ hpos, u32 U, u32 wb,
+                             u64 *__restrict__ keys, IT *__restrict__ iword) {
+  HUMID_GUARD_LAST_VGPR();
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < U; i += (u64)gridDim.x * blockDim.x) {
+    const ET e = ent[i];
+    const u32 h = head[i], rank = hpos[i] + h - 1u;
+    if (h) keys[rank] = acck_key(e, wb);
+    gk_put(&iword[i], ((unsigned __int128)rank << wb) | acck_word(e, wb));              // (wb <= 64)
   }
 }
 

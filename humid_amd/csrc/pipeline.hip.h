@@ -120,6 +120,9 @@ static_assert(std::is_nothrow_move_constructible<DBuf>::value && std::is_nothrow
 //       data of a kind (gk_word_nt, gk_leaf_nt, gk_groups; kr_n; bc_N, bc_posterior) is valid exactly when the record
 //       says the run is of that kind.
 //   dense is orthogonal: humid_stage_map_dense and humid_stage_kernel_ms answer while it is set, whatever holds says.
+//   One STAGE_GRAPH is of a kind: the finish of a keyed accumulator (state_publish_keyed_graph) is RUN_KEYED, and
+//   humid_get_leaf_groups, humid_get_group_keys and humid_get_group_stats / humid_group_stats_device answer for it
+//   (its keys are ac_keys, not kr_keys); first_read and everything else under (b) stay E_STATE.
 // The results of humid_consensus* are no part of this: they survive runs (cs_valid).
 enum RunKind : u8 { RUN_PLAIN, RUN_GROUPED, RUN_KEYED, RUN_CORRECTED };   // ordered: each kind is a case of the one before
 struct CtxState {
@@ -238,7 +241,7 @@ struct humid_ctx {
   u32 gk_nt = 0;             // the group field (nucleotides) of the pass now running; 0 unless pass_kind >= RUN_GROUPED
   u32 gk_epoch = 0;          // value k_gkey_words stores into h_ctr[CTR_N + 1] when a usable read's group is out of range
   u32 gk_word_nt = 0, gk_leaf_nt = 0;   // RUN_GROUPED on: the leaf arrays hold internal words of this caller word length and group field
-  DBuf gk_words, gk_group_in, gk_bad;   // internal words; host entry point staging of the groups; device flag (no mapped memory)
+  DBuf gk_words, gk_group_in, gk_bad;   // internal words (a keyed accumulator: a chunk's entries); host entry point staging of the groups; device flag (no mapped memory)
   // keyed runs (humid_dedup_run_keyed*): grouped runs whose groups are the ranks of 64-bit keys (kernels_keyrank.hip.h)
   u32 kr_n = 0;              // RUN_KEYED on: kr_keys holds the run's kr_n sorted distinct keys
   u32 kr_cap_log2 = 0;       // log2 of the table size of the next ranking (0: 16); remembered from pass to pass, grown on demand
@@ -313,6 +316,12 @@ struct humid_ctx {
   DBuf ac_word[2], ac_cnt[2], ac_first[2];                    // WT[U], u32[U], u64[U]
   DBuf ac_split, ac_tcnt, ac_toff, ac_flag;                   // the merge: tile splits, new words per tile, their scan; overflow flag + unknown reads
   DBuf ac_cid, ac_ismax, ac_lcid, ac_lismax;                  // finish's copy of cid / ismax per word; a mapped chunk's per-leaf results
+  // keyed accumulators (humid_accum_begin_keyed): the list holds entries (key, word) of ac_ent_nt nucleotides as the count
+  // stage sees them -- one u64 `key << 2 * ac_nt | word` up to 32, W2 {key, word} beyond; ac_nt stays the caller's word
+  bool ac_keyed = false;
+  u32 ac_key_nt = 0, ac_ent_nt = 0;
+  u64 ac_G = 0;                                               // ac_finished: distinct keys of the list
+  DBuf ac_head, ac_hpos, ac_keys, ac_iword;                   // finish: key heads u32[U + 1], their scan, the keys u64[G], the pass's internal words
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
@@ -508,6 +517,11 @@ static inline bool state_has_leaves(const humid_ctx *c) { return c->state.holds 
 static inline bool state_has_run(const humid_ctx *c) { return c->state.holds == CtxState::RUN; }   // a complete single-GPU run
 static inline bool state_dense_count(const humid_ctx *c) { return c->state.dense; }   // what humid_stage_map_dense builds on
 static inline bool state_run_is(const humid_ctx *c, RunKind at_least) { return state_has_run(c) && c->state.kind >= at_least; }
+// The finish of a keyed accumulator leaves a STAGE_GRAPH whose leaves carry groups as a keyed run's do: its record is of
+// kind RUN_KEYED (every other STAGE_GRAPH is RUN_PLAIN).  What reads groups off the leaves asks this, not state_run_is.
+static inline int state_publish_keyed_graph(humid_ctx *c) { state_publish(c, CtxState::STAGE_GRAPH); c->state.kind = RUN_KEYED; return HUMID_OK; }
+static inline bool state_keyed_graph(const humid_ctx *c) { return c->state.holds == CtxState::STAGE_GRAPH && c->state.kind == RUN_KEYED; }
+static inline bool state_groups_are(const humid_ctx *c, RunKind at_least) { return state_has_leaves(c) && c->state.kind >= at_least; }
 // The kind of the pass now running: set by the outermost of run_grouped_device, run_keyed_device and
 // run_keyed_corrected_device, read by gkey_check, copied into the record by run_device's state_publish.
 struct PassKind {
@@ -2658,6 +2672,23 @@ static int gkey_check(humid_ctx *c) {
   return HUMID_OK;
 }
 
+// Where a kernel that checks the reads of a pass (k_gkey_words, k_kr_words, k_acck_pack) stores c->gk_epoch: the
+// host-mapped counter mirror the next host wait reads, or, without one, a device word that gkey_bad_fetch copies there
+// behind the kernel.
+static int gkey_bad_word(humid_ctx *c, u32 **bad) {
+  if (c->h_ctr_dev && !c->no_poll) { *bad = (u32 *)&c->h_ctr_dev[CTR_N + 1]; return HUMID_OK; }
+  if (!c->gk_bad.p) {
+    ENSURE(c->gk_bad, 16);
+    HIPCHK(hipMemsetAsync(c->gk_bad.p, 0, 16, c->stream));
+  }
+  *bad = c->gk_bad.as<u32>();
+  return HUMID_OK;
+}
+static int gkey_bad_fetch(humid_ctx *c, const u32 *bad) {
+  if (bad == c->gk_bad.as<u32>()) HIPCHK(hipMemcpyAsync(&c->h_ctr[CTR_N + 1], bad, 4, hipMemcpyDeviceToHost, c->stream));
+  return HUMID_OK;
+}
+
 static int check_run_args(humid_ctx *c, u64 n_reads, u32 word_nt, u32 method, u32 max_nt = 32) {
   if (word_nt == 0) return fail(c, HUMID_E_INVALID, "word_nt must be >= 1");
   if (word_nt > max_nt) return fail(c, HUMID_E_UNSUPPORTED, "word_nt %u > %u is not supported by this entry point", word_nt, max_nt);
@@ -2784,13 +2815,14 @@ template <class WT>
 static int accum_count_chunk(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_reads) {
   humid_summary s;
   memset(&s, 0, sizeof s);
+  const u32 nt = c->ac_keyed ? c->ac_ent_nt : c->ac_nt;       // (a keyed accumulator counts entries)
   c->last_unperm_tiled = false;
   c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
-  c->word_nt = c->ac_nt;
+  c->word_nt = nt;
   c->gU = 0;
   if (n_reads == 0) return HUMID_OK;
-  if constexpr (sizeof(WT) == 16) return stage_count_wide(c, d_words, d_filt, (u32)n_reads, c->ac_nt, s);
-  else return stage_count(c, d_words, d_filt, (u32)n_reads, c->ac_nt, 0ull, ~0ull, 0, s);
+  if constexpr (sizeof(WT) == 16) return stage_count_wide(c, d_words, d_filt, (u32)n_reads, nt, s);
+  else return stage_count(c, d_words, d_filt, (u32)n_reads, nt, 0ull, ~0ull, 0, s);
 }
 
 // The list of set ac_cur merged with the chunk just counted (s_word / s_cnt / s_first of c->U words, first read
@@ -2934,14 +2966,8 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
     hipStream_t st = c->stream;
     const bool wide = n_int > 32, copy = gnt > 0;             // (one group: the caller's words are the internal ones)
     if (copy) ENSURE(c->gk_words, (size_t)N * (wide ? 16 : 8) + 16);
-    u32 *bad = (c->h_ctr_dev && !c->no_poll) ? (u32 *)&c->h_ctr_dev[CTR_N + 1] : nullptr;
-    if (!bad) {                                              // no mapped mirror: a device word, copied at the host wait
-      if (!c->gk_bad.p) {
-        ENSURE(c->gk_bad, 16);
-        HIPCHK(hipMemsetAsync(c->gk_bad.p, 0, 16, st));
-      }
-      bad = c->gk_bad.as<u32>();
-    }
+    u32 *bad = nullptr;
+    TRY(gkey_bad_word(c, &bad));
     if (d_key && wide)
       hipLaunchKernelGGL((k_kr_words<WI, W2>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_key, d_filt, N,
                          (const KrSlot *)c->kr_table.p, c->kr_last_log2, n_groups, word_nt, gnt, c->gk_words.as<W2>(), bad, c->gk_epoch);
@@ -2955,8 +2981,7 @@ static int run_grouped_device(humid_ctx *c, const WI *d_words, const u32 *d_grou
       hipLaunchKernelGGL((k_gkey_words<WI, u64>), dim3(blocks_for(N)), dim3(256), 0, st, d_words, d_group, d_filt, N,
                          word_nt, gnt, n_groups, copy ? c->gk_words.as<u64>() : nullptr, bad, c->gk_epoch);
     HIPCHK(hipGetLastError());
-    if (bad == c->gk_bad.as<u32>())
-      HIPCHK(hipMemcpyAsync(&c->h_ctr[CTR_N + 1], bad, 4, hipMemcpyDeviceToHost, st));
+    TRY(gkey_bad_fetch(c, bad));
     if (!copy) rc = run_device<WI>(c, d_words, d_filt, n_reads, word_nt, distance, method, d_cid, d_keep, sum);
     else if (wide) rc = run_device<W2>(c, c->gk_words.as<W2>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
     else rc = run_device<u64>(c, c->gk_words.as<u64>(), d_filt, n_reads, n_int, distance, method, d_cid, d_keep, sum);
@@ -3030,6 +3055,107 @@ static int run_keyed_device(humid_ctx *c, const WI *d_words, const u64 *d_key, c
   if (n_reads) TRY(rank_keys(c, d_key, d_filt, (u32)n_reads));
   return run_grouped_device<WI>(c, d_words, nullptr, d_filt, n_reads, word_nt, std::max(c->kr_n, 1u), distance, method,
                                 d_cid, d_keep, sum, n_reads ? d_key : nullptr);
+}
+
+// ---- keyed accumulators (humid_accum_*_keyed; the second half of kernels_accum.hip.h) -----------------------------
+// add / map = k_acck_pack over the chunk + the plain accumulator's add / map over the entries; finish = the keys ranked
+// off the sorted list + a keyed graph stage over the internal words.  ET: the entry type.
+// The chunk's entries into c->gk_words and the count stage over them.  A usable key beyond key_nt is seen at the count
+// stage's host wait, before anything of the accumulator is touched.
+template <class ET>
+static int accum_pack_count(humid_ctx *c, const u64 *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads) {
+  const u32 N = (u32)n_reads;
+  if (N) {
+    ENSURE(c->gk_words, (size_t)N * sizeof(ET) + 16);
+    c->gk_epoch = c->gk_epoch + 1 ? c->gk_epoch + 1 : 1;
+    u32 *bad = nullptr;
+    TRY(gkey_bad_word(c, &bad));
+    hipLaunchKernelGGL((k_acck_pack<ET>), dim3(blocks_for(N)), dim3(256), 0, c->stream, d_words, d_key, d_filt, N, c->ac_nt,
+                       c->ac_key_nt, c->gk_words.as<ET>(), bad, c->gk_epoch);
+    HIPCHK(hipGetLastError());
+    TRY(gkey_bad_fetch(c, bad));
+  }
+  TRY(accum_count_chunk(c, (const ET *)c->gk_words.p, d_filt, n_reads));
+  if (N && *(volatile u32 *)&c->h_ctr[CTR_N + 1] == c->gk_epoch)
+    return fail(c, HUMID_E_INVALID, "a usable read has a key >= 4^%u", c->ac_key_nt);
+  return HUMID_OK;
+}
+
+// The distinct keys of the accumulated list: head flags and their scan (left in ac_head / ac_hpos for k_acck_ranks), and
+// finish's ONE extra host wait: *G chooses the group field and with it the internal word type and the plan.
+template <class ET>
+static int accum_rank_keys(humid_ctx *c, u32 *G) {
+  const u32 U = (u32)c->ac_U;
+  PASS_ENSURE(c->ac_head, ((size_t)U + 1) * 4);
+  PASS_ENSURE(c->ac_hpos, ((size_t)U + 1) * 4);
+  hipLaunchKernelGGL((k_acck_heads<ET>), dim3(grid_stride_blocks((u64)U + 1)), dim3(256), 0, c->stream,
+                     c->ac_word[c->ac_cur].as<ET>(), U, 2 * c->ac_nt, c->ac_head.as<u32>());
+  u64 total = 0;
+  TRY(scan_total(c, c->ac_head.as<u32>(), c->ac_hpos.as<u32>(), U, &total));
+  *G = (u32)total;
+  return HUMID_OK;
+}
+
+// The keyed graph stage over the accumulated list: internal words `rank << 2 * word_nt | word` (ascending, because
+// (key, word) order is (rank, word) order) and the keys into the accumulator's buffers, then what accum_finish does,
+// with the context set as run_grouped_device sets it for a keyed pass.  IT: the internal word type.
+template <class ET, class IT>
+static int accum_finish_keyed(humid_ctx *c, u32 G, u32 distance, u32 method, humid_summary &s) {
+  const u32 U = (u32)c->ac_U, cur = c->ac_cur, gnt = gkey_nt_for(G), n_int = c->ac_nt + gnt;
+  PASS_ENSURE(c->ac_keys, (size_t)G * 8 + 16);
+  PASS_ENSURE(c->ac_iword, (size_t)U * sizeof(IT) + 16);
+  hipLaunchKernelGGL((k_acck_ranks<ET, IT>), dim3(grid_stride_blocks(U)), dim3(256), 0, c->stream, c->ac_word[cur].as<ET>(),
+                     (const u32 *)c->ac_head.p, (const u32 *)c->ac_hpos.p, U, 2 * c->ac_nt, c->ac_keys.as<u64>(), c->ac_iword.as<IT>());
+  HIPCHK(hipGetLastError());
+  PassKind pass(c, RUN_KEYED);
+  c->gk_nt = gnt;
+  c->gk_word_nt = c->ac_nt;
+  c->gk_leaf_nt = gnt;
+  c->gk_groups = G;
+  c->kr_n = G;
+  const IT *g_word = c->ac_iword.as<IT>();
+  const u32 *g_cnt = c->ac_cnt[cur].as<u32>();
+  u32 nps = 0;
+  if (c->edit && distance >= 2) {
+    u64 E = 0;
+    TRY(edit_edges<IT>(c, g_word, U, n_int, distance, &E));
+    static const u64 no_edges = 0;
+    TRY(stage_graph<IT>(c, g_word, g_cnt, U, n_int, distance, method, s, nps, E ? c->e_edges.as<u64>() : &no_edges, E));
+  } else
+    TRY(stage_graph<IT>(c, g_word, g_cnt, U, n_int, distance, method, s, nps));
+  TRY(n_clusters_from_scan(c, U, &c->C));
+  s.clusters = c->C;
+  PASS_ENSURE(c->ac_cid, (size_t)U * 4 + 16);
+  PASS_ENSURE(c->ac_ismax, (size_t)U + 16);
+  HIPCHK(hipMemcpyAsync(c->ac_cid.p, c->cid.p, (size_t)U * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->ac_ismax.p, c->ismax.p, (size_t)U, hipMemcpyDeviceToDevice, c->stream));
+  return HUMID_OK;
+}
+
+// finish of a keyed accumulator with a non-empty list
+template <class ET>
+static int accum_finish_keyed_any(humid_ctx *c, u32 distance, u32 method, humid_summary &s) {
+  u32 G = 0;
+  TRY(accum_rank_keys<ET>(c, &G));
+  c->ac_G = G;
+  if constexpr (sizeof(ET) == 16)                              // (a one-word entry holds key_nt >= group nucleotides)
+    if (c->ac_nt + gkey_nt_for(G) > 32) return accum_finish_keyed<ET, W2>(c, G, distance, method, s);
+  return accum_finish_keyed<ET, u64>(c, G, distance, method, s);
+}
+
+// The count stage over a chunk on the device -- over its entries (accum_pack_count) when the accumulator
+// is a keyed one --, then f, called with a null pointer to the type of the list's entries.
+template <class F>
+static int accum_counted(humid_ctx *c, const u64 *d_words, const u64 *d_key, const u8 *d_filt, u64 n_reads, F f) {
+  if (c->ac_keyed)
+    return with_word_type(c->ac_ent_nt, [&](auto *w) {
+      TRY(accum_pack_count<std::remove_cv_t<std::remove_pointer_t<decltype(w)>>>(c, d_words, d_key, d_filt, n_reads));
+      return f(w);
+    });
+  return with_word_type(c->ac_nt, [&](auto *w) {
+    TRY(accum_count_chunk(c, (decltype(w))d_words, d_filt, n_reads));
+    return f(w);
+  });
 }
 
 // ---- barcode whitelist (humid_whitelist_*, humid_dedup_run_keyed_corrected*; kernels_whitelist.hip.h) -----------

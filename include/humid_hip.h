@@ -914,7 +914,8 @@ int humid_get_strands(humid_ctx *ctx, uint8_t *strand, uint64_t cap, uint32_t *t
  * into the accumulated one (equal words combined; one host wait, for the new number of words); finish = the graph stage
  * over the accumulated list; map = the count stage over the chunk + one binary search per unique word of the chunk +
  * the un-permute of humid_dedup_run.  Every add rewrites the accumulated list.
- * Grouped, keyed, corrected, paired and multi-GPU forms, and the post-run passes, are not available for accumulated runs.
+ * The keyed form has accumulators of its own (next section; a corrected one composes from it).  Grouped, paired and
+ * multi-GPU forms, the posterior correction and the post-run passes are not available for accumulated runs.
  * humid_accum_get_leaves: the first min(cap, unique) entries; *n_out = unique; any pointer may be NULL.
  * humid_accum_info: word_nt, chunks added, reads and usable reads added, unique words, finished (0 / 1).
  *   *_device: DEVICE pointers for the per-read arrays; n_unknown stays a host pointer. */
@@ -932,6 +933,57 @@ int humid_accum_get_leaves(humid_ctx *ctx, uint64_t *word, uint32_t *count, uint
 int humid_accum_info(humid_ctx *ctx, uint32_t *word_nt, uint64_t *chunks, uint64_t *total, uint64_t *usable,
                      uint64_t *unique, uint32_t *finished);
 int humid_accum_clear(humid_ctx *ctx);
+
+/* ---- keyed accumulated runs: per-key deduplication of a read set fed in chunks ---------------------------
+ * humid_dedup_run_keyed for a read set that does not fit one call: every read carries a 64-bit key (a cell barcode)
+ * beside its word, and words are compared within one key only.  humid_accum_begin_keyed opens the accumulator: word_nt
+ * is 1 .. 32 (one uint64 per word; above 32 HUMID_E_UNSUPPORTED, 0 HUMID_E_INVALID); key_nt = 0 makes every 64-bit
+ * value a legal key; with key_nt = 1 .. 32 the caller promises keys < 4^key_nt (key_nt > 32: HUMID_E_INVALID), which
+ * lets a key and a word of key_nt + word_nt <= 32 nucleotides share one uint64 on the device.  A usable read with a
+ * larger key makes add / map return HUMID_E_INVALID, the accumulator as it was and the context usable, as a group
+ * >= n_groups does in a grouped run.  Keys of filtered reads are never read.
+ * A context holds ONE accumulator: either begin empties the earlier one of either kind and keeps its memory.  The plain
+ * add / map / get_leaves on a keyed accumulator, and the keyed ones on a plain accumulator, return HUMID_E_STATE;
+ * humid_accum_finish, humid_accum_info (unique = distinct (key, word) pairs) and humid_accum_clear serve both kinds.
+ * The list.  Per distinct (key, word) of the usable reads, ascending by key (unsigned), then word: count (summed over
+ * all chunks) and first_index (the smallest global index, u64).  Nothing depends on the order of the adds.
+ * Results.  Let R be all added reads sorted by global index.
+ *   humid_accum_finish  the summary, leaves, adjacency, clusters and histograms of humid_dedup_run_keyed over R (option
+ *                       "edit_distance" applies as there), left as after a plain finish: humid_get_leaves gives the
+ *                       caller's words, the group field stripped, and no first_read.  Beyond a plain finish,
+ *                       humid_get_group_keys, humid_get_leaf_groups and humid_get_group_stats / humid_group_stats_device
+ *                       answer for that run, until the first map ends the record (as the adjacency does).  The group
+ *                       statistics carry the reads in 32 bits: beyond 2^32 - 1 accumulated usable reads they return
+ *                       HUMID_E_UNSUPPORTED.  After a PLAIN finish nothing changes: they return HUMID_E_STATE.
+ *   humid_accum_map_keyed  per read of the chunk given: cluster_id = the id that run gives to its (key, word); keep = 1
+ *                       iff the read is usable, its entry is its cluster's maxLeaf and its global index is the entry's
+ *                       first_index.  Filtered reads get 0 / 0.  A usable read whose (key, word) was never added -- a
+ *                       known word under an unseen key included -- gets 0 / 0 and is counted in *n_unknown.
+ * States, limits and failures are those of the plain accumulator: 2^31 - 1 reads per chunk, 2^31 - 1 entries, counts
+ * below 2^32; a failing call changes nothing.
+ * Whitelist correction composes, chunk by chunk: humid_whitelist_correct* over the chunk's keys, then add / map key_out
+ * with filtered | (status >= HUMID_BC_AMBIGUOUS).  The result is humid_dedup_run_keyed_corrected over R.  The posterior
+ * correction and humid_whitelist_discover* need counts over the whole read set and do not compose this way.
+ * On the device: one kernel per chunk packs (key, word) into an entry and checks the key; the count stage, the merge and
+ * the lookup of the plain accumulator run over entries.  finish ranks the keys off the sorted list (a flag where the
+ * key changes, one scan) at the cost of ONE more host wait -- the number of distinct keys chooses the group field --
+ * and runs the graph stage as a keyed pass over rank << 2 * word_nt | word.
+ * humid_accum_get_leaves_keyed: the first min(cap, unique) entries; *n_out = unique; any pointer may be NULL.
+ * humid_accum_keyed_info: key_nt, uint64 per entry on the device (1 or 2), distinct keys (after a finish; 0 before).
+ *   *_device: DEVICE pointers for the per-read arrays; n_unknown stays a host pointer. */
+int humid_accum_begin_keyed(humid_ctx *ctx, uint32_t word_nt, uint32_t key_nt);
+int humid_accum_add_keyed(humid_ctx *ctx, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
+                          uint64_t n_reads, uint64_t base_index);
+int humid_accum_add_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint64_t base_index);
+int humid_accum_map_keyed(humid_ctx *ctx, const uint64_t *words, const uint64_t *key, const uint8_t *filtered,
+                          uint64_t n_reads, uint64_t base_index, uint32_t *cluster_id, uint8_t *keep, uint64_t *n_unknown);
+int humid_accum_map_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const uint64_t *d_key, const uint8_t *d_filtered,
+                                 uint64_t n_reads, uint64_t base_index, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                 uint64_t *n_unknown);
+int humid_accum_get_leaves_keyed(humid_ctx *ctx, uint64_t *key, uint64_t *word, uint32_t *count, uint64_t *first_index,
+                                 uint64_t cap, uint64_t *n_out);
+int humid_accum_keyed_info(humid_ctx *ctx, uint32_t *key_nt, uint32_t *entry_words, uint64_t *n_keys);
 
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
