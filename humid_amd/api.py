@@ -823,6 +823,12 @@ class Dedup(Context):
         self._check(self._lib.humid_graph_split_info(self._h, C.byref(a), C.byref(b), C.byref(f)))
         return dict(pairs_direct=a.value, pairs_graph=b.value, full_graph_built=f.value)
 
+    def group_records_info(self):
+        """dict(searched_on_records, orders_stored) of the last run's compact graph stage (humid_group_records_info)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.humid_group_records_info(self._h, C.byref(a), C.byref(b)))
+        return dict(searched_on_records=a.value, orders_stored=b.value)
+
     def run_roads(self):
         """what the last mutating call retried (humid_get_run_roads): dict(events, n_events, graph_attempts).  events:
         the names of the first 32 events in order, of PART_PADDED_REDO, ORDERS_REDONE, REGIONS_REGROWN, FAR_TILES,

@@ -217,6 +217,10 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->pair_split = value != 0;
     return HUMID_OK;
   }
+  if (strcmp(key, "group_records") == 0) {
+    c->group_records = value != 0;
+    return HUMID_OK;
+  }
   if (strcmp(key, "padded_partition") == 0) {
     c->pt_padded = value != 0;
     return HUMID_OK;
@@ -484,6 +488,14 @@ int humid_graph_split_info(humid_ctx *c, uint64_t *pairs_direct, uint64_t *pairs
   if (pairs_direct) *pairs_direct = split ? c->cg_iso : 0;
   if (pairs_graph) *pairs_graph = split ? c->cg_R : c->E;
   if (full_graph_built) *full_graph_built = (!split || c->cg_full) ? 1u : 0u;
+  return HUMID_OK;
+}
+
+int humid_group_records_info(humid_ctx *c, uint32_t *searched_on_records, uint32_t *orders_stored) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!state_has_leaves(c)) return fail(c, HUMID_E_STATE, "no completed dedup run / graph stage in this context");
+  if (searched_on_records) *searched_on_records = c->cg_valid ? c->gr_rides : 0u;
+  if (orders_stored) *orders_stored = c->cg_valid ? c->gr_orders : 0u;
   return HUMID_OK;
 }
 

@@ -292,6 +292,13 @@ struct IdxGrouped {
   const u32 *v_in;
   __device__ __forceinline__ u32 operator()(u32 j) const { return v_in[inv[j]]; }
 };
+// the same where the grouping moved records (k_group_fine_recs): the walk index is the low ibits of the record
+struct IdxRecords {
+  const unsigned short *inv;
+  const u64 *recs;
+  u32 ibits;
+  __device__ __forceinline__ u32 operator()(u32 j) const { return (u32)(recs[inv[j]] & ((1ull << ibits) - 1ull)); }
+};
 template <bool MULTI>
 struct PairSearchDevT {
   static constexpr bool on = true;
@@ -305,6 +312,15 @@ struct PairSearchDevT {
   // bin's end ends a walk as the first word of the next bin would); thread t has the positions t, t + T, ...
   template <u32 NP, u32 T>
   __device__ __forceinline__ void in_bin(const u64 *sw, u32 n, const unsigned short *inv, const u32 *v_in, u32 *scratch) const {
+    walk_bin<NP, T>(sw, n, IdxGrouped{inv, v_in}, scratch);
+  }
+  // k_group_fine_recs: the bin's records at recs
+  template <u32 NP, u32 T>
+  __device__ __forceinline__ void in_bin_recs(const u64 *sw, u32 n, const unsigned short *inv, const u64 *recs, u32 ibits, u32 *scratch) const {
+    walk_bin<NP, T>(sw, n, IdxRecords{inv, recs, ibits}, scratch);
+  }
+  template <u32 NP, u32 T, class IDX>
+  __device__ __forceinline__ void walk_bin(const u64 *sw, u32 n, const IDX &idx, u32 *scratch) const {
     const WordsLds word{sw};
     u32 found[NP], first_off[NP];
 #pragma unroll
@@ -313,7 +329,7 @@ struct PairSearchDevT {
       found[q] = 0; first_off[q] = 0;
       if (i < n) pa_walk(word, sw[i], sw[i + 1 < n ? i + 1 : i], i, n, rule, big, found[q], first_off[q]);
     }
-    pa_emit<NP, T / 64u, MULTI>(word, IdxGrouped{inv, v_in}, threadIdx.x, T, n, found, first_off, rule, er, bits, multi, overflow, scratch);
+    pa_emit<NP, T / 64u, MULTI>(word, idx, threadIdx.x, T, n, found, first_off, rule, er, bits, multi, overflow, scratch);
   }
 };
 

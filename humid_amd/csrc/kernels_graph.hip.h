@@ -111,6 +111,32 @@ struct FieldsSrcW2 {
   __device__ __forceinline__ u64 key(u64 payload) const { return payload; }
 };
 
+// The grouping on 8-BYTE RECORDS (the count stage's idea, kernels_part8.hip.h, whose level-1 scatter moves them here
+// too).  The coarse bin of a word is the top d1 bits of its combination key, and where the key's first field is at
+// least d1 bits wide those are the d1 bits [p, p + d1) of the word itself: inside bin c they are known from WHERE a
+// record sits, so
+//     record = (the word with those d1 bits squeezed out) << ibits | walk index
+// holds the whole of a wb-bit word and its index whenever wb - d1 + ibits <= 64 (the metric workload: 48 - 9 + 22).
+struct RecSqueeze {
+  u32 p, d1;                       // p + d1 <= wb < 64
+  __device__ __forceinline__ u64 low(u64 x) const { return x & ((1ull << p) - 1ull); }
+  __device__ __forceinline__ u32 bin(u64 w) const { return (u32)(w >> p) & ((1u << d1) - 1u); }
+  __device__ __forceinline__ u64 squeeze(u64 w) const { return (w >> p >> d1 << p) | low(w); }
+  // the inverse: the word of bin c whose squeezed form is s
+  __device__ __forceinline__ u64 word(u32 c, u64 s) const { return (s >> p << p << d1) | ((u64)c << p) | low(s); }
+};
+// SRC of k_p8_scatter1 for the grouping: key' = coarse bin << (wb - d1) | squeezed word, kbits = wb
+struct FieldsRecs {
+  const u64 *words;
+  RecSqueeze sq;
+  u32 rbits;                       // wb - d1
+  __device__ __forceinline__ bool load(u32 j, u64 &k) const {
+    const u64 w = words[j];
+    k = ((u64)sq.bin(w) << rbits) | (sq.squeeze(w) & ((1ull << rbits) - 1ull));   // (never a bin beyond 2^d1, whatever the word)
+    return true;
+  }
+};
+
 // --------------------------------------------------------------------------------
 // 4. connected components (lock-free union-find, smaller index wins => root = min rank)
 // --------------------------------------------------------------------------------

@@ -188,7 +188,8 @@ k_pt_scan1(const u32 *__restrict__ hist1, u32 d1, u32 d2, u32 *__restrict__ cbas
 //          counts of c before f, which the first tile of c also writes to pbeg_out[c << d2 | f].
 //          cursor[]: records already placed in each region (zeroed before the launch).
 // THREADS: 1024 (tiles of PT_TILE records: the tile bookkeeping of level 2 assumes it), or 512 for a LEVEL 1 whose 120 KB
-// of LDS per 1024-thread workgroup would leave one workgroup per CU (the graph stage's grouping: 333 tiles on 256 CUs)
+// of LDS per 1024-thread workgroup would leave one workgroup per CU (the graph stage's grouping: 333 tiles on 256 CUs;
+// where its search rides that grouping now moves 8-byte records through k_p8_scatter1 instead, option group_records)
 template <int LEVEL, class SRC, u32 THREADS = 1024u>
 __global__ void __launch_bounds__(THREADS)
 k_pt_scatter(SRC src, u32 n_reads, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in,
@@ -330,8 +331,34 @@ struct NoSearch { static constexpr bool on = false; };
 // bucket lies inside one bin; once the inverse permutation is placed the counter area is dead, and the grouped words
 // (in registers for the stores) go into it in output order: GF_SMALL x 8 B fit its 64 KB.  After a barrier every
 // thread walks its 8 positions there (PairSearchDev::in_bin, kernels_cgraph.hip.h).
+// the exclusive scan of nb 16-bit counters (two per word of cnt) in place, by all GF_THREADS threads; ends with a barrier
+__device__ __forceinline__ void gf_scan16(u32 *cnt, u32 *wsum, u32 nb) {
+  const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const u32 words = nb >= 2 ? nb / 2 : 1u;
+  const u32 n_waves = GF_THREADS / 64u;
+  const u32 per_wave = (words + n_waves - 1) / n_waves, wbeg = wv * per_wave, wend = wbeg + per_wave < words ? wbeg + per_wave : words;
+  u32 tot = 0;
+  for (u32 w = wbeg + lane; w < wend; w += 64) { const u32 x = cnt[w]; tot += (x & 0xffffu) + (x >> 16); }
+#pragma unroll
+  for (u32 dd = 32; dd; dd >>= 1) tot += __shfl_xor(tot, dd);
+  if (lane == 0) wsum[wv] = tot;
+  __syncthreads();
+  u32 run = 0;
+  for (u32 q = 0; q < wv; q++) run += wsum[q];
+  for (u32 w0 = wbeg; w0 < wend; w0 += 64) {                                        // (wave-uniform bounds)
+    const u32 w = w0 + lane;
+    const u32 x = w < wend ? cnt[w] : 0u;
+    const u32 mine = (x & 0xffffu) + (x >> 16);
+    const u32 incl = wave_incl_scan(mine);
+    const u32 lo = run + incl - mine, hi = lo + (x & 0xffffu);
+    if (w < wend) cnt[w] = lo | (hi << 16);                                         // offsets < n <= 2^15
+    run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+  }
+  __syncthreads();
+}
+
 template <class SRC, int SIZE, class SEARCH = NoSearch>
-__global__ void __launch_bounds__(GF_THREADS, SIZE == 0 ? 8 : 4)       // SIZE 0: <= 64 registers, two workgroups per CU
+__global__ void __launch_bounds__(GF_THREADS, SIZE == 0 ? 8 : 4)      // SIZE 0: <= 64 registers, two workgroups per CU
 k_group_fine(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in, const u32 *__restrict__ cbase, u32 d1,
              u32 d2, u64 *__restrict__ k_out, u32 *__restrict__ v_out, u32 cap1, SEARCH srch = SEARCH()) {
   HUMID_GUARD_LAST_VGPR();
@@ -391,27 +418,7 @@ k_group_fine(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in
     // exclusive scan of the 16-bit counters in place.  A wave owns a stretch of words / 16 consecutive words and walks it
     // in rows of 64 (lane l takes word 64 i + l: no bank conflict; a thread owning 16 CONSECUTIVE words, as before,
     // hit two banks with 64 lanes -- 10.7 of the kernel's 20 us per workgroup): totals first, then the offsets.
-    const u32 words = nb >= 2 ? nb / 2 : 1u;
-    const u32 n_waves = GF_THREADS / 64u;
-    const u32 per_wave = (words + n_waves - 1) / n_waves, wbeg = wv * per_wave, wend = wbeg + per_wave < words ? wbeg + per_wave : words;
-    u32 tot = 0;
-    for (u32 w = wbeg + lane; w < wend; w += 64) { const u32 x = gf_lds[w]; tot += (x & 0xffffu) + (x >> 16); }
-#pragma unroll
-    for (u32 dd = 32; dd; dd >>= 1) tot += __shfl_xor(tot, dd);
-    if (lane == 0) wsum[wv] = tot;
-    __syncthreads();
-    u32 run = 0;
-    for (u32 q = 0; q < wv; q++) run += wsum[q];
-    for (u32 w0 = wbeg; w0 < wend; w0 += 64) {                                        // (wave-uniform bounds)
-      const u32 w = w0 + lane;
-      const u32 x = w < wend ? gf_lds[w] : 0u;
-      const u32 mine = (x & 0xffffu) + (x >> 16);
-      const u32 incl = wave_incl_scan(mine);
-      const u32 lo = run + incl - mine, hi = lo + (x & 0xffffu);
-      if (w < wend) gf_lds[w] = lo | (hi << 16);                                      // offsets < n <= 2^15
-      run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-    __syncthreads();
+    gf_scan16(gf_lds, wsum, nb);
     PH(4);
     if constexpr (SIZE == 0) {
       u32 oldq[GF_RPT];
@@ -501,6 +508,73 @@ k_group_fine(SRC src, const u64 *__restrict__ k_in, const u32 *__restrict__ v_in
     k_out[p] = w;
     v_out[p] = v_in[j];
   }
+}
+
+// ---- level 2 for the SEARCH ALONE, on 8-byte records (option group_records) ----
+// SIZE 0 of k_group_fine with a search in it, where nobody reads the order it would store (the compact graph stage
+// when the first attempt of a pass settles and no bucket is beyond the walk: every metric pass).  Level 1 was
+// k_p8_scatter1 over FieldsRecs (kernels_graph.hip.h): bin c holds min(cursor[c], cap1) records (squeezed word <<
+// ibits | walk index) at c * cap1 -- no scan of the cursors in front, and this workgroup, their only reader, leaves
+// cursor[c] at zero for the next grouping.  Count, scan and place as above, by the fine key of the RESTORED word (sq:
+// RecSqueeze); the words go from the registers straight to their output places in the dead counter area -- no second
+// gather, no k_out / v_out -- and srch walks them there.  A hit takes its walk index from the records through inv.
+template <class SRC, class SQ, class SEARCH>
+__global__ void __launch_bounds__(GF_THREADS, 8)
+k_group_fine_recs(SRC src, SQ sq, const u64 *__restrict__ recs, u32 *cursor, u32 d1, u32 d2, u32 ibits, u32 cap1, SEARCH srch) {
+  HUMID_GUARD_LAST_VGPR();
+  constexpr u32 INV_WORDS = GF_SMALL / 2u + 16u;
+  constexpr u32 GF_RPT = 8;
+  static_assert(GF_RPT * GF_THREADS >= GF_SMALL, "a thread holds its share of a full bin");
+  static_assert(GF_SMALL * 2u + 32u <= (1u << (GF_MAXBITS - 1)), "the grouped words and the emit's words fit the counter area");
+  __shared__ __attribute__((aligned(8))) u32 gf_lds[(1u << (GF_MAXBITS - 1)) + INV_WORDS];
+  const u32 nb = 1u << d2, c = blockIdx.x;
+  u32 n = cursor[c];
+  if (n == 0) return;                                        // (uniform; the cursor is at zero already)
+  if (n > cap1) n = cap1;                                    // a full bin (reported by the scatter): never beyond its room
+  if (n > GF_SMALL) n = GF_SMALL;                            // (the host takes this road only with cap1 <= GF_SMALL)
+  recs += (size_t)c * cap1;
+  u32 *wsum = gf_lds + (1u << (GF_MAXBITS - 1)) + INV_WORDS - 16;
+  unsigned short *inv = (unsigned short *)(gf_lds + (1u << (GF_MAXBITS - 1)));
+  u64 kk[GF_RPT];
+  u32 ff[GF_RPT];
+#pragma unroll
+  for (u32 q = 0; q < GF_RPT; q++) {                         // the bin's records requested once, all together
+    const u32 j = threadIdx.x + q * GF_THREADS;
+    kk[q] = j < n ? recs[j] : 0ull;
+  }
+  for (u32 b = threadIdx.x; b < (1u << (GF_MAXBITS - 1)); b += GF_THREADS) gf_lds[b] = 0;
+  __syncthreads();
+  if (threadIdx.x == 0) cursor[c] = 0;                       // (every thread has read it: the barrier above)
+#pragma unroll
+  for (u32 q = 0; q < GF_RPT; q++) {
+    const u32 j = threadIdx.x + q * GF_THREADS;
+    kk[q] = sq.word(c, kk[q] >> ibits);
+    ff[q] = (u32)(src.key(kk[q]) >> (64 - d1 - d2)) & (nb - 1);
+    if (j < n) atomicAdd(&gf_lds[ff[q] >> 1], 1u << (16 * (ff[q] & 1)));
+  }
+  __syncthreads();
+  gf_scan16(gf_lds, wsum, nb);
+  u32 oldq[GF_RPT];
+#pragma unroll
+  for (u32 q = 0; q < GF_RPT; q++) {
+    const u32 j = threadIdx.x + q * GF_THREADS;
+    oldq[q] = j < n ? atomicAdd(&gf_lds[ff[q] >> 1], 1u << (16 * (ff[q] & 1))) : 0u;
+  }
+#pragma unroll
+  for (u32 q = 0; q < GF_RPT; q++) {
+    const u32 j = threadIdx.x + q * GF_THREADS;
+    oldq[q] = (oldq[q] >> (16 * (ff[q] & 1))) & 0xffffu;     // the output place of input position j
+    if (j < n) inv[oldq[q]] = (unsigned short)j;
+  }
+  __syncthreads();
+  u64 *sw = (u64 *)gf_lds;                                   // the counters are dead
+#pragma unroll
+  for (u32 q = 0; q < GF_RPT; q++) {
+    const u32 j = threadIdx.x + q * GF_THREADS;
+    if (j < n) sw[oldq[q]] = kk[q];
+  }
+  __syncthreads();
+  srch.template in_bin_recs<GF_RPT, GF_THREADS>(sw, n, inv, recs, ibits, gf_lds + 2u * GF_SMALL);
 }
 
 // --------------------------------------------------------------------------------

@@ -85,8 +85,9 @@ __device__ __forceinline__ u32 p8_group(u32 records, u32 nb) {
 
 // ---- level 1: reads -> padded coarse bins (top d1 key bits), records as described above ----
 // THREADS x PT_IPT reads per tile (1024: the tile of the other levels; 512: twice the workgroups per CU, whose
-// load / rank / write phases then overlap more)
-template <class SRC, u32 THREADS>
+// load / rank / write phases then overlap more).  OVER: the counter a full bin raises (the count stage: CTR_SPECIAL; the graph
+// stage's grouping, FieldsRecs in kernels_graph.hip.h: CTR_GOVER)
+template <class SRC, u32 THREADS, int OVER = CTR_SPECIAL>
 __global__ void __launch_bounds__(THREADS)
 k_p8_scatter1(SRC src, u32 n_reads, u32 kbits, u32 d1, u32 ibits, u32 cap1, u32 *cursor, u64 *__restrict__ out, ull *ctr) {
   HUMID_GUARD_LAST_VGPR();
@@ -126,7 +127,7 @@ k_p8_scatter1(SRC src, u32 n_reads, u32 kbits, u32 d1, u32 ibits, u32 cap1, u32 
     const u32 c = cnt[threadIdx.x];
     const u32 had = c ? atomicAdd(&cursor[threadIdx.x], c) : 0u;
     goff[threadIdx.x] = threadIdx.x * cap1 + (had < cap1 ? had : cap1);     // (a full bin: its end, room 0)
-    if (had + c > cap1) ctr[CTR_SPECIAL] = 1;                 // the bin outgrew its room: the caller repartitions
+    if (had + c > cap1) ctr[OVER] = 1;                        // the bin outgrew its room: the caller repartitions
   }
   PH(5);
 #pragma unroll

@@ -209,6 +209,8 @@ struct humid_ctx {
   DBuf pt_work, unperm_rec, route_tiles;                                                     // LDS-staged partition / un-permute (kernels_part.hip.h)
   bool group_buckets = true;        // option "group_buckets": bucket order of stretch keys by two-level grouping instead of a library sort
   bool fused_search = true;         // option "fused_search": the compact graph's neighbour search of a grouped combination rides in k_group_fine (0: a launch of k_pairs_append per combination)
+  bool group_records = true;        // option "group_records": a grouping whose search rides moves 8-byte records (squeezed word, walk index) and stores no order (0: the 12-byte pairs, the order stored)
+  u32 gr_rides = 0, gr_orders = 0;  // the last compact graph stage: groupings searched on records; bucket orders stored (humid_group_records_info)
   bool pt_padded = true;            // level 1 of the tile partition into padded coarse bins (no histogram pass); false after an overflow
   bool use_tile_partition = true;   // option "tile_partition": 0 = library radix passes + one-kernel un-permute (round 1)
   bool last_part_tiled = false;     // kev[39]..kev[40] bracket the second-level scatter of the last count
@@ -1419,7 +1421,14 @@ struct GroupRide {
   PairSearchDev group;
   bool did_group = false;
   hipEvent_t ev_group[2] = {nullptr, nullptr};
+  // option group_records: word_bits = the significant bits of a word (0: not known, the order is stored).  Where the
+  // ride is taken and a word squeezed by its coarse bin fits an 8-byte record beside its walk index, the grouping moves
+  // records and stores NO order (ws / vs untouched): no_order.
+  u32 word_bits = 0;
+  bool no_order = false;
 };
+static void group_fine_recs_with_search(humid_ctx *c, const FieldsSrc &src, const RecSqueeze &sq, const u64 *recs, u32 *cursor, u32 d1, u32 d2,
+                                        u32 ibits, u32 cap1, const PairSearchDev &s);
 // (the launch layer of the neighbour search, below)
 static void group_fine_with_search(humid_ctx *c, const FieldsSrc &src, const u64 *k0, const u32 *v0, const u32 *cbase, u32 d1, u32 d2, u64 *ws,
                                    u32 *vs, u32 cap1, const PairSearchDev &s);
@@ -1441,26 +1450,48 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
   const bool padded = may_pad && c->gf_padded;
   const u32 cap1 = padded ? n / nb1 + n / nb1 / 4 + 1024 : 0u;
   const size_t room = padded ? (size_t)nb1 * cap1 : (size_t)n;
-  // scratch: [hist1 512 | cursor1 512] zeroed, then [cbase 513 | tprefix 513 | pbeg dummy 514]
-  ENSURE(c->pt_work, (size_t)(1024 + 513 + 513 + 516) * 4);
-  u32 *hist1 = c->pt_work.as<u32>(), *cursor1 = hist1 + 512, *cbase = cursor1 + 512, *tprefix = cbase + 513, *dummy = tprefix + 513;
-  if (padded) {                                              // its own cursors, cleared by the scan that reads them
+  const SRC src{W, plan_fields(plan, cb), bit_n};
+  const u32 tiles1 = (n + PT_TILE - 1) / PT_TILE;
+  u32 *cursor1 = nullptr;
+  if (padded) {                                              // its own cursors, cleared by the kernel that reads them
     if (!c->gf_cur.p) {
       ENSURE(c->gf_cur, 512 * 4);
       HIPCHK(hipMemsetAsync(c->gf_cur.p, 0, 512 * 4, st));
     }
     cursor1 = c->gf_cur.as<u32>();
-  } else HIPCHK(hipMemsetAsync(c->pt_work.p, 0, 1024 * 4, st));
+  }
   ENSURE(c->seg_k0, room * 8);
+  const bool ride_ok = ride && std::is_same<SRC, FieldsSrc>::value && padded && cap1 <= GF_SMALL;   // every bin is a SIZE-0 bin
+  if constexpr (std::is_same<SRC, FieldsSrc>::value) {
+    // the search rides and nobody else reads this order: 8-byte records through level 1 (8192 of them are 64 KB of LDS: two
+    // workgroups per CU, the tiles of U = 2.7 M words in ONE round), no scan of the cursors (k_group_fine_recs reads and
+    // clears its own), no order stored.  Needs none of the scratch below: no walk indices beside the records, no bin
+    // bases, no tile table.
+    const u32 ibits = bits_for(n), wb = ride_ok ? ride->word_bits : 0u;
+    if (ride_ok && c->group_records && wb && plan.width[cb][0] >= d1 && wb - d1 + ibits <= 64) {
+      const RecSqueeze sq{(u32)plan.shift[cb][0] + plan.width[cb][0] - d1, d1};
+      const FieldsRecs rsrc{W, sq, wb - d1};
+      hipLaunchKernelGGL((k_p8_scatter1<FieldsRecs, 1024, CTR_GOVER>), dim3(tiles1), dim3(1024), 0, st, rsrc, n, wb, d1, ibits, cap1, cursor1,
+                         c->seg_k0.as<u64>(), c->d_ctr);
+      if (ride->ev_group[0]) HIPCHK(hipEventRecord(ride->ev_group[0], st));
+      group_fine_recs_with_search(c, src, sq, c->seg_k0.as<u64>(), cursor1, d1, d2, ibits, cap1, ride->group);
+      if (ride->ev_group[1]) HIPCHK(hipEventRecord(ride->ev_group[1], st));
+      ride->did_group = ride->no_order = true;
+      HIPCHK(hipGetLastError());
+      return HUMID_OK;
+    }
+  }
   ENSURE(c->seg_v0, room * 4);
-  const SRC src{W, plan_fields(plan, cb), bit_n};
-  const u32 tiles1 = (n + PT_TILE - 1) / PT_TILE;
+  // scratch: [hist1 512 | cursor1 512] zeroed, then [cbase 513 | tprefix 513 | pbeg dummy 514]
+  ENSURE(c->pt_work, (size_t)(1024 + 513 + 513 + 516) * 4);
+  u32 *hist1 = c->pt_work.as<u32>(), *cbase = hist1 + 1024, *tprefix = cbase + 513, *dummy = tprefix + 513;
   if (!padded) {
+    cursor1 = hist1 + 512;
+    HIPCHK(hipMemsetAsync(c->pt_work.p, 0, 1024 * 4, st));
     hipLaunchKernelGGL(k_pt_hist1<SRC>, dim3(tiles1 < 512 ? tiles1 : 512), dim3(1024), 0, st, src, n, d1, hist1);
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)hist1, d1, 0u, cbase, tprefix, dummy, dummy + 513, 0u);
   }
   static const bool gs_small = getenv("HUMID_GS_THREADS") ? atoi(getenv("HUMID_GS_THREADS")) == 512 : false;  // (experiments: 512-thread tiles are 7 us slower -- shorter runs per bin)
-  const bool ride_ok = ride && std::is_same<SRC, FieldsSrc>::value && padded && cap1 <= GF_SMALL;   // every bin is a SIZE-0 bin
   if (gs_small)
     hipLaunchKernelGGL((k_pt_scatter<1, SRC, 512>), dim3((n + 4095) / 4096), dim3(512), 0, st, src, n, (const u64 *)nullptr,
                        (const u32 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, (const u32 *)cbase, cursor1,
@@ -1556,7 +1587,7 @@ static int bucket_order(humid_ctx *c, const ComboPlan &plan, u32 seg, const WT *
 // ---- the launch layer of the Hamming neighbour search ------------------------------------
 // A driver of the search (stage_graph, stage_graph_compact, emit_orders in humid_exchange.hip) says WHAT is
 // walked (Walked) and WHERE a found pair goes (CsrSink, EmitSink); k_pairs, k_pairs_tiles, k_pairs_append and the
-// k_group_fine that a search rides in (GroupRide) are launched by the six functions below and nowhere else.  Each holds the one (PASS0, MODE) dispatch of its
+// k_group_fine / k_group_fine_recs that a search rides in (GroupRide) are launched by the seven functions below and nowhere else.  Each holds the one (PASS0, MODE) dispatch of its
 // kernel and the only spelling of the null pointers for the sinks a mode does not use, so a change to how a
 // bucket is walked -- a kernel argument, a bound, a bucket left out -- is made here.
 template <class WT>
@@ -1688,6 +1719,16 @@ static void group_fine_with_search(humid_ctx *c, const FieldsSrc &src, const u64
   else
     hipLaunchKernelGGL((k_group_fine<FieldsSrc, 0, PairSearchDev>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, k0, v0, cbase, d1, d2, ws,
                        vs, cap1, s);
+}
+// the same over the 8-byte records of a padded level 1 (FieldsRecs), for the search alone: no order is stored
+static void group_fine_recs_with_search(humid_ctx *c, const FieldsSrc &src, const RecSqueeze &sq, const u64 *recs, u32 *cursor, u32 d1, u32 d2,
+                                        u32 ibits, u32 cap1, const PairSearchDev &s) {
+  if (s.multi)
+    hipLaunchKernelGGL((k_group_fine_recs<FieldsSrc, RecSqueeze, PairSearchDevT<true>>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, sq, recs,
+                       cursor, d1, d2, ibits, cap1, PairSearchDevT<true>{s.rule, s.er, s.bits, s.multi, s.big, s.overflow});
+  else
+    hipLaunchKernelGGL((k_group_fine_recs<FieldsSrc, RecSqueeze, PairSearchDev>), dim3(1u << d1), dim3(GF_THREADS), 0, c->stream, src, sq, recs, cursor,
+                       d1, d2, ibits, cap1, s);
 }
 // component sizes and what is read from them (M, Mbig, 2E, the roots of the small components) for deg / parent over U nodes
 static void comp_stats(humid_ctx *c, u32 U) {
@@ -1989,6 +2030,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   c->cg_expanded = false;
   c->cg_split = c->cg_full = c->cg_m_late = c->cg_broken = false;
   c->cg_iso = c->cg_R = 0;
+  c->gr_rides = c->gr_orders = 0;
   const bool split = c->pair_split;
   const ComboPlan plan = make_plan(word_nt - c->gk_nt, distance, U, c->force_segments, true, c->gk_nt);
   const PairSearch<WT> ps = pair_search<WT>(c, plan, distance);
@@ -2065,6 +2107,13 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     // launch it rode in) -- where the grouping takes it.  An order kept from an earlier attempt, and the prefix
     // combination's (the walk order itself), are searched by k_pairs_append.
     const bool ride_on = c->fused_search && std::is_same<WT, u64>::value;
+    // Only the first attempt rides.  Where every order is stored that is so by itself (a later attempt finds the orders of
+    // the first, or exact bins, which no search rides in); a search on records stores none, and were it to ride again
+    // behind a full region, the run would take FEWER attempts than with stored orders: a ride spreads a combination's
+    // pairs over one region per coarse bin, k_pairs_append over one per 1024 positions, and at 4 858 words (5 such regions)
+    // the second attempt fits the regrown regions with a ride and fills one again without.  The attempts of a run do not
+    // depend on group_records: a later attempt makes the order and searches it with k_pairs_append.
+    const bool ride_now = ride_on && attempt == 0;
     for (u32 seg = 0; seg < nseg; seg++) {
       bool searched = false;
       if (seg) {
@@ -2074,16 +2123,20 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
         if (!ordered_seg[seg]) {
           GroupRide ride;
           if constexpr (std::is_same<WT, u64>::value) {
-            if (ride_on) {
+            if (ride_now) {
               ride.group = pairs_append_dev(ps, w_from<u64>(plan.mask[seg]), seg, er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
               if (seg < 8 && c->kev_on) { ride.ev_group[0] = c->kev[20 + 2 * seg]; ride.ev_group[1] = c->kev[21 + 2 * seg]; }
+              ride.word_bits = word_nt <= 32 ? 2 * word_nt : 0u;
             }
           }
-          TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true, ride_on ? &ride : nullptr));
+          TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true, ride_now ? &ride : nullptr));
           seg_valid[seg] = c->gf_valid;
           searched = ride.did_group;
+          // a search that rode on records (group_records) stored NO order: a later attempt makes it (no ride then, see
+          // ride_now), and so do the tiles below
+          ordered_seg[seg] = !ride.no_order;
+          if (ride.no_order) c->gr_rides++; else c->gr_orders++;
         }
-        ordered_seg[seg] = true;
       }
       if (!searched) TRY(search_alone(seg));
     }
@@ -2152,6 +2205,13 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
         u64 at = 0;
         for (u32 seg = 0; seg < nseg; seg++) {
           if (!(big_mask >> seg & 1)) continue;
+          if (seg && !ordered_seg[seg]) {
+            // its search rode on records and stored no order: made now, without a ride, and searched by k_pairs_append
+            // from here on.  The padded bins that held every word a moment ago hold them again: the order is complete.
+            TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U), true));
+            ordered_seg[seg] = true;
+            c->gr_orders++;
+          }
           const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
           std::vector<BigRun> runs;
           const BigRun *d_runs = nullptr;

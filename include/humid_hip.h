@@ -1161,6 +1161,11 @@ int humid_stage_scatter(humid_ctx *ctx, const uint32_t *d_perm, const uint32_t *
  * in the context -- 1 after a run that did not split, else 0 until an accessor (humid_get_leaves / _adjacency /
  * _clusters / _histogram) has asked for it; the run's results never depend on it.  Any pointer may be NULL. */
 int humid_graph_split_info(humid_ctx *ctx, uint64_t *pairs_direct, uint64_t *pairs_graph, uint32_t *full_graph_built);
+/* How the compact graph stage of the last run made its bucket orders (option "group_records", default 1), counted over
+ * all attempts of the stage: *searched_on_records = groupings that moved 8-byte records (squeezed word, walk index), had
+ * the combination's search in them and stored no order; *orders_stored = bucket orders written to memory (a grouping
+ * on 12-byte pairs or a sort; with a search in it or without).  Any pointer may be NULL. */
+int humid_group_records_info(humid_ctx *ctx, uint32_t *searched_on_records, uint32_t *orders_stored);
 /* Which attempts the last mutating call (a run, humid_accum_add / _finish / _map, a humid_stage_* call that counts or
  * builds a graph) threw away and took again, in the order they happened.  A record the host keeps while it decides:
  * it costs the GPU nothing and changes no result.  One event per occurrence:
