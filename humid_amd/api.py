@@ -829,6 +829,13 @@ class Dedup(Context):
         self._check(self._lib.humid_group_records_info(self._h, C.byref(a), C.byref(b)))
         return dict(searched_on_records=a.value, orders_stored=b.value)
 
+    def wait_overlap_info(self):
+        """dict(host_waits, overlapped) of the last mutating call (humid_wait_overlap_info): the host's waits for
+        counters, and those of them that had kernels queued between the publishing kernel and the wait"""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.humid_wait_overlap_info(self._h, C.byref(a), C.byref(b)))
+        return dict(host_waits=a.value, overlapped=b.value)
+
     def run_roads(self):
         """what the last mutating call retried (humid_get_run_roads): dict(events, n_events, graph_attempts).  events:
         the names of the first 32 events in order, of PART_PADDED_REDO, ORDERS_REDONE, REGIONS_REGROWN, FAR_TILES,

@@ -221,6 +221,14 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->group_records = value != 0;
     return HUMID_OK;
   }
+  if (strcmp(key, "overlap_waits") == 0) {
+    c->overlap_waits = value != 0;
+    return HUMID_OK;
+  }
+  if (strcmp(key, "static_tiles") == 0) {
+    c->static_tiles = value != 0;
+    return HUMID_OK;
+  }
   if (strcmp(key, "padded_partition") == 0) {
     c->pt_padded = value != 0;
     return HUMID_OK;
@@ -496,6 +504,14 @@ int humid_group_records_info(humid_ctx *c, uint32_t *searched_on_records, uint32
   if (!state_has_leaves(c)) return fail(c, HUMID_E_STATE, "no completed dedup run / graph stage in this context");
   if (searched_on_records) *searched_on_records = c->cg_valid ? c->gr_rides : 0u;
   if (orders_stored) *orders_stored = c->cg_valid ? c->gr_orders : 0u;
+  return HUMID_OK;
+}
+
+int humid_wait_overlap_info(humid_ctx *c, uint32_t *host_waits, uint32_t *overlapped) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (c->state.holds == CtxState::NOTHING) return fail(c, HUMID_E_STATE, "no completed run or stage call in this context");
+  if (host_waits) *host_waits = c->wo_waits;
+  if (overlapped) *overlapped = c->wo_overlapped;
   return HUMID_OK;
 }
 

@@ -143,6 +143,11 @@ k_p8_scatter1(SRC src, u32 n_reads, u32 kbits, u32 d1, u32 ibits, u32 cap1, u32 
 
 // ---- level 2: one tile of one coarse bin -> padded fine buckets (the next d2 key bits) ----
 // bucket g = c << d2 | f owns the positions [g << P8_CAP2_LOG, (g + 1) << P8_CAP2_LOG); cursor2[g] = its reads
+// STATIC (option static_tiles): no tile table.  Level 1 is padded, so the records of coarse bin c lie at c * cap1 and
+// cursor1[c] says how many (cut to cap1: a bin that outgrew its room holds cap1, and the caller discards the run).  The
+// grid is 2^d1 x ceil(cap1 / PT_TILE) workgroups, the tile index t the slow one -- the tiles beyond a bin's fill, which
+// leave at once, are the end of the grid -- and tprefix = cursor1, cbase unused.  Else the table of k_pt_scan1.
+template <bool STATIC>
 static __global__ void __launch_bounds__(1024, 8)
 k_p8_scatter2(const u64 *__restrict__ in, const u32 *__restrict__ tprefix, const u32 *__restrict__ cbase, u32 kbits, u32 d1,
               u32 d2, u32 ibits, u32 cap1, u32 *cursor2, u64 *__restrict__ out, ull *ctr) {
@@ -152,17 +157,30 @@ k_p8_scatter2(const u64 *__restrict__ in, const u32 *__restrict__ tprefix, const
   __shared__ u32 s_c, s_beg, s_cnt;
   PH_DECL;
   PH(0);
-  if (blockIdx.x >= tprefix[1u << d1]) return;                // beyond the last tile (uniform exit)
   const u32 nb = 1u << d2;
-  if (threadIdx.x == 0) {
-    u32 c, b, n;
-    pt_tile_of(tprefix, cbase, 1u << d1, blockIdx.x, cap1, c, b, n);
-    s_c = c; s_beg = b; s_cnt = n;
+  u32 coarse, t_beg, t_cnt;
+  if constexpr (STATIC) {
+    coarse = blockIdx.x & ((1u << d1) - 1u);
+    const u32 done = (blockIdx.x >> d1) * PT_TILE;            // < cap1 + PT_TILE by the grid
+    u32 fill = tprefix[coarse];                               // (uniform: every thread reads the same word)
+    if (fill > cap1) fill = cap1;
+    if (done >= fill) return;                                 // beyond the bin's fill (uniform exit)
+    t_beg = coarse * cap1 + done;
+    t_cnt = fill - done < PT_TILE ? fill - done : PT_TILE;
+    for (u32 b = threadIdx.x; b < nb; b += PT_THREADS) cnt[b] = 0;
+    __syncthreads();
+  } else {
+    if (blockIdx.x >= tprefix[1u << d1]) return;              // beyond the last tile (uniform exit)
+    if (threadIdx.x == 0) {
+      u32 c, b, n;
+      pt_tile_of(tprefix, cbase, 1u << d1, blockIdx.x, cap1, c, b, n);
+      s_c = c; s_beg = b; s_cnt = n;
+    }
+    for (u32 b = threadIdx.x; b < nb; b += PT_THREADS) cnt[b] = 0;
+    __syncthreads();
+    coarse = s_c; t_beg = s_beg; t_cnt = s_cnt;
   }
-  for (u32 b = threadIdx.x; b < nb; b += PT_THREADS) cnt[b] = 0;
-  __syncthreads();
   PH(1);
-  const u32 coarse = s_c, t_beg = s_beg, t_cnt = s_cnt;
   const u32 fshift = ibits + kbits - d1 - d2;                 // where a record keeps the fine bits
   u64 rec[PT_IPT];
   u32 binrank[PT_IPT];

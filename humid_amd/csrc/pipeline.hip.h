@@ -211,6 +211,9 @@ struct humid_ctx {
   bool fused_search = true;         // option "fused_search": the compact graph's neighbour search of a grouped combination rides in k_group_fine (0: a launch of k_pairs_append per combination)
   bool group_records = true;        // option "group_records": a grouping whose search rides moves 8-byte records (squeezed word, walk index) and stores no order (0: the 12-byte pairs, the order stored)
   u32 gr_rides = 0, gr_orders = 0;  // the last compact graph stage: groupings searched on records; bucket orders stored (humid_group_records_info)
+  bool overlap_waits = true;        // option "overlap_waits": the count stage's and the split graph stage's host waits stand behind their publishing kernel with work queued after it (0: publish and wait back to back)
+  bool static_tiles = true;         // option "static_tiles": level 2 of the record count finds its tiles from the padded bins' cursors (0: the tile table of k_pt_scan1)
+  u32 wo_waits = 0, wo_overlapped = 0;   // host waits of the last mutating call; those with work queued between publish and wait (humid_wait_overlap_info): host stores only
   bool pt_padded = true;            // level 1 of the tile partition into padded coarse bins (no histogram pass); false after an overflow
   bool use_tile_partition = true;   // option "tile_partition": 0 = library radix passes + one-kernel un-permute (round 1)
   bool last_part_tiled = false;     // kev[39]..kev[40] bracket the second-level scatter of the last count
@@ -424,8 +427,9 @@ static int exscan_u32(humid_ctx *c, const u32 *in, u32 *out, u64 n) { return exs
 // in h_ctr[CTR_N - 1].
 // One tiny kernel stores the counters (and the extra value) straight into the page-locked mirror and then
 // a sequence number; the host watches that word.  Two blit copies + hipStreamSynchronize cost ~30 us of idle
-// GPU per host wait, this ~10 (three waits per single-GPU pass, eight in the multi-GPU pass; with pair_split a fourth
-// that the GPU works through: read_counters_begin / _end below).
+// GPU per host wait, this ~10 (four waits per single-GPU pass, eight in the multi-GPU pass; three of the four have
+// work queued behind the publishing kernel, which the GPU works through while the host reads: read_counters_begin /
+// _end below, option overlap_waits).
 static __global__ void k_publish_counters(const ull *__restrict__ ctr, const u32 *__restrict__ extra32, const u32 *__restrict__ extra32b,
                                    volatile ull *host, ull seq, const u32 *__restrict__ extra32c = nullptr) {
   HUMID_GUARD_LAST_VGPR();
@@ -454,13 +458,19 @@ static int read_counters_begin(humid_ctx *c, const u32 *extra32 = nullptr, const
   }
   return HUMID_OK;
 }
-static int read_counters_end(humid_ctx *c) {
+// work_queued: the caller has launched kernels since _begin (counted for humid_wait_overlap_info)
+static int read_counters_end(humid_ctx *c, bool work_queued = false) {
   const u32 *extra32 = c->ctr_x[0], *extra32b = c->ctr_x[1], *extra32c = c->ctr_x[2];
+  c->wo_waits++;
+  if (work_queued) c->wo_overlapped++;
   if (c->h_ctr_dev && !c->no_poll) {
     const ull seq = c->ctr_seq;
     volatile ull *flag = (volatile ull *)&c->h_ctr[CTR_N];
     const auto t0 = std::chrono::steady_clock::now();
     u32 spins = 0;
+    // (The query every 4096 looks, 2.5 us, leaves a marker at the end of a busy stream: a kernel queued behind the
+    // publishing kernel is followed by 5.7 us of idle GPU before the next launch starts.  Asking only after 2 ms took
+    // that away but made two plain bench runs of five slower than any of the parent's: profiles/r04d_overlap_waits.md.)
     while (*flag != seq) {
       if ((++spins & 0xfffu) == 0) {
         if (hipStreamQuery(c->stream) != hipErrorNotReady) break;              // drained (the stores are done or lost) or failed: settled below
@@ -501,7 +511,7 @@ static int scan_total(humid_ctx *c, const u32 *in, u32 *out, u64 n, u64 *total) 
 }
 
 // ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
-static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; c->roads = humid_run_roads{}; }
+static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; c->roads = humid_run_roads{}; c->wo_waits = c->wo_overlapped = 0; }
 // one retry of the call now running (HUMID_ROAD_*): behind the host wait that showed it, a store on the host
 static inline void road_taken(humid_ctx *c, u8 road) {
   if (c->roads.n_events < HUMID_ROADS_MAX) c->roads.events[c->roads.n_events] = road;
@@ -677,7 +687,7 @@ static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt,
       hipLaunchKernelGGL(k_cluster_small_lds<false>, dim3(blocks_for(small_cap, 64)), dim3(64), 0, st, c->small_roots.as<u32>(),
                          (const ull *)c->d_ctr, g.parent, g.csize, U, g_cnt, g.off, g.idx, g.cl_of, g.maxleaf, g.cl_size);
     if (late_m) {
-      TRY(read_counters_end(c));
+      TRY(read_counters_end(c, true));
       Mbig = c->h_ctr[CTR_MEMBERS];
       M = c->h_ctr[CTR_N - 3] & 0xffffffffull;
       U = (u32)M;
@@ -1064,11 +1074,20 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   else
     hipLaunchKernelGGL((k_p8_scatter1<Reads8, 1024>), dim3(tiles1), dim3(1024), 0, st, src, N, rk.kbits, d1, ibits, cap1, cursor1,
                        c->p8_a.as<u64>(), c->d_ctr);
-  hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
-                     c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
-  hipLaunchKernelGGL(k_p8_scatter2, dim3(tiles2), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(), (const u32 *)tprefix,
-                     (const u32 *)cbase, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
+  // static_tiles: level 2 reads the padded bins' cursors itself -- no scan, no tile table (and nothing stores
+  // pbeg[n_parts] / ucount[n_parts], which no kernel of the record road reads: its un-permute, k_unperm_bins8, takes
+  // the buckets' fills from cursor2).  One workgroup per tile of every bin's ROOM: those beyond the fill leave at once.
+  if (c->static_tiles) {
+    if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+    hipLaunchKernelGGL(k_p8_scatter2<true>, dim3(nb1 * ((cap1 + PT_TILE - 1) / PT_TILE)), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(),
+                       (const u32 *)cursor1, (const u32 *)nullptr, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
+  } else {
+    hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
+                       c->ucount.as<u32>() + n_parts, cap1);
+    if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+    hipLaunchKernelGGL(k_p8_scatter2<false>, dim3(tiles2), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(), (const u32 *)tprefix,
+                       (const u32 *)cbase, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
+  }
   if (c->kev_on) HIPCHK(hipEventRecord(c->kev[40], st));
   HIPCHK(hipEventRecord(c->kev[0], st));
   hipLaunchKernelGGL(k_dedup_rec, dim3(n_parts), dim3(256), 0, st, c->p8_b.as<u64>(), (const u32 *)cursor2, N, pb, d1, ibits, rk,
@@ -1076,18 +1095,24 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   HIPCHK(hipEventRecord(c->kev[1], st));
   TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, (u64)n_parts + 1));
   // the walk-order arrays are squeezed out of the padded ones BEFORE the host knows how many unique words there are
-  // (at most N: a bucket never reports more words than records it holds): the host's wait for the counters -- it
-  // needs U to shape the graph stage -- then runs beside this kernel instead of an idle GPU
+  // (at most N: a bucket never reports more words than records it holds).  Everything the host's wait reads -- U and
+  // the usable reads (the scan's totals), CTR_SPECIAL, CTR_OVERFULL -- is final behind the scan, so with overlap_waits
+  // the publishing kernel stands IN FRONT of the squeeze: the host sees U, which it needs to shape the graph stage,
+  // while the squeeze runs, and queues that stage behind it.  (Without the option the publishing kernel follows the
+  // squeeze in the stream, and the GPU is idle from the squeeze's end until the host has seen U and launched.)
   ENSURE(c->s_word, (size_t)(N + 1) * 8);
   ENSURE(c->s_slot, (size_t)(N + 1) * 4);
   ENSURE(c->s_cnt, (size_t)(N + 1) * 4);
   ENSURE(c->s_first, (size_t)(N + 1) * 4);
+  const bool early = c->overlap_waits;
+  if (early) TRY(read_counters_begin(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
   hipLaunchKernelGGL(k_compact_padded8, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, c->pad_word.as<u64>(),
                      c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<u64>(),
                      c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
   if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
   HIPCHK(hipGetLastError());
-  TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
+  if (early) TRY(read_counters_end(c, true));
+  else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
   if (getenv("HUMID_TRACE_COUNT"))
     fprintf(stderr, "[rec count] N %u pb %u kbits %u ibits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits,
             ibits, cap1, (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
@@ -1172,17 +1197,20 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
                        c->pad_word.as<W2>(), c->pad_cf.as<uint2>(), agg, c->p8_b.as<u64>(), c->d_ctr);
   HIPCHK(hipEventRecord(c->kev[1], st));
   TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, (u64)n_parts + 1));
-  // (as in stage_count_rec: squeezed out beside the host's wait for the counters; at most N unique words)
+  // (as in stage_count_rec: at most N unique words; overlap_waits publishes the counters in front of the squeeze)
   ENSURE(c->s_word, (size_t)(N + 1) * 16);
   ENSURE(c->s_slot, (size_t)(N + 1) * 4);
   ENSURE(c->s_cnt, (size_t)(N + 1) * 4);
   ENSURE(c->s_first, (size_t)(N + 1) * 4);
+  const bool early = c->overlap_waits;
+  if (early) TRY(read_counters_begin(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
   hipLaunchKernelGGL(k_compact_padded8_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, (const W2 *)c->pad_word.as<W2>(),
                      (const uint2 *)c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<W2>(),
                      c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
   if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
   HIPCHK(hipGetLastError());
-  TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
+  if (early) TRY(read_counters_end(c, true));
+  else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
   if (getenv("HUMID_TRACE_COUNT"))
     fprintf(stderr, "[rec count, wide] N %u pb %u kbits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits, cap1,
             (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
@@ -1908,34 +1936,48 @@ static GraphArrays cg_arrays(humid_ctx *c) {
 }
 // rank structure, nodes, compact pairs, degrees, forest, CSR rows (ascending), component sizes, the trivial
 // components; ONE host wait at the end (every launch before it is sized by bounds: nodes <= 2 x pairs).
-static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
+// In two halves.  cg_build_front is what does not depend on the pairs, only on the bitmap of the marked ids: its rank
+// blocks and the nodes with their per-node arrays, sized by `nodes_bound` >= the bits set.  cg_build_back is the rest,
+// from the relabelling of the pairs on, sized by the pairs' bound.  cg_build is the two back to back; the split graph
+// stage queues the front behind its publishing kernel, before the host knows the number of rest pairs, and the back
+// once it does (stage_graph_compact).
+static int cg_build_front(humid_ctx *c, const u32 *bits, u32 n_ids, const u32 *cnt_by_id, u64 nodes_bound) {
+  hipStream_t st = c->stream;
+  const u32 n_words = (((n_ids + 31) / 32) + 7) & ~7u, n_blk = n_words / 8;
+  const size_t Mb = (size_t)std::min<u64>(n_ids, nodes_bound);
+  ENSURE(c->cg_blk, ((size_t)n_blk + 1) * 4);
+  ENSURE(c->cg_nodes, (Mb + 1) * 4);
+  ENSURE(c->cg_ncnt, (Mb + 1) * 4);
+  ENSURE(c->cg_deg, (Mb + 2) * 4);
+  ENSURE(c->cg_parent, (Mb + 1) * 4);
+  ENSURE(c->cg_csize, (Mb + 1) * 4);
+  ENSURE(c->cg_curs, (Mb + 1) * 4);
+  TRY(exscan_in<u32>(c, BitsBlockIn{bits, n_blk}, c->cg_blk.as<u32>(), (u64)n_blk + 1));
+  const BitRank br{bits, c->cg_blk.as<u32>()};
+  const GraphArrays g = cg_arrays(c);
+  hipLaunchKernelGGL(k_nodes_init, dim3(blocks_for(n_words)), dim3(256), 0, st, br, n_words, cnt_by_id, c->cg_nodes.as<u32>(),
+                     c->cg_ncnt.as<u32>(), g.deg, g.parent, g.csize, c->cg_curs.as<u32>(), n_blk);
+  HIPCHK(hipGetLastError());
+  return HUMID_OK;
+}
+static int cg_build_back(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
   hipStream_t st = c->stream;
   u32 *bits = src.bits ? src.bits : c->cg_bits.as<u32>();
   const u32 n_words = (((src.n_ids + 31) / 32) + 7) & ~7u, n_blk = n_words / 8;
   const u64 pb = std::max<u64>(src.pairs_bound, 1);
   if (2 * pb + 2 > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
   const u32 Mb = (u32)std::min<u64>(src.n_ids, 2 * pb);
-  ENSURE(c->cg_blk, ((size_t)n_blk + 1) * 4);
-  ENSURE(c->cg_nodes, ((size_t)Mb + 1) * 4);
-  ENSURE(c->cg_ncnt, ((size_t)Mb + 1) * 4);
-  ENSURE(c->cg_deg, ((size_t)Mb + 2) * 4);
   ENSURE(c->cg_off, ((size_t)Mb + 2) * 4);
-  ENSURE(c->cg_parent, ((size_t)Mb + 1) * 4);
-  ENSURE(c->cg_csize, ((size_t)Mb + 1) * 4);
-  ENSURE(c->cg_curs, ((size_t)Mb + 1) * 4);
   ENSURE(c->cg_idx, (size_t)(2 * pb + 1) * 4);
   ENSURE(c->cg_cl_of, ((size_t)Mb + 1) * 4);
   ENSURE(c->cg_maxleaf, ((size_t)Mb + 1) * 4);
   ENSURE(c->cg_cl_size, ((size_t)Mb + 1) * 8);
   ENSURE(c->small_roots, ((size_t)Mb / 3 + 2) * 4);
   ENSURE(c->small, 64);
-  TRY(exscan_in<u32>(c, BitsBlockIn{bits, n_blk}, c->cg_blk.as<u32>(), (u64)n_blk + 1));
   const BitRank br{bits, c->cg_blk.as<u32>()};
   const u32 *m_dev = c->cg_blk.as<u32>() + n_blk;
   const GraphArrays g = cg_arrays(c);
   const u32 r_first = src.er.e ? 0u : ER_REGIONS;        // no regions (one dense pair list): the `far` region alone
-  hipLaunchKernelGGL(k_nodes_init, dim3(blocks_for(n_words)), dim3(256), 0, st, br, n_words, src.cnt_by_id, c->cg_nodes.as<u32>(),
-                     c->cg_ncnt.as<u32>(), g.deg, g.parent, g.csize, c->cg_curs.as<u32>(), n_blk);
   const bool by_count = (method & 1) == 0;
   if (src.segs) {
     const u32 n_all = src.segs->first[REC_SEGS];
@@ -1987,6 +2029,12 @@ static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
   out.M = c->h_ctr[CTR_N - 3] & 0xffffffffull;
   out.Mbig = c->h_ctr[CTR_MEMBERS];
   return HUMID_OK;
+}
+static int cg_build(humid_ctx *c, CgSource &src, u32 method, CgStatus &out) {
+  const u64 pb = std::max<u64>(src.pairs_bound, 1);
+  if (2 * pb + 2 > 0xffffffffull) return fail(c, HUMID_E_OVERFLOW, "too many neighbour pairs");
+  TRY(cg_build_front(c, src.bits ? src.bits : c->cg_bits.as<u32>(), src.n_ids, src.cnt_by_id, 2 * pb));
+  return cg_build_back(c, src, method, out);
 }
 // the components of 3 and more nodes, then the nodes that created no cluster as a bitmap over the ids with
 // its rank structure (c->cg_nbits zeroed by the caller; cg_nblk)
@@ -2157,7 +2205,16 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
         hipLaunchKernelGGL(k_pairs_split<false>, dim3(gx, ER_REGIONS + 1), dim3(256), 0, st, er, (const u32 *)multi, g_cnt, c->cg_pres.as<u32>(),
                            c->cg_nbits.as<u32>(), c->cg_rbits.as<u32>(), c->cg_rest.as<u64>(), (u32)rest_cap, U, sp);
       HIPCHK(hipGetLastError());
-      TRY(read_counters(c, sp + SPLIT_REST, sp + SPLIT_RMAX, sp + SPLIT_ALL));
+      if (c->overlap_waits) {
+        // the front of the rest build does not depend on R, only on cg_rbits: it runs while the host waits for R and
+        // the retry flags and decides.  Its arrays are sized by a bound known now: k_pairs_split lists at most rest_cap
+        // pairs (its own argument), so cg_rbits has at most min(U, 2 * rest_cap) bits set.  On a retry its output is
+        // dead: the next attempt zeroes the bitmaps and makes it again.
+        TRY(read_counters_begin(c, sp + SPLIT_REST, sp + SPLIT_RMAX, sp + SPLIT_ALL));
+        TRY(cg_build_front(c, c->cg_rbits.as<u32>(), U, g_cnt, 2 * rest_cap));
+        TRY(read_counters_end(c, true));
+      } else
+        TRY(read_counters(c, sp + SPLIT_REST, sp + SPLIT_RMAX, sp + SPLIT_ALL));
       cgs.wanted = (c->h_ctr[CTR_N - 2] & 0xffffffffull) * ER_REGIONS;
       cgs.overflow = (c->h_ctr[CTR_EOVER] & 0xffffffffull) != 0;
       cgs.group_over = c->h_ctr[CTR_GOVER] != 0;
@@ -2246,7 +2303,8 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
   const u32 *late_m = nullptr;
   bool fetch = false;
   if (split) {
-    // the compact graph over the R rest pairs (a dense list) and their ends (cg_rbits), sized by R; no wait of its own
+    // the compact graph over the R rest pairs (a dense list) and their ends (cg_rbits), sized by R (with overlap_waits
+    // its front, sized by a bound, is in the stream already); no wait of its own
     c->cg_split = true;
     c->cg_method = method;
     c->cg_iso = n_iso; c->cg_R = R;
@@ -2258,7 +2316,8 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       src.pairs_bound = R;
       src.bits = c->cg_rbits.as<u32>();
       src.no_wait = true;
-      TRY(cg_build(c, src, method, cgs));
+      if (c->overlap_waits) TRY(cg_build_back(c, src, method, cgs));   // (its front ran behind the last attempt's publishing kernel)
+      else TRY(cg_build(c, src, method, cgs));
       late_m = c->cg_blk.as<u32>() + n_blk;
       // a component of more than SMALL_COMP nodes has at least SMALL_COMP pairs: with fewer, Mbig = 0 and the node
       // count can wait for the pass's last wait; else both come while k_cluster_small_lds runs
@@ -2315,6 +2374,8 @@ static int cg_build_full(humid_ctx *c) {
   hipStream_t st = c->stream;
   struct NoKernelEvents { humid_ctx *c; bool on; ~NoKernelEvents() { c->kev_on = on; } } quiet{c, c->kev_on};
   c->kev_on = false;
+  // (nor does its wait count among the run's: humid_wait_overlap_info)
+  struct RunsWaits { humid_ctx *c; u32 w, o; ~RunsWaits() { c->wo_waits = w; c->wo_overlapped = o; } } waits{c, c->wo_waits, c->wo_overlapped};
   {
     ZeroList z;
     memset(&z, 0, sizeof z);

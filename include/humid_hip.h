@@ -1166,6 +1166,14 @@ int humid_graph_split_info(humid_ctx *ctx, uint64_t *pairs_direct, uint64_t *pai
  * the combination's search in them and stored no order; *orders_stored = bucket orders written to memory (a grouping
  * on 12-byte pairs or a sort; with a search in it or without).  Any pointer may be NULL. */
 int humid_group_records_info(humid_ctx *ctx, uint32_t *searched_on_records, uint32_t *orders_stored);
+/* The host waits of the last mutating call (the calls humid_get_run_roads speaks of): *host_waits = how often the host
+ * waited for counters the device published, over all attempts and retries of the call; *overlapped = those waits that
+ * had kernels queued between the publishing kernel and the wait, so that the GPU had work while the host read and
+ * decided.  With option "overlap_waits" (default 1) the wait behind the record count and the wait behind the split of
+ * the pairs are of that kind; the fetch of the rest graph's node count beside the small-component kernel is with
+ * either value.  Host stores only: no device work, no result depends on it.  Any pointer may be NULL.  HUMID_E_STATE
+ * before the first successful mutating call and after a failed one. */
+int humid_wait_overlap_info(humid_ctx *ctx, uint32_t *host_waits, uint32_t *overlapped);
 /* Which attempts the last mutating call (a run, humid_accum_add / _finish / _map, a humid_stage_* call that counts or
  * builds a graph) threw away and took again, in the order they happened.  A record the host keeps while it decides:
  * it costs the GPU nothing and changes no result.  One event per occurrence:
