@@ -184,6 +184,21 @@ SYMBOLS = {
                                                   C.c_uint64, C.c_uint32, C.POINTER(HumidCellsSummary)]),
     "humid_get_discovered_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "humid_get_barcode_count_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "humid_cells_begin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "humid_cells_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "humid_cells_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "humid_cells_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(HumidCellsSummary)]),
+    "humid_cells_info": (C.c_int, [C.c_void_p, u32p, u64p, u64p, u64p, u64p, u64p, u32p, u32p]),
+    "humid_cells_clear": (C.c_int, [C.c_void_p]),
+    "humid_whitelist_prior_begin": (C.c_int, [C.c_void_p]),
+    "humid_whitelist_prior_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "humid_whitelist_prior_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "humid_whitelist_correct_posterior_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                          C.c_uint32, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(HumidBcPosteriorSummary)]),
+    "humid_whitelist_correct_posterior_prior_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                                 C.c_uint32, C.c_void_p, C.c_void_p,
+                                                                 C.POINTER(HumidBcPosteriorSummary)]),
     "humid_get_group_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "humid_group_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 4),

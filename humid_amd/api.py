@@ -417,13 +417,18 @@ class Dedup(Context):
         self._check(self._lib.humid_get_barcode_segments(self._h, _vp(sc), _vp(ih)))
         return sc[:s].copy(), ih[:s + 1].copy()
 
-    def correct_keys(self, keys, filtered, quals=None, min_odds=39):
+    def correct_keys(self, keys, filtered, quals=None, min_odds=39, prior=False):
         """Correct keys against the whitelist without running anything else (humid_whitelist_correct): returns
         (keys_out u64[N], status u8[N] of BC_FILTERED .. BC_UNMATCHED, counts u64[5] indexed by status).  The
         results of the last run stay untouched.
         quals (u8[N, K] raw Phred+33 bytes of the barcode's nucleotides): ambiguous keys are decided by quality and
         abundance (humid_whitelist_correct_posterior, see run_keyed) and a fourth value is returned, dict(counts,
-        multi, rescued): the reads with two or more candidates and those of them that were corrected."""
+        multi, rescued): the reads with two or more candidates and those of them that were corrected.
+        prior=True (with quals): the abundances are those fed by prior_add, not this call's -- every read gets what
+        the correction over ALL reads given to prior_add gives it, the counts are those of this chunk
+        (humid_whitelist_correct_posterior_prior)."""
+        if prior and quals is None:
+            raise ValueError("prior=True needs the barcode qualities (quals)")
         f = np.ascontiguousarray(filtered, dtype=np.uint8)
         if f.ndim != 1:
             raise ValueError("filtered must be one-dimensional")
@@ -433,12 +438,40 @@ class Dedup(Context):
         if quals is not None:
             mo = self._min_odds(min_odds)
             q, sm = self._barcode_quals(quals, n), _lib.HumidBcPosteriorSummary()
-            self._check(self._lib.humid_whitelist_correct_posterior(self._h, _vp(k), _vp(q), _vp(f), n, mo,
-                                                                    _vp(out), _vp(status), C.byref(sm)))
+            call = self._lib.humid_whitelist_correct_posterior_prior if prior else self._lib.humid_whitelist_correct_posterior
+            self._check(call(self._h, _vp(k), _vp(q), _vp(f), n, mo, _vp(out), _vp(status), C.byref(sm)))
             d = sm.asdict()
             return out, status, np.asarray(d["counts"], np.uint64), d
         self._check(self._lib.humid_whitelist_correct(self._h, _vp(k), _vp(f), n, _vp(out), _vp(status), _vp(counts)))
         return out, status, counts
+
+    def prior_begin(self):
+        """Opens the posterior's prior fed in chunks over the whitelist in place (humid_whitelist_prior_begin): reads per
+        barcode of its own, zeroed.  It lasts until the whitelist changes."""
+        self._check(self._lib.humid_whitelist_prior_begin(self._h))
+
+    def prior_add(self, keys, filtered):
+        """adds a chunk's usable reads per whitelist barcode to the prior (humid_whitelist_prior_add)"""
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("filtered must be one-dimensional")
+        k = _keys_u64(keys, f.shape)
+        n = len(f)
+        self._check(self._lib.humid_whitelist_prior_add(self._h, _vp(k) if n else None, _vp(f) if n else None, n))
+
+    def prior_add_device(self, d_keys, d_filtered, n_reads):
+        """the same with integer device pointers"""
+        self._check(self._lib.humid_whitelist_prior_add_device(self._h, C.c_void_p(d_keys) if n_reads else None,
+                                                               C.c_void_p(d_filtered) if n_reads else None, n_reads))
+
+    def correct_keys_prior_device(self, d_keys, d_quals, d_filtered, d_keys_out, d_status, n_reads, min_odds=39):
+        """correct_keys(quals=..., prior=True) on device pointers (ints; d_quals u8[N * K]; d_keys_out u64[N] and d_status
+        u8[N] may be 0); returns dict(counts, multi, rescued)"""
+        sm, mo = _lib.HumidBcPosteriorSummary(), self._min_odds(min_odds)
+        self._check(self._lib.humid_whitelist_correct_posterior_prior_device(
+            self._h, C.c_void_p(d_keys), C.c_void_p(d_quals), C.c_void_p(d_filtered), n_reads, mo,
+            C.c_void_p(d_keys_out) if d_keys_out else None, C.c_void_p(d_status) if d_status else None, C.byref(sm)))
+        return sm.asdict()
 
     def correct_keys_device(self, d_keys, d_filtered, d_keys_out, d_status, n_reads):
         """correct_keys on device pointers (ints; d_keys_out u64[N] and d_status u8[N] may be 0); returns counts"""
@@ -473,15 +506,9 @@ class Dedup(Context):
         self._check(self._lib.humid_whitelist_counts(self._h, _vp(b) if len(b) else None, len(b), _vp(out) if len(b) else None))
         return out
 
-    def discover_whitelist(self, keys, filtered, barcode_nt=16, top=None, expected=None, min_reads=None, merge_ratio=0):
-        """The whitelist taken from the data (include/humid_hip.h, humid_whitelist_discover): the reads per barcode are
-        counted on the device, the abundant barcodes are the cells, and they become this object's whitelist as if by
-        set_whitelist.  Exactly one of top (the T most abundant), expected (every barcode with at least a tenth of the
-        reads of the barcode at rank (expected + 50) // 100) and min_reads (every barcode with that many reads) must be
-        given.  merge_ratio R >= 1 removes a selected barcode one substitution away from another with at least R
-        times its reads; 0 keeps all.  keys and filtered are numpy arrays, or both torch tensors on this object's device
-        (8-byte and 1-byte elements).  Returns the summary as a dict (usable, invalid_reads, distinct, selected, merged,
-        cells, threshold_reads, top_reads, reads_in_cells).  The results of the last run stay untouched."""
+    @staticmethod
+    def _cells_mode(top, expected, min_reads, merge_ratio):
+        """(mode, param, merge_ratio) of discover_whitelist's and BarcodeCounter.finish's arguments"""
         given = [(m, v) for m, v in ((CELLS_TOP, top), (CELLS_EXPECTED, expected), (CELLS_MIN_READS, min_reads)) if v is not None]
         if len(given) != 1:
             raise ValueError("exactly one of top, expected and min_reads must be given")
@@ -491,6 +518,18 @@ class Dedup(Context):
             raise ValueError("top, expected and min_reads must be in [1, 2**64)")
         if not 0 <= merge_ratio < 2 ** 32:
             raise ValueError("merge_ratio must be in [0, 2**32)")
+        return mode, param, merge_ratio
+
+    def discover_whitelist(self, keys, filtered, barcode_nt=16, top=None, expected=None, min_reads=None, merge_ratio=0):
+        """The whitelist taken from the data (include/humid_hip.h, humid_whitelist_discover): the reads per barcode are
+        counted on the device, the abundant barcodes are the cells, and they become this object's whitelist as if by
+        set_whitelist.  Exactly one of top (the T most abundant), expected (every barcode with at least a tenth of the
+        reads of the barcode at rank (expected + 50) // 100) and min_reads (every barcode with that many reads) must be
+        given.  merge_ratio R >= 1 removes a selected barcode one substitution away from another with at least R
+        times its reads; 0 keeps all.  keys and filtered are numpy arrays, or both torch tensors on this object's device
+        (8-byte and 1-byte elements).  Returns the summary as a dict (usable, invalid_reads, distinct, selected, merged,
+        cells, threshold_reads, top_reads, reads_in_cells).  The results of the last run stay untouched."""
+        mode, param, merge_ratio = self._cells_mode(top, expected, min_reads, merge_ratio)
         if not 1 <= int(barcode_nt) <= 32:
             raise ValueError("barcode_nt must be 1 .. 32")
         sm = _lib.HumidCellsSummary()
@@ -880,6 +919,11 @@ class Dedup(Context):
         object and returns the new one."""
         return Accumulator(self, word_nt)
 
+    def barcode_counter(self, barcode_nt=16):
+        """The reads per barcode of a read set fed in chunks (include/humid_hip.h, humid_cells_*): empties any earlier
+        counter of this object and returns the new one."""
+        return BarcodeCounter(self, barcode_nt)
+
     def keyed_accumulator(self, word_nt=12, key_nt=0):
         """A read set with 64-bit keys fed in chunks (include/humid_hip.h, humid_accum_*_keyed): empties any earlier
         accumulator of this object, of either kind, and returns the new one."""
@@ -1064,6 +1108,55 @@ class KeyedAccumulator:
 
     def clear(self):
         self._dd._check(self._lib.humid_accum_clear(self._dd._h))
+
+
+class BarcodeCounter:
+    """The whitelist taken from a read set fed in chunks (include/humid_hip.h, humid_cells_*): add() every chunk's keys,
+    then finish() with discover_whitelist's arguments.
+
+    finish() gives what Dedup.discover_whitelist gives over all added reads, whatever their order and cut: the same dict,
+    the same whitelist in place, the same dd.discovered_cells() and dd.barcode_count_hist().  It does not consume the
+    counter: it may be called again with other arguments, and more chunks may be added behind it.  The counter lives
+    in the Dedup object's context, in memory of its own: runs, accumulators and one-shot discover calls leave it alone."""
+
+    def __init__(self, dd: Dedup, barcode_nt: int):
+        self._dd = dd
+        self._lib = dd._lib
+        dd._check(self._lib.humid_cells_begin(dd._h, int(barcode_nt)))
+        self.barcode_nt = int(barcode_nt)
+
+    def add(self, keys, filtered):
+        """adds a chunk (numpy arrays: keys u64[N], filtered u8[N])"""
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("filtered must be one-dimensional")
+        k = _keys_u64(keys, f.shape)
+        n = len(f)
+        self._dd._check(self._lib.humid_cells_add(self._dd._h, _vp(k) if n else None, _vp(f) if n else None, n))
+
+    def add_device(self, d_keys, d_filtered, n_reads):
+        """the same with integer device pointers"""
+        self._dd._check(self._lib.humid_cells_add_device(self._dd._h, C.c_void_p(d_keys) if n_reads else None,
+                                                         C.c_void_p(d_filtered) if n_reads else None, n_reads))
+
+    def finish(self, top=None, expected=None, min_reads=None, merge_ratio=0):
+        """selects the cells over everything added and installs them as the whitelist; returns discover_whitelist's dict"""
+        mode, param, merge_ratio = Dedup._cells_mode(top, expected, min_reads, merge_ratio)
+        sm = _lib.HumidCellsSummary()
+        self._dd._check(self._lib.humid_cells_finish(self._dd._h, mode, param, merge_ratio, C.byref(sm)))
+        return sm.asdict()
+
+    def info(self):
+        """dict(barcode_nt, chunks, reads, usable, invalid_reads, distinct, table_log2, n_grown)"""
+        nt, log2, grown = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        v = [C.c_uint64() for _ in range(5)]
+        self._dd._check(self._lib.humid_cells_info(self._dd._h, C.byref(nt), *[C.byref(x) for x in v], C.byref(log2),
+                                                   C.byref(grown)))
+        return dict(barcode_nt=nt.value, chunks=v[0].value, reads=v[1].value, usable=v[2].value, invalid_reads=v[3].value,
+                    distinct=v[4].value, table_log2=log2.value, n_grown=grown.value)
+
+    def clear(self):
+        self._dd._check(self._lib.humid_cells_clear(self._dd._h))
 
 
 class ClusterGraph(Context):

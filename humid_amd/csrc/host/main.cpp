@@ -81,11 +81,13 @@ struct Args {
   unsigned duplex_strand_cap = 40;   // --duplex-strand-cap
   bool chunked = false;        // --chunk-reads given (not in the reference): the device part runs as an accumulated run over chunks
   unsigned long long chunk_reads = 0;   // --chunk-reads: records per chunk
+  bool bchunked = false;       // --chunk-barcoded given (not in the reference): a run with a barcode whose device part runs over chunks
+  unsigned long long bchunk_reads = 0;  // --chunk-barcoded: records per chunk
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] [--chunk-reads N] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] [--chunk-reads N] [--chunk-barcoded N] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -157,7 +159,15 @@ void usage(const char *argv0) {
                "      accumulated list, the list is clustered once, and every chunk is then given its results.  All outputs are\n"
                "      those of the run without the flag; the device holds one chunk and the distinct words, not the whole read\n"
                "      set.  Works with -n, -m, -e, -x, -s, -a, -q; one GPU; not with -g, -b, -w, --cells-*, --word-pattern, -P, -Q,\n"
-               "      -C, -D or -O.  The host still holds all words at once: its limit of 2^31 - 1 records stays\n",
+               "      -C, -D or -O.  The host still holds all words at once: its limit of 2^31 - 1 records stays\n"
+               "  --chunk-barcoded N  the same for a run with a barcode (-b K, or a --word-pattern with C letters): the GPU sees the\n"
+               "      records N at a time (N >= 1).  With --cells-* a first pass over the chunks counts the barcodes and selects the\n"
+               "      cells; with --barcode-posterior a pass adds up the reads per whitelist barcode; then every chunk's barcodes are\n"
+               "      corrected and its (barcode, word) entries merged into one accumulated list, the list is clustered once, and\n"
+               "      every chunk is given its results.  All outputs are those of the run without the flag.  Works with -n, -m, -e,\n"
+               "      -x, -s, -a, -q, -b, -w (one or several), --barcode-max-inexact, --barcode-posterior, --barcode-min-odds,\n"
+               "      --cells-* and --word-pattern; the word behind the barcode has at most 32 letters; one GPU; not with -g,\n"
+               "      --chunk-reads, -P, -Q, -C, -D or -O\n",
                argv0);
 }
 
@@ -240,6 +250,14 @@ bool parse(int argc, char **argv, Args &a) {
       if (*v < '0' || *v > '9' || *end != 0) { std::fprintf(stderr, "humid: --chunk-reads takes a number of records, 1 or more\n"); return false; }
       a.chunked = true;
     }
+    else if (t == "--chunk-barcoded") {
+      const char *v = need("--chunk-barcoded");
+      if (!v) return false;
+      char *end = nullptr;
+      a.bchunk_reads = std::strtoull(v, &end, 10);
+      if (*v < '0' || *v > '9' || *end != 0) { std::fprintf(stderr, "humid: --chunk-barcoded takes a number of records, 1 or more\n"); return false; }
+      a.bchunked = true;
+    }
     else if (t == "-P") a.paired = !a.paired;
     else if (t == "-D") a.duplex = !a.duplex;
     else if (t == "-Q") a.best = !a.best;
@@ -302,19 +320,31 @@ int write_hist(humid_ctx *ctx, uint32_t which, const std::string &path) {
 // -b K with -s: groups.dat, one line per distinct barcode in ascending order: "<barcode> <reads> <unique> <clusters>",
 // the barcode as its K letters (first nucleotide first); the table comes reduced from the device
 // (humid_get_group_stats).  Returns like write_hist.
-int write_groups(humid_ctx *ctx, size_t barcode_nt, const std::string &path) {
+struct GroupsTable {
+  uint64_t n = 0;
+  std::vector<uint64_t> key, reads;
+  std::vector<uint32_t> leaf_off, cluster_off;
+};
+// (apart from the writing: an accumulated run answers only until its first map)
+int fetch_groups(humid_ctx *ctx, GroupsTable &t) {
   uint64_t n = 0, nk = 0;
   if (humid_get_group_stats(ctx, 0, &n, nullptr, nullptr, nullptr, nullptr) != HUMID_OK) return 0;
-  std::vector<uint64_t> key(n ? n : 1), reads(n ? n : 1);
-  std::vector<uint32_t> leaf_off(n + 1), cluster_off(n + 1);
-  if (humid_get_group_stats(ctx, n, &n, reads.data(), leaf_off.data(), cluster_off.data(), nullptr) != HUMID_OK) return 0;
-  if (humid_get_group_keys(ctx, key.data(), n, &nk) != HUMID_OK) return 0;
+  t.key.assign(n ? n : 1, 0);
+  t.reads.assign(n ? n : 1, 0);
+  t.leaf_off.assign(n + 1, 0);
+  t.cluster_off.assign(n + 1, 0);
+  if (humid_get_group_stats(ctx, n, &n, t.reads.data(), t.leaf_off.data(), t.cluster_off.data(), nullptr) != HUMID_OK) return 0;
+  if (humid_get_group_keys(ctx, t.key.data(), n, &nk) != HUMID_OK) return 0;
   if (nk != n) return -1;
+  t.n = n;
+  return 1;
+}
+int write_groups(const GroupsTable &t, size_t barcode_nt, const std::string &path) {
   std::ofstream out(path, std::ios::out | std::ios::binary);
   std::string letters(barcode_nt, 'A');
-  for (uint64_t g = 0; g < n; g++) {
-    for (size_t i = 0; i < barcode_nt; i++) letters[i] = "ACGT"[(key[g] >> (2 * (barcode_nt - 1 - i))) & 3];
-    out << letters << ' ' << reads[g] << ' ' << leaf_off[g + 1] - leaf_off[g] << ' ' << cluster_off[g + 1] - cluster_off[g] << '\n';
+  for (uint64_t g = 0; g < t.n; g++) {
+    for (size_t i = 0; i < barcode_nt; i++) letters[i] = "ACGT"[(t.key[g] >> (2 * (barcode_nt - 1 - i))) & 3];
+    out << letters << ' ' << t.reads[g] << ' ' << t.leaf_off[g + 1] - t.leaf_off[g] << ' ' << t.cluster_off[g + 1] - t.cluster_off[g] << '\n';
   }
   out.close();
   return out.fail() ? -1 : 1;
@@ -545,6 +575,21 @@ int main(int argc, char **argv) {
   // HUMID_FORCE_SHARDED=1: the rank orchestration also for -g 1 (one rank; exercises the transport)
   const bool sharded = a.gpus > 1 || getenv("HUMID_FORCE_SHARDED") != nullptr;
   const bool discover = a.cells_mode >= 0;                 // the whitelist comes from the data
+  if (a.bchunked) {
+    // what a keyed accumulated run does not do, as far as the flags alone tell: one line, before anything is opened and
+    // before any GPU use (the length of the word behind the barcode follows below, once --word-pattern is read)
+    const char *why = nullptr;
+    if (a.bchunk_reads == 0) why = "--chunk-barcoded takes a number of records, 1 or more";
+    else if (a.chunked) why = "--chunk-barcoded does not work with --chunk-reads (the one is for runs with a barcode, the other for runs without)";
+    else if (sharded) why = "--chunk-barcoded runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+    else if (!a.keyed && a.word_pattern.empty()) why = "--chunk-barcoded needs a barcode (-b K, or a --word-pattern with C letters); without one it is --chunk-reads";
+    else if (a.paired) why = "--chunk-barcoded does not work with -P";
+    else if (a.best) why = "--chunk-barcoded does not work with -Q (the post-run passes need a complete run)";
+    else if (a.consensus) why = "--chunk-barcoded does not work with -C (the post-run passes need a complete run)";
+    else if (a.duplex) why = "--chunk-barcoded does not work with -D";
+    else if (a.optical) why = "--chunk-barcoded does not work with -O (the post-run passes need a complete run)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
   if (a.chunked) {
     // what an accumulated run does not do: one line, before anything is opened and before any GPU use
     const char *why = nullptr;
@@ -599,6 +644,13 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "humid: --word-pattern takes the word from the reads alone: %s has a UMI in its headers\n", a.files.front().c_str());
       return 1;
     }
+  }
+  if (a.bchunked) {
+    const char *why = nullptr;
+    if (!a.keyed) why = "--chunk-barcoded needs a barcode (-b K, or a --word-pattern with C letters); without one it is --chunk-reads";
+    else if (a.barcode < a.word_length && a.word_length - a.barcode > 32)
+      why = "--chunk-barcoded takes a word of at most 32 letters behind the barcode (-n minus -b)";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
   }
   if (discover || a.cells_ratio_given) {
     const char *why = nullptr;
@@ -737,7 +789,8 @@ int main(int argc, char **argv) {
         if (getenv("HUMID_NO_PINNED") == nullptr && !a.keyed)   // (-b: keys and shorter words, from ordinary memory)
           pin_thread = std::thread([&] { pinned = (uint8_t *)humid_host_alloc(pin_bytes); t_pin = since(); });
         if (getenv("HUMID_NO_SLAB") == nullptr)
-          humid_ctx_reserve(ctx, a.chunked ? std::min<uint64_t>((uint64_t)n, a.chunk_reads) : (uint64_t)n,
+          humid_ctx_reserve(ctx, a.chunked ? std::min<uint64_t>((uint64_t)n, a.chunk_reads) :
+                                 a.bchunked ? std::min<uint64_t>((uint64_t)n, a.bchunk_reads) : (uint64_t)n,
                             (uint32_t)a.word_length);   // one slab (--chunk-reads: for one chunk) + the code object loaded
         t_slab = since();
         if (pin_thread.joinable()) pin_thread.join();
@@ -1039,8 +1092,18 @@ int main(int argc, char **argv) {
   if (discover) {
     // the whitelist from the data: the barcodes of all usable reads are counted on the device, the cells become the
     // context's whitelist, and what follows is the -w path
-    if (humid_whitelist_discover(ctx, keys.data(), run_filt, N, (uint32_t)a.barcode, (uint32_t)a.cells_mode, a.cells_param,
-                                 (uint32_t)a.cells_ratio, &csum) != HUMID_OK) {
+    // (--chunk-barcoded: the same counts from a counter fed in chunks, the same selection over them)
+    int drc = HUMID_OK;
+    if (a.bchunked) {
+      drc = humid_cells_begin(ctx, (uint32_t)a.barcode);
+      for (uint64_t b = 0; drc == HUMID_OK && b < N; b += a.bchunk_reads)
+        drc = humid_cells_add(ctx, keys.data() + b, run_filt + b, std::min<uint64_t>(a.bchunk_reads, N - b));
+      if (drc == HUMID_OK) drc = humid_cells_finish(ctx, (uint32_t)a.cells_mode, a.cells_param, (uint32_t)a.cells_ratio, &csum);
+      if (drc == HUMID_OK) drc = humid_cells_clear(ctx);
+    } else
+      drc = humid_whitelist_discover(ctx, keys.data(), run_filt, N, (uint32_t)a.barcode, (uint32_t)a.cells_mode, a.cells_param,
+                                     (uint32_t)a.cells_ratio, &csum);
+    if (drc != HUMID_OK) {
       std::fprintf(stderr, "humid: %s\n", humid_last_error(ctx));
       humid_ctx_destroy(ctx);
       return 1;
@@ -1058,6 +1121,10 @@ int main(int argc, char **argv) {
   const uint32_t method = a.maximum ? HUMID_METHOD_MAXIMUM : HUMID_METHOD_DIRECTIONAL;
   ShardedResult shr;
   int rc;
+  uint64_t bc_counts[5] = {0, 0, 0, 0, 0};
+  uint64_t bc_multi = 0, bc_rescued = 0;
+  uint64_t seg_counts[8 * 4] = {}, inexact_hist[9] = {};
+  GroupsTable groups;                                    // --chunk-barcoded -s: fetched before the first map
   if (sharded) {
     // the read set in input-order shards, one rank (thread + context + GPU) per shard: sharded.cpp
     rc = ranks->run(run_words, run_filt, N, (uint32_t)a.word_length, (uint32_t)a.distance, method, a.stats, cluster_id, keep, shr,
@@ -1077,6 +1144,56 @@ int main(int argc, char **argv) {
     for (uint64_t b = 0; rc == HUMID_OK && b < N; b += a.chunk_reads)
       rc = humid_accum_map(ctx, run_words + b * wpr, run_filt + b, std::min<uint64_t>(a.chunk_reads, N - b), b, cluster_id + b, keep + b,
                            nullptr);
+  } else if (a.bchunked) {
+    // a keyed accumulated run (include/humid_hip.h): with --barcode-posterior the reads per whitelist barcode over all
+    // chunks first; then every chunk's barcodes corrected (plain, segmented, or by the posterior against that prior; not at
+    // all with -b alone) and its entries added with the index of its first record as its base; the list clustered; the
+    // histograms and the group table fetched at once (the first map ends the record finish published); every chunk
+    // mapped with the corrected keys, which the host keeps.  The status counts are the sums over the chunks.
+    const uint64_t cb = a.bchunk_reads;
+    std::vector<uint64_t> ckeys(corrected ? (N ? N : 1) : 0);
+    std::vector<uint8_t> cfilt(corrected ? (N ? N : 1) : 0), status(corrected ? (size_t)std::min<uint64_t>(cb, N ? N : 1) : 0);
+    const uint64_t *akeys = corrected ? ckeys.data() : keys.data();
+    const uint8_t *afilt = corrected ? cfilt.data() : run_filt;
+    rc = HUMID_OK;
+    if (a.posterior) {
+      rc = humid_whitelist_prior_begin(ctx);
+      for (uint64_t b = 0; rc == HUMID_OK && b < N; b += cb)
+        rc = humid_whitelist_prior_add(ctx, keys.data() + b, run_filt + b, std::min<uint64_t>(cb, N - b));
+    }
+    if (rc == HUMID_OK) rc = humid_accum_begin_keyed(ctx, (uint32_t)run_nt, (uint32_t)a.barcode);
+    for (uint64_t b = 0; rc == HUMID_OK && b < N; b += cb) {
+      const uint64_t n = std::min<uint64_t>(cb, N - b);
+      if (corrected) {
+        uint64_t counts[5] = {0, 0, 0, 0, 0};
+        if (a.posterior) {
+          humid_bc_posterior_summary ps;
+          std::memset(&ps, 0, sizeof ps);
+          rc = humid_whitelist_correct_posterior_prior(ctx, keys.data() + b, bcq.data() + b * K, run_filt + b, n, (uint32_t)a.min_odds,
+                                                       ckeys.data() + b, status.data(), &ps);
+          for (int k = 0; k < 5; k++) counts[k] = ps.counts[k];
+          bc_multi += ps.multi;
+          bc_rescued += ps.rescued;
+        } else
+          rc = humid_whitelist_correct(ctx, keys.data() + b, run_filt + b, n, ckeys.data() + b, status.data(), counts);
+        if (rc == HUMID_OK && segmented) {                   // (answers per correct call)
+          uint64_t sc[8 * 4] = {}, ih[9] = {};
+          rc = humid_get_barcode_segments(ctx, sc, ih);
+          for (int k = 0; k < 8 * 4; k++) seg_counts[k] += sc[k];
+          for (int k = 0; k < 9; k++) inexact_hist[k] += ih[k];
+        }
+        if (rc != HUMID_OK) break;
+        for (int k = 0; k < 5; k++) bc_counts[k] += counts[k];
+        for (uint64_t i = 0; i < n; i++) cfilt[b + i] = (uint8_t)(run_filt[b + i] | (status[i] >= HUMID_BC_AMBIGUOUS ? 1 : 0));
+      }
+      rc = humid_accum_add_keyed(ctx, run_words + b, akeys + b, afilt + b, n, b);
+    }
+    if (rc == HUMID_OK) rc = humid_accum_finish(ctx, (uint32_t)a.distance, method, &sum);
+    for (uint32_t which = 0; rc == HUMID_OK && a.stats && which < 3; which++) rc = fetch_hist(ctx, which, shr.hist[which]);
+    if (rc == HUMID_OK && a.stats && fetch_groups(ctx, groups) != 1) rc = HUMID_E_STATE;
+    for (uint64_t b = 0; rc == HUMID_OK && b < N; b += cb)
+      rc = humid_accum_map_keyed(ctx, run_words + b, akeys + b, afilt + b, std::min<uint64_t>(cb, N - b), b, cluster_id + b, keep + b,
+                                 nullptr);
   } else if (a.posterior)
     rc = humid_dedup_run_keyed_posterior(ctx, run_words, keys.data(), bcq.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance,
                                          method, (uint32_t)a.min_odds, cluster_id, keep, &sum);
@@ -1101,12 +1218,10 @@ int main(int argc, char **argv) {
     humid_ctx_destroy(ctx);
     return 1;
   }
-  uint64_t bc_counts[5] = {0, 0, 0, 0, 0};
-  if (rc == HUMID_OK && corrected) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
-  uint64_t bc_multi = 0, bc_rescued = 0;
-  if (rc == HUMID_OK && a.posterior) rc = humid_get_barcode_posterior(ctx, &bc_multi, &bc_rescued);
-  uint64_t seg_counts[8 * 4] = {}, inexact_hist[9] = {};
-  if (rc == HUMID_OK && segmented) rc = humid_get_barcode_segments(ctx, seg_counts, inexact_hist);
+  // (--chunk-barcoded has summed these over its chunks)
+  if (rc == HUMID_OK && corrected && !a.bchunked) rc = humid_get_barcode_status(ctx, nullptr, 0, bc_counts);
+  if (rc == HUMID_OK && a.posterior && !a.bchunked) rc = humid_get_barcode_posterior(ctx, &bc_multi, &bc_rescued);
+  if (rc == HUMID_OK && segmented && !a.bchunked) rc = humid_get_barcode_segments(ctx, seg_counts, inexact_hist);
   humid_strand_summary ssum;
   std::memset(&ssum, 0, sizeof ssum);
   if (rc == HUMID_OK && a.paired) {
@@ -1450,13 +1565,14 @@ int main(int argc, char **argv) {
     const char *names[3] = {"/counts.dat", "/neigh.dat", "/clusters.dat"};
     int ok = 1;
     for (uint32_t which = 0; which < 3 && ok == 1; which++) {
-      if (!sharded && !a.chunked) { ok = write_hist(ctx, which, a.dir_name + names[which]); continue; }
+      if (!sharded && !a.chunked && !a.bchunked) { ok = write_hist(ctx, which, a.dir_name + names[which]); continue; }
       std::ofstream out(a.dir_name + names[which], std::ios::out | std::ios::binary);   // gathered by the ranks, or fetched after the finish of an accumulated run
       for (auto &kv : shr.hist[which]) out << kv.first << ' ' << kv.second << '\n';
       out.close();
       if (out.fail()) ok = -1;
     }
-    if (ok == 1 && a.keyed) ok = write_groups(ctx, a.barcode, a.dir_name + "/groups.dat");   // (-b is never sharded)
+    if (ok == 1 && a.keyed && !a.bchunked) ok = fetch_groups(ctx, groups);   // (-b is never sharded)
+    if (ok == 1 && a.keyed) ok = write_groups(groups, a.barcode, a.dir_name + "/groups.dat");
     if (ok == 1 && corrected) {
       std::ofstream out(a.dir_name + "/barcodes.dat", std::ios::out | std::ios::binary);
       out << "exact: " << bc_counts[HUMID_BC_EXACT] << '\n';

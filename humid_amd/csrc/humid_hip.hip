@@ -592,7 +592,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
     c->wl_table.release();
     seg_drop(c);
     c->wl_n = 0; c->wl_nt = 0; c->wl_log2 = 0;
-    c->wp_valid = false;
+    wl_counts_drop(c);
     c->cd_valid = false;
     return HUMID_OK;
   }
@@ -623,7 +623,7 @@ int humid_whitelist_set(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint
   c->wl_table = std::move(fresh);
   seg_drop(c);
   c->wl_n = distinct; c->wl_nt = barcode_nt; c->wl_log2 = log2;
-  c->wp_valid = false;                                       // (the reads per slot went with the table they index)
+  wl_counts_drop(c);                                       // (the reads per slot went with the table they index)
   c->cd_valid = false;                                       // (nor is this whitelist one a discover call installed)
   return HUMID_OK;
 }
@@ -689,7 +689,7 @@ int humid_whitelist_set_segments(humid_ctx *c, uint32_t n_seg, const uint32_t *s
   c->sg_sum_valid = false;
   c->wl_n = product > (unsigned __int128)~0ull ? ~0ull : (u64)product;   // (all 4^32 keys of K = 32: one more than a u64 holds)
   c->wl_nt = plan.key_nt; c->wl_log2 = 0;
-  c->wp_valid = false;
+  wl_counts_drop(c);
   c->cd_valid = false;
   return HUMID_OK;
 }
@@ -818,6 +818,88 @@ int humid_get_barcode_count_hist(humid_ctx *c, uint64_t *reads, uint64_t *barcod
   return HUMID_OK;
 }
 
+// ---- the barcode counter fed in chunks (kernels_cells.hip.h) ---------------------------------------------------------
+#define CELLS_NEED_COUNTER()                                                                                                   \
+  do {                                                                                                                         \
+    if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");                                                              \
+    if (c->cc_state == CC_NONE) return fail(c, HUMID_E_STATE, "no barcode counter is open in this context (humid_cells_begin)"); \
+    if (c->cc_state == CC_INVALID)                                                                                             \
+      return fail(c, HUMID_E_STATE, "the barcode counter is invalid after a failed add (humid_cells_begin starts a new one)");  \
+  } while (0)
+
+int humid_cells_begin(humid_ctx *c, uint32_t barcode_nt) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (barcode_nt < 1 || barcode_nt > 32) return fail(c, HUMID_E_INVALID, "barcode_nt must be 1 .. 32");
+  return cells_accum_begin(c, barcode_nt);
+}
+
+static int cells_add_args(humid_ctx *c, const void *key, const void *filtered, uint64_t n_reads) {
+  CELLS_NEED_COUNTER();
+  if (n_reads && (!key || !filtered)) return fail(c, HUMID_E_INVALID, "null buffer");
+  if (n_reads > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "n_reads %llu exceeds 2^31-1", (ull)n_reads);
+  return HUMID_OK;
+}
+
+int humid_cells_add_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads) {
+  TRY(cells_add_args(c, d_key, d_filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  return cells_accum_add(c, d_key, d_filtered, n_reads);
+}
+
+int humid_cells_add(humid_ctx *c, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads) {
+  TRY(cells_add_args(c, key, filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  u64 *d_key = nullptr;
+  u8 *d_filt = nullptr;
+  if (n) {
+    const int rc = [&]() -> int {
+      STAGE_IN(d_key, 0, key, n * 8);
+      STAGE_IN(d_filt, 1, filtered, n);
+      return HUMID_OK;
+    }();
+    if (rc != HUMID_OK) {                                        // (an allocation or HIP failure during an add)
+      c->cc_state = CC_INVALID;
+      return rc;
+    }
+  }
+  return cells_accum_add(c, d_key, d_filt, n_reads);
+}
+
+int humid_cells_finish(humid_ctx *c, uint32_t mode, uint64_t param, uint32_t merge_ratio, humid_cells_summary *summary) {
+  CELLS_NEED_COUNTER();
+  if (mode > HUMID_CELLS_MIN_READS) return fail(c, HUMID_E_INVALID, "mode %u is none of HUMID_CELLS_TOP, _EXPECTED, _MIN_READS", mode);
+  if (param == 0) return fail(c, HUMID_E_INVALID, "the mode's parameter must be >= 1");
+  return cells_accum_finish(c, mode, param, merge_ratio, summary);
+}
+
+int humid_cells_info(humid_ctx *c, uint32_t *barcode_nt, uint64_t *chunks, uint64_t *reads, uint64_t *usable, uint64_t *invalid_reads,
+                     uint64_t *distinct, uint32_t *table_log2, uint32_t *n_grown) {
+  CELLS_NEED_COUNTER();
+  if (barcode_nt) *barcode_nt = c->cc_nt;
+  if (chunks) *chunks = c->cc_chunks;
+  if (reads) *reads = c->cc_reads;
+  if (usable) *usable = c->cc_usable;
+  if (invalid_reads) *invalid_reads = c->cc_invalid;
+  if (distinct) *distinct = c->cc_distinct;
+  if (table_log2) *table_log2 = c->cc_log2;
+  if (n_grown) *n_grown = c->cc_grown;
+  return HUMID_OK;
+}
+
+int humid_cells_clear(humid_ctx *c) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (c->cc_state == CC_NONE) return fail(c, HUMID_E_STATE, "no barcode counter is open in this context (humid_cells_begin)");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->cc_table.release();
+  c->cc_cnt.release();
+  c->cc_ctr.release();
+  c->cc_pend.release();
+  c->cc_state = CC_NONE;
+  return HUMID_OK;
+}
+
 // ---- correction by quality and abundance (kernels_wlpost.hip.h) ------------------------------------------------
 static int whitelist_posterior_args(humid_ctx *c, const void *key, const void *qual, const void *filtered, uint64_t n_reads,
                                     uint32_t min_odds) {
@@ -871,6 +953,84 @@ int humid_whitelist_correct_posterior(humid_ctx *c, const uint64_t *key, const u
   return whitelist_posterior_finish(c, summary);
 }
 
+// ---- the posterior's prior fed in chunks -----------------------------------------------------------------------------
+int humid_whitelist_prior_begin(humid_ctx *c) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (c->sg.n_seg) return fail(c, HUMID_E_UNSUPPORTED, SEG_NO_POSTERIOR);
+  return wl_prior_begin(c);
+}
+
+// what the prior calls refuse before anything moves: no whitelist, a segmented one, no (valid) prior
+static int whitelist_prior_state(humid_ctx *c) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!c->wl_n) return fail(c, HUMID_E_STATE, "no whitelist is set in this context (humid_whitelist_set)");
+  if (c->sg.n_seg) return fail(c, HUMID_E_UNSUPPORTED, SEG_NO_POSTERIOR);
+  if (c->pr_state == CC_NONE)
+    return fail(c, HUMID_E_STATE, "no prior is open over the whitelist of this context (humid_whitelist_prior_begin)");
+  if (c->pr_state == CC_INVALID)
+    return fail(c, HUMID_E_STATE, "the prior is invalid after a failed add (humid_whitelist_prior_begin starts a new one)");
+  return HUMID_OK;
+}
+
+int humid_whitelist_prior_add_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads) {
+  TRY(whitelist_prior_state(c));
+  TRY(whitelist_correct_args(c, d_key, d_filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  return wl_prior_add(c, d_key, d_filtered, (u32)n_reads);
+}
+
+int humid_whitelist_prior_add(humid_ctx *c, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads) {
+  TRY(whitelist_prior_state(c));
+  TRY(whitelist_correct_args(c, key, filtered, n_reads));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  u64 *d_key = nullptr;
+  u8 *d_filt = nullptr;
+  const int rc = [&]() -> int {
+    STAGE_IN(d_key, 0, key, n * 8);
+    STAGE_IN(d_filt, 1, filtered, n);
+    return HUMID_OK;
+  }();
+  if (rc != HUMID_OK) {                                          // (an allocation or HIP failure during an add)
+    c->pr_state = CC_INVALID;
+    return rc;
+  }
+  return wl_prior_add(c, d_key, d_filt, (u32)n);
+}
+
+int humid_whitelist_correct_posterior_prior_device(humid_ctx *c, const uint64_t *d_key, const uint8_t *d_qual, const uint8_t *d_filtered,
+                                                   uint64_t n_reads, uint32_t min_odds, uint64_t *d_key_out, uint8_t *d_status,
+                                                   humid_bc_posterior_summary *summary) {
+  TRY(whitelist_prior_state(c));
+  TRY(whitelist_posterior_args(c, d_key, d_qual, d_filtered, n_reads, min_odds));
+  HIPCHK(hipSetDevice(c->device));
+  PASS_ENSURE(c->wc_counts, WLP_CTRS * sizeof(ull));
+  TRY(wl_posterior_prior_launch(c, d_key, d_filtered, d_qual, (u32)n_reads, min_odds, d_key_out, d_status, c->wc_counts.as<ull>()));
+  return whitelist_posterior_finish(c, summary);
+}
+
+int humid_whitelist_correct_posterior_prior(humid_ctx *c, const uint64_t *key, const uint8_t *qual, const uint8_t *filtered,
+                                            uint64_t n_reads, uint32_t min_odds, uint64_t *key_out, uint8_t *status,
+                                            humid_bc_posterior_summary *summary) {
+  TRY(whitelist_prior_state(c));
+  TRY(whitelist_posterior_args(c, key, qual, filtered, n_reads, min_odds));
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n = (size_t)n_reads;
+  u64 *d_key, *d_out;
+  u8 *d_filt, *d_qual, *d_status;
+  STAGE_IN(d_key, 0, key, n * 8);
+  STAGE_IN(d_filt, 1, filtered, n);
+  STAGE_IN(d_qual, 2, qual, n * c->wl_nt);
+  STAGE_OUT(d_out, 0, n * 8);
+  STAGE_OUT(d_status, 1, n);
+  PASS_ENSURE(c->wc_counts, WLP_CTRS * sizeof(ull));
+  TRY(wl_posterior_prior_launch(c, d_key, d_filt, d_qual, (u32)n, min_odds, d_out, d_status, c->wc_counts.as<ull>()));
+  D2H(key_out, d_out, n * 8);
+  D2H(status, d_status, n);
+  return whitelist_posterior_finish(c, summary);
+}
+
 int humid_get_barcode_posterior(humid_ctx *c, uint64_t *multi, uint64_t *rescued) {
   NEED_LEAVES();
   if (!state_run_is(c, RUN_CORRECTED) || !c->bc_posterior)
@@ -883,7 +1043,9 @@ int humid_get_barcode_posterior(humid_ctx *c, uint64_t *multi, uint64_t *rescued
 
 int humid_whitelist_counts(humid_ctx *c, const uint64_t *barcodes, uint64_t n, uint32_t *counts_out) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!c->wl_n || !c->wp_valid) return fail(c, HUMID_E_STATE, "no posterior correction has run over the whitelist of this context");
+  const bool prior = c->wp_prior && c->pr_state == CC_ON;       // the later of the two: an accumulated prior, or a one-shot posterior
+  if (!c->wl_n || !(prior || c->wp_valid))
+    return fail(c, HUMID_E_STATE, "no posterior correction has run over the whitelist of this context");
   if (n > 0x7fffffffull) return fail(c, HUMID_E_OVERFLOW, "%llu barcodes exceed 2^31-1", (ull)n);
   if (n && (!barcodes || !counts_out)) return fail(c, HUMID_E_INVALID, "null buffer");
   if (n == 0) return HUMID_OK;
@@ -893,7 +1055,7 @@ int humid_whitelist_counts(humid_ctx *c, const uint64_t *barcodes, uint64_t n, u
   STAGE_IN(d_bc, 0, barcodes, (size_t)n * 8);
   STAGE_OUT(d_out, 0, (size_t)n * 4);
   hipLaunchKernelGGL(k_wlp_counts, dim3(grid_stride_blocks(n)), dim3(256), 0, c->stream, (const u64 *)d_bc, (u32)n,
-                     (const u64 *)c->wl_table.p, c->wl_log2, (const u32 *)c->wp_cnt.p, d_out);
+                     (const u64 *)c->wl_table.p, c->wl_log2, (const u32 *)(prior ? c->pr_cnt.p : c->wp_cnt.p), d_out);
   HIPCHK(hipGetLastError());
   D2H(counts_out, d_out, (size_t)n * 4);
   HIPCHK(hipStreamSynchronize(c->stream));

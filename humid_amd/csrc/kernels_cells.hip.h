@@ -2,6 +2,8 @@
 // has the definition): the reads per barcode are counted, the abundant barcodes are selected as cells, those that look
 // like one-substitution errors of a larger cell are removed, and the rest becomes the context's whitelist.
 //   k_cd_count    per read: one probe per run of equal keys inside a wave, the run's length added to the key's count
+//   k_cd_accum    the same count into a table that is KEPT (humid_cells_*: a read set fed in chunks): never leaves early, reads
+//                 whose key found no slot are marked pending and swept again after k_cd_grow moved the table into a larger one
 //   k_cd_compact  occupied slots -> (key, ~count) list, their number, the OR of the keys and the largest count
 //   (rs_sort, prims.hip.h, twice: by key, then stable by ~count -- the ORDER of the definition)
 //   k_cd_cut      the selection's size and its last member (count, key) from the ORDER; the summary's top and threshold
@@ -72,6 +74,127 @@ k_cd_count(const u64 *__restrict__ key, const u8 *__restrict__ filt, u32 n, u64 
   if (lane == 0) {
     if (n_usable) atomicAdd(&ctr[CD_USABLE], (ull)n_usable);
     if (n_invalid) atomicAdd(&ctr[CD_INVALID], (ull)n_invalid);
+  }
+}
+
+// ---- the counter fed in chunks (humid_cells_*): the same table, kept from add to add and grown while it holds counts --
+// the counters of one add (u64 each)
+enum { CA_USABLE = 0, CA_INVALID, CA_PENDING, CA_CLAIMED, CA_OVERFLOW, CA_LOST, CA_CTRS = 8 };
+
+// the largest count a barcode may reach (the merge's 64-bit product and the posterior's weights rely on it)
+#define CD_MAX_COUNT 0x7fffffffu
+
+__device__ __forceinline__ u32 cd_wave_sum(u32 v) {
+#pragma unroll
+  for (u32 d = 32; d >= 1; d >>= 1) v += (u32)__shfl_xor((int)v, d);
+  return v;
+}
+
+// k_cd_count for a table that is kept: nothing may be counted twice and nothing dropped, so the kernel never leaves
+// early.  A run whose head finds no slot within max_probe steps is PENDING: pend[r] = 1 for its reads (the head hands
+// the byte to its run by the shuffle k_wlp_prior hands the slot with) and its length goes to ctr[CA_PENDING]; the host
+// grows the table and runs the SWEEP over the pending reads alone, as often as it takes.
+//   !SWEEP  every read; pend[r] is written for every r < n; ctr[CA_USABLE] and ctr[CA_INVALID] are raised
+//   SWEEP   the reads with pend[r] != 0 (usable, valid keys: the first pass saw to that); pend[r] is rewritten
+// ctr[CA_CLAIMED] counts the slots this launch claimed (the compare-and-swap that wins, or the reserved slot's first
+// add), ctr[CA_OVERFLOW] = 1 when a count passed CD_MAX_COUNT: the adding lane sees the old value from its atomic.
+// A count never wraps: it is at most CD_MAX_COUNT before the add that raises the flag, and an add has n <= 2^31 - 1.
+template <bool SWEEP>
+__global__ void __launch_bounds__(256)
+k_cd_accum(const u64 *__restrict__ key, const u8 *__restrict__ filt, u32 n, u64 *tab, u32 *cnt, u32 cap_log2, u32 max_probe,
+           u64 lim, u8 *pend, ull *ctr) {
+  HUMID_GUARD_LAST_VGPR();
+  const u32 cap = 1u << cap_log2, mask = cap - 1u, lane = threadIdx.x & 63u;
+  const u32 n_up = (n + 63u) & ~63u;                               // whole waves stay in the loop: the shuffles need every lane
+  u32 n_usable = 0, n_invalid = 0;                                 // (the wave's, kept in every lane)
+  u32 n_pending = 0, n_claimed = 0;                                // (this lane's)
+  bool over = false;
+  for (u32 r = blockIdx.x * blockDim.x + threadIdx.x; r < n_up; r += gridDim.x * blockDim.x) {
+    bool usable, valid;
+    u64 k;
+    if (SWEEP) {
+      usable = valid = r < n && pend[r] != 0;
+      k = valid ? key[r] : 0ull;
+    } else {
+      usable = r < n && filt[r] == 0;
+      k = usable ? key[r] : 0ull;
+      valid = usable && (lim == 0ull || k < lim);
+      n_usable += (u32)__popcll(__ballot(usable));
+      n_invalid += (u32)__popcll(__ballot(usable && !valid));
+    }
+    const u64 valid_m = __ballot(valid);
+    const bool head = kr_run_head(k, valid, lane);
+    const u64 heads = __ballot(head);
+    u32 left = 0;                                                  // 1: the run found no slot
+    if (head) {
+      const u64 above = lane == 63u ? 0ull : heads & ~((2ull << lane) - 1ull);
+      const u64 upto = above ? (above & (0ull - above)) - 1ull : ~0ull;
+      const u32 len = (u32)__popcll(valid_m & ~((1ull << lane) - 1ull) & upto);
+      u32 s = cap;
+      bool claimed = false;
+      if (k != EMPTY_KEY) {
+        s = kr_home(k, cap_log2) & mask;
+        u32 probes = 0;
+        while (true) {
+          u64 t = tab[s];
+          if (t == EMPTY_KEY) {
+            t = atomicCAS((ull *)&tab[s], EMPTY_KEY, (ull)k);
+            claimed = t == EMPTY_KEY;
+          }
+          if (t == EMPTY_KEY || t == k) break;
+          s = (s + 1u) & mask;
+          if (++probes > max_probe) { s = NOSLOT; break; }         // never spin forever
+        }
+      }
+      if (s != NOSLOT) {
+        const u32 old = atomicAdd(&cnt[s], len);
+        if (s == cap) claimed = old == 0u;                         // (len >= 1: exactly one add sees the empty reserved slot)
+        if ((u64)old + (u64)len > (u64)CD_MAX_COUNT) over = true;
+        n_claimed += claimed ? 1u : 0u;
+      } else {
+        left = 1u;
+        n_pending += len;
+      }
+    }
+    const u64 below = heads & (lane == 63u ? ~0ull : ((2ull << lane) - 1ull));
+    const int src = below ? 63 - __clzll((long long)below) : (int)lane;
+    left = (u32)__shfl((int)left, src);
+    if (r < n && (!SWEEP || valid)) pend[r] = (u8)(valid ? left : 0u);
+  }
+  n_pending = cd_wave_sum(n_pending);
+  n_claimed = cd_wave_sum(n_claimed);
+  const bool any_over = __ballot(over) != 0ull;
+  if (lane == 0) {
+    if (n_usable) atomicAdd(&ctr[CA_USABLE], (ull)n_usable);
+    if (n_invalid) atomicAdd(&ctr[CA_INVALID], (ull)n_invalid);
+    if (n_pending) atomicAdd(&ctr[CA_PENDING], (ull)n_pending);
+    if (n_claimed) atomicAdd(&ctr[CA_CLAIMED], (ull)n_claimed);
+    if (any_over) ctr[CA_OVERFLOW] = 1;
+  }
+}
+
+// Growth: every occupied slot of the old table tab[0, cap) claims a slot of the new key array ntab (0xff-emptied,
+// 2^ncap_log2 > cap slots: there is always room, the probe bound is only there so that nothing spins forever) and stores
+// its count beside it in ncnt (zeroed); the reserved slot carries over.  The old keys are distinct, so every
+// compare-and-swap on an empty slot wins or meets ANOTHER key.  ctr[CA_LOST] counts the slots that found no room (the
+// host refuses anything but 0).
+static __global__ void __launch_bounds__(256)
+k_cd_grow(const u64 *__restrict__ tab, const u32 *__restrict__ cnt, u32 cap, u64 *ntab, u32 *__restrict__ ncnt, u32 ncap_log2,
+          ull *ctr) {
+  HUMID_GUARD_LAST_VGPR();
+  const u32 ncap = 1u << ncap_log2, nmask = ncap - 1u;
+  for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s <= (u64)cap; s += (u64)gridDim.x * blockDim.x) {
+    if (s == (u64)cap) { ncnt[ncap] = cnt[cap]; continue; }
+    const u64 k = tab[s];
+    if (k == EMPTY_KEY) continue;
+    u32 t = kr_home(k, ncap_log2) & nmask, probes = 0;
+    while (true) {
+      u64 o = ntab[t];
+      if (o == EMPTY_KEY) o = atomicCAS((ull *)&ntab[t], EMPTY_KEY, (ull)k);
+      if (o == EMPTY_KEY) { ncnt[t] = cnt[s]; break; }
+      t = (t + 1u) & nmask;
+      if (++probes > ncap) { atomicAdd(&ctr[CA_LOST], 1ull); break; }   // never spin forever
+    }
   }
 }
 

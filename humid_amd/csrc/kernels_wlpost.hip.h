@@ -34,9 +34,15 @@ __device__ __forceinline__ u64 wlp_xor64(u64 x, int d) {
 // with ONE atomic (a barcode that holds every read costs a wave one atomic, not 64) and hands the slot to the run.
 // cnt[cap + 1] is zero on entry.  slot_out[r] = NOSLOT for a read that is filtered or whose key is no barcode.
 // The grid covers whole waves; no lane leaves before the last shuffle.
-static __global__ void __launch_bounds__(256)
+// The prior fed in chunks (humid_whitelist_prior_*) splits the two halves: COUNT && !SLOTS adds a chunk to counts that
+// are NOT zero on entry and raises *over when the atomic's old value shows a count beyond WLP_MAX_PRIOR (a count never
+// wraps: it is at most WLP_MAX_PRIOR before the add that raises the flag, and a chunk has n <= 2^31 - 1 reads);
+// !COUNT && SLOTS is the lookup alone, the decision pass then reads the accumulated counts.
+#define WLP_MAX_PRIOR 0x7ffffffeu
+template <bool COUNT, bool SLOTS>
+__global__ void __launch_bounds__(256)
 k_wlp_prior(const u64 *__restrict__ key, const u8 *__restrict__ filt, u32 n, const u64 *__restrict__ tab, u32 cap_log2,
-            u32 *cnt, u32 *__restrict__ slot_out) {
+            u32 *cnt, u32 *__restrict__ slot_out, ull *over) {
   HUMID_GUARD_LAST_VGPR();
   const u32 lane = threadIdx.x & 63u;
   const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -49,16 +55,20 @@ k_wlp_prior(const u64 *__restrict__ key, const u8 *__restrict__ filt, u32 n, con
   // a run: its head and the usable lanes up to the next head (an unusable lane ends a run: the usable lane behind it
   // is a head)
   const u64 heads = __ballot(head), usable_m = __ballot(usable);
-  if (head && s != NOSLOT) {
+  if (COUNT && head && s != NOSLOT) {
     const u64 above = lane == 63u ? 0ull : heads & ~((2ull << lane) - 1ull);
     const u64 upto = above ? (above & (0ull - above)) - 1ull : ~0ull;         // lanes below the next head
     const u64 from = ~((1ull << lane) - 1ull);
-    atomicAdd(&cnt[s], (u32)__popcll(usable_m & from & upto));
+    const u32 len = (u32)__popcll(usable_m & from & upto);
+    const u32 old = atomicAdd(&cnt[s], len);
+    if (over && (u64)old + (u64)len > (u64)WLP_MAX_PRIOR) *over = 1ull;
   }
-  const u64 below = heads & (lane == 63u ? ~0ull : ((2ull << lane) - 1ull));
-  const int src = below ? 63 - __clzll((long long)below) : (int)lane;
-  s = (u32)__shfl((int)s, src);
-  if (in) slot_out[r] = usable ? s : NOSLOT;
+  if (SLOTS) {
+    const u64 below = heads & (lane == 63u ? ~0ull : ((2ull << lane) - 1ull));
+    const int src = below ? 63 - __clzll((long long)below) : (int)lane;
+    s = (u32)__shfl((int)s, src);
+    if (in) slot_out[r] = usable ? s : NOSLOT;
+  }
 }
 
 // weight of the candidate in slot s, reached from read r's key through variant v (the nucleotide at bits 2 (v / 3),

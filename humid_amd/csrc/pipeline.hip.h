@@ -125,6 +125,7 @@ static_assert(std::is_nothrow_move_constructible<DBuf>::value && std::is_nothrow
 //   (its keys are ac_keys, not kr_keys); first_read and everything else under (b) stay E_STATE.
 // The results of humid_consensus* are no part of this: they survive runs (cs_valid).
 enum RunKind : u8 { RUN_PLAIN, RUN_GROUPED, RUN_KEYED, RUN_CORRECTED };   // ordered: each kind is a case of the one before
+enum : u32 { CC_NONE = 0, CC_ON, CC_INVALID };   // a count fed in chunks (humid_cells_*, humid_whitelist_prior_*)
 struct CtxState {
   enum Holds : u8 { NOTHING, COUNT, STAGE_GRAPH, HAND_GRAPH, RUN } holds = NOTHING;
   RunKind kind = RUN_PLAIN;    // of a RUN
@@ -284,6 +285,18 @@ struct humid_ctx {
   DBuf cd_cells, cd_cellcnt, cd_hist_n, cd_hist_first;   // results: cells ascending u64 / u32; histogram bins u64 / u32 (first rank)
   bool cd_valid = false;     // the whitelist in place (or its absence: zero cells) was installed by a discover call
   u64 cd_n_cells = 0, cd_n_hist = 0, cd_G = 0;           // entries of the result buffers; distinct barcodes of that call
+  // the barcode counter fed in chunks (humid_cells_*): a counting table of its own that outlives the adds and grows while it
+  // holds counts; no discover call, run or accumulator touches it, and it touches none of them (finish shares the
+  // discovery's scratch lists and installs its results as a discover call does)
+  u32 cc_state = CC_NONE;    // CC_NONE before humid_cells_begin / after _clear, CC_ON, CC_INVALID after a failed add
+  u32 cc_nt = 0, cc_log2 = 0, cc_grown = 0;               // barcode length; log2 of the table's slots; growths since begin
+  u64 cc_chunks = 0, cc_reads = 0, cc_usable = 0, cc_invalid = 0, cc_distinct = 0;
+  DBuf cc_table, cc_cnt, cc_ctr, cc_pend;                // u64[cap + 1], u32[cap + 1], ull[CA_CTRS], u8[reads of a chunk]
+  // the posterior's prior fed in chunks (humid_whitelist_prior_*): reads per slot of wl_table in an array of its own (wp_cnt
+  // is zeroed by every one-shot posterior call); it goes with the table it indexes
+  u32 pr_state = CC_NONE;    // CC_NONE before humid_whitelist_prior_begin / once the whitelist changed, CC_ON, CC_INVALID
+  bool wp_prior = false;     // humid_whitelist_counts answers from pr_cnt: a prior call came later than any one-shot posterior
+  DBuf pr_cnt, pr_ctr;       // u32[cap + 1]; ull[1] the overflow flag
   // per-group statistics (humid_get_group_stats / humid_group_stats_device, kernels_gstats.hip.h): computed by the first
   // accessor call after a run, kept until the next one; the runs themselves launch nothing for them
   u32 gk_groups = 1;         // n_groups of the last grouped run
@@ -3288,6 +3301,14 @@ static void seg_drop(humid_ctx *c) {
   c->sg_sum_valid = false;
 }
 
+// the whitelist in place changed: the reads per slot of a posterior call, and a prior fed in chunks, went with the table
+// they index
+static void wl_counts_drop(humid_ctx *c) {
+  c->wp_valid = false;
+  c->wp_prior = false;
+  c->pr_state = CC_NONE;
+}
+
 // The correction pass over device arrays: zeroes d_counts (u64[5]) and launches the kernel; nothing waits here.
 static int wl_correct_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N, u64 *d_key_out, u8 *d_status,
                              u8 *d_filt_out, ull *d_counts) {
@@ -3330,7 +3351,8 @@ static int wl_posterior_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt,
   if (N) {
     const u64 *tab = (const u64 *)c->wl_table.p;
     const dim3 grid(blocks_for(N)), block(256);
-    hipLaunchKernelGGL(k_wlp_prior, grid, block, 0, st, d_key, d_filt, N, tab, c->wl_log2, c->wp_cnt.as<u32>(), c->wp_slot.as<u32>());
+    hipLaunchKernelGGL((k_wlp_prior<true, true>), grid, block, 0, st, d_key, d_filt, N, tab, c->wl_log2, c->wp_cnt.as<u32>(), c->wp_slot.as<u32>(),
+                       (ull *)nullptr);
     if (c->wl_coop)
       hipLaunchKernelGGL(k_wlp_decide<true>, grid, block, 0, st, d_key, d_filt, d_qual, N, (const u32 *)c->wp_slot.p, tab, c->wl_log2,
                          (const u32 *)c->wp_cnt.p, c->wl_nt, min_odds, d_key_out, d_status, d_filt_out, d_counts);
@@ -3340,6 +3362,66 @@ static int wl_posterior_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt,
     HIPCHK(hipGetLastError());
   }
   c->wp_valid = true;
+  c->wp_prior = false;                                              // (humid_whitelist_counts answers this call's counts)
+  return HUMID_OK;
+}
+
+// The prior fed in chunks (humid_whitelist_prior_*; state and arguments checked by the entry points).  begin: the
+// counts per slot of the table in place, zeroed, in an array of their own.
+static int wl_prior_begin(humid_ctx *c) {
+  HIPCHK(hipSetDevice(c->device));
+  const size_t cap = (size_t)1 << c->wl_log2;
+  c->pr_state = CC_NONE;
+  PASS_ENSURE(c->pr_cnt, (cap + 1) * 4);
+  PASS_ENSURE(c->pr_ctr, sizeof(ull));
+  HIPCHK(hipMemsetAsync(c->pr_cnt.p, 0, (cap + 1) * 4, c->stream));
+  HIPCHK(hipMemsetAsync(c->pr_ctr.p, 0, sizeof(ull), c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->pr_state = CC_ON;
+  c->wp_prior = true;                                               // (humid_whitelist_counts answers the accumulated counts)
+  return HUMID_OK;
+}
+
+// add: the counting half of k_wlp_prior over a chunk, and one host wait for the overflow flag
+static int wl_prior_add_chunk(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N) {
+  if (N == 0) return HUMID_OK;
+  hipLaunchKernelGGL((k_wlp_prior<true, false>), dim3(blocks_for(N)), dim3(256), 0, c->stream, d_key, d_filt, N, (const u64 *)c->wl_table.p,
+                     c->wl_log2, c->pr_cnt.as<u32>(), (u32 *)nullptr, c->pr_ctr.as<ull>());
+  HIPCHK(hipGetLastError());
+  ull over = 0;
+  HIPCHK(hipMemcpyAsync(&over, c->pr_ctr.p, sizeof over, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (over) return fail(c, HUMID_E_OVERFLOW, "a barcode's reads exceed 2^31-2: the prior is invalid until humid_whitelist_prior_begin");
+  return HUMID_OK;
+}
+static int wl_prior_add(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N) {
+  const int rc = wl_prior_add_chunk(c, d_key, d_filt, N);
+  if (rc != HUMID_OK) c->pr_state = CC_INVALID;
+  else c->wp_prior = true;
+  return rc;
+}
+
+// The posterior correction of a chunk against the accumulated prior: zeroes d_counts (u64[WLP_CTRS]), then the lookup
+// half of k_wlp_prior and the decision pass, unchanged, over pr_cnt; nothing waits here.  wp_cnt is not touched.
+static int wl_posterior_prior_launch(humid_ctx *c, const u64 *d_key, const u8 *d_filt, const u8 *d_qual, u32 N, u32 min_odds,
+                                     u64 *d_key_out, u8 *d_status, ull *d_counts) {
+  hipStream_t st = c->stream;
+  PASS_ENSURE(c->wp_slot, (size_t)N * 4 + 16);
+  HIPCHK(hipMemsetAsync(d_counts, 0, WLP_CTRS * sizeof(ull), st));
+  if (N) {
+    const u64 *tab = (const u64 *)c->wl_table.p;
+    const dim3 grid(blocks_for(N)), block(256);
+    hipLaunchKernelGGL((k_wlp_prior<false, true>), grid, block, 0, st, d_key, d_filt, N, tab, c->wl_log2, (u32 *)nullptr, c->wp_slot.as<u32>(),
+                       (ull *)nullptr);
+    if (c->wl_coop)
+      hipLaunchKernelGGL(k_wlp_decide<true>, grid, block, 0, st, d_key, d_filt, d_qual, N, (const u32 *)c->wp_slot.p, tab, c->wl_log2,
+                         (const u32 *)c->pr_cnt.p, c->wl_nt, min_odds, d_key_out, d_status, (u8 *)nullptr, d_counts);
+    else
+      hipLaunchKernelGGL(k_wlp_decide<false>, grid, block, 0, st, d_key, d_filt, d_qual, N, (const u32 *)c->wp_slot.p, tab, c->wl_log2,
+                         (const u32 *)c->pr_cnt.p, c->wl_nt, min_odds, d_key_out, d_status, (u8 *)nullptr, d_counts);
+    HIPCHK(hipGetLastError());
+  }
+  c->wp_prior = true;
   return HUMID_OK;
 }
 
@@ -3439,9 +3521,13 @@ struct CdMarks {
   }
 };
 
+static int cells_tail(humid_ctx *c, const u64 *tab, const u32 *cnt, u32 cap_log2, u32 G, u64 n_reads, u32 K, u32 mode, u64 param,
+                      u32 ratio, ull *h, CdMarks &marks, humid_cells_summary *sum);
+
 // The whole discovery over device arrays (arguments checked).  Four host waits at most: the distinct barcodes (again
 // after every table that was too small), the selection's size with the histogram's, the cells after the merge (only
-// with a merge), the installed table.  Nothing of the context changes before the last one succeeded.
+// with a merge), the installed table.  Nothing of the context changes before the last one succeeded.  The count is
+// here, everything behind it in cells_tail, which humid_cells_finish runs over its own table.
 static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u64 n_reads, u32 K, u32 mode, u64 param,
                                  u32 ratio, humid_cells_summary *sum) {
   HIPCHK(hipSetDevice(c->device));
@@ -3487,6 +3573,16 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
     while (next < full_log2 && ((u64)1 << next) < 3 * (u64)G) next++;
     c->cd_cap_log2 = next;
   }
+  return cells_tail(c, (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap_log2, G, N, K, mode, param, ratio, h, marks, sum);
+}
+
+// The discovery behind the count: tab / cnt (2^cap_log2 slots and the reserved one) hold the reads per barcode, cd_k0 /
+// cd_c0 their G occupied slots as k_cd_compact left them, h that wait's counters with the usable and invalid reads.
+// n_reads bounds the histogram's bins: the reads that were counted, or any number not below them.
+static int cells_tail(humid_ctx *c, const u64 *tab, const u32 *cnt, u32 cap_log2, u32 G, u64 n_reads, u32 K, u32 mode, u64 param,
+                      u32 ratio, ull *h, CdMarks &marks, humid_cells_summary *sum) {
+  hipStream_t st = c->stream;
+  ull *ctr = c->cd_ctr.as<ull>();
   humid_cells_summary s;
   memset(&s, 0, sizeof s);
   s.usable = h[CD_USABLE];
@@ -3511,7 +3607,7 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
     TRY((cd_sort<u32, u64>(c, c->cd_kccnt.as<u32>(), occnt, c->cd_kkey.as<u64>(), okey, G, 64u - (u32)__builtin_clzll(h[CD_MAXCNT] | 1ull))));
     // a histogram bin per distinct count: H (H + 1) / 2 <= the reads
     u64 hist_cap = 1;
-    while (hist_cap * (hist_cap + 1) / 2 <= (u64)N) hist_cap++;
+    while (hist_cap < G && hist_cap * (hist_cap + 1) / 2 <= n_reads) hist_cap++;   // (in 64 bits: hist_cap <= G < 2^32)
     hist_cap = std::min<u64>(hist_cap, G);
     HIPCHK(hist_n.ensure((size_t)hist_cap * 8 + 16));
     HIPCHK(hist_first.ensure((size_t)hist_cap * 4 + 16));
@@ -3549,10 +3645,10 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
       // (flag and pos are free again: the decisions and their scan take them, S + 1 <= G + 1 entries)
       if (c->wl_coop)
         hipLaunchKernelGGL(k_cd_merge<true>, dim3(grid_stride_blocks((u64)S * 64)), dim3(256), 0, st, (const u64 *)c->cd_skey.p,
-                           (const u32 *)c->cd_scnt.p, S, (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap_log2, 3 * K, ratio, flag);
+                           (const u32 *)c->cd_scnt.p, S, tab, cnt, cap_log2, 3 * K, ratio, flag);
       else
         hipLaunchKernelGGL(k_cd_merge<false>, dim3(blocks_for(S)), dim3(256), 0, st, (const u64 *)c->cd_skey.p,
-                           (const u32 *)c->cd_scnt.p, S, (const u64 *)c->cd_table.p, (const u32 *)c->cd_cnt.p, cap_log2, 3 * K, ratio, flag);
+                           (const u32 *)c->cd_scnt.p, S, tab, cnt, cap_log2, 3 * K, ratio, flag);
       TRY(cd_scan(c, flag, pos, S));
       u32 kept = 0;
       TRY(cd_wait(c, h, pos + S, &kept));                       // host wait 3
@@ -3592,7 +3688,7 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
   c->wl_n = n_cells;
   c->wl_nt = n_cells ? K : 0;
   c->wl_log2 = wl_log2;
-  c->wp_valid = false;                                            // (the reads per slot went with the table they index)
+  wl_counts_drop(c);                                            // (the reads per slot went with the table they index)
   c->cd_cells = std::move(cells);
   c->cd_cellcnt = std::move(cellcnt);
   c->cd_hist_n = std::move(hist_n);
@@ -3603,6 +3699,155 @@ static int cells_discover_device(humid_ctx *c, const u64 *d_key, const u8 *d_fil
   c->cd_valid = true;
   if (sum) *sum = s;
   return HUMID_OK;
+}
+
+// ---- the barcode counter fed in chunks (humid_cells_*; kernels_cells.hip.h) -----------------------------------------
+// State and arguments are checked by the entry points.  begin: an empty table of the starting size in the counter's own
+// buffers (an earlier counter's memory is kept).
+static int cells_accum_begin(humid_ctx *c, u32 K) {
+  HIPCHK(hipSetDevice(c->device));
+  c->cc_state = CC_NONE;
+  const u32 log2 = std::min(std::max(c->cd_force_log2 ? c->cd_force_log2 : 16u, 4u), 31u);
+  const size_t cap = (size_t)1 << log2;
+  PASS_ENSURE(c->cc_table, (cap + 1) * 8);
+  PASS_ENSURE(c->cc_cnt, (cap + 1) * 4);
+  PASS_ENSURE(c->cc_ctr, CA_CTRS * sizeof(ull));
+  HIPCHK(hipMemsetAsync(c->cc_table.p, 0xff, (cap + 1) * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->cc_cnt.p, 0, (cap + 1) * 4, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->cc_nt = K;
+  c->cc_log2 = log2;
+  c->cc_grown = 0;
+  c->cc_chunks = c->cc_reads = c->cc_usable = c->cc_invalid = c->cc_distinct = 0;
+  c->cc_state = CC_ON;
+  return HUMID_OK;
+}
+
+// the smallest power of two at or above n, as a logarithm, 4 at least (64: beyond 2^63)
+static u32 cells_log2_for(u64 n) {
+  u32 b = 4;
+  while (b < 64 && ((u64)1 << b) < n) b++;
+  return b;
+}
+
+// The table moves into fresh buffers of 2^new_log2 slots, which replace the old ones once the kernel has been queued
+// without error (the stream orders it before whatever reads the new table; the old buffers are freed behind it).
+static int cells_accum_grow(humid_ctx *c, u32 new_log2) {
+  hipStream_t st = c->stream;
+  const u32 cap = 1u << c->cc_log2;
+  const size_t ncap = (size_t)1 << new_log2;
+  DBuf ntab, ncnt;                                                  // (both free themselves on every early return)
+  HIPCHK(ntab.ensure((ncap + 1) * 8));
+  HIPCHK(ncnt.ensure((ncap + 1) * 4));
+  HIPCHK(hipMemsetAsync(ntab.p, 0xff, (ncap + 1) * 8, st));
+  HIPCHK(hipMemsetAsync(ncnt.p, 0, (ncap + 1) * 4, st));
+  hipLaunchKernelGGL(k_cd_grow, dim3(grid_stride_blocks((u64)cap + 1)), dim3(256), 0, st, (const u64 *)c->cc_table.p, (const u32 *)c->cc_cnt.p,
+                     cap, ntab.as<u64>(), ncnt.as<u32>(), new_log2, c->cc_ctr.as<ull>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));                                 // (the old buffers are read until here)
+  c->cc_table = std::move(ntab);
+  c->cc_cnt = std::move(ncnt);
+  c->cc_log2 = new_log2;
+  c->cc_grown++;
+  return HUMID_OK;
+}
+
+// a host wait of an add: its counters
+static int cells_accum_wait(humid_ctx *c, ull *h) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, c->cc_ctr.p, CA_CTRS * sizeof(ull), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return HUMID_OK;
+}
+
+// One chunk (1 <= N <= 2^31 - 1).  The first sweep counts every read whose run finds a slot and marks the others
+// pending; while reads are pending the table grows -- 16 times the slots, at most to the size that cannot be too small,
+// the smallest power of two at or above 2 (distinct + pending), where max_probe is the capacity itself -- and the
+// pending reads alone are swept again.  So every usable valid read is counted exactly once.  One host wait per sweep.
+static int cells_accum_chunk(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u32 N) {
+  hipStream_t st = c->stream;
+  const u32 K = c->cc_nt;
+  const u64 lim = K < 32 ? (u64)1 << (2 * K) : 0ull;
+  ull h[CA_CTRS] = {};
+  ull *ctr = c->cc_ctr.as<ull>();
+  PASS_ENSURE(c->cc_pend, (size_t)N + 16);
+  HIPCHK(hipMemsetAsync(ctr, 0, CA_CTRS * sizeof(ull), st));
+  const dim3 grid(grid_stride_blocks(N)), block(256);
+  u32 probe = std::min<u32>(128u, 1u << c->cc_log2);
+  hipLaunchKernelGGL(k_cd_accum<false>, grid, block, 0, st, d_key, d_filt, N, c->cc_table.as<u64>(), c->cc_cnt.as<u32>(), c->cc_log2, probe, lim,
+                     c->cc_pend.as<u8>(), ctr);
+  TRY(cells_accum_wait(c, h));
+  while (h[CA_PENDING]) {
+    const u64 need = 2 * (c->cc_distinct + h[CA_CLAIMED] + h[CA_PENDING]);
+    const u32 ceil_log2 = cells_log2_for(need);
+    if (ceil_log2 > 31) return fail(c, HUMID_E_OVERFLOW, "a counting table for %llu barcodes exceeds 2^31 slots", (ull)(need / 2));
+    if (c->cc_log2 >= ceil_log2) return fail(c, HUMID_E_INVALID, "internal: the barcode table of 2^%u slots overflowed", c->cc_log2);
+    const u32 next = std::min(c->cc_log2 + 4, ceil_log2);
+    TRY(cells_accum_grow(c, next));
+    HIPCHK(hipMemsetAsync(&ctr[CA_PENDING], 0, sizeof(ull), st));
+    probe = next == ceil_log2 ? 1u << next : 128u;
+    hipLaunchKernelGGL(k_cd_accum<true>, grid, block, 0, st, d_key, d_filt, N, c->cc_table.as<u64>(), c->cc_cnt.as<u32>(), next, probe, lim,
+                       c->cc_pend.as<u8>(), ctr);
+    TRY(cells_accum_wait(c, h));
+    if (h[CA_LOST]) return fail(c, HUMID_E_INVALID, "internal: the growth of the barcode table lost %llu slots", (ull)h[CA_LOST]);
+  }
+  if (h[CA_OVERFLOW])
+    return fail(c, HUMID_E_OVERFLOW, "a barcode's reads exceed 2^31-1: the counter is invalid until humid_cells_begin");
+  c->cc_distinct += h[CA_CLAIMED];
+  c->cc_usable += h[CA_USABLE];
+  c->cc_invalid += h[CA_INVALID];
+  // more than half full: later chunks would probe long chains.  At most a quarter full afterwards, 16 times the slots at most.
+  if (2 * c->cc_distinct > ((u64)1 << c->cc_log2)) {
+    const u32 next = std::min(std::min(c->cc_log2 + 4, cells_log2_for(4 * c->cc_distinct)), 31u);
+    if (next > c->cc_log2) {
+      TRY(cells_accum_grow(c, next));
+      TRY(cells_accum_wait(c, h));
+      if (h[CA_LOST]) return fail(c, HUMID_E_INVALID, "internal: the growth of the barcode table lost %llu slots", (ull)h[CA_LOST]);
+    }
+  }
+  return HUMID_OK;
+}
+
+// add: after a failure the counter is invalid until the next begin (a chunk may be half counted)
+static int cells_accum_add(humid_ctx *c, const u64 *d_key, const u8 *d_filt, u64 n_reads) {
+  if (n_reads) {
+    const int rc = cells_accum_chunk(c, d_key, d_filt, (u32)n_reads);
+    if (rc != HUMID_OK) {
+      c->cc_state = CC_INVALID;
+      return rc;
+    }
+  }
+  c->cc_chunks++;
+  c->cc_reads += n_reads;
+  return HUMID_OK;
+}
+
+// finish: the occupied slots of the counter's table into the discovery's lists (their number is known: one host wait
+// checks it), then the discovery's tail.  The counter is read, not changed.
+static int cells_accum_finish(humid_ctx *c, u32 mode, u64 param, u32 ratio, humid_cells_summary *sum) {
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  ull h[CD_CTRS] = {};
+  PASS_ENSURE(c->cd_ctr, CD_CTRS * sizeof(ull));
+  ull *ctr = c->cd_ctr.as<ull>();
+  HIPCHK(hipMemsetAsync(ctr, 0, CD_CTRS * sizeof(ull), st));
+  CdMarks marks{c->kev_on, st, {}};
+  marks.mark("start");
+  const u32 G = (u32)c->cc_distinct;
+  if (G) {
+    const u32 cap = 1u << c->cc_log2;
+    PASS_ENSURE(c->cd_k0, (size_t)G * 8 + 16);
+    PASS_ENSURE(c->cd_c0, (size_t)G * 4 + 16);
+    hipLaunchKernelGGL(k_cd_compact, dim3(std::min<u32>(COMPACT_BLOCKS, blocks_for((u64)cap + 1))), dim3(256), 0, st,
+                       (const u64 *)c->cc_table.p, (const u32 *)c->cc_cnt.p, cap, c->cd_k0.as<u64>(), c->cd_c0.as<u32>(), G, ctr);
+    TRY(cd_wait(c, h));
+    marks.mark("k_cd_compact+wait");
+    if (h[CD_G] != G) return fail(c, HUMID_E_INVALID, "internal: %llu occupied slots for %u barcodes", (ull)h[CD_G], G);
+  }
+  h[CD_USABLE] = c->cc_usable;
+  h[CD_INVALID] = c->cc_invalid;
+  return cells_tail(c, (const u64 *)c->cc_table.p, (const u32 *)c->cc_cnt.p, c->cc_log2, G, c->cc_usable, c->cc_nt, mode, param, ratio, h,
+                    marks, sum);
 }
 
 // ---- strand-symmetric runs (humid_dedup_run_paired*) ------------------------------------------------------------

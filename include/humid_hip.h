@@ -914,8 +914,9 @@ int humid_get_strands(humid_ctx *ctx, uint8_t *strand, uint64_t cap, uint32_t *t
  * into the accumulated one (equal words combined; one host wait, for the new number of words); finish = the graph stage
  * over the accumulated list; map = the count stage over the chunk + one binary search per unique word of the chunk +
  * the un-permute of humid_dedup_run.  Every add rewrites the accumulated list.
- * The keyed form has accumulators of its own (next section; a corrected one composes from it).  Grouped, paired and
- * multi-GPU forms, the posterior correction and the post-run passes are not available for accumulated runs.
+ * The keyed form has accumulators of its own (next section; a corrected one composes from it, the posterior correction
+ * and a whitelist from the data included: the section behind it).  Grouped, paired and multi-GPU forms and the post-run
+ * passes are not available for accumulated runs.
  * humid_accum_get_leaves: the first min(cap, unique) entries; *n_out = unique; any pointer may be NULL.
  * humid_accum_info: word_nt, chunks added, reads and usable reads added, unique words, finished (0 / 1).
  *   *_device: DEVICE pointers for the per-read arrays; n_unknown stays a host pointer. */
@@ -963,7 +964,9 @@ int humid_accum_clear(humid_ctx *ctx);
  * below 2^32; a failing call changes nothing.
  * Whitelist correction composes, chunk by chunk: humid_whitelist_correct* over the chunk's keys, then add / map key_out
  * with filtered | (status >= HUMID_BC_AMBIGUOUS).  The result is humid_dedup_run_keyed_corrected over R.  The posterior
- * correction and humid_whitelist_discover* need counts over the whole read set and do not compose this way.
+ * correction and humid_whitelist_discover* need counts over the whole read set: those counts are fed in chunks as well
+ * (next section: humid_cells_* gives the discovered whitelist, humid_whitelist_prior_* the posterior's prior), in a pass
+ * over the chunks BEFORE the one that corrects and adds them.
  * On the device: one kernel per chunk packs (key, word) into an entry and checks the key; the count stage, the merge and
  * the lookup of the plain accumulator run over entries.  finish ranks the keys off the sorted list (a flag where the
  * key changes, one scan) at the cost of ONE more host wait -- the number of distinct keys chooses the group field --
@@ -984,6 +987,76 @@ int humid_accum_map_keyed_device(humid_ctx *ctx, const uint64_t *d_words, const 
 int humid_accum_get_leaves_keyed(humid_ctx *ctx, uint64_t *key, uint64_t *word, uint32_t *count, uint64_t *first_index,
                                  uint64_t cap, uint64_t *n_out);
 int humid_accum_keyed_info(humid_ctx *ctx, uint32_t *key_nt, uint32_t *entry_words, uint64_t *n_keys);
+
+/* ---- barcode counts fed in chunks: the whitelist from the data and the posterior's prior over all chunks ------------
+ * What a chunked single-cell run needs beside the keyed accumulator: the reads per barcode over the WHOLE read set.
+ *
+ * The barcode counter.  Let R be the concatenation of all chunks added since humid_cells_begin, in any order.
+ * humid_cells_finish(mode, param, merge_ratio) gives exactly what humid_whitelist_discover(R, barcode_nt, mode, param,
+ * merge_ratio) gives: the summary, the installed whitelist (a segmented one dropped), humid_get_discovered_cells,
+ * humid_get_barcode_count_hist and that call's consequences for humid_whitelist_info and humid_whitelist_counts.  Counts
+ * are sums: no result depends on the order or the cut of the chunks.
+ * States.  finish does not consume the counter: it may be called again with another mode, param or ratio (its work is
+ * proportional to the distinct barcodes), and an add after a finish is legal.  Every call returns HUMID_E_STATE before
+ * begin.  begin empties an earlier counter and keeps its memory, clear returns the memory.  The counter lives in
+ * buffers of its own: a one-shot humid_whitelist_discover*, a run of any kind and a keyed or plain accumulator on the
+ * same context do not disturb it, and it disturbs none of them; add and finish touch nothing of the last run, as
+ * discover does.
+ * Limits.  barcode_nt outside 1 .. 32, mode > 2, param == 0 or a NULL buffer with n_reads > 0 return HUMID_E_INVALID, a
+ * chunk of more than 2^31 - 1 reads HUMID_E_OVERFLOW: refused on the host before anything moves, the counter as it was.
+ * The total number of reads is a u64 with no limit.  One barcode's count may not exceed 2^31 - 1 (the merge's 64-bit
+ * product and the posterior's weights rely on it): the add that passes it returns HUMID_E_OVERFLOW.  After that, or after
+ * an allocation or HIP failure during an add, the counter is INVALID: add, finish and info return HUMID_E_STATE until
+ * the next begin; the context and the whitelist in place stay usable and unchanged.  A chunk of 0 reads and a chunk of
+ * filtered reads only are legal.
+ * On the device (kernels_cells.hip.h): the counting table of humid_whitelist_discover, kept from add to add.  A run of
+ * equal keys whose head finds no slot within the probe bound marks its reads pending instead of ending the pass; the
+ * host's one wait per sweep reads the pending reads, the slots claimed and the overflow flag, grows the table into
+ * fresh buffers (16 times the slots, at most to the smallest power of two at or above 2 (distinct + pending), where the
+ * probe bound is the capacity) and sweeps the pending reads alone: every usable valid read is counted exactly once.
+ * An add that leaves the table more than half full grows it as well.  Option "cells_table_log2" sets the size a counter
+ * starts with (0: 2^16 slots) and never changes a result.  finish compacts the table and runs the rest of the discovery.
+ *   humid_cells_info: barcode_nt, chunks, reads, usable reads and invalid reads added, distinct barcodes, log2 of the
+ *     table's slots, growths since begin.  Any pointer may be NULL.
+ *   humid_cells_add_device: DEVICE pointers for key and filtered.
+ *
+ * The prior.  humid_whitelist_prior_begin needs a plain whitelist in place (HUMID_E_STATE without one,
+ * HUMID_E_UNSUPPORTED over a segmented one, as the posterior calls) and zeroes reads per barcode of its own -- not those
+ * of the one-shot posterior calls and runs, which stay what they are.  humid_whitelist_prior_add adds, per whitelist
+ * barcode w, the usable reads of the chunk whose key equals w; n_w <= 2^31 - 2, beyond it the add returns
+ * HUMID_E_OVERFLOW and the prior is invalid (HUMID_E_STATE until the next begin).  Let R be the concatenation of the
+ * chunks given to prior_add.  For a chunk C (usually one of them, in any order)
+ * humid_whitelist_correct_posterior_prior(C) writes for every read of C the key_out and status that
+ * humid_whitelist_correct_posterior(R) writes for that read; its summary counts the reads of C alone, so over a
+ * partition of R the summaries add up to the one-shot summary (counts, multi, rescued).  humid_whitelist_counts then
+ * answers the accumulated n_w (until a one-shot posterior call or run comes later: then that call's).
+ * The prior dies with the table it indexes: once humid_whitelist_set, _set_segments, _discover*, humid_cells_finish or a
+ * clear has run, the prior calls return HUMID_E_STATE until the next humid_whitelist_prior_begin.
+ * On the device (kernels_wlpost.hip.h): add is the counting half of the prior pass (one atomic per run of equal keys,
+ * whose old value guards the limit); the correction is its lookup half, then the decision pass unchanged over the
+ * accumulated counts.
+ *   *_device: DEVICE pointers for the per-read arrays (the summary is written on the host).
+ *
+ * A whole chunked single-cell run: humid_cells_begin / _add per chunk / _finish (only without a shipped whitelist);
+ * humid_whitelist_prior_begin / _add per chunk (only for the posterior correction); per chunk the correction and
+ * humid_accum_add_keyed; humid_accum_finish; per chunk humid_accum_map_keyed. */
+int humid_cells_begin(humid_ctx *ctx, uint32_t barcode_nt);
+int humid_cells_add(humid_ctx *ctx, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads);
+int humid_cells_add_device(humid_ctx *ctx, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads);
+int humid_cells_finish(humid_ctx *ctx, uint32_t mode, uint64_t param, uint32_t merge_ratio, humid_cells_summary *summary);
+int humid_cells_info(humid_ctx *ctx, uint32_t *barcode_nt, uint64_t *chunks, uint64_t *reads, uint64_t *usable,
+                     uint64_t *invalid_reads, uint64_t *distinct, uint32_t *table_log2, uint32_t *n_grown);
+int humid_cells_clear(humid_ctx *ctx);
+int humid_whitelist_prior_begin(humid_ctx *ctx);
+int humid_whitelist_prior_add(humid_ctx *ctx, const uint64_t *key, const uint8_t *filtered, uint64_t n_reads);
+int humid_whitelist_prior_add_device(humid_ctx *ctx, const uint64_t *d_key, const uint8_t *d_filtered, uint64_t n_reads);
+int humid_whitelist_correct_posterior_prior(humid_ctx *ctx, const uint64_t *key, const uint8_t *qual, const uint8_t *filtered,
+                                            uint64_t n_reads, uint32_t min_odds, uint64_t *key_out, uint8_t *status,
+                                            humid_bc_posterior_summary *summary);
+int humid_whitelist_correct_posterior_prior_device(humid_ctx *ctx, const uint64_t *d_key, const uint8_t *d_qual,
+                                                   const uint8_t *d_filtered, uint64_t n_reads, uint32_t min_odds,
+                                                   uint64_t *d_key_out, uint8_t *d_status,
+                                                   humid_bc_posterior_summary *summary);
 
 /* ---- results of the last run, per unique word in Trie::walk() order ---------
  * (what a caller would read through Result<NLeaf>{leaf,path}, src/humid.cc:117,178,307;
