@@ -81,6 +81,15 @@ class HumidRunRoads(C.Structure):
                     graph_attempts=int(self.graph_attempts))
 
 
+class HumidLongInfo(C.Structure):
+    """humid_long_info_t of include/humid_hip.h"""
+    _fields_ = [("words_per_read", C.c_uint32), ("joins", C.c_uint32), ("key_bits", C.c_uint32), ("piece_joins", C.c_uint32),
+                ("candidates", C.c_uint64), ("raw_edges", C.c_uint64), ("edges", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 HOST_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_int, C.c_void_p)
 
@@ -133,6 +142,11 @@ SYMBOLS = {
     "humid_dedup_run_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
     "humid_get_packed_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "humid_dedup_run_long": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
+    "humid_dedup_run_long_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(HumidSummary)]),
+    "humid_long_info": (C.c_int, [C.c_void_p, C.POINTER(HumidLongInfo)]),
     "humid_dedup_run_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.POINTER(HumidSummary)]),

@@ -150,6 +150,47 @@ class Dedup(Context):
         self._wide = word_nt > 32
         return self.summary
 
+    def run_long(self, words, filtered, word_nt, distance=1, method=DIRECTIONAL):
+        """Words of 1 .. 512 nucleotides (include/humid_hip.h, humid_dedup_run_long): words is u64[N, k] with
+        k = ceil(word_nt / 32), [:, 0] = the first word_nt - 32 (k - 1) nucleotides right-aligned (bits above them are
+        ignored), every following column the next 32; a one-dimensional array is accepted for k = 1.  Hamming
+        neighbours only.  Returns (cluster_id, keep, summary) like run(); leaves()["word"] is then u64[U, k], and
+        long_info() says what the search did.  Up to 64 nucleotides the results are those of run()."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        f = np.ascontiguousarray(filtered, dtype=np.uint8)
+        k = (int(word_nt) + 31) // 32
+        if w.ndim == 1 and k == 1:
+            w = w.reshape(-1, 1)
+        if f.ndim != 1 or (k >= 1 and w.shape != (len(f), k)):
+            raise ValueError("words must have shape %r for word_nt=%d (filtered: %r)" % ((len(f), k), word_nt, f.shape))
+        n = len(f)
+        cid = np.zeros(n, dtype=np.uint32)
+        keep = np.zeros(n, dtype=np.uint8)
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_long(self._h, _vp(w), _vp(f), n, word_nt, distance, method,
+                                                   _vp(cid), _vp(keep), C.byref(s)))
+        self.summary = self._long_summary = s.asdict()
+        self._long_k = k
+        return cid, keep, self.summary
+
+    def run_long_device(self, d_words, d_filtered, d_cluster_id, d_keep, n_reads, word_nt, distance=1,
+                        method=DIRECTIONAL):
+        """run_long() over device pointers (ints; the words need 8-byte alignment only); results stay in HBM."""
+        s = _lib.HumidSummary()
+        self._check(self._lib.humid_dedup_run_long_device(
+            self._h, C.c_void_p(d_words), C.c_void_p(d_filtered), n_reads, word_nt, distance, method,
+            C.c_void_p(d_cluster_id), C.c_void_p(d_keep), C.byref(s)))
+        self.summary = self._long_summary = s.asdict()
+        self._long_k = (int(word_nt) + 31) // 32
+        return self.summary
+
+    def long_info(self):
+        """what the last long run's search did (humid_long_info): dict(words_per_read, joins, key_bits, piece_joins,
+        candidates, raw_edges, edges)"""
+        info = _lib.HumidLongInfo()
+        self._check(self._lib.humid_long_info(self._h, C.byref(info)))
+        return info.asdict()
+
     def run_grouped(self, words, groups, filtered, word_nt=24, n_groups=None, distance=1, method=DIRECTIONAL,
                     edit=False):
         """Deduplicate within groups (include/humid_hip.h, humid_dedup_run_grouped): the results are those of
@@ -843,6 +884,8 @@ class Dedup(Context):
     def leaves(self):
         u = int(self.summary["unique"])
         wshape = (u, 2) if getattr(self, "_wide", False) else u
+        if getattr(self, "_long_summary", None) is self.summary:         # the last run was a long one
+            wshape = (u, self._long_k)
         out = dict(word=np.zeros(wshape, np.uint64), count=np.zeros(u, np.uint32),
                    first_read=np.zeros(u, np.uint32), degree=np.zeros(u, np.uint32),
                    cluster_id=np.zeros(u, np.uint32), is_max_leaf=np.zeros(u, np.uint8))

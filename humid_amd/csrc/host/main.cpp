@@ -83,11 +83,13 @@ struct Args {
   unsigned long long chunk_reads = 0;   // --chunk-reads: records per chunk
   bool bchunked = false;       // --chunk-barcoded given (not in the reference): a run with a barcode whose device part runs over chunks
   unsigned long long bchunk_reads = 0;  // --chunk-barcoded: records per chunk
+  bool barcode_opts_given = false;    // --barcode-min-odds was given (--long-words refuses every --barcode-* flag)
+  bool long_words = false;     // --long-words (the reference takes any -n): words of up to 512 nucleotides, ceil(n / 32) uint64 each, through humid_dedup_run_long
 };
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] [--chunk-reads N] [--chunk-barcoded N] files...\n"
+               "usage: %s [-n 24] [-m 1] [-l /dev/stderr] [-d .] [-s] [-q] [-a] [-e] [-x] [-g 1] [-b K [-w FILE ... | --cells-expected N] [--barcode-posterior]] [--word-pattern P] [-Q] [-C] [-O D] [-P [-D]] [--chunk-reads N] [--chunk-barcoded N] [--long-words] files...\n"
                "Deduplicate a dataset.\n"
                "  -n  word length\n  -m  allowed mismatches\n  -l  log file name\n  -d  output directory\n"
                "  -s  calculate statistics\n  -q  write deduplicated FastQ files (flag turns it OFF)\n"
@@ -167,7 +169,11 @@ void usage(const char *argv0) {
                "      every chunk is given its results.  All outputs are those of the run without the flag.  Works with -n, -m, -e,\n"
                "      -x, -s, -a, -q, -b, -w (one or several), --barcode-max-inexact, --barcode-posterior, --barcode-min-odds,\n"
                "      --cells-* and --word-pattern; the word behind the barcode has at most 32 letters; one GPU; not with -g,\n"
-               "      --chunk-reads, -P, -Q, -C, -D or -O\n",
+               "      --chunk-reads, -P, -Q, -C, -D or -O\n"
+               "  --long-words  word lengths up to 512 (-n 1 .. 512; without the flag 64 is the limit): a word takes ceil(n / 32)\n"
+               "      uint64 and the GPU runs the long-word path for every n.  Outputs are those of the run without the flag\n"
+               "      where both apply.  Works with -n, -m, -x, -d, -l, -s, -a, -q; one GPU; not with -e, -g, -b, -w, -P, -Q, -C, -D,\n"
+               "      -O, --chunk-reads, --chunk-barcoded, --cells-*, --word-pattern or --barcode-*\n",
                argv0);
 }
 
@@ -204,6 +210,7 @@ bool parse(int argc, char **argv, Args &a) {
       if (!v) return false;
       char *end = nullptr;
       a.min_odds = std::strtoull(v, &end, 10);
+      a.barcode_opts_given = true;
       if (*v < '0' || *v > '9' || *end != 0 || a.min_odds < 1 || a.min_odds > 0xffffffffull) {
         std::fprintf(stderr, "humid: --barcode-min-odds takes odds of 1 .. 4294967295\n");
         return false;
@@ -258,6 +265,7 @@ bool parse(int argc, char **argv, Args &a) {
       if (*v < '0' || *v > '9' || *end != 0) { std::fprintf(stderr, "humid: --chunk-barcoded takes a number of records, 1 or more\n"); return false; }
       a.bchunked = true;
     }
+    else if (t == "--long-words") a.long_words = !a.long_words;
     else if (t == "-P") a.paired = !a.paired;
     else if (t == "-D") a.duplex = !a.duplex;
     else if (t == "-Q") a.best = !a.best;
@@ -563,11 +571,31 @@ int main(int argc, char **argv) {
   }
   Args a;
   if (!parse(argc, argv, a)) { usage(argv[0]); return 2; }
-  if (a.word_length == 0 || a.word_length > 64) {
-    std::fprintf(stderr, "humid: word length %zu is not supported by the HIP path (1..64)\n", a.word_length);
+  if (a.word_length == 0 || a.word_length > (a.long_words ? (size_t)HUMID_LONG_MAX_NT : 64)) {
+    if (a.long_words) std::fprintf(stderr, "humid: word length %zu is not supported by the HIP path (1..%u with --long-words)\n", a.word_length, HUMID_LONG_MAX_NT);
+    else std::fprintf(stderr, "humid: word length %zu is not supported by the HIP path (1..64; --long-words takes 1..%u)\n", a.word_length, HUMID_LONG_MAX_NT);
     return 2;
   }
   if (a.gpus == 1 && getenv("HUMID_GPUS")) a.gpus = (unsigned)std::strtoul(getenv("HUMID_GPUS"), nullptr, 10);
+  if (a.long_words) {
+    // what a long-word run does not do: one line, before anything is opened and before any GPU use
+    const char *why = nullptr;
+    if (a.edit) why = "--long-words does not work with -e (Hamming neighbours only)";
+    else if (a.gpus != 1 || getenv("HUMID_FORCE_SHARDED")) why = "--long-words runs on one GPU (not with -g, HUMID_GPUS or HUMID_FORCE_SHARDED)";
+    else if (a.keyed) why = "--long-words does not work with -b";
+    else if (!a.whitelists.empty()) why = "--long-words does not work with -w";
+    else if (a.paired) why = "--long-words does not work with -P";
+    else if (a.best) why = "--long-words does not work with -Q";
+    else if (a.consensus) why = "--long-words does not work with -C";
+    else if (a.duplex) why = "--long-words does not work with -D";
+    else if (a.optical) why = "--long-words does not work with -O";
+    else if (a.chunked) why = "--long-words does not work with --chunk-reads";
+    else if (a.bchunked) why = "--long-words does not work with --chunk-barcoded";
+    else if (a.cells_mode >= 0 || a.cells_ratio_given) why = "--long-words does not work with --cells-top / --cells-expected / --cells-min-reads / --cells-merge-ratio";
+    else if (!a.word_pattern.empty()) why = "--long-words does not work with --word-pattern";
+    else if (a.posterior || a.max_inexact_given || a.barcode_opts_given) why = "--long-words does not work with --barcode-posterior / --barcode-min-odds / --barcode-max-inexact";
+    if (why) { std::fprintf(stderr, "humid: %s\n", why); return 2; }
+  }
   if (a.gpus < 1 || a.gpus > 16) {
     std::fprintf(stderr, "humid: -g takes 1 .. 16 GPUs\n");
     return 2;
@@ -783,7 +811,7 @@ int main(int argc, char **argv) {
       double t_pin = t_wait, t_slab = t_wait;
       if (n > 0) {
         // page-locked staging for what crosses PCIe: packed words + flags in, cluster ids + keep flags out
-        const uint64_t wb = (uint64_t)n * (a.word_length > 32 ? 16 : 8);
+        const uint64_t wb = (uint64_t)n * (a.long_words ? 8 * ((a.word_length + 31) / 32) : a.word_length > 32 ? 16 : 8);
         pin_bytes = wb + (uint64_t)n + (uint64_t)n * 4 + (uint64_t)n + 64;
         std::thread pin_thread;                            // the two take ~30 ms and ~40 ms: side by side
         if (getenv("HUMID_NO_PINNED") == nullptr && !a.keyed)   // (-b: keys and shorter words, from ordinary memory)
@@ -791,7 +819,7 @@ int main(int argc, char **argv) {
         if (getenv("HUMID_NO_SLAB") == nullptr)
           humid_ctx_reserve(ctx, a.chunked ? std::min<uint64_t>((uint64_t)n, a.chunk_reads) :
                                  a.bchunked ? std::min<uint64_t>((uint64_t)n, a.bchunk_reads) : (uint64_t)n,
-                            (uint32_t)a.word_length);   // one slab (--chunk-reads: for one chunk) + the code object loaded
+                            (uint32_t)std::min<size_t>(a.word_length, 64));   // one slab (--chunk-reads: for one chunk) + the code object loaded
         t_slab = since();
         if (pin_thread.joinable()) pin_thread.join();
       }
@@ -869,7 +897,7 @@ int main(int argc, char **argv) {
   if (!dump_only && cons_out) start_ctx();
   // ---- pass 1: readData (src/humid.cc:89-100) ----
   t = start_message(log, "Reading data");
-  const size_t wpr = a.word_length > 32 ? 2 : 1;   // uint64 per word (include/humid_hip.h)
+  const size_t wpr = a.long_words ? (a.word_length + 31) / 32 : a.word_length > 32 ? 2 : 1;   // uint64 per word (include/humid_hip.h)
   std::vector<uint64_t> words;
   std::vector<uint8_t> filtered;
   std::vector<uint8_t> bases;                      // device-side packing: word_length raw symbols per record
@@ -877,7 +905,7 @@ int main(int argc, char **argv) {
   // (humid_dedup_run_bases).  Not the default: 24 raw bytes per read instead of 9 packed ones cross
   // PCIe, which costs more than the host's packing saves (profiles/r02d_cli_e2e.txt).
   // (-Q: the selection compares the packed words, so the host packs them)
-  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && !a.paired && !a.chunked && getenv("HUMID_DEVICE_PACK") != nullptr;
+  const bool device_pack = fast && !dump_only && !sharded && !a.keyed && !a.best && !a.optical && !a.paired && !a.chunked && !a.long_words && getenv("HUMID_DEVICE_PACK") != nullptr;
   uint64_t n_records = 0;
   std::vector<uint32_t> scores;                    // -Q: one per record
   std::vector<uint32_t> pos_tile, pos_x, pos_y;    // -O: the position of every record (position.hpp)
@@ -926,7 +954,9 @@ int main(int argc, char **argv) {
         }
         if (scoring) scores[i] = clamp_score(qsum);
         if (positions) { const Position ps = parse_position(name0); pos_tile[i] = ps.tile; pos_x[i] = ps.x; pos_y[i] = ps.y; }
-        if (wpr == 2) {
+        if (a.long_words) {
+          filtered[i] = make_word_long(name0, seqs, nf, plan, &words[wpr * i]) ? 1 : 0;
+        } else if (wpr == 2) {
           filtered[i] = make_word_wide(name0, seqs, nf, plan, &words[2 * i]) ? 1 : 0;
         } else {
           uint64_t w;
@@ -942,10 +972,9 @@ int main(int argc, char **argv) {
     if (!in.ok()) { std::fprintf(stderr, "humid: cannot open %s\n", in.bad_file().c_str()); return 1; }
     std::vector<FastqRecord> recs;
     while (in.next(recs)) {
-      uint64_t w[2];
-      bool f = wpr == 2 ? make_word_wide(recs, plan, w) : make_word(recs, plan, w[0]);
-      words.push_back(w[0]);
-      if (wpr == 2) words.push_back(w[1]);
+      uint64_t w[(HUMID_LONG_MAX_NT + 31) / 32];
+      bool f = a.long_words ? make_word_long(recs, plan, w) : wpr == 2 ? make_word_wide(recs, plan, w) : make_word(recs, plan, w[0]);
+      words.insert(words.end(), w, w + wpr);
       filtered.push_back(f ? 1 : 0);
       if (scoring) {
         uint64_t qsum = 0;
@@ -1206,6 +1235,9 @@ int main(int argc, char **argv) {
   else if (a.keyed)
     rc = humid_dedup_run_keyed(ctx, run_words, keys.data(), run_filt, N, (uint32_t)run_nt, (uint32_t)a.distance, method,
                                cluster_id, keep, &sum);
+  else if (a.long_words)
+    rc = humid_dedup_run_long(ctx, run_words, run_filt, N, (uint32_t)a.word_length, (uint32_t)a.distance, method, cluster_id, keep,
+                              &sum);
   else
   rc = device_pack
                ? humid_dedup_run_bases(ctx, bases.data(), N, (uint32_t)a.word_length, (uint32_t)a.distance, method,

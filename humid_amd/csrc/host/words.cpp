@@ -148,6 +148,45 @@ bool make_word_wide(std::string_view first_header, const std::string_view *seqs,
   return filtered;
 }
 
+// --long-words: the symbols arrive in order, so each goes to the low end of its uint64 -- [0] takes the first
+// word_nt - 32 (k - 1), every following one the next 32
+struct LongAcc {
+  uint64_t *out;
+  size_t head_nt, p;
+  void push(unsigned c) {
+    const size_t col = p < head_nt ? 0 : 1 + (p - head_nt) / 32;
+    out[col] = (out[col] << 2) | c;
+    p++;
+  }
+};
+static inline void push_symbols(std::string_view s, size_t want, LongAcc &w, bool &filtered) {
+  const size_t have = s.size() < want ? s.size() : want;
+  for (size_t i = 0; i < have; i++) {
+    int c = code_of(s[i]);
+    if (c < 0) { c = 2; filtered = true; }
+    w.push((unsigned)c);
+  }
+  for (size_t i = have; i < want; i++) { w.push(2u); filtered = true; }
+}
+
+bool make_word_long(std::string_view first_header, const std::string_view *seqs, size_t n_files, const WordPlan &plan,
+                    uint64_t *word) {
+  const size_t k = (plan.word_nt + 31) / 32;
+  memset(word, 0, k * sizeof(uint64_t));
+  LongAcc w{word, plan.word_nt - 32 * (k - 1), 0};
+  bool filtered = false;
+  if (plan.header_umi > 0) push_symbols(header_umi(first_header), plan.header_umi, w, filtered);
+  for (size_t f = 0; f < n_files; f++) push_symbols(seqs[f], plan.take[f], w, filtered);
+  return filtered;
+}
+
+bool make_word_long(const std::vector<FastqRecord> &recs, const WordPlan &plan, uint64_t *word) {
+  std::string_view seqs[64];
+  const size_t n = recs.size() < 64 ? recs.size() : 64;
+  for (size_t f = 0; f < n; f++) seqs[f] = recs[f].seq;
+  return make_word_long(recs.front().name, seqs, n, plan, word);
+}
+
 bool make_word_wide(const std::vector<FastqRecord> &recs, const WordPlan &plan, uint64_t word[2]) {
   std::string_view seqs[64];
   const size_t n = recs.size() < 64 ? recs.size() : 64;

@@ -55,6 +55,13 @@ bool make_word_wide(const std::vector<FastqRecord> &recs, const WordPlan &plan, 
 bool make_word_wide(std::string_view first_header, const std::string_view *seqs, size_t n_files,
                     const WordPlan &plan, uint64_t word[2]);
 
+// --long-words, 1 <= plan.word_nt <= 512 (no --word-pattern): k = ceil(word_nt / 32) uint64, [0] = the first
+// word_nt - 32 (k - 1) symbols right-aligned, every following one the next 32 (humid_dedup_run_long); up to 64 symbols
+// that is what make_word / make_word_wide write
+bool make_word_long(const std::vector<FastqRecord> &recs, const WordPlan &plan, uint64_t *word);
+bool make_word_long(std::string_view first_header, const std::string_view *seqs, size_t n_files, const WordPlan &plan,
+                    uint64_t *word);
+
 // -P (strand-symmetric words, include/humid_hip.h): the word A.B of word_nt = 2 h nucleotides becomes the smaller of
 // itself and its mirror B.A, in place (wpr uint64 per word: 1 up to 32 nucleotides, 2 beyond).  Returns true when the
 // mirror was the smaller one (a bottom-strand read).

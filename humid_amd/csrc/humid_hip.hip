@@ -252,6 +252,11 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
     c->force_segments = (u32)value;
     return HUMID_OK;
   }
+  if (strcmp(key, "long_key_bits") == 0) {
+    if (value < 1 || value > 64) return fail(c, HUMID_E_INVALID, "long_key_bits must be 1 .. 64");
+    c->lg_key_bits = (u32)value;
+    return HUMID_OK;
+  }
   if (strcmp(key, "accum_tile") == 0) {
     if (value < 64 || value > ACC_TILE || (value & (value - 1))) return fail(c, HUMID_E_INVALID, "accum_tile must be a power of two, 64 .. %u", ACC_TILE);
     c->ac_tile = (u32)value;
@@ -452,10 +457,70 @@ int humid_dedup_run_bases(humid_ctx *c, const uint8_t *bases, uint64_t n_reads, 
                   method, cluster_id, keep, summary);
 }
 
+// ---- long words (kernels_long.hip.h; run_device_long in pipeline.hip.h) --------------------------------------------
+int humid_dedup_run_long_device(humid_ctx *c, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *d_cluster_id, uint8_t *d_keep,
+                                humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  return run_device_long(c, d_words, d_filtered, n_reads, word_nt, distance, method, d_cluster_id, d_keep, summary);
+}
+
+// host buffers: the staging of run_host with ceil(word_nt / 32) uint64 per read; a refused shape moves nothing
+int humid_dedup_run_long(humid_ctx *c, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads, uint32_t word_nt,
+                         uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep, humid_summary *summary) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  state_reset(c);
+  TRY(check_run_args(c, n_reads, word_nt, method, HUMID_LONG_MAX_NT));
+  if (c->edit) return fail(c, HUMID_E_UNSUPPORTED, "option edit_distance is not supported for long words");
+  if (n_reads && (!words || !filtered || !cluster_id || !keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  humid_summary s;
+  memset(&s, 0, sizeof s);
+  const size_t n = (size_t)n_reads, wbytes = (size_t)((word_nt + 31) / 32) * 8;
+  ENSURE(c->in_words, n * wbytes + 16);
+  ENSURE(c->in_filt, n + 8);
+  ENSURE(c->out_cid, n * 4 + 8);
+  ENSURE(c->out_keep, n + 8);
+  hipEvent_t e0 = c->ev[5], e1, e2, e3;
+  HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2)); HIPCHK(hipEventCreate(&e3));
+  int rc = HUMID_OK;
+  hipError_t he = hipEventRecord(e0, st);
+  if (he == hipSuccess && n) he = hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess && n) he = hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipEventRecord(e1, st);
+  if (he != hipSuccess) rc = fail(c, HUMID_E_HIP, "copy in: %s", hipGetErrorString(he));
+  if (rc == HUMID_OK)
+    rc = run_device_long(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method, c->out_cid.as<u32>(),
+                         c->out_keep.as<u8>(), &s);
+  if (rc == HUMID_OK) {
+    he = hipEventRecord(e2, st);
+    if (he == hipSuccess && n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipEventRecord(e3, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
+    if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
+  }
+  (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
+  if (rc == HUMID_OK && summary) *summary = s;
+  return rc;
+}
+
+int humid_long_info(humid_ctx *c, humid_long_info_t *out) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (!out) return fail(c, HUMID_E_INVALID, "null argument");
+  if (!state_has_run(c) || !c->state.long_words) return fail(c, HUMID_E_STATE, "the last run was not a long-word run");
+  *out = c->lg_info;
+  return HUMID_OK;
+}
+
 // the packed words and flags of the last humid_dedup_run_bases (what makeWord would have returned)
 int humid_get_packed_words(humid_ctx *c, uint64_t *words, uint8_t *filtered) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (!state_has_run(c)) return fail(c, HUMID_E_STATE, "no completed dedup run in this context");
+  if (c->state.long_words) return fail(c, HUMID_E_STATE, "the last run was a long-word run: its words are the caller's");
   HIPCHK(hipSetDevice(c->device));
   const size_t n = (size_t)c->N, wbytes = c->word_nt > 32 ? 16 : 8;
   if (n * wbytes > c->in_words.cap || n > c->in_filt.cap) return fail(c, HUMID_E_STATE, "the last run did not go through a host entry point");
@@ -1167,6 +1232,7 @@ int humid_get_histogram(humid_ctx *c, uint32_t which, uint64_t *keys, uint64_t *
 static int group_stats(humid_ctx *c) {
   if (!state_has_run(c) && !state_keyed_graph(c))
     return fail(c, HUMID_E_STATE, "group statistics need a completed single-GPU humid_dedup_run*");
+  if (c->state.long_words) return fail(c, HUMID_E_STATE, "group statistics are not available after a long-word run");
   if (c->state.stats_current) return HUMID_OK;
   // (the scan below carries the reads in 32 bits: a run holds fewer, the reads of a keyed accumulator need not)
   if (c->usable > 0xffffffffull)
@@ -1316,6 +1382,10 @@ static int select_best_args(humid_ctx *c, const void *words, const void *cid, co
   if (scope > HUMID_BEST_CLUSTER) return fail(c, HUMID_E_INVALID, "scope must be 0 (leaf) or 1 (cluster)");
   if (!state_has_run(c))
     return fail(c, HUMID_E_INVALID, "humid_select_best needs a completed single-GPU humid_dedup_run* in this context");
+  // words of k uint64: best_pass reads one or two per read (the word_nt == c->word_nt test below refused every length
+  // beyond 64 only while no run could have one)
+  if (c->state.long_words) return fail(c, HUMID_E_STATE, "humid_select_best is not available after a long-word run");
+  if (word_nt > 64) return fail(c, HUMID_E_UNSUPPORTED, "word_nt %u > 64 is not supported by this entry point", word_nt);
   if (n_reads != c->N || word_nt != c->word_nt)
     return fail(c, HUMID_E_INVALID, "humid_select_best: %llu reads of %u nt, the last run had %llu of %u", (ull)n_reads, word_nt,
                 (ull)c->N, c->word_nt);

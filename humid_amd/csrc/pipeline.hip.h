@@ -37,6 +37,7 @@
 #include "kernels_cells.hip.h"
 #include "kernels_paired.hip.h"
 #include "kernels_accum.hip.h"
+#include "kernels_long.hip.h"
 
 // --------------------------------------------------------------------------------
 // host side
@@ -132,6 +133,7 @@ struct CtxState {
   bool dense = false;          // the last count ran on a compacted list of this rank's reads; a stage graph after it keeps this
   bool stats_current = false;  // derived on demand from a RUN: gs_* hold its group statistics for gs_G groups
   bool paired = false;         // the RUN was humid_dedup_run_paired*: pd_strand / pd_top / pd_bottom / pd_sum are its (humid_get_strands)
+  bool long_words = false;     // the RUN was humid_dedup_run_long*: g_word holds g_wpr = ceil(word_nt / 32) uint64 per leaf, lg_info is its (humid_long_info)
 };
 
 struct humid_ctx {
@@ -322,6 +324,10 @@ struct humid_ctx {
   DBuf pd_words, pd_strand, pd_mir, pd_top, pd_bottom, pd_ctr;   // canonical words, strands, mirrored leaves, tallies u32[C + 1], ull[PD_CTRS]
   u64 pd_N = 0;              // state.paired: pd_strand holds the strands of the run's pd_N reads
   humid_strand_summary pd_sum = {};
+  // long words (humid_dedup_run_long*, kernels_long.hip.h)
+  u32 lg_key_bits = 64;      // option "long_key_bits": the join keys are masked to this many bits (tests force collisions with 2)
+  humid_long_info_t lg_info = {};   // state.long_words: what the run's search did
+  DBuf lg_cand;              // ull[MAX_COMBOS][LONG_CAND_SLOTS]: candidates verified, per join
   // accumulated runs (humid_accum_*, kernels_accum.hip.h): a read set fed in chunks.  The list -- distinct words ascending,
   // reads per word, smallest global read index per word -- lives in TWO buffer sets of its own (never the slab): a merge
   // reads set ac_cur and writes the other, and the sets swap only when it succeeded.  Kept until humid_accum_begin,
@@ -2938,6 +2944,208 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   }
   if (sum) *sum = s;
   return state_publish(c, CtxState::RUN);
+}
+
+// ---- long words (humid_dedup_run_long*, kernels_long.hip.h): k = ceil(word_nt / 32) uint64 per read ----------------
+// Stage A: the sorting count of stage_count_wide for k words.  Leaves s_word (k per leaf) / s_cnt / s_first / s_slot
+// and, for stage C, the partition-order arrays pk_vals / pslot; count_mode_used is 3.
+static int stage_count_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt, humid_summary &s) {
+  hipStream_t st = c->stream;
+  const u32 k = (word_nt + 31) / 32, hbits = 2 * (word_nt - 32 * (k - 1));
+  c->last_count_lds = true;          // stage C walks pk_vals/pslot (k_read_map_part)
+  c->last_count_ordered = false;
+  c->last_count_sorted = true;
+  c->last_rec8 = false;
+  c->n_parts = 0;
+  const u32 grid = grid_stride_blocks(N);
+  ENSURE(c->pk_keys, (size_t)N * 8);
+  ENSURE(c->pad_word, (size_t)N * 8);
+  ENSURE(c->pk_vals, (size_t)N * 4);
+  ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
+  ENSURE(c->pslot, (size_t)N * 4);
+  ENSURE(c->w_sorted, (size_t)N * k * 8);
+  ENSURE(c->w_head, ((size_t)N + 1) * 4);
+  ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
+  HIPCHK(hipEventRecord(c->ev[0], st));
+  HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
+  HIPCHK(hipEventRecord(c->kev[0], st));
+  u64 *k0 = c->pk_keys.as<u64>(), *k1 = c->pad_word.as<u64>();
+  u32 *v = c->uniq_slot.as<u32>(), *v_other = c->pk_vals.as<u32>();   // v: the order so far
+  for (u32 pass = 0; pass < k; pass++) {                               // least significant uint64 first
+    const u32 j = k - 1 - pass;
+    hipLaunchKernelGGL(k_long_keys, dim3(grid), dim3(256), 0, st, d_words, d_filt, pass ? (const u32 *)v : (const u32 *)nullptr, N, k, j,
+                       hbits, k0, v, c->d_ctr);
+    TRY(sort_pairs<u64, u32>(c, k0, k1, v, v_other, N, 0, j ? 64 : (hbits < 64 ? hbits + 1 : 64)));   // the head: by (filtered,) head
+    std::swap(v, v_other);
+  }
+  if (hbits == 64) {                                                   // word_nt a multiple of 32: no spare key bit
+    hipLaunchKernelGGL(k_wide_keys_flag, dim3(grid), dim3(256), 0, st, d_filt, (const u32 *)v, N, (u32 *)k0);
+    TRY(sort_pairs<u32, u32>(c, (u32 *)k0, (u32 *)k1, v, v_other, N, 0, 1));
+    std::swap(v, v_other);
+  }
+  HIPCHK(hipEventRecord(c->kev[1], st));
+  u64 *sw = c->w_sorted.as<u64>();
+  hipLaunchKernelGGL(k_long_gather, dim3(grid_stride_blocks((u64)N * k)), dim3(256), 0, st, d_words, (const u32 *)v, N, k, hbits, sw);
+  hipLaunchKernelGGL(k_long_heads, dim3(grid), dim3(256), 0, st, (const u64 *)sw, N, k, c->d_ctr, c->w_head.as<u32>());
+  u64 n_unique = 0;
+  TRY(scan_total(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), N, &n_unique));
+  const u32 U = (u32)n_unique;
+  s.usable = c->usable = c->h_ctr[CTR_USABLE];
+  s.unique = c->U = U;
+  ENSURE(c->s_word, (size_t)(U + 1) * k * 8);
+  ENSURE(c->s_slot, (size_t)(U + 1) * 4);
+  ENSURE(c->s_cnt, (size_t)(U + 1) * 4);
+  ENSURE(c->s_first, (size_t)(U + 1) * 4);
+  ENSURE(c->w_start, (size_t)(U + 2) * 4);
+  ENSURE(c->slot_out, (size_t)(U + 1) * 8);
+  hipLaunchKernelGGL(k_long_unique, dim3(grid), dim3(256), 0, st, (const u64 *)sw, (const u32 *)v, c->w_head.as<u32>(),
+                     c->w_hpos.as<u32>(), N, k, c->d_ctr, c->s_word.as<u64>(), c->s_first.as<u32>(), c->w_start.as<u32>(),
+                     c->pslot.as<u32>(), c->pk_vals.as<u32>());
+  if (U)
+    hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U, c->s_cnt.as<u32>(),
+                       c->s_slot.as<u32>());
+  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  HIPCHK(hipGetLastError());
+  return HUMID_OK;
+}
+
+// Pairs of leaves u < v within Hamming distance `distance` over all word_nt nucleotides, as a duplicate-free ascending
+// edge list in c->e_edges.  leaf: the U leaves ascending, k uint64 each.  Pigeonhole over distance + 1 contiguous
+// segments (lengths differ by at most one): two words within the distance agree on some segment, so per segment the
+// leaves are joined with themselves on a key of the segment (k_long_seg_keys) and every candidate is verified over
+// the whole word -- a key collision only adds candidates.  distance >= word_nt, or more segments than MAX_COMBOS:
+// one join of all pairs.  The host waits are those of join_append; c->lg_info says what was done.
+static int long_edges(humid_ctx *c, const u64 *leaf, u32 U, u32 k, u32 word_nt, u32 distance, u64 *n_edges_out) {
+  hipStream_t st = c->stream;
+  *n_edges_out = 0;
+  if (U < 2) return HUMID_OK;
+  // distance 0: the plan's one segment is the whole word, and distinct leaves share none: its join is empty, not launched
+  if (distance == 0) { c->lg_info.joins = 1; return HUMID_OK; }
+  const bool all_pairs = distance >= word_nt || distance + 1 > MAX_COMBOS;
+  if (all_pairs && U > (1u << 18))
+    return fail(c, HUMID_E_OVERFLOW, "distance %u over %u-nt words compares all pairs of %u unique words: too many neighbour pairs",
+                distance, word_nt, U);
+  const u32 nseg = all_pairs ? 1u : distance + 1;
+  ENSURE(c->e_kx, (size_t)U * 8);
+  ENSURE(c->e_vx, (size_t)U * 4);
+  ENSURE(c->seg_k0, (size_t)U * 8);
+  ENSURE(c->seg_v0, (size_t)U * 4);
+  ENSURE(c->pc, ((size_t)U + 1) * 4);
+  ENSURE(c->poff, ((size_t)U + 1) * 4);
+  ENSURE(c->lg_cand, (size_t)MAX_COMBOS * LONG_CAND_SLOTS * sizeof(ull));
+  HIPCHK(hipMemsetAsync(c->lg_cand.p, 0, (size_t)MAX_COMBOS * LONG_CAND_SLOTS * sizeof(ull), st));
+  const u32 pad = 64 * k - 2 * word_nt;            // bits in front of the word in its string of 64 k bits
+  const u32 base = word_nt / nseg, rem = word_nt % nseg;
+  u64 raw = 0;                                     // pairs collected so far (with duplicates)
+  u32 pos = 0;
+  for (u32 seg = 0; seg < nseg; seg++) {
+    const u32 len = all_pairs ? 0u : base + (seg < rem ? 1u : 0u);
+    const u32 nbits = 2 * len;
+    const u32 kb = std::min<u32>(c->lg_key_bits, nbits == 0 ? 1u : std::min<u32>(nbits, 64u));
+    const u64 kmask = kb >= 64 ? ~0ull : ((1ull << kb) - 1ull);
+    hipLaunchKernelGGL(k_long_seg_keys, dim3(blocks_for(U)), dim3(256), 0, st, leaf, U, k, pad + 2 * pos, nbits, kmask,
+                       c->seg_k0.as<u64>(), c->seg_v0.as<u32>());
+    TRY(sort_pairs<u64, u32>(c, c->seg_k0.as<u64>(), c->e_kx.as<u64>(), c->seg_v0.as<u32>(), c->e_vx.as<u32>(), U, 0, kb));
+    ull *cand = c->lg_cand.as<ull>() + (size_t)seg * LONG_CAND_SLOTS;
+    bool in_pieces = false;                        // join_append took this join through the pieces
+    auto launch = [&](auto fill, auto keys, u64 n_pieces, u32 *pc, const u32 *poff, u64 *out) {
+      constexpr bool FILL = decltype(fill)::value;
+      using KT = typename decltype(keys)::key_type;
+      if (n_pieces) {
+        in_pieces = true;
+        if (!FILL) (void)hipMemsetAsync(cand, 0, LONG_CAND_SLOTS * sizeof(ull), st);     // (what the join over the entries counted before it gave up)
+        hipLaunchKernelGGL((k_long_join_chunks<FILL, KT>), dim3(blocks_for(n_pieces)), dim3(256), 0, st, keys.kx, keys.vx, keys.U,
+                           (const u32 *)c->e_runlo.as<u32>(), (const u32 *)c->e_choff.as<u32>(), (u32)n_pieces, c->walk_max, leaf, k,
+                           distance, pc, poff, out, cand);
+      } else
+        hipLaunchKernelGGL((k_long_join<FILL, KT>), dim3(blocks_for(keys.U)), dim3(256), 0, st, keys.kx, keys.vx, keys.U, leaf, k,
+                           distance, pc, poff, out, c->walk_max, &c->d_ctr[CTR_BIGMASK], cand);
+    };
+    TRY(join_append(c, "long-word", c->e_kx.p, c->e_vx.as<u32>(), c->e_kx.p, c->e_vx.as<u32>(), U, false, launch, raw));
+    if (in_pieces) c->lg_info.piece_joins++;
+    c->lg_info.joins++;
+    c->lg_info.key_bits = std::max<u32>(c->lg_info.key_bits, kb);
+    pos += len;
+  }
+  HIPCHK(hipGetLastError());
+  ull h_cand[MAX_COMBOS * LONG_CAND_SLOTS];
+  HIPCHK(hipMemcpyAsync(h_cand, c->lg_cand.p, (size_t)nseg * LONG_CAND_SLOTS * sizeof(ull), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (u32 i = 0; i < nseg * LONG_CAND_SLOTS; i++) c->lg_info.candidates += h_cand[i];
+  c->lg_info.raw_edges = raw;
+  if (raw == 0) return HUMID_OK;
+  TRY(unique_edges(c, c->e_raw.as<u64>(), raw, U, n_edges_out));
+  c->lg_info.edges = *n_edges_out;
+  return HUMID_OK;
+}
+
+// The full pipeline on device buffers for long words: stage_count_long, long_edges, the graph stage with the pairs
+// GIVEN (as the strand-symmetric and edit-distance runs give theirs), then the unchanged stage_map.
+static int run_device_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u64 n_reads, u32 word_nt, u32 distance,
+                           u32 method, u32 *d_cid, u8 *d_keep, humid_summary *sum) {
+  if (!c) return HUMID_E_INVALID;
+  state_reset(c);
+  TRY(check_run_args(c, n_reads, word_nt, method, HUMID_LONG_MAX_NT));
+  if (c->edit) return fail(c, HUMID_E_UNSUPPORTED, "option edit_distance is not supported for long words");
+  if ((uintptr_t)d_words & 7) return fail(c, HUMID_E_INVALID, "long words must be 8-byte aligned on the device");
+  if (n_reads && (!d_words || !d_filt || !d_cid || !d_keep)) return fail(c, HUMID_E_INVALID, "null buffer");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const u32 N = (u32)n_reads, k = (word_nt + 31) / 32;
+  humid_summary s;
+  memset(&s, 0, sizeof s);
+  s.total = n_reads;
+  c->last_unperm_tiled = false;
+  c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
+  c->word_nt = word_nt; c->distance = distance; c->method = method;
+  c->gU = 0;
+  c->lg_info = humid_long_info_t{};
+  c->lg_info.words_per_read = k;
+  auto publish = [&]() { if (sum) *sum = s; state_publish(c, CtxState::RUN); c->state.long_words = true; return HUMID_OK; };
+  s.count_mode_used = 3u;
+  if (N == 0) return publish();
+  struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = false; } } lean_guard{c};
+  c->lean_events = !c->kev_on && getenv("HUMID_ALL_EVENTS") == nullptr;
+  TRY(stage_count_long(c, d_words, d_filt, N, word_nt, s));
+  const u32 U = (u32)c->U;
+  if (U == 0) {   // everything filtered
+    HIPCHK(hipMemsetAsync(d_cid, 0, (size_t)N * 4, st));
+    HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)N, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return publish();
+  }
+  const u64 *leaf = c->s_word.as<u64>();
+  u64 E = 0;
+  TRY(long_edges(c, leaf, U, k, word_nt, distance, &E));
+  static const u64 no_edges = 0;
+  u32 n_pair_segs = 0;
+  // (the graph stage reads no word when its pairs are given: it runs as over one-uint64 leaves and the record is set right behind it)
+  const u32 plan_nt = std::min<u32>(word_nt, 32u);
+  if (c->use_compact)
+    TRY(stage_graph_compact<u64>(c, leaf, c->s_cnt.as<u32>(), U, plan_nt, distance, method, s, n_pair_segs,
+                                 E ? c->e_edges.as<u64>() : &no_edges, E));
+  else
+    TRY(stage_graph<u64>(c, leaf, c->s_cnt.as<u32>(), U, plan_nt, distance, method, s, n_pair_segs,
+                         E ? c->e_edges.as<u64>() : &no_edges, E));
+  c->g_wpr = k;
+  TRY(stage_map(c, c->cid.as<u32>(), c->ismax.as<u8>(), N, d_cid, d_keep));
+  if (c->cg_valid) TRY(n_clusters_compact(c, U, &c->C));
+  else TRY(n_clusters_from_scan(c, U, &c->C));
+  s.clusters = c->C;
+  s.nonsingle = c->M;
+  HIPCHK(hipEventSynchronize(c->ev[4]));
+  const bool lean = c->lean_events;
+  c->lean_events = false;
+  if (!lean) {                                               // the stages' shares: option kernel_timing
+    HIPCHK(hipEventElapsedTime(&s.ms_count, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&s.ms_neighbours, c->ev[1], c->ev[2]));
+    HIPCHK(hipEventElapsedTime(&s.ms_cluster, c->ev[2], c->ev[3]));
+    HIPCHK(hipEventElapsedTime(&s.ms_map, c->ev[3], c->ev[4]));
+  }
+  HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
+  HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));   // the k sorts
+  s.ms_k_map = s.ms_map;
+  return publish();
 }
 
 // ---- accumulated runs (humid_accum_*): a read set fed in chunks (kernels_accum.hip.h) --------------------------

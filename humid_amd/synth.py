@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-__all__ = ["synth_words", "synth_wide_words", "synth_fastq", "fast_fastq", "CONFIG_SEEDS", "pack_bases"]
+__all__ = ["synth_words", "synth_wide_words", "synth_long_words", "synth_fastq", "fast_fastq", "CONFIG_SEEDS", "pack_bases"]
 
 CONFIG_SEEDS = {1: 1001, 2: 1002, 3: 1003, 4: 1004, 5: 1005}
 
@@ -153,6 +153,47 @@ def synth_wide_words(n_reads: int, seed: int, word_nt: int = 48, p_sub: float = 
         for r, c, sh in zip(rd.tolist(), col.tolist(), shift.tolist()):   # code of 'G', src/fastq.cc:156
             words[r, c] = (int(words[r, c]) & ~(3 << sh)) | (2 << sh)
     if shuffle and n_reads:
+        perm = rng.permutation(n_reads)
+        words = words[perm]
+        filtered = filtered[perm]
+    return np.ascontiguousarray(words), np.ascontiguousarray(filtered)
+
+
+def synth_long_words(n_reads: int, seed: int, word_nt: int = 150, p_sub: float = 1e-3,
+                     p_n: float = 1e-4, shuffle: bool = True):
+    """`synth_wide_words` for any word_nt >= 1: u64[N, k] words with k = ceil(word_nt / 32) ([:, 0] = the first
+    word_nt - 32 (k - 1) nucleotides right-aligned, every following column the next 32) + filtered flags.  A
+    substitution XORs a nucleotide's code with 1 .. 3; everything is array arithmetic, so 10^7 reads take seconds."""
+    if word_nt < 1:
+        raise ValueError("word_nt must be >= 1")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    mol, n_mol = _family_of_read(rng, n_reads)
+    k = (word_nt + 31) // 32
+    nh = word_nt - 32 * (k - 1)
+    if not n_reads:
+        return np.zeros((0, k), dtype=np.uint64), np.zeros(0, dtype=np.uint8)
+    words = np.stack([_rand_bits(rng, 2 * nh if j == 0 else 64, n_mol)[mol] for j in range(k)], axis=1)
+    flat = words.reshape(-1)
+    total_bases = n_reads * word_nt
+
+    def place(idx):   # index of a nucleotide over all reads -> (index into flat, bit shift)
+        rd, pos = idx // word_nt, idx % word_nt
+        col = np.where(pos < nh, 0, 1 + (pos - nh) // 32)
+        shift = np.where(pos < nh, 2 * (nh - 1 - pos), 2 * (31 - (pos - nh) % 32)).astype(np.uint64)
+        return rd, rd * k + col, shift
+
+    n_sub = int(rng.binomial(total_bases, p_sub))
+    if n_sub:
+        _, at, shift = place(rng.integers(0, total_bases, size=n_sub))
+        np.bitwise_xor.at(flat, at, rng.integers(1, 4, size=n_sub).astype(np.uint64) << shift)
+    filtered = np.zeros(n_reads, dtype=np.uint8)
+    n_n = int(rng.binomial(total_bases, p_n))
+    if n_n:
+        rd, at, shift = place(rng.integers(0, total_bases, size=n_n))
+        filtered[rd] = 1
+        np.bitwise_and.at(flat, at, ~(np.uint64(3) << shift))      # code of 'G', src/fastq.cc:156
+        np.bitwise_or.at(flat, at, np.uint64(2) << shift)
+    if shuffle:
         perm = rng.permutation(n_reads)
         words = words[perm]
         filtered = filtered[perm]

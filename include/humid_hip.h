@@ -18,7 +18,8 @@
  * 33 <= n <= 64 ("wide" words): TWO uint64 per read, [2r] = the first n-32 nucleotides packed the
  * same way (right-aligned), [2r+1] = the last 32; every words / word array of the single-GPU entry
  * points (humid_dedup_run, humid_dedup_run_device, humid_get_leaves) then holds 2 entries per
- * read / leaf, 16-byte aligned on the device.  n > 64 returns HUMID_E_UNSUPPORTED.  Several GPUs:
+ * read / leaf, 16-byte aligned on the device.  n > 64 returns HUMID_E_UNSUPPORTED from the entry points below;
+ * see humid_dedup_run_long (up to HUMID_LONG_MAX_NT nucleotides, ceil(n / 32) uint64 per read).  Several GPUs:
  * humid_dedup_run_exchange takes wide words; of the humid_stage_* entry points those of the all-gather mode do
  * (humid_stage_histogram, _count_dense with a filter array, _unique, _graph, _graph_edges,
  * humid_stage_owner_perm_wide: value ranges are then ranges of HEADS, the top 64 bits of a word's 2n-bit value, and
@@ -128,7 +129,9 @@ const char *humid_last_error(const humid_ctx *ctx);   /* ctx may be NULL */
  * cluster of 10^5 reads on one spot).  Results do not depend on it.
  * "accum_tile": merge positions per workgroup of humid_accum_add*'s merge, a power of two from 64 to 2048 (default
  * 2048: the staged tile takes 16 KB of LDS for one-word words, 32 KB for two-word words).  Results do not depend on it;
- * small values make small inputs cross many tile boundaries (tests). */
+ * small values make small inputs cross many tile boundaries (tests).
+ * "long_key_bits": 1 .. 64 (default 64), the bits of the join keys of humid_dedup_run_long*'s neighbour search.  Results
+ * do not depend on it; 2 makes nearly all leaves share a key, which sends small inputs through the long buckets (tests). */
 int  humid_ctx_set_option(humid_ctx *ctx, const char *key, int64_t value);
 /* Optional: one slab of device memory for a run over about n_reads reads, so that the first run does
  * not pay ~35 separate allocations (the `humid` host calls it while pass 1 still parses).  Never
@@ -174,6 +177,47 @@ int humid_dedup_run_bases(humid_ctx *ctx, const uint8_t *bases, uint64_t n_reads
                           uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep,
                           humid_summary *summary);
 int humid_get_packed_words(humid_ctx *ctx, uint64_t *words, uint8_t *filtered);
+
+/* ---- long words: the whole hot path beyond 64 nucleotides -------------------------------------
+ * (reference-free deduplication on read prefixes: -n is a plain size_t in src/humid.cc:419-420.)
+ * 1 <= word_nt <= HUMID_LONG_MAX_NT; 0 returns HUMID_E_INVALID, more HUMID_E_UNSUPPORTED.  k = ceil(word_nt / 32)
+ * uint64 per read, words[k * r + j]: [k * r + 0] holds the first word_nt - 32 (k - 1) nucleotides right-aligned (the
+ * bits above them are ignored), every following uint64 the next 32, packed as everywhere in this library.  For
+ * word_nt <= 32 and 33 .. 64 that IS the one- and two-word layout above.  Device pointers need 8-byte alignment only.
+ * The results are those of humid_dedup_run's contract with "word" read as the k-uint64 value in lexicographic
+ * (= numeric, most significant first) order: leaves = the distinct usable words ascending, counts, Hamming neighbours
+ * over all word_nt nucleotides, directional / maximum clusters, id numbering, keep = the first read of the cluster's
+ * maxLeaf, summary (count_mode_used is 3: the count sorts).  For word_nt <= 64 the outputs equal humid_dedup_run's
+ * bit for bit; the long kernels run there too, nothing is forwarded.
+ * The search: pigeonhole over distance + 1 contiguous segments of the word; per segment the leaves are joined on a
+ * 64-bit key of the segment's nucleotides (masked to option "long_key_bits", 1 .. 64, default 64: results never depend
+ * on it, small values force key collisions) and every candidate pair is verified by the exact Hamming distance over
+ * all k uint64.  distance >= word_nt, or more segments than the plan's combinations allow, compares all pairs
+ * (HUMID_E_OVERFLOW beyond 2^18 distinct words).
+ * Option "edit_distance" set returns HUMID_E_UNSUPPORTED.  After a long run humid_get_leaves writes k uint64 per leaf;
+ * humid_get_adjacency, _clusters and _histogram answer as after any run; humid_get_group_stats / humid_group_stats_device
+ * and humid_get_packed_words return HUMID_E_STATE, and so do humid_select_best / humid_select_best_device (they read one or
+ * two uint64 per read; word_nt > 64 is HUMID_E_UNSUPPORTED there after any other run).  Grouped, keyed, paired, accumulated, sharded and stage runs,
+ * humid_dedup_run_bases and humid_select_best stay at 64 nucleotides. */
+#define HUMID_LONG_MAX_NT 512u
+int humid_dedup_run_long(humid_ctx *ctx, const uint64_t *words, const uint8_t *filtered, uint64_t n_reads,
+                         uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *cluster_id, uint8_t *keep,
+                         humid_summary *summary);
+int humid_dedup_run_long_device(humid_ctx *ctx, const uint64_t *d_words, const uint8_t *d_filtered, uint64_t n_reads,
+                                uint32_t word_nt, uint32_t distance, uint32_t method, uint32_t *d_cluster_id,
+                                uint8_t *d_keep, humid_summary *summary);
+/* Which road the last long run took (tests assert it); HUMID_E_STATE unless the last run was a long one. */
+typedef struct humid_long_info_t {
+  uint32_t words_per_read;   /* k                                                            */
+  uint32_t joins;            /* segments of the search: distance + 1 (1: all pairs, and distance 0, where the one segment is
+                              * the whole word and distinct leaves share none: nothing is launched); 0: fewer than 2 leaves */
+  uint32_t key_bits;         /* bits of the join keys                                         */
+  uint32_t piece_joins;      /* joins whose runs of equal keys were cut into pieces           */
+  uint64_t candidates;       /* pairs handed to the full-word verification, over all joins    */
+  uint64_t raw_edges;        /* pairs that passed it, before duplicates were removed          */
+  uint64_t edges;
+} humid_long_info_t;
+int humid_long_info(humid_ctx *ctx, humid_long_info_t *out);
 
 /* ---- grouped deduplication: words are clustered only within caller-given groups ----------------
  * (per cell barcode, per alignment position, per sample: UMI-tools --per-cell / dedup, fgbio
