@@ -293,6 +293,7 @@ SYMBOLS = {
     "humid_graph_split_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
     "humid_group_records_info": (C.c_int, [C.c_void_p, u32p, u32p]),
     "humid_wait_overlap_info": (C.c_int, [C.c_void_p, u32p, u32p]),
+    "humid_stamp_info": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_uint64), u32p]),
     "humid_get_run_roads": (C.c_int, [C.c_void_p, C.POINTER(HumidRunRoads)]),
     "humid_stage_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), u32p]),
     "humid_stage_route_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),

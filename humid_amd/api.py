@@ -918,6 +918,15 @@ class Dedup(Context):
         self._check(self._lib.humid_wait_overlap_info(self._h, C.byref(a), C.byref(b)))
         return dict(host_waits=a.value, overlapped=b.value)
 
+    def stamp_info(self):
+        """dict(used, stamps, event_records) of the last mutating call (humid_stamp_info): whether its ms_total and
+        ms_k_insert came from device stamps, the four raw stamps in ticks of 10 ns (pass start, count kernel start and
+        end, pass end; zeros where the pass stored none) and the number of event records the call made"""
+        used, n = C.c_uint32(), C.c_uint32()
+        st = (C.c_uint64 * 4)()
+        self._check(self._lib.humid_stamp_info(self._h, C.byref(used), st, C.byref(n)))
+        return dict(used=bool(used.value), stamps=[int(x) for x in st], event_records=n.value)
+
     def run_roads(self):
         """what the last mutating call retried (humid_get_run_roads): dict(events, n_events, graph_attempts).  events:
         the names of the first 32 events in order, of PART_PADDED_REDO, ORDERS_REDONE, REGIONS_REGROWN, FAR_TILES,

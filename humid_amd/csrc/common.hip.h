@@ -73,6 +73,11 @@ __device__ __forceinline__ T wave_incl_scan(T x) {
   x = wave_dpp_add<0x143, 0xc>(x);       // row_bcast:31 -> rows 2 and 3 take the total of the first half
   return x;
 }
+// A device stamp: thread 0 of workgroup 0 of a kernel that runs anyway stores the 100 MHz wall clock at its entry
+// (a null pointer everywhere but in the launches a lean pass is timed by: pipeline.hip.h, humid_ctx::d_stamp).
+__device__ __forceinline__ void device_stamp(u64 *stamp) {
+  if (stamp && blockIdx.x == 0 && threadIdx.x == 0) *stamp = wall_clock64();
+}
 // Experiment builds only (-DHUMID_PHASE_CLOCKS; tools/phase_clocks.sh): thread 0 of a sampled workgroup reads the
 // 100 MHz wall clock at the phase boundaries PH(k) of a kernel and adds the differences to humid_phase[id][k];
 // [id][0] counts the sampled workgroups.  humid_ctx_destroy prints the table.

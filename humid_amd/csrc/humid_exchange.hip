@@ -374,7 +374,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
       src.er.e = nullptr; src.er.cap_r = 0; src.er.cur = c->cg_cur.as<u32>(); src.er.far = c->e_edges.as<u64>(); src.er.n_far = (u32)E_e;
       src.recs = nullptr; src.n_recs = 0; src.segs = nullptr; src.cnt_by_id = gc; src.n_ids = n_ids;
       src.pairs_bound = E_e;
-      if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[2], st));
+      if (!c->lean_events) EVREC(c->ev[2], st);
       TRY(cg_build(c, src, method, cgs));
       if (c->h_ctr[CTR_OVERFULL]) return fail(c, HUMID_E_INVALID, "internal: an edit-distance pair outside the unique words");
       M_e = cgs.M;
@@ -769,7 +769,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
     src.er.e = nullptr; src.er.cap_r = 0; src.er.cur = c->cg_cur.as<u32>(); src.er.far = nullptr; src.er.n_far = 0;
     src.recs = nullptr; src.n_recs = 0; src.segs = &segs; src.cnt_by_id = nullptr; src.n_ids = n_ids;
     src.pairs_bound = n_recs_all;
-    if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[2], st));
+    if (!c->lean_events) EVREC(c->ev[2], st);
     TRY(cg_build(c, src, method, cgs));
     if (c->h_ctr[CTR_OVERFULL]) return fail(c, HUMID_E_INVALID, "a pair record with an index outside the unique words");
     M_mine = cgs.M;
@@ -1054,7 +1054,7 @@ int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, cons
                        c->s_first.as<u32>(), c->s_slot.as<u32>(), U, c->slot_out.as<u64>());
   c->slots_done = false;
   ENSURE(c->own_packed, ((size_t)N + 1) * 4);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[37], st));
+  if (c->kev_on) EVREC(c->kev[37], st);
   bool tiled = false;
   if (c->last_count_lds) TRY(unpermute_tiled(c, N, true, c->own_packed.as<u32>(), (u8 *)nullptr, c->kev[42], &tiled));
   if (tiled) {
@@ -1071,7 +1071,7 @@ int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, cons
   } else
     hipLaunchKernelGGL(k_read_map_packed, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->slot_of_read.as<u32>(),
                        c->slot_out.as<u64>(), N, c->own_packed.as<u32>());
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[38], st));
+  if (c->kev_on) EVREC(c->kev[38], st);
   c->stage_map_timed = true;
   HIPCHK(hipGetLastError());
   *d_packed = c->own_packed.as<u32>();     // queued on the context's stream

@@ -75,8 +75,10 @@ int humid_ctx_create(humid_ctx **out, int device, void *stream) {
   if ((e = hipMalloc((void **)&c->d_ctr, CTR_N * sizeof(ull) + sizeof(PsChain))) != hipSuccess) return bail(e, "hipMalloc");
   c->ps_chain = (PsChain *)(c->d_ctr + CTR_N);                 // the scans' chain (prims.hip.h): zero once, epochs after that
   if ((e = hipMemset(c->ps_chain, 0, sizeof(PsChain))) != hipSuccess) return bail(e, "hipMemset");
-  if ((e = hipHostMalloc((void **)&c->h_ctr, (CTR_N + 2) * sizeof(ull), hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
-  memset(c->h_ctr, 0, (CTR_N + 2) * sizeof(ull));
+  if ((e = hipMalloc((void **)&c->d_stamp, STAMP_N * sizeof(u64))) != hipSuccess) return bail(e, "hipMalloc");
+  if ((e = hipMemset(c->d_stamp, 0, STAMP_N * sizeof(u64))) != hipSuccess) return bail(e, "hipMemset");
+  if ((e = hipHostMalloc((void **)&c->h_ctr, (STAMP_AT + STAMP_N) * sizeof(ull), hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
+  memset(c->h_ctr, 0, (STAMP_AT + STAMP_N) * sizeof(ull));
   if (hipHostGetDevicePointer((void **)&c->h_ctr_dev, c->h_ctr, 0) != hipSuccess) { c->h_ctr_dev = nullptr; (void)hipGetLastError(); }
   c->no_poll = getenv("HUMID_NO_POLL") != nullptr;
   c->no_chain = getenv("HUMID_NO_SCAN_CHAIN") != nullptr;
@@ -111,6 +113,7 @@ void humid_ctx_destroy(humid_ctx *c) {
 #endif
   if (c->arena.base) (void)hipFree(c->arena.base);
   if (c->d_ctr) (void)hipFree(c->d_ctr);
+  if (c->d_stamp) (void)hipFree(c->d_stamp);
   if (c->h_ctr) (void)hipHostFree(c->h_ctr);
   for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : c->kev) if (ev) (void)hipEventDestroy(ev);
@@ -223,6 +226,10 @@ int humid_ctx_set_option(humid_ctx *c, const char *key, int64_t value) {
   }
   if (strcmp(key, "overlap_waits") == 0) {
     c->overlap_waits = value != 0;
+    return HUMID_OK;
+  }
+  if (strcmp(key, "device_stamps") == 0) {
+    c->device_stamps = value != 0;
     return HUMID_OK;
   }
   if (strcmp(key, "static_tiles") == 0) {
@@ -408,6 +415,7 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
+    c->ev_records += 4;                                      // e0 .. e3 around the two copies (the pass's reset came behind the first two)
     if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
   }
   (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
@@ -501,6 +509,7 @@ int humid_dedup_run_long(humid_ctx *c, const uint64_t *words, const uint8_t *fil
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
     if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
+    c->ev_records += 4;                                      // e0 .. e3 around the two copies (the pass's reset came behind the first two)
     if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
   }
   (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
@@ -577,6 +586,15 @@ int humid_wait_overlap_info(humid_ctx *c, uint32_t *host_waits, uint32_t *overla
   if (c->state.holds == CtxState::NOTHING) return fail(c, HUMID_E_STATE, "no completed run or stage call in this context");
   if (host_waits) *host_waits = c->wo_waits;
   if (overlapped) *overlapped = c->wo_overlapped;
+  return HUMID_OK;
+}
+
+int humid_stamp_info(humid_ctx *c, uint32_t *stamps_used, uint64_t stamps[4], uint32_t *event_records) {
+  if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
+  if (c->state.holds == CtxState::NOTHING) return fail(c, HUMID_E_STATE, "no completed run or stage call in this context");
+  if (stamps_used) *stamps_used = c->last_stamp_timed ? 1u : 0u;
+  if (stamps) for (u32 k = 0; k < STAMP_N; k++) stamps[k] = c->last_stamp_live ? c->last_stamps[k] : 0;
+  if (event_records) *event_records = c->ev_records;
   return HUMID_OK;
 }
 

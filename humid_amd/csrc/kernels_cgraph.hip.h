@@ -108,8 +108,9 @@ struct ZeroList {
   u32 n[ZERO_MAX];               // in u32
 };
 static __global__ void __launch_bounds__(256)
-k_zero_many(ZeroList z) {
+k_zero_many(ZeroList z, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   const u32 stride = gridDim.x * blockDim.x;
 #pragma unroll
   for (u32 q = 0; q < ZERO_MAX; q++) {

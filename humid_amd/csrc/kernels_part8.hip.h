@@ -275,8 +275,9 @@ __device__ __forceinline__ void dr_run_bounds(const u32 *lbits, u32 w, u32 bit, 
 #define DR_EARLY 1u                                // of the P8_RPT records per thread: requested before the fill is known
 static __global__ void __launch_bounds__(256)
 k_dedup_rec(u64 *recs, const u32 *__restrict__ cursor2, u32 n_reads, u32 pb, u32 d1, u32 ibits, RecKey rk,
-            u64 *__restrict__ pad_word, uint2 *__restrict__ pad_cf, u64 *__restrict__ agg, ull *ctr) {
+            u64 *__restrict__ pad_word, uint2 *__restrict__ pad_cf, u64 *__restrict__ agg, ull *ctr, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   PH_DECL;
   __shared__ u64 lkey[DR_SLOTS];
   __shared__ uint2 lcf[DR_SLOTS];                      // (count, first read); after the rank phase .y = the entry's rank

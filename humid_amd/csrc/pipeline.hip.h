@@ -151,6 +151,18 @@ struct humid_ctx {
   ull *h_ctr = nullptr;   // pinned mirror (CTR_N counters + the sequence word of read_counters)
   ull *h_ctr_dev = nullptr;   // the same memory as the device sees it
   ull ctr_seq = 0;
+  // Device stamps (option "device_stamps"): the four points a lean pass is timed between -- pass start, count kernel
+  // start and end, pass end -- as the 100 MHz wall clock read by thread 0 of workgroup 0 of a kernel that runs there
+  // anyway, where the events ev[0], kev[0], kev[1], ev[4] would put four markers into the stream.  d_stamp: STAMP_N
+  // u64 of their own (on no ZeroList); the pass's last k_publish_counters copies them to h_ctr[STAMP_AT ..].
+  u64 *d_stamp = nullptr;
+  bool device_stamps = true;   // the option
+  bool stamp_ok = false;       // run_device, before the first launch: this pass may take its times from stamps (cleared when a count is discarded)
+  bool stamp_live = false;     // stage_count_rec counted this pass: its kernels store the stamps
+  bool stamp_timed = false;    // ... and the pass is lean: none of the four events is recorded, the summary's times are the stamps'
+  bool last_stamp_timed = false, last_stamp_live = false;   // of the last mutating call (humid_stamp_info)
+  u64 last_stamps[4] = {};
+  u32 ev_records = 0;          // hipEventRecord calls of the last mutating call: host stores only (EVREC)
   const u32 *gf_valid = nullptr; // set by the last bucket order: device count of the words it holds (padded grouping), or null
   u32 *ucur_clean = nullptr;     // the un-permute's bin cursors at this address are all zero
   DBuf gf_cur;                    // cursors of the padded grouping (512 u32, kept at zero between uses)
@@ -383,6 +395,12 @@ static int fail(humid_ctx *c, int code, const char *fmt, ...) {
                   #expr, hipGetErrorString(_e), __FILE__, __LINE__);                        \
   } while (0)
 
+// every event record of the library's passes goes through here: counted for humid_stamp_info
+#define EVREC(ev, st) do { c->ev_records++; HIPCHK(hipEventRecord((ev), (st))); } while (0)
+#define STAMP_N 4
+#define STAMP_AT (CTR_N + 2)   // h_ctr: CTR_N counters, the sequence word, the grouped runs' check word, the stamps
+enum { STAMP_START = 0, STAMP_K0, STAMP_K1, STAMP_END };
+
 // Two memory rules.  A run's buffers and its own staging may be carved from the slab (ENSURE).  Every post-run pass
 // allocates plainly (PASS_ENSURE): the slab is sized for one run and takes nothing back.
 #define ENSURE(buf, bytes) HIPCHK((buf).ensure((bytes), &c->arena))
@@ -435,9 +453,9 @@ static int sort_keys(humid_ctx *c, const K *kin, K *kout, u64 n, u32 b0, u32 b1)
   return HUMID_OK;
 }
 template <class T, class In>
-static int exscan_in(humid_ctx *c, In in, T *out, u64 n) {
+static int exscan_in(humid_ctx *c, In in, T *out, u64 n, u64 *stamp = nullptr) {
   ENSURE(c->tmp, ps_scan_scratch_items(n) * sizeof(T) + 256);
-  HIPCHK((ps_exscan<T>(in, out, n, (T *)c->tmp.p, c->stream, c->no_chain ? nullptr : c->ps_chain, &c->ps_epoch)));
+  HIPCHK((ps_exscan<T>(in, out, n, (T *)c->tmp.p, c->stream, c->no_chain ? nullptr : c->ps_chain, &c->ps_epoch, stamp)));
   return HUMID_OK;
 }
 static int exscan_u32(humid_ctx *c, const u32 *in, u32 *out, u64 n) { return exscan_in<u32>(c, PtrIn<u32>{in}, out, n); }
@@ -450,8 +468,16 @@ static int exscan_u32(humid_ctx *c, const u32 *in, u32 *out, u64 n) { return exs
 // work queued behind the publishing kernel, which the GPU works through while the host reads: read_counters_begin /
 // _end below, option overlap_waits).
 static __global__ void k_publish_counters(const ull *__restrict__ ctr, const u32 *__restrict__ extra32, const u32 *__restrict__ extra32b,
-                                   volatile ull *host, ull seq, const u32 *__restrict__ extra32c = nullptr) {
+                                   volatile ull *host, ull seq, const u32 *__restrict__ extra32c = nullptr, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  if (stamp && threadIdx.x == 0) {   // the pass's last launch: its entry is the pass's end; the four stamps travel with the counters
+    const u64 t = wall_clock64();
+    stamp[STAMP_END] = t;
+    host[STAMP_AT + STAMP_START] = stamp[STAMP_START];
+    host[STAMP_AT + STAMP_K0] = stamp[STAMP_K0];
+    host[STAMP_AT + STAMP_K1] = stamp[STAMP_K1];
+    host[STAMP_AT + STAMP_END] = t;
+  }
   if (threadIdx.x < CTR_N) {
     ull v = ctr[threadIdx.x];
     if (threadIdx.x == CTR_N - 1 && extra32) v = (v & ~0xffffffffull) | (ull)*extra32;
@@ -467,17 +493,20 @@ static __global__ void k_publish_counters(const ull *__restrict__ ctr, const u32
 // The wait in two halves: _begin puts the publishing kernel into the stream, _end waits for it.  Kernels launched in
 // between run while the host waits and decides (their results are not in the counters the host sees): a wait that
 // costs the GPU no idle time.  read_counters is the two back to back.
-static int read_counters_begin(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr) {
+// stamp (the pass's last wait only): the device stamps, see humid_ctx::d_stamp
+static int read_counters_begin(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr,
+                               u64 *stamp = nullptr) {
   c->ctr_x[0] = extra32; c->ctr_x[1] = extra32b; c->ctr_x[2] = extra32c;
   if (c->h_ctr_dev && !c->no_poll) {
     const ull seq = ++c->ctr_seq;
     hipLaunchKernelGGL(k_publish_counters, dim3(1), dim3(64), 0, c->stream, (const ull *)c->d_ctr, extra32, extra32b,
-                       (volatile ull *)c->h_ctr_dev, seq, extra32c);
+                       (volatile ull *)c->h_ctr_dev, seq, extra32c, stamp);
     HIPCHK(hipGetLastError());
   }
   return HUMID_OK;
 }
 // work_queued: the caller has launched kernels since _begin (counted for humid_wait_overlap_info)
+#define POLL_QUIET_US 2000   // with overlap_waits: the host asks the stream nothing for its first 2 ms at a wait
 static int read_counters_end(humid_ctx *c, bool work_queued = false) {
   const u32 *extra32 = c->ctr_x[0], *extra32b = c->ctr_x[1], *extra32c = c->ctr_x[2];
   c->wo_waits++;
@@ -487,13 +516,17 @@ static int read_counters_end(humid_ctx *c, bool work_queued = false) {
     volatile ull *flag = (volatile ull *)&c->h_ctr[CTR_N];
     const auto t0 = std::chrono::steady_clock::now();
     u32 spins = 0;
-    // (The query every 4096 looks, 2.5 us, leaves a marker at the end of a busy stream: a kernel queued behind the
-    // publishing kernel is followed by 5.7 us of idle GPU before the next launch starts.  Asking only after 2 ms took
-    // that away but made two plain bench runs of five slower than any of the parent's: profiles/r04d_overlap_waits.md.)
+    // (A query of a busy stream leaves a marker at its end: a kernel queued behind the publishing kernel was followed by
+    // 5.7 us of idle GPU before the next launch started.  With overlap_waits the host watches 95-170 us ahead of the GPU
+    // at two waits of a pass, so the first query comes only after POLL_QUIET_US of watching; from then on one every 4096
+    // looks, 2.5 us, as without the option: profiles/r04e_device_stamps.md.)
+    const auto quiet = std::chrono::microseconds(c->overlap_waits ? POLL_QUIET_US : 0);
     while (*flag != seq) {
       if ((++spins & 0xfffu) == 0) {
+        const auto waited = std::chrono::steady_clock::now() - t0;
+        if (waited < quiet) continue;
         if (hipStreamQuery(c->stream) != hipErrorNotReady) break;              // drained (the stores are done or lost) or failed: settled below
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30)) break;
+        if (waited > std::chrono::seconds(30)) break;
       }
     }
     if (*flag == seq) { std::atomic_thread_fence(std::memory_order_acquire); return HUMID_OK; }
@@ -512,8 +545,9 @@ static int read_counters_end(humid_ctx *c, bool work_queued = false) {
   HIPCHK(hipStreamSynchronize(c->stream));
   return HUMID_OK;
 }
-static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr) {
-  const int rc = read_counters_begin(c, extra32, extra32b, extra32c);
+static int read_counters(humid_ctx *c, const u32 *extra32 = nullptr, const u32 *extra32b = nullptr, const u32 *extra32c = nullptr,
+                         u64 *stamp = nullptr) {
+  const int rc = read_counters_begin(c, extra32, extra32b, extra32c, stamp);
   return rc != HUMID_OK ? rc : read_counters_end(c);
 }
 
@@ -530,7 +564,10 @@ static int scan_total(humid_ctx *c, const u32 *in, u32 *out, u64 n, u64 *total) 
 }
 
 // ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
-static inline void state_reset(humid_ctx *c) { c->state = CtxState{}; c->roads = humid_run_roads{}; c->wo_waits = c->wo_overlapped = 0; }
+static inline void state_reset(humid_ctx *c) {
+  c->state = CtxState{}; c->roads = humid_run_roads{}; c->wo_waits = c->wo_overlapped = 0;
+  c->ev_records = 0; c->last_stamp_timed = c->last_stamp_live = false; memset(c->last_stamps, 0, sizeof c->last_stamps);
+}
 // one retry of the call now running (HUMID_ROAD_*): behind the host wait that showed it, a store on the host
 static inline void road_taken(humid_ctx *c, u8 road) {
   if (c->roads.n_events < HUMID_ROADS_MAX) c->roads.events[c->roads.n_events] = road;
@@ -688,7 +725,7 @@ static GraphArrays legacy_arrays(humid_ctx *c) {
 static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt, u32 U, u64 M, u64 Mbig, u32 method,
                            bool trivial_done = false, const u32 *late_m = nullptr, u64 *late_m_out = nullptr) {
   hipStream_t st = c->stream;
-  if (!trivial_done && c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));
+  if (!trivial_done && c->kev_on) EVREC(c->kev[2], st);
   if (trivial_done) {
   } else if (method == HUMID_METHOD_MAXIMUM)
     hipLaunchKernelGGL(k_cluster_trivial<true>, dim3(blocks_for(U)), dim3(256), 0, st, g.deg, g.parent, g.csize, U, g_cnt, g.off,
@@ -738,7 +775,7 @@ static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt,
       }
     }
   }
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[3], st));
+  if (c->kev_on) EVREC(c->kev[3], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -763,7 +800,7 @@ static int cluster_stage(humid_ctx *c, const u32 *g_cnt, u32 U, u64 M, u64 Mbig,
 
 static int n_clusters_from_scan(humid_ctx *c, u32 U, u64 *out) {
   // (the pass's last host wait: both values through the counters' mapped store)
-  TRY(read_counters(c, c->pos.as<u32>() + (U - 1), c->flag.as<u32>() + (U - 1)));
+  TRY(read_counters(c, c->pos.as<u32>() + (U - 1), c->flag.as<u32>() + (U - 1), nullptr, c->stamp_live ? c->d_stamp : nullptr));
   *out = (c->h_ctr[CTR_N - 1] & 0xffffffffull) + (c->h_ctr[CTR_N - 2] & 0xffffffffull);
   return HUMID_OK;
 }
@@ -788,14 +825,14 @@ static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt
   ENSURE(c->slot_of_read, (size_t)N * 4);
   ENSURE(c->uniq_slot, (size_t)expected_reads * 4 + 4);
   ENSURE(c->uniq_word, (size_t)expected_reads * 8 + 8);
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  EVREC(c->ev[0], st);
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
   HIPCHK(hipMemsetAsync(c->table.p, 0xff, (cap + 1) * sizeof(Slot), st));
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  EVREC(c->kev[0], st);
   hipLaunchKernelGGL(k_hash_insert, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_words, d_filt, N,
                      c->table.as<Slot>(), cap_log2, c->slot_of_read.as<u32>(), range_lo, range_hi,
                      (u32)(cap - cap / 8), c->d_ctr);
-  HIPCHK(hipEventRecord(c->kev[1], st));
+  EVREC(c->kev[1], st);
   hipLaunchKernelGGL(k_compact_table, dim3(COMPACT_BLOCKS), dim3(256), 0, st,
                      c->table.as<Slot>(), (u32)(cap + 1), c->uniq_word.as<u64>(), c->uniq_slot.as<u32>(),
                      (u32)expected_reads, c->d_ctr);
@@ -806,7 +843,7 @@ static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt
   const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
   s.usable = c->usable = c->h_ctr[CTR_USABLE];
   s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st)); return HUMID_OK; }
+  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
   ENSURE(c->s_word, (size_t)U * 8);
   ENSURE(c->s_slot, (size_t)U * 4);
   ENSURE(c->s_cnt, (size_t)U * 4);
@@ -815,7 +852,7 @@ static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt
                            c->s_slot.as<u32>(), U, 0, 2 * word_nt));
   hipLaunchKernelGGL(k_post_sort, dim3(blocks_for(U)), dim3(256), 0, st, c->s_slot.as<u32>(),
                      c->table.as<Slot>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -906,13 +943,13 @@ static int count_partition(humid_ctx *c, const SRC &src, u32 N, u32 pb, bool *us
   if (padded)
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
                        c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+  if (c->kev_on) EVREC(c->kev[39], st);
   if (d2) {
     hipLaunchKernelGGL(k_pt_hist2<SRC>, dim3(tiles2), dim3(1024), 0, st, src, k1, tprefix, cbase, d1, d2, hist_fine, cap1);
     hipLaunchKernelGGL((k_pt_scatter<2, SRC>), dim3(tiles2), dim3(1024), 0, st, src, N, k1, v1, tprefix, cbase, d1, d2,
                        hist_fine, cursor2, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(), c->pbeg.as<u32>(), cap1, &c->d_ctr[CTR_SPECIAL]);
   }
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[40], st));
+  if (c->kev_on) EVREC(c->kev[40], st);
   return HUMID_OK;
 }
 
@@ -948,7 +985,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   ENSURE(c->slot_out, ((size_t)N + 1) * 8);
   ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
   ENSURE(c->uniq_word, (size_t)N * 8 + 8);
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  EVREC(c->ev[0], st);
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
   const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
   c->last_part_tiled = c->use_tile_partition && pb <= 2 * 9;
@@ -968,7 +1005,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
     hipLaunchKernelGGL(k_part_bounds, dim3(blocks_for(n_parts + 1)), dim3(256), 0, st, c->pk_keys.as<u64>(), N,
                        pb, n_parts, c->pbeg.as<u32>(), c->ucount.as<u32>());
   }
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  EVREC(c->kev[0], st);
   if (wide) {
     hipLaunchKernelGGL((k_dedup_lds_wide<9, 512, 0, WL_SMALL_LEN>), dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
                        c->pbeg.as<u32>(), wide, 2 * (word_nt - 32), N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(),
@@ -985,7 +1022,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
     hipLaunchKernelGGL(k_dedup_lds<false>, dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
                        c->pbeg.as<u32>(), N, pb, km.lo, km.scale, km.shift, c->pad_word.as<u64>(), c->pad_cf.as<uint2>(),
                        c->ucount.as<u32>(), c->pusable.as<u32>(), c->pslot.as<u32>(), c->d_ctr);
-  HIPCHK(hipEventRecord(c->kev[1], st));
+  EVREC(c->kev[1], st);
   hipLaunchKernelGGL(k_part_totals, dim3(n_parts >= 16384 ? 64 : 4), dim3(256), 0, st, c->ucount.as<u32>(),
                      c->pusable.as<u32>(), n_parts, c->d_ctr);
   TRY(exscan_u32(c, c->ucount.as<u32>(), c->ubase.as<u32>(), (u64)n_parts + 1));
@@ -1000,7 +1037,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
   s.usable = c->usable = c->h_ctr[CTR_USABLE];
   s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st)); return HUMID_OK; }
+  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
   ENSURE(c->s_word, (size_t)(U + 1) * wsize);
   ENSURE(c->s_slot, (size_t)(U + 1) * 4);
   ENSURE(c->s_cnt, (size_t)(U + 1) * 4);
@@ -1026,7 +1063,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
     hipLaunchKernelGGL(k_post_sort_padded, dim3(blocks_for(U)), dim3(256), 0, st, c->s_slot.as<u32>(),
                        c->pad_cf.as<uint2>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
   }
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -1074,14 +1111,21 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   // stage's grouping uses pt_work in between.)
   ENSURE(c->p8_cur, ((size_t)PT_MAXBINS1 + n_parts + 2 * (PT_MAXBINS1 + 1)) * 4);
   u32 *cursor1 = c->p8_cur.as<u32>(), *cursor2 = cursor1 + PT_MAXBINS1, *cbase = cursor2 + n_parts, *tprefix = cbase + PT_MAXBINS1 + 1;
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  // the pass's four times from device stamps (humid_ctx::d_stamp)
+  const u64 n_agg = (u64)n_parts + 1;
+  const bool stamp = c->stamp_ok;
+  u64 *const sp = stamp ? c->d_stamp : nullptr;
+  c->stamp_live = stamp;
+  c->stamp_timed = stamp && c->lean_events;
+  const bool events = !c->stamp_timed;                        // ev[0], kev[0], kev[1] here and ev[4] in stage_map
+  if (events) EVREC(c->ev[0], st);
   {
     ZeroList z;
     memset(&z, 0, sizeof z);
     z.p[0] = cursor1; z.n[0] = PT_MAXBINS1 + n_parts;
     z.p[1] = (u32 *)c->d_ctr; z.n[1] = 2 * CTR_N;
     z.p[2] = (u32 *)(agg + n_parts); z.n[2] = 2;
-    hipLaunchKernelGGL(k_zero_many, dim3(32), dim3(256), 0, st, z);
+    hipLaunchKernelGGL(k_zero_many, dim3(32), dim3(256), 0, st, z, sp ? sp + STAMP_START : (u64 *)nullptr);
   }
   const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
   const Reads8 src{d_words, d_filt, range_lo, range_hi, check_range ? 1u : 0u, rk};
@@ -1097,22 +1141,22 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   // pbeg[n_parts] / ucount[n_parts], which no kernel of the record road reads: its un-permute, k_unperm_bins8, takes
   // the buckets' fills from cursor2).  One workgroup per tile of every bin's ROOM: those beyond the fill leave at once.
   if (c->static_tiles) {
-    if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+    if (c->kev_on) EVREC(c->kev[39], st);
     hipLaunchKernelGGL(k_p8_scatter2<true>, dim3(nb1 * ((cap1 + PT_TILE - 1) / PT_TILE)), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(),
                        (const u32 *)cursor1, (const u32 *)nullptr, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
   } else {
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
                        c->ucount.as<u32>() + n_parts, cap1);
-    if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+    if (c->kev_on) EVREC(c->kev[39], st);
     hipLaunchKernelGGL(k_p8_scatter2<false>, dim3(tiles2), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(), (const u32 *)tprefix,
                        (const u32 *)cbase, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
   }
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[40], st));
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  if (c->kev_on) EVREC(c->kev[40], st);
+  if (events) EVREC(c->kev[0], st);
   hipLaunchKernelGGL(k_dedup_rec, dim3(n_parts), dim3(256), 0, st, c->p8_b.as<u64>(), (const u32 *)cursor2, N, pb, d1, ibits, rk,
-                     c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), agg, c->d_ctr);
-  HIPCHK(hipEventRecord(c->kev[1], st));
-  TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, (u64)n_parts + 1));
+                     c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), agg, c->d_ctr, sp ? sp + STAMP_K0 : (u64 *)nullptr);
+  if (events) EVREC(c->kev[1], st);
+  TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, n_agg, sp ? sp + STAMP_K1 : (u64 *)nullptr));
   // the walk-order arrays are squeezed out of the padded ones BEFORE the host knows how many unique words there are
   // (at most N: a bucket never reports more words than records it holds).  Everything the host's wait reads -- U and
   // the usable reads (the scan's totals), CTR_SPECIAL, CTR_OVERFULL -- is final behind the scan, so with overlap_waits
@@ -1128,13 +1172,15 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   hipLaunchKernelGGL(k_compact_padded8, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, c->pad_word.as<u64>(),
                      c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<u64>(),
                      c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   if (early) TRY(read_counters_end(c, true));
   else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
   if (getenv("HUMID_TRACE_COUNT"))
     fprintf(stderr, "[rec count] N %u pb %u kbits %u ibits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits,
             ibits, cap1, (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
+  // a count that is discarded: the road that takes it again records the events, and the pass's four times are theirs
+  if (c->h_ctr[CTR_SPECIAL] || c->h_ctr[CTR_OVERFULL]) c->stamp_ok = c->stamp_live = c->stamp_timed = false;
   if (c->h_ctr[CTR_SPECIAL]) { c->pt_padded = false; road_taken(c, HUMID_ROAD_PART_PADDED_REDO); return HUMID_OK; }     // a bin outgrew its room: the exact kernels from now on
   if (c->h_ctr[CTR_OVERFULL]) return HUMID_OK;
   c->last_count_lds = true;
@@ -1187,7 +1233,7 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
   u64 *agg = c->p8_status.as<u64>(), *abase = agg + n_parts + 1;
   ENSURE(c->p8_cur, ((size_t)512 + n_parts + 1026) * 4);
   u32 *cursor1 = c->p8_cur.as<u32>(), *cursor2 = cursor1 + 512, *cbase = cursor2 + n_parts, *tprefix = cbase + 513;
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  EVREC(c->ev[0], st);
   {
     ZeroList z;
     memset(&z, 0, sizeof z);
@@ -1201,12 +1247,12 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
                      (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, cap1, cursor1, c->pw_a.as<W2>(), c->pw_ai.as<u32>(), c->d_ctr);
   hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
                      c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[39], st));
+  if (c->kev_on) EVREC(c->kev[39], st);
   hipLaunchKernelGGL(k_pw_scatter<2>, dim3(tiles2), dim3(1024), 0, st, (const W2 *)c->pw_a.as<W2>(), (const u8 *)nullptr,
                      (const u32 *)c->pw_ai.as<u32>(), N, hbits, rk, (const u32 *)tprefix, (const u32 *)cbase, d1, d2, cap1, cursor2,
                      c->pw_b.as<W2>(), c->pw_bi.as<u32>(), c->d_ctr);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[40], st));
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  if (c->kev_on) EVREC(c->kev[40], st);
+  EVREC(c->kev[0], st);
   hipLaunchKernelGGL((k_dedup_wide_rec<9, 512, 0, WL_SMALL_LEN>), dim3(n_parts), dim3(256), 0, st, (const W2 *)c->pw_b.as<W2>(),
                      (const u32 *)c->pw_bi.as<u32>(), (const u32 *)cursor2, hbits, rk, N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(),
                      agg, c->p8_b.as<u64>(), c->d_ctr);
@@ -1214,7 +1260,7 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
     hipLaunchKernelGGL((k_dedup_wide_rec<10, 1024, WL_SMALL_LEN, WL_STAGE>), dim3(n_parts), dim3(256), 0, st,
                        (const W2 *)c->pw_b.as<W2>(), (const u32 *)c->pw_bi.as<u32>(), (const u32 *)cursor2, hbits, rk, N, pb,
                        c->pad_word.as<W2>(), c->pad_cf.as<uint2>(), agg, c->p8_b.as<u64>(), c->d_ctr);
-  HIPCHK(hipEventRecord(c->kev[1], st));
+  EVREC(c->kev[1], st);
   TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, (u64)n_parts + 1));
   // (as in stage_count_rec: at most N unique words; overlap_waits publishes the counters in front of the squeeze)
   ENSURE(c->s_word, (size_t)(N + 1) * 16);
@@ -1226,7 +1272,7 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
   hipLaunchKernelGGL(k_compact_padded8_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, (const W2 *)c->pad_word.as<W2>(),
                      (const uint2 *)c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<W2>(),
                      c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   if (early) TRY(read_counters_end(c, true));
   else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
@@ -1375,9 +1421,9 @@ static int stage_count_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u
   ENSURE(c->w_sorted, (size_t)N * sizeof(W2));
   ENSURE(c->w_head, ((size_t)N + 1) * 4);
   ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  EVREC(c->ev[0], st);
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  EVREC(c->kev[0], st);
   u64 *k0 = c->pk_keys.as<u64>(), *k1 = c->pad_word.as<u64>();
   u32 *va = c->uniq_slot.as<u32>(), *vb = c->pk_vals.as<u32>();
   hipLaunchKernelGGL(k_wide_keys_lo, dim3(grid), dim3(256), 0, st, d_words, d_filt, N, k0, va, c->d_ctr);
@@ -1390,7 +1436,7 @@ static int stage_count_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u
     TRY(sort_pairs<u32, u32>(c, (u32 *)k0, (u32 *)k1, va, vb, N, 0, 1));
     v = vb;
   }
-  HIPCHK(hipEventRecord(c->kev[1], st));
+  EVREC(c->kev[1], st);
   hipLaunchKernelGGL(k_wide_gather, dim3(grid), dim3(256), 0, st, d_words, v, N, hbits, c->w_sorted.as<W2>());
   hipLaunchKernelGGL(k_wide_heads, dim3(grid), dim3(256), 0, st, c->w_sorted.as<W2>(), N, c->d_ctr,
                      c->w_head.as<u32>());
@@ -1411,7 +1457,7 @@ static int stage_count_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u
   if (U)
     hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U,
                        c->s_cnt.as<u32>(), c->s_slot.as<u32>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -1520,9 +1566,9 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
       const FieldsRecs rsrc{W, sq, wb - d1};
       hipLaunchKernelGGL((k_p8_scatter1<FieldsRecs, 1024, CTR_GOVER>), dim3(tiles1), dim3(1024), 0, st, rsrc, n, wb, d1, ibits, cap1, cursor1,
                          c->seg_k0.as<u64>(), c->d_ctr);
-      if (ride->ev_group[0]) HIPCHK(hipEventRecord(ride->ev_group[0], st));
+      if (ride->ev_group[0]) EVREC(ride->ev_group[0], st);
       group_fine_recs_with_search(c, src, sq, c->seg_k0.as<u64>(), cursor1, d1, d2, ibits, cap1, ride->group);
-      if (ride->ev_group[1]) HIPCHK(hipEventRecord(ride->ev_group[1], st));
+      if (ride->ev_group[1]) EVREC(ride->ev_group[1], st);
       ride->did_group = ride->no_order = true;
       HIPCHK(hipGetLastError());
       return HUMID_OK;
@@ -1556,9 +1602,9 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
   const u32 largest = padded ? cap1 : n;
   if (ride_ok) {
     if constexpr (std::is_same<SRC, FieldsSrc>::value) {
-      if (ride->ev_group[0]) HIPCHK(hipEventRecord(ride->ev_group[0], st));
+      if (ride->ev_group[0]) EVREC(ride->ev_group[0], st);
       group_fine_with_search(c, src, c->seg_k0.as<u64>(), c->seg_v0.as<u32>(), cbase, d1, d2, ws, vs, cap1, ride->group);
-      if (ride->ev_group[1]) HIPCHK(hipEventRecord(ride->ev_group[1], st));
+      if (ride->ev_group[1]) EVREC(ride->ev_group[1], st);
       ride->did_group = true;
     }
   } else
@@ -1850,10 +1896,10 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     for (u32 seg = 0; seg < plan.ncombo; seg++) {
       if (seg && mode == PM_COUNT) TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U)));
       const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[ev0 + 2 * seg], st));
+      if (seg < 8 && c->kev_on) EVREC(c->kev[ev0 + 2 * seg], st);
       pairs_csr<WT>(c, ps, w, mode, 0u, U, sink(seg), &c->d_ctr[CTR_BIGMASK]);
       if (mode == PM_FILL && (big_mask >> seg & 1)) tiles_csr<WT>(c, ps, w, d_runs[seg], h_runs[seg], PM_FILL, sink(seg));
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[ev0 + 1 + 2 * seg], st));
+      if (seg < 8 && c->kev_on) EVREC(c->kev[ev0 + 1 + 2 * seg], st);
     }
     HIPCHK(hipGetLastError());
     return HUMID_OK;
@@ -1911,7 +1957,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(U)), dim3(256), 0, st, c->nbr_off.as<u32>(), U,
                        c->nbr_idx.as<u32>());
   }
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[2], st));
+  if (!c->lean_events) EVREC(c->ev[2], st);
 
   // clusters
   TRY(cluster_stage(c, g_cnt, U, M, Mbig, method));
@@ -2027,7 +2073,7 @@ static int cg_build_back(humid_ctx *c, CgSource &src, u32 method, CgStatus &out)
                        c->cg_curs.as<u32>(), g.idx, src.no_wait ? (u32 *)nullptr : c->small.as<u32>(), gx, (const u32 *)g.deg, g.parent, Mb, g.csize, m_dev, r_first);
   }
   hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(Mb)), dim3(256), 0, st, (const u32 *)g.off, Mb, g.idx);
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));
+  if (c->kev_on) EVREC(c->kev[2], st);
   const u32 tg = (u32)std::min<u64>(std::max<u64>(blocks_for(Mb), 1), 512);
   if (method == HUMID_METHOD_MAXIMUM)
     hipLaunchKernelGGL(k_cg_trivial<true>, dim3(tg), dim3(256), 0, st, (const u32 *)g.parent, (const u32 *)g.csize, m_dev,
@@ -2065,7 +2111,7 @@ static int cg_cluster_rest(humid_ctx *c, u32 n_ids, u64 M, u64 Mbig, u32 method,
   const GraphArrays g = cg_arrays(c);
   ENSURE(c->cg_nblk, ((size_t)n_blk + 1) * 4);
   if (M > 0) TRY(cluster_kernels(c, g, c->cg_ncnt.as<u32>(), (u32)M, M, Mbig, method, true, fetch ? late_m : (const u32 *)nullptr, late_m_out));
-  else if (c->kev_on) HIPCHK(hipEventRecord(c->kev[3], st));
+  else if (c->kev_on) EVREC(c->kev[3], st);
   if (M > 0)
     hipLaunchKernelGGL(k_noncreator_bits, dim3(blocks_for(M)), dim3(256), 0, st, (const u32 *)g.cl_of, c->cg_nodes.as<u32>(), (u32)M,
                        c->cg_nbits.as<u32>(), late_m);
@@ -2164,10 +2210,10 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     // a launch of k_pairs_append over the order of combination seg, between its two events
     auto search_alone = [&](u32 seg) -> int {
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[20 + 2 * seg], st));
+      if (seg < 8 && c->kev_on) EVREC(c->kev[20 + 2 * seg], st);
       pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK],
                        (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
-      if (seg < 8 && c->kev_on) HIPCHK(hipEventRecord(c->kev[21 + 2 * seg], st));
+      if (seg < 8 && c->kev_on) EVREC(c->kev[21 + 2 * seg], st);
       return HUMID_OK;
     };
     // fused_search: while an order is MADE its search rides in the grouping (GroupRide; the events then bracket the
@@ -2344,10 +2390,10 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       c->cg_m_late = !fetch;
       M = std::min<u64>(U, 2 * R);                       // (a bound)
       Mbig = 0;
-    } else if (c->kev_on) HIPCHK(hipEventRecord(c->kev[2], st));   // (no rest pair, no cg_build: the cluster kernels' first event is its)
+    } else if (c->kev_on) EVREC(c->kev[2], st);   // (no rest pair, no cg_build: the cluster kernels' first event is its)
   }
   s.edges = c->E = E;
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[2], st));
+  if (!c->lean_events) EVREC(c->ev[2], st);
   u64 M_rest = 0;
   TRY(cg_cluster_rest(c, U, M, Mbig, method, late_m, fetch, &M_rest));
   if (split) M = 2 * n_iso + (fetch ? M_rest : 0);       // (cg_m_late: n_clusters_compact adds the rest graph's nodes)
@@ -2373,7 +2419,8 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
 
 // clusters = unique words - graph nodes that created no cluster (the pass's last host wait)
 static int n_clusters_compact(humid_ctx *c, u32 U, u64 *out) {
-  TRY(read_counters(c, c->cg_nblk.as<u32>() + c->cg_nblocks, c->cg_m_late ? c->cg_blk.as<u32>() + c->cg_nblocks : (const u32 *)nullptr));
+  TRY(read_counters(c, c->cg_nblk.as<u32>() + c->cg_nblocks, c->cg_m_late ? c->cg_blk.as<u32>() + c->cg_nblocks : (const u32 *)nullptr,
+                    nullptr, c->stamp_live ? c->d_stamp : nullptr));
   *out = (u64)U - (c->h_ctr[CTR_N - 1] & 0xffffffffull);
   if (c->cg_m_late) { c->M += c->h_ctr[CTR_N - 2] & 0xffffffffull; c->cg_m_late = false; }   // (the rest graph's nodes)
   return HUMID_OK;
@@ -2749,7 +2796,7 @@ static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_k
   else
   hipLaunchKernelGGL(k_unperm_bins, dim3((N + PT_TILE - 1) / PT_TILE), dim3(1024), 0, st, c->pk_vals.as<u32>(),
                      c->pslot.as<u32>(), c->slot_out.as<u64>(), n_pos_dev, N, N, wshift, n_bins, ucur, rec);
-  if (!c->lean_events) HIPCHK(hipEventRecord(ev_mid, st));
+  if (!c->lean_events) EVREC(ev_mid, st);
   if (packed) {
     if (wshift == 14) hipLaunchKernelGGL((k_unperm_window<true, 14>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
     else hipLaunchKernelGGL((k_unperm_window<true, 15>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
@@ -2757,7 +2804,7 @@ static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_k
     if (wshift == 14) hipLaunchKernelGGL((k_unperm_window<false, 14>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
     else hipLaunchKernelGGL((k_unperm_window<false, 15>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
   }
-  if (c->kev_on) HIPCHK(hipEventRecord(c->kev[41], st));
+  if (c->kev_on) EVREC(c->kev[41], st);
   HIPCHK(hipGetLastError());
   c->ucur_clean = ucur;
   *done = true;
@@ -2775,7 +2822,7 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
   if (U > 0 && !fused)
     hipLaunchKernelGGL(k_slot_results, dim3(blocks_for(U)), dim3(256), 0, st, l_cid, l_ismax,
                        c->s_first.as<u32>(), c->s_slot.as<u32>(), U, c->slot_out.as<u64>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[3], st));
+  if (!c->lean_events) EVREC(c->ev[3], st);
   if (c->last_count_lds) {
     bool tiled = false;
     TRY(unpermute_tiled(c, N, false, d_cid, d_keep, c->kev[36], &tiled));
@@ -2792,13 +2839,13 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
       else
         hipLaunchKernelGGL(k_read_map_part, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->pk_vals.as<u32>(),
                            c->pslot.as<u32>(), c->slot_out.as<u64>(), N, packed);
-      if (c->kev_on) HIPCHK(hipEventRecord(c->kev[36], st));
+      if (c->kev_on) EVREC(c->kev[36], st);
       hipLaunchKernelGGL(k_split_out, dim3(grid_stride_blocks(N)), dim3(256), 0, st, packed, N, d_cid, d_keep);
     }
   } else
     hipLaunchKernelGGL(k_read_map, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->slot_of_read.as<u32>(),
                        c->slot_out.as<u64>(), N, d_cid, d_keep);
-  HIPCHK(hipEventRecord(c->ev[4], st));
+  if (!c->stamp_timed) EVREC(c->ev[4], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -2865,9 +2912,15 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   c->gU = 0;
   if (N == 0) { if (sum) *sum = s; return state_publish(c, CtxState::RUN); }
   // the stages' own events only with the per-kernel timing (ms_count .. ms_map are 0 without it; ms_total and the
-  // count kernel's time are always measured)
-  struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = false; } } lean_guard{c};
+  // count kernel's time are always measured: by device stamps where the pass takes the record road, by events elsewhere)
+  struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = c->stamp_ok = c->stamp_live = c->stamp_timed = false; } } lean_guard{c};
   c->lean_events = !c->kev_on && getenv("HUMID_ALL_EVENTS") == nullptr;
+  // decided once, before the first launch: a plain run of one-word words whose counters reach the host through the
+  // mapped mirror may take its four times from device stamps.  stage_count_rec takes the offer up (no other count road
+  // does) and withdraws it when its count is discarded; the graph stage and the pass's end are the same on every road.
+  c->stamp_live = c->stamp_timed = false;
+  c->stamp_ok = !WIDE && c->device_stamps && c->d_stamp && c->pass_kind == RUN_PLAIN && !c->pd_run && !(c->edit && distance >= 2) &&
+                c->h_ctr_dev && !c->no_poll;
   if constexpr (WIDE) TRY(stage_count_wide(c, d_words, d_filt, N, word_nt, s));
   else TRY(stage_count(c, d_words, d_filt, N, word_nt, 0ull, ~0ull, 0, s));
   TRY(gkey_check(c));                                        // (the count stage's host wait has seen k_gkey_words)
@@ -2914,7 +2967,17 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   const u64 E = c->E, M = c->M;
   // (the last host wait watches a mapped flag, not the stream: the runtime may not have seen the last
   // event's signal yet -- "device not ready" from hipEventElapsedTime once in ~10^3 runs)
-  HIPCHK(hipEventSynchronize(c->ev[4]));
+  const bool timed = c->stamp_timed;
+  // the last host wait delivered the stamps with the counters.  (Not so in the one pass of a context whose first wait
+  // finds the mapped stores invisible, no_poll: no publishing kernel ran at its end.  That pass reports no times; the
+  // passes behind it record their events.)
+  const bool delivered = c->stamp_live && !c->no_poll;
+  if (delivered) {
+    for (u32 k = 0; k < STAMP_N; k++) c->last_stamps[k] = c->h_ctr[STAMP_AT + k];
+    c->last_stamp_live = true;
+    c->last_stamp_timed = timed;
+  }
+  if (!timed) HIPCHK(hipEventSynchronize(c->ev[4]));
   const bool lean = c->lean_events;
   c->lean_events = false;
   if (!lean) {                                               // the stages' shares: option kernel_timing
@@ -2923,9 +2986,12 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     HIPCHK(hipEventElapsedTime(&s.ms_cluster, c->ev[2], c->ev[3]));
     HIPCHK(hipEventElapsedTime(&s.ms_map, c->ev[3], c->ev[4]));
   }
-  HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
+  if (timed && delivered) {                                  // ticks of 10 ns
+    s.ms_total = (float)((double)(c->last_stamps[STAMP_END] - c->last_stamps[STAMP_START]) / 1e5);
+    s.ms_k_insert = (float)((double)(c->last_stamps[STAMP_K1] - c->last_stamps[STAMP_K0]) / 1e5);
+  } else if (!timed) HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
   TRY(gkey_check(c));
-  HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));
+  if (!timed) HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));
   if (!c->kev_on) s.ms_k_map = s.ms_map;
   else if (c->last_count_lds) HIPCHK(hipEventElapsedTime(&s.ms_k_map, c->ev[3], c->kev[36]));   // first map kernel alone
   else s.ms_k_map = s.ms_map;   // ev[3]..ev[4] bracket exactly the k_read_map launch
@@ -2966,9 +3032,9 @@ static int stage_count_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, 
   ENSURE(c->w_sorted, (size_t)N * k * 8);
   ENSURE(c->w_head, ((size_t)N + 1) * 4);
   ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
-  HIPCHK(hipEventRecord(c->ev[0], st));
+  EVREC(c->ev[0], st);
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  HIPCHK(hipEventRecord(c->kev[0], st));
+  EVREC(c->kev[0], st);
   u64 *k0 = c->pk_keys.as<u64>(), *k1 = c->pad_word.as<u64>();
   u32 *v = c->uniq_slot.as<u32>(), *v_other = c->pk_vals.as<u32>();   // v: the order so far
   for (u32 pass = 0; pass < k; pass++) {                               // least significant uint64 first
@@ -2983,7 +3049,7 @@ static int stage_count_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, 
     TRY(sort_pairs<u32, u32>(c, (u32 *)k0, (u32 *)k1, v, v_other, N, 0, 1));
     std::swap(v, v_other);
   }
-  HIPCHK(hipEventRecord(c->kev[1], st));
+  EVREC(c->kev[1], st);
   u64 *sw = c->w_sorted.as<u64>();
   hipLaunchKernelGGL(k_long_gather, dim3(grid_stride_blocks((u64)N * k)), dim3(256), 0, st, d_words, (const u32 *)v, N, k, hbits, sw);
   hipLaunchKernelGGL(k_long_heads, dim3(grid), dim3(256), 0, st, (const u64 *)sw, N, k, c->d_ctr, c->w_head.as<u32>());
@@ -3004,7 +3070,7 @@ static int stage_count_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, 
   if (U)
     hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U, c->s_cnt.as<u32>(),
                        c->s_slot.as<u32>());
-  if (!c->lean_events) HIPCHK(hipEventRecord(c->ev[1], st));
+  if (!c->lean_events) EVREC(c->ev[1], st);
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }

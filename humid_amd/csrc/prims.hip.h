@@ -70,8 +70,9 @@ __device__ __forceinline__ T ps_block_exscan(T x, T *lds, T *total) {
 template <class T, class In>
 __global__ void __launch_bounds__(PS_SMALL_THREADS)
 // (out may be the array `in` reads: a chunk is staged before it is written)
-k_ps_scan_small(In in, u32 n, T *out) {
+k_ps_scan_small(In in, u32 n, T *out, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   // (one pad per PS_SMALL_ITEMS entries: thread t's items start at entry 9 t, so the lanes of a wave spread
   // over the banks when each reads ITS items -- unpadded, a stride of 8 entries put every fourth lane on one bank)
   __shared__ T stage[PS_SMALL_THREADS * (PS_SMALL_ITEMS + 1)];
@@ -107,8 +108,9 @@ k_ps_scan_small(In in, u32 n, T *out) {
 // tile sums
 template <class T, class In>
 __global__ void __launch_bounds__(PS_THREADS)
-k_ps_reduce(In in, u64 n, T *__restrict__ tile_sum) {
+k_ps_reduce(In in, u64 n, T *__restrict__ tile_sum, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   __shared__ T lds[PS_THREADS / 64 + 1];
   const u64 base = (u64)blockIdx.x * PS_TILE;
   T s = 0;
@@ -185,8 +187,9 @@ k_ps_down(In in, u64 n, const T *__restrict__ tile_base, T *out) {
 template <class T, class In>
 __global__ void __launch_bounds__(PS_SMALL_THREADS)
 // (out may be the array `in` reads: a thread reads its items before it writes them)
-k_ps_scan_tiny(In in, u32 n, T *out) {
+k_ps_scan_tiny(In in, u32 n, T *out, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   __shared__ T lds[PS_SMALL_THREADS / 64 + 1];
   const u32 per = (n + PS_SMALL_THREADS - 1) / PS_SMALL_THREADS;
   const u32 lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
@@ -219,8 +222,9 @@ struct PsChain {
 template <class T, class In, u32 ITEMS>
 __global__ void __launch_bounds__(PS_SMALL_THREADS)
 // (out may be the array `in` reads: a workgroup reads its tile before it writes it, tiles are disjoint)
-k_ps_scan_chain(In in, u32 n, T *out, PsChain *ch, u32 epoch) {
+k_ps_scan_chain(In in, u32 n, T *out, PsChain *ch, u32 epoch, u64 *stamp = nullptr) {
   HUMID_GUARD_LAST_VGPR();
+  device_stamp(stamp);
   __shared__ T stage[ITEMS > 1 ? PS_SMALL_THREADS * (ITEMS + 1) : 1];
   __shared__ T lds[PS_SMALL_THREADS / 64 + 1];
   __shared__ T s_before;
@@ -281,8 +285,10 @@ static inline size_t ps_scan_scratch_items(u64 n) { return n <= PS_SMALL_MAX ? 0
 // out[i] = sum of in(j), j < i, for i < n.  scratch: ps_scan_scratch_items(n) entries of T.
 // chain + epoch (optional): a zero-initialised PsChain in device memory and a counter that is different for
 // every launch on it (never 0); then up to PS_CHAIN_MAX items are scanned by k_ps_scan_chain in one launch.
+// stamp (optional): a device stamp at the entry of the scan's first launch (common.hip.h).
 template <class T, class In>
-static inline hipError_t ps_exscan(In in, T *out, u64 n, T *scratch, hipStream_t st, PsChain *chain = nullptr, u32 *epoch = nullptr) {
+static inline hipError_t ps_exscan(In in, T *out, u64 n, T *scratch, hipStream_t st, PsChain *chain = nullptr, u32 *epoch = nullptr,
+                                   u64 *stamp = nullptr) {
   if (n == 0) return hipSuccess;
   if (chain && n > 2048 && n <= (sizeof(T) == 4 ? PS_CHAIN_MAX32 : PS_CHAIN_MAX)) {
     if (++*epoch == 0) {   // the 32-bit epoch wrapped: a flag some launch left 2^32 - 1 launches ago would pass for the next one's
@@ -292,27 +298,27 @@ static inline hipError_t ps_exscan(In in, T *out, u64 n, T *scratch, hipStream_t
     }
     const u32 per = (u32)((n + PS_CHAIN_WGS * PS_SMALL_THREADS - 1) / (PS_CHAIN_WGS * PS_SMALL_THREADS));   // items per thread at 64 workgroups
     if (per <= 1)
-      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 1>), dim3((u32)((n + 1023) / 1024)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch);
+      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 1>), dim3((u32)((n + 1023) / 1024)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch, stamp);
     else if (per <= 2)
-      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 2>), dim3((u32)((n + 2047) / 2048)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch);
+      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 2>), dim3((u32)((n + 2047) / 2048)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch, stamp);
     else if (per <= 4)
-      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 4>), dim3((u32)((n + 4095) / 4096)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch);
+      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 4>), dim3((u32)((n + 4095) / 4096)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch, stamp);
     else if (per <= 8)
-      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 8>), dim3((u32)((n + 8191) / 8192)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch);
+      hipLaunchKernelGGL((k_ps_scan_chain<T, In, 8>), dim3((u32)((n + 8191) / 8192)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch, stamp);
     else
-      hipLaunchKernelGGL((k_ps_scan_chain<T, In, (sizeof(T) == 4 ? 16 : 8)>), dim3((u32)((n + 16383) / 16384)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch);
+      hipLaunchKernelGGL((k_ps_scan_chain<T, In, (sizeof(T) == 4 ? 16 : 8)>), dim3((u32)((n + 16383) / 16384)), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, chain, *epoch, stamp);
     return hipGetLastError();
   }
   if (n <= PS_TINY_MAX) {
-    hipLaunchKernelGGL((k_ps_scan_tiny<T, In>), dim3(1), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out);
+    hipLaunchKernelGGL((k_ps_scan_tiny<T, In>), dim3(1), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, stamp);
     return hipGetLastError();
   }
   if (n <= PS_SMALL_MAX) {
-    hipLaunchKernelGGL((k_ps_scan_small<T, In>), dim3(1), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out);
+    hipLaunchKernelGGL((k_ps_scan_small<T, In>), dim3(1), dim3(PS_SMALL_THREADS), 0, st, in, (u32)n, out, stamp);
     return hipGetLastError();
   }
   const u32 n_tiles = (u32)((n + PS_TILE - 1) / PS_TILE);
-  hipLaunchKernelGGL((k_ps_reduce<T, In>), dim3(n_tiles), dim3(PS_THREADS), 0, st, in, n, scratch);
+  hipLaunchKernelGGL((k_ps_reduce<T, In>), dim3(n_tiles), dim3(PS_THREADS), 0, st, in, n, scratch, stamp);
   hipLaunchKernelGGL((k_ps_top<T>), dim3(1), dim3(PS_SMALL_THREADS), 0, st, scratch, n_tiles);
   hipLaunchKernelGGL((k_ps_down<T, In>), dim3(n_tiles), dim3(PS_THREADS), 0, st, in, n, (const T *)scratch, out);
   return hipGetLastError();

@@ -60,15 +60,18 @@ typedef struct humid_summary {
   uint64_t edges;       /* undirected neighbour pairs                             */
   uint64_t nonsingle;   /* unique words with >= 1 neighbour                       */
   /* the four stage times: filled by humid_dedup_run* only with option "kernel_timing" (0 otherwise; round 3: an
-   * event record between two kernels costs ~4 us of idle GPU); ms_total and ms_k_insert are always measured       */
+   * event record between two kernels costs ~4-6 us of idle GPU); ms_total and ms_k_insert are always measured: on
+   * the record road of a lean pass by device stamps (option "device_stamps": the 100 MHz wall clock read at the
+   * entry of four kernels that run anyway, no marker in the stream), by four event records elsewhere              */
   float ms_count;       /* hash insert + unique sort     (Trie::add, walk order)  */
   float ms_neighbours;  /* bucket passes + CSR           (findHammingNeighbours)  */
   float ms_cluster;     /* components + cluster kernel   (findClusters)           */
   float ms_map;         /* per-read map                  (writeFiltered/Annotated)*/
-  float ms_total;       /* first kernel to last kernel on the stream              */
+  float ms_total;       /* first kernel to last kernel on the stream (device stamps: entry of the first to entry of the last) */
   float ms_h2d, ms_d2h; /* host-buffer entry point only                           */
   /* single kernels, HIP events directly around the launches on the ctx stream:      */
-  float ms_k_insert;    /* the count kernel: k_dedup_rec / k_dedup_lds / k_hash_insert (one launch) */
+  float ms_k_insert;    /* the count kernel: k_dedup_rec / k_dedup_lds / k_hash_insert (one launch); device stamps: its
+                         * entry to the entry of the launch behind it, so with the dispatch between the two */
   float ms_k_pairs;     /* sum over the 2(d+1) k_pairs launches (count + fill)      */
   float ms_k_cluster;   /* k_cluster_pairs + _small (+ _components): 2-3 launches   */
   float ms_k_map;       /* first kernel of the un-permute: k_unperm_bins (or k_read_map_bucket, _part, k_read_map) */
@@ -114,6 +117,12 @@ const char *humid_last_error(const humid_ctx *ctx);   /* ctx may be NULL */
  * humid_summary.ms_k_pairs / ms_k_cluster / ms_k_map / ms_k_part / ms_k_unperm and the stage times ms_count ..
  * ms_map of humid_dedup_run* are filled (default 0, also HUMID_KERNEL_TIMING: the 17 extra event records cost
  * 30-50 us of a 0.7 ms pass; ms_k_insert and ms_total are always there).
+ * "device_stamps": 1 (default) = a pass without "kernel_timing" that counts on 8-byte records (one-word words,
+ * humid_dedup_run / _device) takes ms_total and ms_k_insert from four device stamps -- thread 0 of workgroup 0 of
+ * the first k_zero_many, of k_dedup_rec, of the scan behind it and of the pass's last k_publish_counters stores the
+ * 100 MHz wall clock, and the last host wait delivers the four with the counters -- and records no event; 0 = the
+ * four event records ev[0], kev[0], kev[1], ev[4] on every road (each a marker the next kernel waits ~6 us behind).
+ * Every other road and every pass with "kernel_timing" records its events with either value.  humid_stamp_info.
  * "padded_partition": 1 (default) = the first level of the tile partition scatters into coarse bins of a
  * fixed room and needs no histogram pass over the reads; a bin that outgrows its room (heavily duplicated
  * words) is detected, the run repeated with the histogram pass, and the option stays 0 for this context.
@@ -1291,6 +1300,13 @@ int humid_group_records_info(humid_ctx *ctx, uint32_t *searched_on_records, uint
  * either value.  Host stores only: no device work, no result depends on it.  Any pointer may be NULL.  HUMID_E_STATE
  * before the first successful mutating call and after a failed one. */
 int humid_wait_overlap_info(humid_ctx *ctx, uint32_t *host_waits, uint32_t *overlapped);
+/* How the last mutating call was timed.  stamps_used: 1 = its ms_total and ms_k_insert are differences of device
+ * stamps and the call recorded none of the four events (option "device_stamps").  stamps[4]: the raw stamps, ticks of
+ * 10 ns -- pass start, count kernel start, count kernel end, pass end; also filled (beside the summary's event times)
+ * for a pass on the record road with "kernel_timing" = 1, whose kernels store them all the same; zeros where the pass
+ * stored none.  event_records: the hipEventRecord calls the call made, counted on the host.  Any pointer may be NULL.
+ * HUMID_E_STATE before the first successful mutating call and after a failed one. */
+int humid_stamp_info(humid_ctx *ctx, uint32_t *stamps_used, uint64_t stamps[4], uint32_t *event_records);
 /* Which attempts the last mutating call (a run, humid_accum_add / _finish / _map, a humid_stage_* call that counts or
  * builds a graph) threw away and took again, in the order they happened.  A record the host keeps while it decides:
  * it costs the GPU nothing and changes no result.  One event per occurrence:
