@@ -1056,15 +1056,15 @@ int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, cons
   ENSURE(c->own_packed, ((size_t)N + 1) * 4);
   if (c->kev_on) EVREC(c->kev[37], st);
   bool tiled = false;
-  if (c->last_count_lds) TRY(unpermute_tiled(c, N, true, c->own_packed.as<u32>(), (u8 *)nullptr, c->kev[42], &tiled));
+  if (count_in_partition_order(c)) TRY(unpermute_tiled(c, N, true, c->own_packed.as<u32>(), (u8 *)nullptr, c->kev[42], &tiled));
   if (tiled) {
     // both kernels of the un-permute are inside kev[37]..kev[38]
-  } else if (c->last_count_lds && c->n_parts && !c->last_count_sorted) {
+  } else if (count_bucketed(c)) {
     HIPCHK(hipMemsetAsync(c->own_packed.p, 0, (size_t)N * 4, st));
-    hipLaunchKernelGGL(k_read_map_bucket, dim3(c->n_parts), dim3(256), 0, st, c->pk_vals.as<u32>(),
+    hipLaunchKernelGGL(k_read_map_bucket, dim3(c->count_left.n_parts), dim3(256), 0, st, c->pk_vals.as<u32>(),
                        c->pslot.as<u32>(), c->slot_out.as<u64>(), c->pbeg.as<u32>(), c->ucount.as<u32>(), N,
                        c->own_packed.as<u32>());
-  } else if (c->last_count_lds) {
+  } else if (count_in_partition_order(c)) {
     HIPCHK(hipMemsetAsync(c->own_packed.p, 0, (size_t)N * 4, st));
     hipLaunchKernelGGL(k_read_map_part, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->pk_vals.as<u32>(),
                        c->pslot.as<u32>(), c->slot_out.as<u64>(), N, c->own_packed.as<u32>());
@@ -1671,7 +1671,7 @@ int humid_stage_kernel_ms(humid_ctx *c, float *ms_k_insert, float *ms_k_map, uin
   }
   if (ms_k_insert) *ms_k_insert = a;
   if (ms_k_map) *ms_k_map = b;
-  if (count_mode_used) *count_mode_used = (c->last_count_sorted ? 3u : c->last_count_lds ? (c->last_count_ordered ? 2u : 0u) : 1u) | (c->last_rec8 ? 0x100u : 0u);
+  if (count_mode_used) *count_mode_used = ::count_mode_used(c);
   return HUMID_OK;
 }
 
@@ -1831,7 +1831,7 @@ int humid_stage_owned_results(humid_ctx *c, const uint32_t *d_local_cluster_id, 
                               const uint64_t *shard_begin, uint32_t n_shards, const uint32_t **d_packed,
                               uint64_t *counts) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (c->last_count_lds) return fail(c, HUMID_E_STATE, "owned results need the global-table count variant (count_mode 1)");
+  if (count_in_partition_order(c)) return fail(c, HUMID_E_STATE, "owned results need the global-table count variant (count_mode 1)");
   if (!shard_begin || !counts || !d_packed || n_shards == 0 || n_shards > 4096) return fail(c, HUMID_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;

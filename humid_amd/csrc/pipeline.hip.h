@@ -136,6 +136,32 @@ struct CtxState {
   bool long_words = false;     // the RUN was humid_dedup_run_long*: g_word holds g_wpr = ceil(word_nt / 32) uint64 per leaf, lg_info is its (humid_long_info)
 };
 
+// What the last count that was KEPT left behind (stage_count.hip.h): the road it took and what the stages behind it
+// need of that road.  Assigned whole by count_publish, once per kept count -- a discarded record attempt and an
+// overflowed LDS attempt publish nothing -- and replaced only by the next kept count: not by state_reset, for
+// humid_stage_count* -> humid_stage_graph* -> humid_stage_map* are separate calls that rely on it.  Read through the
+// predicates below only.
+enum CountRoad : u8 {
+  COUNT_GLOBAL,        // one hash table in HBM; slot_of_read maps the reads
+  COUNT_LDS_HASHED,    // LDS tables over hashed buckets, (key, read) pairs
+  COUNT_LDS_ORDERED,   // LDS tables over word-ordered buckets, (key, read) pairs (two-word words: keys + gather)
+  COUNT_REC,           // word-ordered buckets on records; positions are (bucket << 9 | j), the un-permute reads p8_b
+  COUNT_SORTED         // the sorting count of two-word and long words: no buckets
+};
+struct CountLeft {
+  CountRoad road = COUNT_GLOBAL;
+  u32 n_parts = 0;               // buckets (0: the road has none)
+  bool part_tiled = false;       // kev[39]..kev[40] bracket a second-level scatter
+  const u32 *cursor2 = nullptr;  // COUNT_REC: reads per bucket
+};
+// The remembered answer of prefix_fits_ordered for (reads, word length, key map): the sampled histogram and its host
+// wait run once per shape, not once per pass; an overflowing ordered run sets it to "no"
+struct OrderedMemo {
+  bool valid = false, fits = false;
+  u32 n = 0, nt = 0;
+  u64 lo = 0, scale = 0;
+};
+
 struct humid_ctx {
   int device = 0;
   CtxState state;
@@ -219,8 +245,7 @@ struct humid_ctx {
   DBuf pw_a, pw_ai, pw_b, pw_bi;    // two-word words: (word, read index) records of the two partition levels
   DBuf p8_a, p8_b, p8_cur, p8_status;               // 8-byte records of the count stage: level-1 output, level-2 output (kernels_part8.hip.h)
   bool use_rec8 = true;             // option "records8": 0 = always the 12-byte (key, read) pairs of kernels_part.hip.h
-  bool last_rec8 = false;           // the last count ran on records: positions are (bucket << 9 | j), the un-permute reads p8_b
-  const u32 *rec_cursor2 = nullptr; // reads per bucket of that count
+  CountLeft count_left;             // what the last kept count left behind
   DBuf pt_work, unperm_rec, route_tiles;                                                     // LDS-staged partition / un-permute (kernels_part.hip.h)
   bool group_buckets = true;        // option "group_buckets": bucket order of stretch keys by two-level grouping instead of a library sort
   bool fused_search = true;         // option "fused_search": the compact graph's neighbour search of a grouped combination rides in k_group_fine (0: a launch of k_pairs_append per combination)
@@ -231,20 +256,13 @@ struct humid_ctx {
   u32 wo_waits = 0, wo_overlapped = 0;   // host waits of the last mutating call; those with work queued between publish and wait (humid_wait_overlap_info): host stores only
   bool pt_padded = true;            // level 1 of the tile partition into padded coarse bins (no histogram pass); false after an overflow
   bool use_tile_partition = true;   // option "tile_partition": 0 = library radix passes + one-kernel un-permute (round 1)
-  bool last_part_tiled = false;     // kev[39]..kev[40] bracket the second-level scatter of the last count
   int x_test_fail_after = -1, x_gathers = 0;   // option "test_fail_before_gather": this rank leaves the pass with an error in the compute phase before its k-th gather (tests)
   bool x_hist_done = false, x_peer_failed = false;   // humid_dedup_run_exchange: the pass's first gather is done; a peer's failure was seen
   bool route_checked = true;        // no humid_stage_route since the last humid_stage_route_check
   const u32 *route_bad = nullptr;   // device flag of the last humid_stage_route
   bool last_unperm_tiled = false;   // kev[36]..kev[41] bracket k_unperm_window of the last map
-  // cached answer of prefix_fits_ordered for (reads, word length, key map): the sampled histogram and
-  // its host wait run once per shape, not once per pass; an overflowing ordered run resets it
-  bool oc_valid = false, oc_fits = false;
-  u32 oc_n = 0, oc_nt = 0;
-  u64 oc_lo = 0, oc_scale = 0;
-  u32 n_parts = 0;           // buckets of the last LDS-partitioned count (0: none, e.g. the sorted wide count)
+  OrderedMemo ordered_memo;
   bool stage_map_timed = false;                                                   // kev[37..38] bracket the last humid_stage_map_dense
-  bool last_count_sorted = false;                                                 // last count was the wide-word sort
   u32 g_wpr = 1;                                                                  // uint64 per word of g_word
   bool slots_done = false;   // slot_out already written by k_finalize_nodes (one-GPU fusion)
   int count_mode = 0;        // 0: hash-partitioned LDS tables (default), 1: one global HBM table
@@ -252,8 +270,6 @@ struct humid_ctx {
   bool force_comm = false;   // humid_dedup_run_exchange: call the humid_comm callbacks even with one rank (transport tests)
   u32 walk_max = PT2_TILE;   // k_pairs compares a position with this many followers; longer buckets go to k_pairs_tiles (0: never)
   bool coop_big = true;      // big components: workgroup-cooperative kernel (directional method)
-  bool last_count_lds = false;
-  bool last_count_ordered = false;
   int count_order = -1;      // LDS buckets by word prefix: -1 automatic (uniform prefix), 0 never, 1 always
   // grouped runs (humid_dedup_run_grouped*): the pass runs over internal words that carry the group ("gkey")
   // in gk_nt nucleotides above the caller's word; the count sorts them into (group, word) walk order and every
@@ -399,6 +415,17 @@ static int fail(humid_ctx *c, int code, const char *fmt, ...) {
 #define EVREC(ev, st) do { c->ev_records++; HIPCHK(hipEventRecord((ev), (st))); } while (0)
 #define STAMP_N 4
 #define STAMP_AT (CTR_N + 2)   // h_ctr: CTR_N counters, the sequence word, the grouped runs' check word, the stamps
+// what the stages behind a count ask of its record
+static inline bool count_in_partition_order(const humid_ctx *c) { return c->count_left.road != COUNT_GLOBAL; }   // stage C walks pk_vals / pslot (or the records), not slot_of_read
+static inline bool count_bucketed(const humid_ctx *c) { return c->count_left.n_parts != 0; }                      // positions end at pbeg[n_parts]; the read map goes bucket by bucket
+static inline bool count_on_records(const humid_ctx *c) { return c->count_left.road == COUNT_REC; }
+static inline bool count_part_timed(const humid_ctx *c) { return c->count_left.part_tiled; }
+// humid_summary::count_mode_used: 3 sorted, 2 ordered buckets, 0 hashed buckets, 1 global table; bit 8: on records
+static inline u32 count_mode_used(const humid_ctx *c) {
+  static const u32 mode[] = {1u, 0u, 2u, 2u | 0x100u, 3u};   // by CountRoad
+  return mode[c->count_left.road];
+}
+
 enum { STAMP_START = 0, STAMP_K0, STAMP_K1, STAMP_END };
 
 // Two memory rules.  A run's buffers and its own staging may be carved from the slab (ENSURE).  Every post-run pass
@@ -805,662 +832,7 @@ static int n_clusters_from_scan(humid_ctx *c, u32 U, u64 *out) {
   return HUMID_OK;
 }
 
-// ---- stage A: exact counts + walk order ------------------------------------------------
-// Inserts the reads whose word lies in [range_lo, range_hi] (inclusive; the multi-GPU path
-// gives every rank one range, a single GPU takes everything), compacts the table and sorts
-// the unique words.  Leaves table/slot_of_read/s_word/s_slot/s_cnt/s_first in the context.
-static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt,
-                              u64 range_lo, u64 range_hi, u64 expected_reads, humid_summary &s) {
-  hipStream_t st = c->stream;
-  c->last_count_lds = false;
-  c->last_count_sorted = false;
-  c->last_rec8 = false;
-  if (expected_reads == 0 || expected_reads > N) expected_reads = N;
-  u32 cap_log2 = 10;
-  while (((u64)1 << cap_log2) < expected_reads + expected_reads / 2) cap_log2++;
-  const u64 cap = (u64)1 << cap_log2;
-  c->cap_log2 = cap_log2;
-  ENSURE(c->table, (cap + 1) * sizeof(Slot));
-  ENSURE(c->slot_out, (cap + 1) * 8);
-  ENSURE(c->slot_of_read, (size_t)N * 4);
-  ENSURE(c->uniq_slot, (size_t)expected_reads * 4 + 4);
-  ENSURE(c->uniq_word, (size_t)expected_reads * 8 + 8);
-  EVREC(c->ev[0], st);
-  HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  HIPCHK(hipMemsetAsync(c->table.p, 0xff, (cap + 1) * sizeof(Slot), st));
-  EVREC(c->kev[0], st);
-  hipLaunchKernelGGL(k_hash_insert, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_words, d_filt, N,
-                     c->table.as<Slot>(), cap_log2, c->slot_of_read.as<u32>(), range_lo, range_hi,
-                     (u32)(cap - cap / 8), c->d_ctr);
-  EVREC(c->kev[1], st);
-  hipLaunchKernelGGL(k_compact_table, dim3(COMPACT_BLOCKS), dim3(256), 0, st,
-                     c->table.as<Slot>(), (u32)(cap + 1), c->uniq_word.as<u64>(), c->uniq_slot.as<u32>(),
-                     (u32)expected_reads, c->d_ctr);
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c));
-  if (c->h_ctr[CTR_OVERFULL])
-    return fail(c, HUMID_E_INVALID, "hash table over-full: more reads fell into this range than expected_reads");
-  const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
-  s.usable = c->usable = c->h_ctr[CTR_USABLE];
-  s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
-  ENSURE(c->s_word, (size_t)U * 8);
-  ENSURE(c->s_slot, (size_t)U * 4);
-  ENSURE(c->s_cnt, (size_t)U * 4);
-  ENSURE(c->s_first, (size_t)U * 4);
-  TRY(sort_pairs<u64, u32>(c, c->uniq_word.as<u64>(), c->s_word.as<u64>(), c->uniq_slot.as<u32>(),
-                           c->s_slot.as<u32>(), U, 0, 2 * word_nt));
-  hipLaunchKernelGGL(k_post_sort, dim3(blocks_for(U)), dim3(256), 0, st, c->s_slot.as<u32>(),
-                     c->table.as<Slot>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  return HUMID_OK;
-}
-
-// bucket bits of the partitioned count: 2^pb buckets of about PART_TARGET reads
-static inline u32 part_bits(u32 N) {
-  static const u64 target = getenv("HUMID_PART_TARGET") ? (u64)std::max(32, atoi(getenv("HUMID_PART_TARGET"))) : (u64)PART_TARGET;   // experiments
-  u32 pb = 1;
-  while (pb < 26 && (target << pb) < (u64)N) pb++;
-  return pb;
-}
-
-// Ordered partition key = (word - lo) * scale: the value range the reads lie in, stretched over the
-// whole 64-bit key space (see PartKeyOp).  shift < 64 iff scale == 2^shift.
-struct KeyMap {
-  u64 lo, scale;
-  u32 shift;
-};
-static KeyMap key_map(u32 word_nt, u64 lo, u64 hi, bool within) {
-  const u64 top = word_nt >= 32 ? ~0ull : (((u64)1 << (2 * word_nt)) - 1);
-  if (!within) { lo = 0; hi = top; }
-  if (hi > top) hi = top;
-  if (lo > hi) { lo = 0; hi = top; }
-  KeyMap m;
-  m.lo = lo;
-  const u64 span = hi - lo;
-  if (span == ~0ull) { m.scale = 1; m.shift = 0; return m; }
-  const u64 cnt = span + 1;
-  if ((cnt & (cnt - 1)) == 0 && cnt > 1) {
-    const u32 k = (u32)__builtin_ctzll(cnt);
-    m.shift = 64 - k;
-    m.scale = (u64)1 << m.shift;
-  } else {
-    m.shift = 64;
-    m.scale = ~0ull / cnt;
-  }
-  return m;
-}
-
-// Partitioned variant of stage A (see section 1b of the kernels).  Returns HUMID_OK with
-// *overflowed = true when a bucket held more unique words than its LDS table (the caller then
-// runs the global-table variant; results are never taken from an overflowed run).
-// The count stage's two-level tile partition of the reads `src` yields (kernels_part.hip.h) into pk_keys / pk_vals,
-// bucket bounds in pbeg.  SRC: ReadsSrc (one-word words) or WideReadsSrc (the heads of two-word words).
-template <class SRC>
-static int count_partition(humid_ctx *c, const SRC &src, u32 N, u32 pb, bool *used_padded) {
-  hipStream_t st = c->stream;
-  const u32 n_parts = 1u << pb;
-  // hand-written partition (kernels_part.hip.h): two levels of LDS-staged scatter; excluded reads
-  // (filtered, or outside this rank's value range) never enter it
-  const u32 d1 = (pb + 1) / 2, d2 = pb - d1;
-  const u32 nb1 = 1u << d1;
-  // pt_work, in u32: [hist1 512 | cursor1 512 | hist_fine n_parts + 1 | cursor2 n_parts] zeroed, then
-  // [cbase 513 | tprefix 513]
-  const size_t zero_words = 1024 + (size_t)n_parts + 1 + n_parts;
-  ENSURE(c->pt_work, (zero_words + 1026) * 4);
-  u32 *hist1 = c->pt_work.as<u32>(), *cursor1 = hist1 + 512, *hist_fine = cursor1 + 512,
-      *cursor2 = hist_fine + n_parts + 1, *cbase = cursor2 + n_parts, *tprefix = cbase + 513;
-  HIPCHK(hipMemsetAsync(c->pt_work.p, 0, zero_words * 4, st));
-  const u32 tiles1 = (N + PT_TILE - 1) / PT_TILE, tiles2 = tiles1 + nb1;
-  // Two levels and keys that spread evenly over the coarse bins (hashed keys always do, word-ordered
-  // keys were only chosen because their prefix does): level 1 scatters into PADDED coarse bins of a
-  // fixed room (mean + 25 % + 1024) and needs no histogram pass over the reads in front; the bins'
-  // counts are the cursors it leaves behind.  A bin that outgrows its room (heavily duplicated words:
-  // all reads of a word share a bin) is reported, the run discarded, and this context goes back to the
-  // histogram form (pt_padded = false).
-  static const u32 pad_div = getenv("HUMID_PAD_DIV") ? (u32)std::max(1, atoi(getenv("HUMID_PAD_DIV"))) : 4u;   // head room = mean / pad_div
-  const bool padded = d2 > 0 && c->pt_padded;
-  const u32 cap1 = padded ? (u32)std::min<u64>(0xffffffffull / nb1, (u64)N / nb1 + (u64)N / nb1 / pad_div + 1024) : 0u;
-  const size_t room1 = padded ? (size_t)nb1 * cap1 : (size_t)N;
-  *used_padded = padded;
-  if (padded) {
-    ENSURE(c->pad_word, room1 * 8);
-    ENSURE(c->pslot, room1 * 4);
-  }
-  // level-1 output: the final arrays when there is no second level, else scratch that is dead until
-  // k_dedup_lds writes it (pad_word, pslot)
-  u64 *k1 = d2 ? c->pad_word.as<u64>() : c->pk_keys.as<u64>();
-  u32 *v1 = d2 ? c->pslot.as<u32>() : c->pk_vals.as<u32>();
-  if (!padded) {
-    hipLaunchKernelGGL(k_pt_hist1<SRC>, dim3(tiles1 < 512 ? tiles1 : 512), dim3(1024), 0, st, src, N, d1, hist1);
-    hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, hist1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
-                       c->ucount.as<u32>() + n_parts, 0u);
-  }
-  hipLaunchKernelGGL((k_pt_scatter<1, SRC>), dim3(tiles1), dim3(1024), 0, st, src, N, (const u64 *)nullptr,
-                     (const u32 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, cbase, cursor1, k1, v1,
-                     (u32 *)nullptr, cap1, &c->d_ctr[CTR_SPECIAL]);
-  if (padded)
-    hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
-                       c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) EVREC(c->kev[39], st);
-  if (d2) {
-    hipLaunchKernelGGL(k_pt_hist2<SRC>, dim3(tiles2), dim3(1024), 0, st, src, k1, tprefix, cbase, d1, d2, hist_fine, cap1);
-    hipLaunchKernelGGL((k_pt_scatter<2, SRC>), dim3(tiles2), dim3(1024), 0, st, src, N, k1, v1, tprefix, cbase, d1, d2,
-                       hist_fine, cursor2, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(), c->pbeg.as<u32>(), cap1, &c->d_ctr[CTR_SPECIAL]);
-  }
-  if (c->kev_on) EVREC(c->kev[40], st);
-  return HUMID_OK;
-}
-
-// wide != null (33 <= word_nt <= 64, `ordered` and the tile partition only; d_words unused): buckets are cut
-// by the words' heads (WideReadsSrc) and counted by k_dedup_lds_wide (kernels_wide.hip.h).
-static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt,
-                           u64 range_lo, u64 range_hi, const KeyMap &km, bool ordered, humid_summary &s,
-                           bool *overflowed, const W2 *wide = nullptr) {
-  hipStream_t st = c->stream;
-  if (wide && !(ordered && c->use_tile_partition && part_bits(N) <= 18))
-    return fail(c, HUMID_E_INVALID, "wide words are counted in word-ordered buckets of the tile partition only");
-  const size_t wsize = wide ? sizeof(W2) : 8;
-  *overflowed = false;
-  c->last_count_lds = true;
-  c->last_count_sorted = false;
-  c->last_rec8 = false;
-  c->last_count_ordered = ordered;
-  const u32 pb = part_bits(N);
-  const u32 n_parts = 1u << pb;
-  c->n_parts = n_parts;
-  ENSURE(c->pk_keys, (size_t)N * 8);
-  ENSURE(c->pk_vals, (size_t)N * 4);
-  ENSURE(c->pbeg, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->ucount, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->pusable, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->ubase, (size_t)(n_parts + 1) * 4);
-  // pad_word / pslot double as the output of the padded first partition level (below): sized for that at
-  // once, so that they are carved from the context's slab a single time
-  const size_t room_early = (size_t)N + (size_t)N / 4 + ((size_t)1024 << ((pb + 1) / 2));
-  ENSURE(c->pad_word, std::max(room_early * 8, (size_t)N * wsize));
-  ENSURE(c->pad_cf, (size_t)N * 8);
-  ENSURE(c->pslot, room_early * 4);
-  ENSURE(c->slot_out, ((size_t)N + 1) * 8);
-  ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
-  ENSURE(c->uniq_word, (size_t)N * 8 + 8);
-  EVREC(c->ev[0], st);
-  HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
-  c->last_part_tiled = c->use_tile_partition && pb <= 2 * 9;
-  bool used_padded = false;
-  if (c->last_part_tiled) {
-    PtInput in;
-    in.words = d_words; in.filtered = d_filt; in.rlo = range_lo; in.rhi = range_hi;
-    in.check_range = check_range ? 1u : 0u;
-    in.key = PartKeyOp{ordered ? 1u : 0u, km.lo, km.scale};
-    if (wide) TRY(count_partition(c, WideReadsSrc{wide, d_filt, 2 * (word_nt - 32), in.key}, N, pb, &used_padded));
-    else TRY(count_partition(c, ReadsSrc{in}, N, pb, &used_padded));
-  } else {
-    // beyond 2^18 buckets (> ~90 M reads): radix passes over the top pb key bits (prims.hip.h)
-    ComposeIn<PartKeyOp, PtrIn<u64>> kin{PartKeyOp{ordered ? 1u : 0u, km.lo, km.scale}, PtrIn<u64>{d_words}};
-    ComposeIn<ReadTagOp, IotaIn> vin{ReadTagOp{check_range ? d_words : nullptr, d_filt, range_lo, range_hi}, IotaIn{}};
-    TRY((sort_pairs_in<u64, u32>(c, kin, c->pk_keys.as<u64>(), vin, c->pk_vals.as<u32>(), N, 64 - pb, 64)));
-    hipLaunchKernelGGL(k_part_bounds, dim3(blocks_for(n_parts + 1)), dim3(256), 0, st, c->pk_keys.as<u64>(), N,
-                       pb, n_parts, c->pbeg.as<u32>(), c->ucount.as<u32>());
-  }
-  EVREC(c->kev[0], st);
-  if (wide) {
-    hipLaunchKernelGGL((k_dedup_lds_wide<9, 512, 0, WL_SMALL_LEN>), dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
-                       c->pbeg.as<u32>(), wide, 2 * (word_nt - 32), N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(),
-                       c->ucount.as<u32>(), c->pusable.as<u32>(), c->pslot.as<u32>(), c->d_ctr);
-    if (N > WL_SMALL_LEN)
-      hipLaunchKernelGGL((k_dedup_lds_wide<10, 1024, WL_SMALL_LEN, WL_STAGE>), dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
-                         c->pbeg.as<u32>(), wide, 2 * (word_nt - 32), N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(),
-                         c->ucount.as<u32>(), c->pusable.as<u32>(), c->pslot.as<u32>(), c->d_ctr);
-  } else if (ordered)
-    hipLaunchKernelGGL(k_dedup_lds<true>, dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
-                       c->pbeg.as<u32>(), N, pb, km.lo, km.scale, km.shift, c->pad_word.as<u64>(), c->pad_cf.as<uint2>(),
-                       c->ucount.as<u32>(), c->pusable.as<u32>(), c->pslot.as<u32>(), c->d_ctr);
-  else
-    hipLaunchKernelGGL(k_dedup_lds<false>, dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(),
-                       c->pbeg.as<u32>(), N, pb, km.lo, km.scale, km.shift, c->pad_word.as<u64>(), c->pad_cf.as<uint2>(),
-                       c->ucount.as<u32>(), c->pusable.as<u32>(), c->pslot.as<u32>(), c->d_ctr);
-  EVREC(c->kev[1], st);
-  hipLaunchKernelGGL(k_part_totals, dim3(n_parts >= 16384 ? 64 : 4), dim3(256), 0, st, c->ucount.as<u32>(),
-                     c->pusable.as<u32>(), n_parts, c->d_ctr);
-  TRY(exscan_u32(c, c->ucount.as<u32>(), c->ubase.as<u32>(), (u64)n_parts + 1));
-  HIPCHK(hipGetLastError());
-  TRY(read_counters(c));
-  if (used_padded && c->h_ctr[CTR_SPECIAL]) {          // a coarse bin outgrew its padded room: once more, with the histogram pass
-    c->pt_padded = false;
-    road_taken(c, HUMID_ROAD_PART_PADDED_REDO);
-    return stage_count_lds(c, d_words, d_filt, N, word_nt, range_lo, range_hi, km, ordered, s, overflowed, wide);
-  }
-  if (c->h_ctr[CTR_OVERFULL]) { *overflowed = true; return HUMID_OK; }
-  const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
-  s.usable = c->usable = c->h_ctr[CTR_USABLE];
-  s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
-  ENSURE(c->s_word, (size_t)(U + 1) * wsize);
-  ENSURE(c->s_slot, (size_t)(U + 1) * 4);
-  ENSURE(c->s_cnt, (size_t)(U + 1) * 4);
-  ENSURE(c->s_first, (size_t)(U + 1) * 4);
-  if (wide) {
-    hipLaunchKernelGGL(k_compact_padded_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st,
-                       c->pad_word.as<W2>(), c->pad_cf.as<uint2>(), c->pbeg.as<u32>(), c->ucount.as<u32>(),
-                       c->ubase.as<u32>(), n_parts, c->s_word.as<W2>(), c->s_slot.as<u32>(),
-                       c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  } else if (ordered) {
-    // buckets are runs of the word order and sorted inside: squeezing out the holes IS the sort
-    hipLaunchKernelGGL(k_compact_padded<true>, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st,
-                       c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), c->pbeg.as<u32>(), c->ucount.as<u32>(),
-                       c->ubase.as<u32>(), n_parts, c->s_word.as<u64>(), c->s_slot.as<u32>(),
-                       c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  } else {
-    hipLaunchKernelGGL(k_compact_padded<false>, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st,
-                       c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), c->pbeg.as<u32>(), c->ucount.as<u32>(),
-                       c->ubase.as<u32>(), n_parts, c->uniq_word.as<u64>(), c->uniq_slot.as<u32>(),
-                       (u32 *)nullptr, (u32 *)nullptr);
-    TRY(sort_pairs<u64, u32>(c, c->uniq_word.as<u64>(), c->s_word.as<u64>(), c->uniq_slot.as<u32>(),
-                             c->s_slot.as<u32>(), U, 0, 2 * word_nt));
-    hipLaunchKernelGGL(k_post_sort_padded, dim3(blocks_for(U)), dim3(256), 0, st, c->s_slot.as<u32>(),
-                       c->pad_cf.as<uint2>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  }
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  return HUMID_OK;
-}
-
-// Stage A on 8-byte records (kernels_part8.hip.h): word-ordered buckets only, both partition levels padded.
-// *done = false: not this shape (the record would not fit 64 bits, too few / too many buckets, the read
-// set too large for the tiled un-permute) or a bin outgrew its room -- the caller takes stage_count_lds.
-static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt, u64 range_lo, u64 range_hi,
-                           const KeyMap &km, humid_summary &s, bool *done) {
-  hipStream_t st = c->stream;
-  *done = false;
-  if (!c->use_rec8 || !c->use_tile_partition || !c->pt_padded) return HUMID_OK;
-  const u32 pb = part_bits(N);
-  if (pb < 6 || pb > 18) return HUMID_OK;
-  if ((((u64)N + (1u << UW_MAXSHIFT) - 1) >> UW_MAXSHIFT) > UW_MAXBINS) return HUMID_OK;
-  RecKey rk;
-  rk.lo = km.lo; rk.scale = km.scale;
-  rk.pow2 = km.shift < 64 ? 1u : 0u;
-  rk.z = rk.pow2 ? km.shift : 63u - (u32)__builtin_clzll(km.scale);
-  rk.kbits = 64 - rk.z;
-  const u32 ibits = bits_for(N);
-  // a record = the key bits below the coarse bin + the read index: kbits - d1 + ibits <= 64.  24-nt words over their
-  // whole range have 48 key bits: with the balanced split d1 = pb / 2 <= 9 that ends at 2^25 = 33 M reads; one more
-  // bit in the FIRST level (1024 coarse bins: half as long runs per bin and tile there) carries the record path to the
-  // 67 M reads of the un-permute's bin table (BASELINE configs 3 and 5: 50 M reads)
-  u32 d1 = (pb + 1) / 2;
-  while (d1 < 10 && pb - d1 > 1 && rk.kbits - d1 + ibits > 64) d1++;
-  const u32 d2 = pb - d1, nb1 = 1u << d1, n_parts = 1u << pb;
-  if (rk.kbits < pb + 1 || rk.kbits - d1 + ibits > 64 || d2 > 9 || d2 == 0) return HUMID_OK;
-  static const u32 pad_div = getenv("HUMID_PAD_DIV") ? (u32)std::max(1, atoi(getenv("HUMID_PAD_DIV"))) : 4u;
-  const u32 cap1 = (u32)std::min<u64>(0xffffffffull / nb1, (u64)N / nb1 + (u64)N / nb1 / pad_div + 1024);
-  const size_t room1 = (size_t)nb1 * cap1, room2 = (size_t)n_parts << P8_CAP2_LOG;
-  ENSURE(c->p8_a, room1 * 8);
-  ENSURE(c->p8_b, room2 * 8);
-  ENSURE(c->pad_word, room2 * 8);
-  ENSURE(c->pad_cf, room2 * 8);
-  ENSURE(c->slot_out, (room2 + 1) * 8);
-  ENSURE(c->pbeg, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->ucount, (size_t)(n_parts + 1) * 4);
-  // per bucket (reads << 32 | unique words) and its exclusive scan; entry n_parts = the scan's sentinel -> the totals
-  ENSURE(c->p8_status, ((size_t)n_parts + 1) * 16);
-  u64 *agg = c->p8_status.as<u64>(), *abase = agg + n_parts + 1;
-  // p8_cur, in u32: [cursor1 1024 | cursor2 n_parts] zeroed, then [cbase 1025 | tprefix 1025].  (Not pt_work: the
-  // reads per bucket, cursor2, are read again by the un-permute at the end of the pass, and the graph
-  // stage's grouping uses pt_work in between.)
-  ENSURE(c->p8_cur, ((size_t)PT_MAXBINS1 + n_parts + 2 * (PT_MAXBINS1 + 1)) * 4);
-  u32 *cursor1 = c->p8_cur.as<u32>(), *cursor2 = cursor1 + PT_MAXBINS1, *cbase = cursor2 + n_parts, *tprefix = cbase + PT_MAXBINS1 + 1;
-  // the pass's four times from device stamps (humid_ctx::d_stamp)
-  const u64 n_agg = (u64)n_parts + 1;
-  const bool stamp = c->stamp_ok;
-  u64 *const sp = stamp ? c->d_stamp : nullptr;
-  c->stamp_live = stamp;
-  c->stamp_timed = stamp && c->lean_events;
-  const bool events = !c->stamp_timed;                        // ev[0], kev[0], kev[1] here and ev[4] in stage_map
-  if (events) EVREC(c->ev[0], st);
-  {
-    ZeroList z;
-    memset(&z, 0, sizeof z);
-    z.p[0] = cursor1; z.n[0] = PT_MAXBINS1 + n_parts;
-    z.p[1] = (u32 *)c->d_ctr; z.n[1] = 2 * CTR_N;
-    z.p[2] = (u32 *)(agg + n_parts); z.n[2] = 2;
-    hipLaunchKernelGGL(k_zero_many, dim3(32), dim3(256), 0, st, z, sp ? sp + STAMP_START : (u64 *)nullptr);
-  }
-  const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
-  const Reads8 src{d_words, d_filt, range_lo, range_hi, check_range ? 1u : 0u, rk};
-  const u32 tiles1 = (N + PT_TILE - 1) / PT_TILE, tiles2 = tiles1 + nb1;
-  static const bool s1_small = getenv("HUMID_S1_THREADS") ? atoi(getenv("HUMID_S1_THREADS")) == 512 : false;  // (experiments: 512 is 20 us slower)
-  if (s1_small && nb1 <= 512)
-    hipLaunchKernelGGL((k_p8_scatter1<Reads8, 512>), dim3((N + 4095) / 4096), dim3(512), 0, st, src, N, rk.kbits, d1, ibits, cap1, cursor1,
-                       c->p8_a.as<u64>(), c->d_ctr);
-  else
-    hipLaunchKernelGGL((k_p8_scatter1<Reads8, 1024>), dim3(tiles1), dim3(1024), 0, st, src, N, rk.kbits, d1, ibits, cap1, cursor1,
-                       c->p8_a.as<u64>(), c->d_ctr);
-  // static_tiles: level 2 reads the padded bins' cursors itself -- no scan, no tile table (and nothing stores
-  // pbeg[n_parts] / ucount[n_parts], which no kernel of the record road reads: its un-permute, k_unperm_bins8, takes
-  // the buckets' fills from cursor2).  One workgroup per tile of every bin's ROOM: those beyond the fill leave at once.
-  if (c->static_tiles) {
-    if (c->kev_on) EVREC(c->kev[39], st);
-    hipLaunchKernelGGL(k_p8_scatter2<true>, dim3(nb1 * ((cap1 + PT_TILE - 1) / PT_TILE)), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(),
-                       (const u32 *)cursor1, (const u32 *)nullptr, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
-  } else {
-    hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
-                       c->ucount.as<u32>() + n_parts, cap1);
-    if (c->kev_on) EVREC(c->kev[39], st);
-    hipLaunchKernelGGL(k_p8_scatter2<false>, dim3(tiles2), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(), (const u32 *)tprefix,
-                       (const u32 *)cbase, rk.kbits, d1, d2, ibits, cap1, cursor2, c->p8_b.as<u64>(), c->d_ctr);
-  }
-  if (c->kev_on) EVREC(c->kev[40], st);
-  if (events) EVREC(c->kev[0], st);
-  hipLaunchKernelGGL(k_dedup_rec, dim3(n_parts), dim3(256), 0, st, c->p8_b.as<u64>(), (const u32 *)cursor2, N, pb, d1, ibits, rk,
-                     c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), agg, c->d_ctr, sp ? sp + STAMP_K0 : (u64 *)nullptr);
-  if (events) EVREC(c->kev[1], st);
-  TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, n_agg, sp ? sp + STAMP_K1 : (u64 *)nullptr));
-  // the walk-order arrays are squeezed out of the padded ones BEFORE the host knows how many unique words there are
-  // (at most N: a bucket never reports more words than records it holds).  Everything the host's wait reads -- U and
-  // the usable reads (the scan's totals), CTR_SPECIAL, CTR_OVERFULL -- is final behind the scan, so with overlap_waits
-  // the publishing kernel stands IN FRONT of the squeeze: the host sees U, which it needs to shape the graph stage,
-  // while the squeeze runs, and queues that stage behind it.  (Without the option the publishing kernel follows the
-  // squeeze in the stream, and the GPU is idle from the squeeze's end until the host has seen U and launched.)
-  ENSURE(c->s_word, (size_t)(N + 1) * 8);
-  ENSURE(c->s_slot, (size_t)(N + 1) * 4);
-  ENSURE(c->s_cnt, (size_t)(N + 1) * 4);
-  ENSURE(c->s_first, (size_t)(N + 1) * 4);
-  const bool early = c->overlap_waits;
-  if (early) TRY(read_counters_begin(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
-  hipLaunchKernelGGL(k_compact_padded8, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, c->pad_word.as<u64>(),
-                     c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<u64>(),
-                     c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  if (early) TRY(read_counters_end(c, true));
-  else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
-  if (getenv("HUMID_TRACE_COUNT"))
-    fprintf(stderr, "[rec count] N %u pb %u kbits %u ibits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits,
-            ibits, cap1, (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
-  // a count that is discarded: the road that takes it again records the events, and the pass's four times are theirs
-  if (c->h_ctr[CTR_SPECIAL] || c->h_ctr[CTR_OVERFULL]) c->stamp_ok = c->stamp_live = c->stamp_timed = false;
-  if (c->h_ctr[CTR_SPECIAL]) { c->pt_padded = false; road_taken(c, HUMID_ROAD_PART_PADDED_REDO); return HUMID_OK; }     // a bin outgrew its room: the exact kernels from now on
-  if (c->h_ctr[CTR_OVERFULL]) return HUMID_OK;
-  c->last_count_lds = true;
-  c->last_count_sorted = false;
-  c->last_count_ordered = true;
-  c->last_part_tiled = true;
-  c->last_rec8 = true;
-  c->rec_cursor2 = cursor2;
-  c->n_parts = n_parts;
-  const u32 U = (u32)(c->h_ctr[CTR_N - 1] & 0xffffffffull);
-  s.usable = c->usable = c->h_ctr[CTR_N - 2] & 0xffffffffull;
-  s.unique = c->U = U;
-  *done = true;
-  return HUMID_OK;
-}
-
-// Stage A for two-word words on records (kernels_part8.hip.h, second half): the 16-byte word + its read index travel
-// through both padded partition levels, k_dedup_wide_rec reads its bucket as two contiguous streams.  *done = false:
-// not this shape, or a bin outgrew its room -- the caller takes stage_count_lds (keys + gather) or the sort.
-static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u32 N, u32 word_nt, const KeyMap &km,
-                                humid_summary &s, bool *done) {
-  hipStream_t st = c->stream;
-  *done = false;
-  if (!c->use_rec8 || !c->use_tile_partition || !c->pt_padded) return HUMID_OK;
-  const u32 pb = part_bits(N);
-  if (pb < 6 || pb > 18) return HUMID_OK;
-  if ((((u64)N + (1u << UW_MAXSHIFT) - 1) >> UW_MAXSHIFT) > UW_MAXBINS) return HUMID_OK;
-  const u32 d1 = (pb + 1) / 2, d2 = pb - d1, nb1 = 1u << d1, n_parts = 1u << pb;
-  RecKey rk;
-  rk.lo = km.lo; rk.scale = km.scale;
-  rk.pow2 = km.shift < 64 ? 1u : 0u;
-  rk.z = rk.pow2 ? km.shift : 63u - (u32)__builtin_clzll(km.scale);
-  rk.kbits = 64 - rk.z;
-  if (rk.kbits < pb + 1) return HUMID_OK;
-  const u32 hbits = 2 * (word_nt - 32);
-  static const u32 pad_div = getenv("HUMID_PAD_DIV") ? (u32)std::max(1, atoi(getenv("HUMID_PAD_DIV"))) : 4u;
-  const u32 cap1 = (u32)std::min<u64>(0xffffffffull / nb1, (u64)N / nb1 + (u64)N / nb1 / pad_div + 1024);
-  const size_t room1 = (size_t)nb1 * cap1, room2 = (size_t)n_parts << P8_CAP2_LOG;
-  ENSURE(c->pw_a, room1 * 16);
-  ENSURE(c->pw_ai, room1 * 4);
-  ENSURE(c->pw_b, room2 * 16);
-  ENSURE(c->pw_bi, room2 * 4);
-  ENSURE(c->p8_b, room2 * 8);
-  ENSURE(c->pad_word, room2 * 16);
-  ENSURE(c->pad_cf, room2 * 8);
-  ENSURE(c->slot_out, (room2 + 1) * 8);
-  ENSURE(c->pbeg, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->ucount, (size_t)(n_parts + 1) * 4);
-  ENSURE(c->p8_status, ((size_t)n_parts + 1) * 16);
-  u64 *agg = c->p8_status.as<u64>(), *abase = agg + n_parts + 1;
-  ENSURE(c->p8_cur, ((size_t)512 + n_parts + 1026) * 4);
-  u32 *cursor1 = c->p8_cur.as<u32>(), *cursor2 = cursor1 + 512, *cbase = cursor2 + n_parts, *tprefix = cbase + 513;
-  EVREC(c->ev[0], st);
-  {
-    ZeroList z;
-    memset(&z, 0, sizeof z);
-    z.p[0] = cursor1; z.n[0] = 512 + n_parts;
-    z.p[1] = (u32 *)c->d_ctr; z.n[1] = 2 * CTR_N;
-    z.p[2] = (u32 *)(agg + n_parts); z.n[2] = 2;
-    hipLaunchKernelGGL(k_zero_many, dim3(32), dim3(256), 0, st, z);
-  }
-  const u32 tiles1 = (N + PT_TILE - 1) / PT_TILE, tiles2 = tiles1 + nb1;
-  hipLaunchKernelGGL(k_pw_scatter<1>, dim3(tiles1), dim3(1024), 0, st, d_words, d_filt, (const u32 *)nullptr, N, hbits, rk,
-                     (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, cap1, cursor1, c->pw_a.as<W2>(), c->pw_ai.as<u32>(), c->d_ctr);
-  hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
-                     c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) EVREC(c->kev[39], st);
-  hipLaunchKernelGGL(k_pw_scatter<2>, dim3(tiles2), dim3(1024), 0, st, (const W2 *)c->pw_a.as<W2>(), (const u8 *)nullptr,
-                     (const u32 *)c->pw_ai.as<u32>(), N, hbits, rk, (const u32 *)tprefix, (const u32 *)cbase, d1, d2, cap1, cursor2,
-                     c->pw_b.as<W2>(), c->pw_bi.as<u32>(), c->d_ctr);
-  if (c->kev_on) EVREC(c->kev[40], st);
-  EVREC(c->kev[0], st);
-  hipLaunchKernelGGL((k_dedup_wide_rec<9, 512, 0, WL_SMALL_LEN>), dim3(n_parts), dim3(256), 0, st, (const W2 *)c->pw_b.as<W2>(),
-                     (const u32 *)c->pw_bi.as<u32>(), (const u32 *)cursor2, hbits, rk, N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(),
-                     agg, c->p8_b.as<u64>(), c->d_ctr);
-  if (N > WL_SMALL_LEN)
-    hipLaunchKernelGGL((k_dedup_wide_rec<10, 1024, WL_SMALL_LEN, WL_STAGE>), dim3(n_parts), dim3(256), 0, st,
-                       (const W2 *)c->pw_b.as<W2>(), (const u32 *)c->pw_bi.as<u32>(), (const u32 *)cursor2, hbits, rk, N, pb,
-                       c->pad_word.as<W2>(), c->pad_cf.as<uint2>(), agg, c->p8_b.as<u64>(), c->d_ctr);
-  EVREC(c->kev[1], st);
-  TRY(exscan_in<u64>(c, PtrIn<u64>{agg}, abase, (u64)n_parts + 1));
-  // (as in stage_count_rec: at most N unique words; overlap_waits publishes the counters in front of the squeeze)
-  ENSURE(c->s_word, (size_t)(N + 1) * 16);
-  ENSURE(c->s_slot, (size_t)(N + 1) * 4);
-  ENSURE(c->s_cnt, (size_t)(N + 1) * 4);
-  ENSURE(c->s_first, (size_t)(N + 1) * 4);
-  const bool early = c->overlap_waits;
-  if (early) TRY(read_counters_begin(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
-  hipLaunchKernelGGL(k_compact_padded8_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, (const W2 *)c->pad_word.as<W2>(),
-                     (const uint2 *)c->pad_cf.as<uint2>(), (const u64 *)agg, (const u64 *)abase, n_parts, c->s_word.as<W2>(),
-                     c->s_slot.as<u32>(), c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  if (early) TRY(read_counters_end(c, true));
-  else TRY(read_counters(c, (const u32 *)(abase + n_parts), (const u32 *)(abase + n_parts) + 1));   // U, usable
-  if (getenv("HUMID_TRACE_COUNT"))
-    fprintf(stderr, "[rec count, wide] N %u pb %u kbits %u cap1 %u special %llu overfull %llu unique %llu usable %llu\n", N, pb, rk.kbits, cap1,
-            (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL], (ull)(c->h_ctr[CTR_N - 1] & 0xffffffffull), (ull)(c->h_ctr[CTR_N - 2] & 0xffffffffull));
-  if (c->h_ctr[CTR_SPECIAL] || c->h_ctr[CTR_OVERFULL]) return HUMID_OK;       // (the key + gather road decides by itself what to do next)
-  c->last_count_lds = true;
-  c->last_count_sorted = false;
-  c->last_count_ordered = true;
-  c->last_part_tiled = true;
-  c->last_rec8 = true;
-  c->rec_cursor2 = cursor2;
-  c->n_parts = n_parts;
-  const u32 U = (u32)(c->h_ctr[CTR_N - 1] & 0xffffffffull);
-  s.usable = c->usable = c->h_ctr[CTR_N - 2] & 0xffffffffull;
-  s.unique = c->U = U;
-  *done = true;
-  return HUMID_OK;
-}
-
-// Would word-ordered buckets fit their LDS tables?  Histogram of the top (up to 12) word bits over
-// a sample of the reads, folded / scaled to the 2^pb buckets the partition will use: the fullest
-// bucket, with a 1.5x margin, must stay below the table's fill limit (a bucket's unique words
-// cannot exceed its reads).  UMI-first layouts pass; read-prefix-first amplicon or low-complexity
-// data does not and keeps the hashed buckets.  A wrong "yes" only costs the overflow fallback.
-static int prefix_fits_ordered(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt,
-                               const KeyMap &km, bool *fits) {
-  *fits = false;
-  // the answer for this shape is remembered: the sample and its host wait are paid once, not per
-  // pass (a wrong "yes" on other data of the same shape costs the overflow fallback and resets it)
-  if (c->oc_valid && c->oc_n == N && c->oc_nt == word_nt && c->oc_lo == km.lo && c->oc_scale == km.scale) {
-    *fits = c->oc_fits;
-    return HUMID_OK;
-  }
-  const u32 bits = 2 * word_nt < 12 ? 2 * word_nt : 12;
-  const u32 n_bins = 1u << bits;
-  if (N < 65536) return HUMID_OK;                              // small inputs: not worth a decision
-  // a sample is enough: the first 512 K reads (FastQ order is unrelated to the word value)
-  const u32 n_sample = N < (1u << 19) ? N : (1u << 19);
-  ENSURE(c->small, (size_t)n_bins * 4);
-  HIPCHK(hipMemsetAsync(c->small.p, 0, (size_t)n_bins * 4, c->stream));
-  hipLaunchKernelGGL(k_top_hist, dim3(128), dim3(1024), n_bins * 4, c->stream, d_words, d_filt, n_sample,
-                     km.lo, km.scale, bits, c->small.as<u32>());
-  std::vector<u32> h(n_bins);
-  HIPCHK(hipMemcpyAsync(h.data(), c->small.p, (size_t)n_bins * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const u32 pb = part_bits(N);
-  double worst = 0;
-  if (pb >= bits) {                    // several buckets per bin: assume the bin splits evenly
-    u32 mx = 0;
-    for (u32 v : h) if (v > mx) mx = v;
-    worst = (double)mx / (double)(1u << (pb - bits));
-  } else {                             // several bins per bucket: fold
-    const u32 per = 1u << (bits - pb);
-    for (u32 b = 0; b < n_bins; b += per) {
-      u64 t = 0;
-      for (u32 k = 0; k < per; k++) t += h[b + k];
-      if ((double)t > worst) worst = (double)t;
-    }
-  }
-  worst *= (double)N / (double)n_sample;
-  *fits = worst * 1.5 <= (double)LDS_FILL_LIMIT;
-  c->oc_valid = true; c->oc_fits = *fits;
-  c->oc_n = N; c->oc_nt = word_nt; c->oc_lo = km.lo; c->oc_scale = km.scale;
-  return HUMID_OK;
-}
-
-// stage A dispatcher: partitioned LDS tables when every usable read is counted here (one GPU; a
-// multi-GPU rank in exchange mode, `within`: all reads lie in [range_lo, range_hi]), the global
-// table for a partial range of a larger array or after a bucket overflow.
-static int stage_count(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt,
-                       u64 range_lo, u64 range_hi, u64 expected_reads, humid_summary &s, bool within = false) {
-  const bool full_range = (range_lo == 0 && range_hi == ~0ull);
-  if (c->count_mode == 0 && (full_range || within)) {
-    const KeyMap km = key_map(word_nt, range_lo, range_hi, within);
-    bool overflowed = false;
-    bool ordered = c->count_order == 1;
-    if (c->count_order < 0) TRY(prefix_fits_ordered(c, d_words, d_filt, N, word_nt, km, &ordered));
-    c->last_rec8 = false;
-    if (ordered) {
-      bool done = false;
-      TRY(stage_count_rec(c, d_words, d_filt, N, word_nt, range_lo, range_hi, km, s, &done));
-      if (done) return HUMID_OK;
-      TRY(stage_count_lds(c, d_words, d_filt, N, word_nt, range_lo, range_hi, km, true, s, &overflowed));
-      if (!overflowed) return HUMID_OK;
-      // these words do not fit word-ordered buckets after all: remember that for this shape
-      c->oc_valid = true; c->oc_fits = false;
-      c->oc_n = N; c->oc_nt = word_nt; c->oc_lo = km.lo; c->oc_scale = km.scale;
-    }
-    TRY(stage_count_lds(c, d_words, d_filt, N, word_nt, range_lo, range_hi, km, false, s, &overflowed));
-    if (!overflowed) return HUMID_OK;
-  }
-  return stage_count_global(c, d_words, d_filt, N, word_nt, range_lo, range_hi, expected_reads, s);
-}
-
-// Stage A for wide words (two uint64 per read): counts by sorting, see kernels_wide.hip.h.
-// Leaves s_word (W2)/s_cnt/s_first/s_slot and, for stage C, the partition-order arrays
-// pk_vals/pslot in the context.
-// head_lo / head_hi (within): every word's head lies in that range (a rank's value range in the exchange pass).
-static int stage_count_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u32 N, u32 word_nt, humid_summary &s,
-                            u64 head_lo = 0, u64 head_hi = ~0ull, bool within = false) {
-  hipStream_t st = c->stream;
-  // LDS tables over head-ordered buckets when the heads spread evenly (count_mode 0, as for one-word
-  // words; count_order 0 keeps the sort); the sort below otherwise and after an overflow
-  if (c->count_mode == 0 && c->count_order != 0 && c->use_tile_partition && (N >= 65536 || c->count_order == 1) &&
-      part_bits(N) <= 18) {
-    const KeyMap km = key_map(24, head_lo >> WIDE_KEY_DROP, head_hi >> WIDE_KEY_DROP, within);   // (the keys: 48-bit numbers, see WideReadsSrc)
-    bool ordered = c->count_order == 1;
-    if (c->count_order < 0) {
-      // the decision samples the first 512 K reads (and is remembered for the shape): heads of those only;
-      // the partition itself computes a word's head as it reads the word (WideReadsSrc)
-      const u32 n_sample = N < (1u << 19) ? N : (1u << 19);
-      ENSURE(c->w_heads, (size_t)n_sample * 8);
-      hipLaunchKernelGGL(k_wide_head64, dim3(blocks_for(n_sample)), dim3(256), 0, st, d_words, n_sample, 2 * (word_nt - 32), c->w_heads.as<u64>(),
-                         WIDE_KEY_DROP);
-      TRY(prefix_fits_ordered(c, c->w_heads.as<u64>(), d_filt, N, word_nt, km, &ordered));
-    }
-    if (getenv("HUMID_TRACE_COUNT")) fprintf(stderr, "[wide count] N %u order %d fits %d lo %llx scale %llx shift %u\n", N, c->count_order, (int)ordered, (ull)km.lo, (ull)km.scale, km.shift);
-    c->last_rec8 = false;
-    if (ordered) {
-      bool done8 = false;
-      TRY(stage_count_rec_wide(c, d_words, d_filt, N, word_nt, km, s, &done8));
-      if (done8) return HUMID_OK;
-      bool overflowed = false;
-      TRY(stage_count_lds(c, nullptr, d_filt, N, word_nt, 0ull, ~0ull, km, true, s, &overflowed, d_words));
-      if (getenv("HUMID_TRACE_COUNT")) fprintf(stderr, "[wide count] overflowed %d special %llu overfull %llu\n", (int)overflowed, (ull)c->h_ctr[CTR_SPECIAL], (ull)c->h_ctr[CTR_OVERFULL]);
-      if (!overflowed) return HUMID_OK;
-      c->oc_valid = true; c->oc_fits = false;
-      c->oc_n = N; c->oc_nt = word_nt; c->oc_lo = km.lo; c->oc_scale = km.scale;
-    }
-  }
-  c->last_count_lds = true;          // stage C walks pk_vals/pslot (k_read_map_part)
-  c->last_count_ordered = false;
-  c->last_count_sorted = true;
-  c->last_rec8 = false;
-  c->n_parts = 0;
-  const u32 hbits = 2 * (word_nt - 32);
-  const u32 grid = grid_stride_blocks(N);
-  ENSURE(c->pk_keys, (size_t)N * 8);
-  ENSURE(c->pad_word, (size_t)N * 8);
-  ENSURE(c->pk_vals, (size_t)N * 4);
-  ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
-  ENSURE(c->pslot, (size_t)N * 4);
-  ENSURE(c->w_sorted, (size_t)N * sizeof(W2));
-  ENSURE(c->w_head, ((size_t)N + 1) * 4);
-  ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
-  EVREC(c->ev[0], st);
-  HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  EVREC(c->kev[0], st);
-  u64 *k0 = c->pk_keys.as<u64>(), *k1 = c->pad_word.as<u64>();
-  u32 *va = c->uniq_slot.as<u32>(), *vb = c->pk_vals.as<u32>();
-  hipLaunchKernelGGL(k_wide_keys_lo, dim3(grid), dim3(256), 0, st, d_words, d_filt, N, k0, va, c->d_ctr);
-  TRY(sort_pairs<u64, u32>(c, k0, k1, va, vb, N, 0, 64));                       // by lo
-  hipLaunchKernelGGL(k_wide_keys_hi, dim3(grid), dim3(256), 0, st, d_words, d_filt, vb, N, hbits, k0);
-  TRY(sort_pairs<u64, u32>(c, k0, k1, vb, va, N, 0, hbits < 64 ? hbits + 1 : 64));   // by (filtered,) hi
-  u32 *v = va;
-  if (hbits == 64) {                                                            // n = 64: no spare key bit
-    hipLaunchKernelGGL(k_wide_keys_flag, dim3(grid), dim3(256), 0, st, d_filt, va, N, (u32 *)k0);
-    TRY(sort_pairs<u32, u32>(c, (u32 *)k0, (u32 *)k1, va, vb, N, 0, 1));
-    v = vb;
-  }
-  EVREC(c->kev[1], st);
-  hipLaunchKernelGGL(k_wide_gather, dim3(grid), dim3(256), 0, st, d_words, v, N, hbits, c->w_sorted.as<W2>());
-  hipLaunchKernelGGL(k_wide_heads, dim3(grid), dim3(256), 0, st, c->w_sorted.as<W2>(), N, c->d_ctr,
-                     c->w_head.as<u32>());
-  u64 n_unique = 0;
-  TRY(scan_total(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), N, &n_unique));
-  const u32 U = (u32)n_unique;
-  s.usable = c->usable = c->h_ctr[CTR_USABLE];
-  s.unique = c->U = U;
-  ENSURE(c->s_word, (size_t)(U + 1) * sizeof(W2));
-  ENSURE(c->s_slot, (size_t)(U + 1) * 4);
-  ENSURE(c->s_cnt, (size_t)(U + 1) * 4);
-  ENSURE(c->s_first, (size_t)(U + 1) * 4);
-  ENSURE(c->w_start, (size_t)(U + 2) * 4);
-  ENSURE(c->slot_out, (size_t)(U + 1) * 8);
-  hipLaunchKernelGGL(k_wide_unique, dim3(grid), dim3(256), 0, st, c->w_sorted.as<W2>(), v, c->w_head.as<u32>(),
-                     c->w_hpos.as<u32>(), N, c->d_ctr, c->s_word.as<W2>(), c->s_first.as<u32>(),
-                     c->w_start.as<u32>(), c->pslot.as<u32>(), c->pk_vals.as<u32>());
-  if (U)
-    hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U,
-                       c->s_cnt.as<u32>(), c->s_slot.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  return HUMID_OK;
-}
+#include "stage_count.hip.h"
 
 // buckets longer than k_pairs' bounded walk, over the walked order W[0, n) of one combination: device list at
 // c->big_runs + slot * cap (start, length, first tile), host copy in `runs` with the total as a last entry
@@ -2775,23 +2147,23 @@ static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_k
   if (c->ucur_clean != ucur) HIPCHK(hipMemsetAsync(ucur, 0, (size_t)UW_MAXBINS * 4, st));
   c->ucur_clean = nullptr;
   // positions in use: all N for the sorted (wide-word) count, else up to pbeg[n_parts] (on the device)
-  const bool bucketed = c->n_parts && !c->last_count_sorted;
-  const u32 *n_pos_dev = bucketed ? c->pbeg.as<u32>() + c->n_parts : (const u32 *)nullptr;
-  if (c->last_rec8) {
+  const CountLeft &cl = c->count_left;
+  const u32 *n_pos_dev = count_bucketed(c) ? c->pbeg.as<u32>() + cl.n_parts : (const u32 *)nullptr;
+  if (count_on_records(c)) {
     // buckets per workgroup: about 7/8 of a tile's worth of records (reads per bucket: usable / buckets)
-    const u64 mean = std::max<u64>(1, c->usable / c->n_parts);
+    const u64 mean = std::max<u64>(1, c->usable / cl.n_parts);
     const u32 chunk = (n_bins > 1024 && n_bins <= 1536) ? 7u * PT_THREADS : PT_TILE;     // records the variant below stages at a time
     const u32 B = (u32)std::min<u64>(64, std::max<u64>(1, (chunk - chunk / 8) / mean));
-    const u32 grid = (c->n_parts + B - 1) / B;
+    const u32 grid = (cl.n_parts + B - 1) / B;
     if (n_bins <= 1024)
-      hipLaunchKernelGGL(k_unperm_bins8<1024>, dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), c->rec_cursor2,
-                         (const u64 *)c->slot_out.as<u64>(), c->n_parts, B, N, wshift, n_bins, ucur, rec);
+      hipLaunchKernelGGL(k_unperm_bins8<1024>, dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), cl.cursor2,
+                         (const u64 *)c->slot_out.as<u64>(), cl.n_parts, B, N, wshift, n_bins, ucur, rec);
     else if (n_bins <= 1536)
-      hipLaunchKernelGGL((k_unperm_bins8<1536, 7>), dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), c->rec_cursor2,
-                         (const u64 *)c->slot_out.as<u64>(), c->n_parts, B, N, wshift, n_bins, ucur, rec);
+      hipLaunchKernelGGL((k_unperm_bins8<1536, 7>), dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), cl.cursor2,
+                         (const u64 *)c->slot_out.as<u64>(), cl.n_parts, B, N, wshift, n_bins, ucur, rec);
     else
-      hipLaunchKernelGGL(k_unperm_bins8<2048>, dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), c->rec_cursor2,
-                         (const u64 *)c->slot_out.as<u64>(), c->n_parts, B, N, wshift, n_bins, ucur, rec);
+      hipLaunchKernelGGL(k_unperm_bins8<2048>, dim3(grid), dim3(1024), 0, st, (const u64 *)c->p8_b.as<u64>(), cl.cursor2,
+                         (const u64 *)c->slot_out.as<u64>(), cl.n_parts, B, N, wshift, n_bins, ucur, rec);
   }
   else
   hipLaunchKernelGGL(k_unperm_bins, dim3((N + PT_TILE - 1) / PT_TILE), dim3(1024), 0, st, c->pk_vals.as<u32>(),
@@ -2823,7 +2195,7 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
     hipLaunchKernelGGL(k_slot_results, dim3(blocks_for(U)), dim3(256), 0, st, l_cid, l_ismax,
                        c->s_first.as<u32>(), c->s_slot.as<u32>(), U, c->slot_out.as<u64>());
   if (!c->lean_events) EVREC(c->ev[3], st);
-  if (c->last_count_lds) {
+  if (count_in_partition_order(c)) {
     bool tiled = false;
     TRY(unpermute_tiled(c, N, false, d_cid, d_keep, c->kev[36], &tiled));
     c->last_unperm_tiled = tiled;
@@ -2833,8 +2205,8 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
       // excluded from the partition are not in it, so the array starts as zeros
       u32 *packed = c->pk_keys.as<u32>();
       HIPCHK(hipMemsetAsync(packed, 0, (size_t)N * 4, st));
-      if (c->n_parts && !c->last_count_sorted)
-        hipLaunchKernelGGL(k_read_map_bucket, dim3(c->n_parts), dim3(256), 0, st, c->pk_vals.as<u32>(),
+      if (count_bucketed(c))
+        hipLaunchKernelGGL(k_read_map_bucket, dim3(c->count_left.n_parts), dim3(256), 0, st, c->pk_vals.as<u32>(),
                            c->pslot.as<u32>(), c->slot_out.as<u64>(), c->pbeg.as<u32>(), c->ucount.as<u32>(), N, packed);
       else
         hipLaunchKernelGGL(k_read_map_part, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->pk_vals.as<u32>(),
@@ -2993,11 +2365,11 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   TRY(gkey_check(c));
   if (!timed) HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));
   if (!c->kev_on) s.ms_k_map = s.ms_map;
-  else if (c->last_count_lds) HIPCHK(hipEventElapsedTime(&s.ms_k_map, c->ev[3], c->kev[36]));   // first map kernel alone
+  else if (count_in_partition_order(c)) HIPCHK(hipEventElapsedTime(&s.ms_k_map, c->ev[3], c->kev[36]));   // first map kernel alone
   else s.ms_k_map = s.ms_map;   // ev[3]..ev[4] bracket exactly the k_read_map launch
-  if (c->kev_on && c->last_count_lds && c->last_unperm_tiled) HIPCHK(hipEventElapsedTime(&s.ms_k_unperm, c->kev[36], c->kev[41]));
-  if (c->kev_on && c->last_count_lds && c->last_part_tiled && !c->last_count_sorted) HIPCHK(hipEventElapsedTime(&s.ms_k_part, c->kev[39], c->kev[40]));
-  s.count_mode_used = (c->last_count_sorted ? 3u : c->last_count_lds ? (c->last_count_ordered ? 2u : 0u) : 1u) | (c->last_rec8 ? 0x100u : 0u);
+  if (c->kev_on && count_in_partition_order(c) && c->last_unperm_tiled) HIPCHK(hipEventElapsedTime(&s.ms_k_unperm, c->kev[36], c->kev[41]));
+  if (c->kev_on && count_part_timed(c)) HIPCHK(hipEventElapsedTime(&s.ms_k_part, c->kev[39], c->kev[40]));
+  s.count_mode_used = count_mode_used(c);
   if (c->kev_on) HIPCHK(hipEventElapsedTime(&s.ms_k_cluster, c->kev[2], c->kev[3]));
   for (u32 g = 0; c->kev_on && g < n_pair_segs; g++) {
     float t = 0;
@@ -3012,69 +2384,7 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   return state_publish(c, CtxState::RUN);
 }
 
-// ---- long words (humid_dedup_run_long*, kernels_long.hip.h): k = ceil(word_nt / 32) uint64 per read ----------------
-// Stage A: the sorting count of stage_count_wide for k words.  Leaves s_word (k per leaf) / s_cnt / s_first / s_slot
-// and, for stage C, the partition-order arrays pk_vals / pslot; count_mode_used is 3.
-static int stage_count_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N, u32 word_nt, humid_summary &s) {
-  hipStream_t st = c->stream;
-  const u32 k = (word_nt + 31) / 32, hbits = 2 * (word_nt - 32 * (k - 1));
-  c->last_count_lds = true;          // stage C walks pk_vals/pslot (k_read_map_part)
-  c->last_count_ordered = false;
-  c->last_count_sorted = true;
-  c->last_rec8 = false;
-  c->n_parts = 0;
-  const u32 grid = grid_stride_blocks(N);
-  ENSURE(c->pk_keys, (size_t)N * 8);
-  ENSURE(c->pad_word, (size_t)N * 8);
-  ENSURE(c->pk_vals, (size_t)N * 4);
-  ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
-  ENSURE(c->pslot, (size_t)N * 4);
-  ENSURE(c->w_sorted, (size_t)N * k * 8);
-  ENSURE(c->w_head, ((size_t)N + 1) * 4);
-  ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
-  EVREC(c->ev[0], st);
-  HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  EVREC(c->kev[0], st);
-  u64 *k0 = c->pk_keys.as<u64>(), *k1 = c->pad_word.as<u64>();
-  u32 *v = c->uniq_slot.as<u32>(), *v_other = c->pk_vals.as<u32>();   // v: the order so far
-  for (u32 pass = 0; pass < k; pass++) {                               // least significant uint64 first
-    const u32 j = k - 1 - pass;
-    hipLaunchKernelGGL(k_long_keys, dim3(grid), dim3(256), 0, st, d_words, d_filt, pass ? (const u32 *)v : (const u32 *)nullptr, N, k, j,
-                       hbits, k0, v, c->d_ctr);
-    TRY(sort_pairs<u64, u32>(c, k0, k1, v, v_other, N, 0, j ? 64 : (hbits < 64 ? hbits + 1 : 64)));   // the head: by (filtered,) head
-    std::swap(v, v_other);
-  }
-  if (hbits == 64) {                                                   // word_nt a multiple of 32: no spare key bit
-    hipLaunchKernelGGL(k_wide_keys_flag, dim3(grid), dim3(256), 0, st, d_filt, (const u32 *)v, N, (u32 *)k0);
-    TRY(sort_pairs<u32, u32>(c, (u32 *)k0, (u32 *)k1, v, v_other, N, 0, 1));
-    std::swap(v, v_other);
-  }
-  EVREC(c->kev[1], st);
-  u64 *sw = c->w_sorted.as<u64>();
-  hipLaunchKernelGGL(k_long_gather, dim3(grid_stride_blocks((u64)N * k)), dim3(256), 0, st, d_words, (const u32 *)v, N, k, hbits, sw);
-  hipLaunchKernelGGL(k_long_heads, dim3(grid), dim3(256), 0, st, (const u64 *)sw, N, k, c->d_ctr, c->w_head.as<u32>());
-  u64 n_unique = 0;
-  TRY(scan_total(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), N, &n_unique));
-  const u32 U = (u32)n_unique;
-  s.usable = c->usable = c->h_ctr[CTR_USABLE];
-  s.unique = c->U = U;
-  ENSURE(c->s_word, (size_t)(U + 1) * k * 8);
-  ENSURE(c->s_slot, (size_t)(U + 1) * 4);
-  ENSURE(c->s_cnt, (size_t)(U + 1) * 4);
-  ENSURE(c->s_first, (size_t)(U + 1) * 4);
-  ENSURE(c->w_start, (size_t)(U + 2) * 4);
-  ENSURE(c->slot_out, (size_t)(U + 1) * 8);
-  hipLaunchKernelGGL(k_long_unique, dim3(grid), dim3(256), 0, st, (const u64 *)sw, (const u32 *)v, c->w_head.as<u32>(),
-                     c->w_hpos.as<u32>(), N, k, c->d_ctr, c->s_word.as<u64>(), c->s_first.as<u32>(), c->w_start.as<u32>(),
-                     c->pslot.as<u32>(), c->pk_vals.as<u32>());
-  if (U)
-    hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U, c->s_cnt.as<u32>(),
-                       c->s_slot.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
-  HIPCHK(hipGetLastError());
-  return HUMID_OK;
-}
-
+// ---- long words (humid_dedup_run_long*, kernels_long.hip.h): k = ceil(word_nt / 32) uint64 per read; their count: stage_count_long ----
 // Pairs of leaves u < v within Hamming distance `distance` over all word_nt nucleotides, as a duplicate-free ascending
 // edge list in c->e_edges.  leaf: the U leaves ascending, k uint64 each.  Pigeonhole over distance + 1 contiguous
 // segments (lengths differ by at most one): two words within the distance agree on some segment, so per segment the
