@@ -274,7 +274,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
     state_reset(c);
     c->N = c->U = c->E = c->M = c->C = c->usable = 0;
     c->word_nt = n;
-    c->stage_map_timed = false;
+    c->timing.dense_map_timed = false;
     if (n_recv) {
       ENSURE(c->xr_zero, n_recv + 16);
       HIPCHK(hipMemsetAsync(c->xr_zero.p, 0, n_recv, st));
@@ -374,7 +374,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
       src.er.e = nullptr; src.er.cap_r = 0; src.er.cur = c->cg_cur.as<u32>(); src.er.far = c->e_edges.as<u64>(); src.er.n_far = (u32)E_e;
       src.recs = nullptr; src.n_recs = 0; src.segs = nullptr; src.cnt_by_id = gc; src.n_ids = n_ids;
       src.pairs_bound = E_e;
-      if (!c->lean_events) EVREC(c->ev[2], st);
+      TRY(mark_stage(c, c->ev[EV_GRAPH_BUILT]));
       TRY(cg_build(c, src, method, cgs));
       if (c->h_ctr[CTR_OVERFULL]) return fail(c, HUMID_E_INVALID, "internal: an edit-distance pair outside the unique words");
       M_e = cgs.M;
@@ -769,7 +769,7 @@ static int run_exchange_impl(humid_ctx *c, const humid_comm *cm, const uint64_t 
     src.er.e = nullptr; src.er.cap_r = 0; src.er.cur = c->cg_cur.as<u32>(); src.er.far = nullptr; src.er.n_far = 0;
     src.recs = nullptr; src.n_recs = 0; src.segs = &segs; src.cnt_by_id = nullptr; src.n_ids = n_ids;
     src.pairs_bound = n_recs_all;
-    if (!c->lean_events) EVREC(c->ev[2], st);
+    TRY(mark_stage(c, c->ev[EV_GRAPH_BUILT]));
     TRY(cg_build(c, src, method, cgs));
     if (c->h_ctr[CTR_OVERFULL]) return fail(c, HUMID_E_INVALID, "a pair record with an index outside the unique words");
     M_mine = cgs.M;
@@ -988,7 +988,7 @@ int humid_stage_count_dense(humid_ctx *c, const uint64_t *d_words, const uint8_t
   for (u32 q = 0; q < n_shards; q++) counts[q] = 0;
   if (n_unique) *n_unique = 0;
   if (n_usable) *n_usable = 0;
-  c->stage_map_timed = false;
+  c->timing.dense_map_timed = false;
   auto counted = [&] {                                       // every successful end of the count
     if (n_unique) *n_unique = c->U;
     if (n_usable) *n_usable = c->usable;
@@ -1054,11 +1054,11 @@ int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, cons
                        c->s_first.as<u32>(), c->s_slot.as<u32>(), U, c->slot_out.as<u64>());
   c->slots_done = false;
   ENSURE(c->own_packed, ((size_t)N + 1) * 4);
-  if (c->kev_on) EVREC(c->kev[37], st);
+  TRY(mark_kernel(c, c->kev[KEV_DENSE_MAP_BEGIN]));
   bool tiled = false;
-  if (count_in_partition_order(c)) TRY(unpermute_tiled(c, N, true, c->own_packed.as<u32>(), (u8 *)nullptr, c->kev[42], &tiled));
+  if (count_in_partition_order(c)) TRY(unpermute_tiled(c, N, true, c->own_packed.as<u32>(), (u8 *)nullptr, KEV_DENSE_MAP_MID, &tiled));
   if (tiled) {
-    // both kernels of the un-permute are inside kev[37]..kev[38]
+    // both kernels of the un-permute are inside the dense map's pair of kernel marks
   } else if (count_bucketed(c)) {
     HIPCHK(hipMemsetAsync(c->own_packed.p, 0, (size_t)N * 4, st));
     hipLaunchKernelGGL(k_read_map_bucket, dim3(c->count_left.n_parts), dim3(256), 0, st, c->pk_vals.as<u32>(),
@@ -1071,8 +1071,8 @@ int humid_stage_map_dense(humid_ctx *c, const uint32_t *d_local_cluster_id, cons
   } else
     hipLaunchKernelGGL(k_read_map_packed, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->slot_of_read.as<u32>(),
                        c->slot_out.as<u64>(), N, c->own_packed.as<u32>());
-  if (c->kev_on) EVREC(c->kev[38], st);
-  c->stage_map_timed = true;
+  TRY(mark_kernel(c, c->kev[KEV_DENSE_MAP_END]));
+  c->timing.dense_map_timed = true;
   HIPCHK(hipGetLastError());
   *d_packed = c->own_packed.as<u32>();     // queued on the context's stream
   return HUMID_OK;
@@ -1168,14 +1168,14 @@ int humid_stage_graph_edges(humid_ctx *c, const uint64_t *d_g_word, const uint32
   if (n_unique) {
     if (!d_g_word || !d_g_count || (n_edges && !d_edges)) return fail(c, HUMID_E_INVALID, "null buffer");
     u32 nps = 0;
-    static const u64 no_edges = 0;
+    const u64 *edges = edges_or_empty(d_edges, n_edges);
     if (word_nt > 32) {
       if ((uintptr_t)d_g_word & 15) return fail(c, HUMID_E_INVALID, "wide words must be 16-byte aligned on the device");
       TRY(stage_graph<W2>(c, (const W2 *)d_g_word, d_g_count, (u32)n_unique, word_nt, distance, method, s, nps,
-                          n_edges ? d_edges : &no_edges, n_edges));
+                          edges, n_edges));
     } else
     TRY(stage_graph(c, d_g_word, d_g_count, (u32)n_unique, word_nt, distance, method, s, nps,
-                    n_edges ? d_edges : &no_edges, n_edges));
+                    edges, n_edges));
     TRY(n_clusters_from_scan(c, (u32)n_unique, &c->C));
     s.clusters = c->C;
     if (d_cluster_id) *d_cluster_id = c->cid.as<u32>();
@@ -1660,14 +1660,14 @@ int humid_stage_unique_edges(humid_ctx *c, const uint64_t *d_edges, uint64_t n_e
 // this context (bench.py's roofline leg in multi-GPU runs); waits for the stream.
 int humid_stage_kernel_ms(humid_ctx *c, float *ms_k_insert, float *ms_k_map, uint32_t *count_mode_used) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
-  if (!state_dense_count(c) || (c->N && !c->stage_map_timed))
+  if (!state_dense_count(c) || (c->N && !c->timing.dense_map_timed))
     return fail(c, HUMID_E_STATE, "no completed humid_stage_count_dense + humid_stage_map_dense");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   float a = 0, b = 0;
   if (c->N) {
-    HIPCHK(hipEventElapsedTime(&a, c->kev[0], c->kev[1]));
-    if (c->kev_on) HIPCHK(hipEventElapsedTime(&b, c->kev[37], c->kev[38]));
+    HIPCHK(hipEventElapsedTime(&a, c->kev[KEV_INSERT_BEGIN], c->kev[KEV_INSERT_END]));
+    if (c->kev_on) HIPCHK(hipEventElapsedTime(&b, c->kev[KEV_DENSE_MAP_BEGIN], c->kev[KEV_DENSE_MAP_END]));
   }
   if (ms_k_insert) *ms_k_insert = a;
   if (ms_k_map) *ms_k_map = b;

@@ -323,6 +323,38 @@ int humid_dedup_run_keyed_posterior_device(humid_ctx *c, const uint64_t *d_words
   });
 }
 
+// The frame of a host entry point around its pass: four events around the two copies -- the first is the context's, the
+// other three live as long as the frame -- and the copy back with ms_h2d / ms_d2h.
+struct HostFrame {
+  humid_ctx *c;
+  hipEvent_t e[4] = {};
+  explicit HostFrame(humid_ctx *ctx) : c(ctx) { e[0] = c->ev[EV_HOST_FRAME]; }
+  HostFrame(const HostFrame &) = delete;
+  ~HostFrame() { for (int i = 1; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+  hipError_t create() {
+    hipError_t he = hipSuccess;
+    for (int i = 1; i < 4 && he == hipSuccess; i++) he = hipEventCreate(&e[i]);
+    return he;
+  }
+  hipError_t staging_begin() { return hipEventRecord(e[0], c->stream); }
+  hipError_t staging_end() { return hipEventRecord(e[1], c->stream); }
+  // behind a pass that succeeded: the results of n reads to the host and the two copy times into s.  The four event
+  // records count for the call (the pass's reset came behind the first two); a failed copy leaves no record of the run.
+  int copy_back(size_t n, uint32_t *cluster_id, uint8_t *keep, humid_summary &s) {
+    hipStream_t st = c->stream;
+    hipError_t he = hipEventRecord(e[2], st);
+    if (he == hipSuccess && n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipEventRecord(e[3], st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e[0], e[1]);
+    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e[2], e[3]);
+    if (he != hipSuccess) { state_reset(c); return fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
+    c->timing_left.event_records += 4;
+    return HUMID_OK;
+  }
+};
+
 // host buffers in, host buffers out: words + flags, or (bases != null) the raw symbols, packed on the device.
 // kind: what the run is (RUN_GROUPED: group may be null with n_groups = 1; RUN_KEYED on: key, null only without reads);
 // paired: the strand-symmetric run (RUN_PLAIN only; CtxState::paired).
@@ -354,9 +386,8 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
   hipStream_t st = c->stream;
   humid_summary s;
   memset(&s, 0, sizeof s);
-  hipEvent_t e0 = c->ev[5];
-  hipEvent_t e1, e2, e3;
-  HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2)); HIPCHK(hipEventCreate(&e3));
+  HostFrame frame(c);
+  HIPCHK(frame.create());
   size_t n = (size_t)n_reads;
   const size_t wbytes = word_nt > 32 ? 16 : 8;
   ENSURE(c->in_words, n * wbytes + 16);
@@ -364,7 +395,7 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
   ENSURE(c->out_cid, n * 4 + 8);
   ENSURE(c->out_keep, n + 8);
   if (bases) ENSURE(c->in_bases, n * word_nt + 16);
-  HIPCHK(hipEventRecord(e0, st));
+  HIPCHK(frame.staging_begin());
   if (n && bases) {
     // device-side packing (makeWord, src/fastq.cc:146-161): the host only gathered the symbols
     HIPCHK(hipMemcpyAsync(c->in_bases.p, bases, n * word_nt, hipMemcpyHostToDevice, st));
@@ -390,7 +421,7 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
     ENSURE(c->bc_qual_in, n * c->wl_nt + 8);
     HIPCHK(hipMemcpyAsync(c->bc_qual_in.p, qual, n * c->wl_nt, hipMemcpyHostToDevice, st));
   }
-  HIPCHK(hipEventRecord(e1, st));
+  HIPCHK(frame.staging_end());
   int rc = with_word_type(word_nt, [&](auto *w) {
     auto *d_w = (decltype(w))c->in_words.p;
     const u8 *d_f = c->in_filt.as<u8>();
@@ -407,18 +438,7 @@ static int run_host(humid_ctx *c, RunKind kind, bool paired, const uint64_t *wor
       default: return run_device(c, d_w, d_f, n_reads, word_nt, distance, method, d_cid, d_keep, &s);
     }
   });
-  if (rc == HUMID_OK) {
-    hipError_t he = hipEventRecord(e2, st);
-    if (he == hipSuccess && n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipEventRecord(e3, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
-    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
-    c->ev_records += 4;                                      // e0 .. e3 around the two copies (the pass's reset came behind the first two)
-    if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
-  }
-  (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
+  if (rc == HUMID_OK) rc = frame.copy_back(n, cluster_id, keep, s);
   if (rc == HUMID_OK && summary) *summary = s;
   return rc;
 }
@@ -490,29 +510,18 @@ int humid_dedup_run_long(humid_ctx *c, const uint64_t *words, const uint8_t *fil
   ENSURE(c->in_filt, n + 8);
   ENSURE(c->out_cid, n * 4 + 8);
   ENSURE(c->out_keep, n + 8);
-  hipEvent_t e0 = c->ev[5], e1, e2, e3;
-  HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2)); HIPCHK(hipEventCreate(&e3));
+  HostFrame frame(c);
+  HIPCHK(frame.create());
   int rc = HUMID_OK;
-  hipError_t he = hipEventRecord(e0, st);
+  hipError_t he = frame.staging_begin();
   if (he == hipSuccess && n) he = hipMemcpyAsync(c->in_words.p, words, n * wbytes, hipMemcpyHostToDevice, st);
   if (he == hipSuccess && n) he = hipMemcpyAsync(c->in_filt.p, filtered, n, hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipEventRecord(e1, st);
+  if (he == hipSuccess) he = frame.staging_end();
   if (he != hipSuccess) rc = fail(c, HUMID_E_HIP, "copy in: %s", hipGetErrorString(he));
   if (rc == HUMID_OK)
     rc = run_device_long(c, c->in_words.as<u64>(), c->in_filt.as<u8>(), n_reads, word_nt, distance, method, c->out_cid.as<u32>(),
                          c->out_keep.as<u8>(), &s);
-  if (rc == HUMID_OK) {
-    he = hipEventRecord(e2, st);
-    if (he == hipSuccess && n) he = hipMemcpyAsync(cluster_id, c->out_cid.p, n * 4, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && n) he = hipMemcpyAsync(keep, c->out_keep.p, n, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipEventRecord(e3, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_h2d, e0, e1);
-    if (he == hipSuccess) he = hipEventElapsedTime(&s.ms_d2h, e2, e3);
-    c->ev_records += 4;                                      // e0 .. e3 around the two copies (the pass's reset came behind the first two)
-    if (he != hipSuccess) { state_reset(c); rc = fail(c, HUMID_E_HIP, "copy back: %s", hipGetErrorString(he)); }
-  }
-  (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
+  if (rc == HUMID_OK) rc = frame.copy_back(n, cluster_id, keep, s);
   if (rc == HUMID_OK && summary) *summary = s;
   return rc;
 }
@@ -592,9 +601,10 @@ int humid_wait_overlap_info(humid_ctx *c, uint32_t *host_waits, uint32_t *overla
 int humid_stamp_info(humid_ctx *c, uint32_t *stamps_used, uint64_t stamps[4], uint32_t *event_records) {
   if (!c) return fail(nullptr, HUMID_E_INVALID, "ctx is null");
   if (c->state.holds == CtxState::NOTHING) return fail(c, HUMID_E_STATE, "no completed run or stage call in this context");
-  if (stamps_used) *stamps_used = c->last_stamp_timed ? 1u : 0u;
-  if (stamps) for (u32 k = 0; k < STAMP_N; k++) stamps[k] = c->last_stamp_live ? c->last_stamps[k] : 0;
-  if (event_records) *event_records = c->ev_records;
+  const TimingLeft &left = c->timing_left;
+  if (stamps_used) *stamps_used = left.stamp_timed ? 1u : 0u;
+  if (stamps) for (u32 k = 0; k < STAMP_N; k++) stamps[k] = left.stamp_live ? left.stamps[k] : 0;
+  if (event_records) *event_records = left.event_records;
   return HUMID_OK;
 }
 

@@ -151,7 +151,7 @@ enum CountRoad : u8 {
 struct CountLeft {
   CountRoad road = COUNT_GLOBAL;
   u32 n_parts = 0;               // buckets (0: the road has none)
-  bool part_tiled = false;       // kev[39]..kev[40] bracket a second-level scatter
+  bool part_tiled = false;       // KEV_PART_BEGIN .. KEV_PART_END bracket a second-level scatter
   const u32 *cursor2 = nullptr;  // COUNT_REC: reads per bucket
 };
 // The remembered answer of prefix_fits_ordered for (reads, word length, key map): the sampled histogram and its host
@@ -160,6 +160,47 @@ struct OrderedMemo {
   bool valid = false, fits = false;
   u32 n = 0, nt = 0;
   u64 lo = 0, scale = 0;
+};
+
+// ---- the timing of a pass: named event slots and two records (the functions over them: pass_timing.hip.h; the table
+// of who records and who reads which slot: DESIGN.md, "The events of a pass") ----
+#define STAMP_N 4
+enum StageEvent : u32 {              // humid_ctx::ev
+  EV_PASS_START, EV_COUNT_END, EV_GRAPH_BUILT, EV_CLUSTERS_DONE, EV_PASS_END,
+  EV_HOST_FRAME,                     // the first of the four events around a host entry point's copies (HostFrame)
+  EV_N
+};
+enum { KEV_PAIR_COMBOS = 8 };        // combinations of a neighbour search that have events of their own
+enum KernelEvent : u32 {             // humid_ctx::kev
+  KEV_INSERT_BEGIN, KEV_INSERT_END,  // the count kernel
+  KEV_CLUSTER_BEGIN, KEV_CLUSTER_END,
+  KEV_PAIRS_FILL,                    // (begin, end) per combination: kev_pairs()
+  KEV_PAIRS_COUNT = KEV_PAIRS_FILL + 2 * KEV_PAIR_COMBOS,
+  KEV_MAP_MID = KEV_PAIRS_COUNT + 2 * KEV_PAIR_COMBOS,   // behind the first kernel of the read map
+  KEV_DENSE_MAP_BEGIN, KEV_DENSE_MAP_END,                // humid_stage_map_dense
+  KEV_PART_BEGIN, KEV_PART_END,      // the count's second-level scatter
+  KEV_UNPERM_END,                    // behind k_unperm_window
+  KEV_DENSE_MAP_MID,                 // between the two kernels of the dense map's tiled un-permute
+  KEV_N
+};
+static_assert(EV_N == 6 && KEV_PAIRS_COUNT == 20 && KEV_MAP_MID == 36 && KEV_N == 43, "the event slots");
+// What the pass now running has decided about its timing.  All false between calls, but for the last two, which the
+// stage calls behind a map read: PassTimingGuard opens and closes it.
+struct PassTiming {
+  bool lean = false;             // the per-kernel timing is off: of the stage events only pass start and pass end are recorded, and the count kernel's pair
+                                 // (an event record between two kernels is a marker the second one waits behind: ~4 us of idle GPU each, 8 per pass)
+  bool stamp_ok = false;         // before the first launch: this pass may take its times from device stamps (cleared when a count is discarded)
+  bool stamp_live = false;       // stage_count_rec counted this pass: its kernels store the stamps
+  bool stamp_timed = false;      // ... and the pass is lean: no frame mark is recorded, the summary's times are the stamps'
+  bool kernels_quiet = false;    // cg_build_full: the kernel marks are off whatever the option says
+  bool unperm_tiled = false;     // KEV_MAP_MID .. KEV_UNPERM_END bracket k_unperm_window of the last map
+  bool dense_map_timed = false;  // KEV_DENSE_MAP_BEGIN .. _END bracket the last humid_stage_map_dense
+};
+// What the last mutating call left for humid_stamp_info: cleared whole by state_reset
+struct TimingLeft {
+  u64 stamps[STAMP_N] = {};
+  bool stamp_live = false, stamp_timed = false;
+  u32 event_records = 0;         // hipEventRecord calls of that call: host stores only (EVREC, HostFrame)
 };
 
 struct humid_ctx {
@@ -179,16 +220,12 @@ struct humid_ctx {
   ull ctr_seq = 0;
   // Device stamps (option "device_stamps"): the four points a lean pass is timed between -- pass start, count kernel
   // start and end, pass end -- as the 100 MHz wall clock read by thread 0 of workgroup 0 of a kernel that runs there
-  // anyway, where the events ev[0], kev[0], kev[1], ev[4] would put four markers into the stream.  d_stamp: STAMP_N
+  // anyway, where the four frame marks would put as many markers into the stream.  d_stamp: STAMP_N
   // u64 of their own (on no ZeroList); the pass's last k_publish_counters copies them to h_ctr[STAMP_AT ..].
   u64 *d_stamp = nullptr;
   bool device_stamps = true;   // the option
-  bool stamp_ok = false;       // run_device, before the first launch: this pass may take its times from stamps (cleared when a count is discarded)
-  bool stamp_live = false;     // stage_count_rec counted this pass: its kernels store the stamps
-  bool stamp_timed = false;    // ... and the pass is lean: none of the four events is recorded, the summary's times are the stamps'
-  bool last_stamp_timed = false, last_stamp_live = false;   // of the last mutating call (humid_stamp_info)
-  u64 last_stamps[4] = {};
-  u32 ev_records = 0;          // hipEventRecord calls of the last mutating call: host stores only (EVREC)
+  PassTiming timing;           // of the pass now running
+  TimingLeft timing_left;      // of the last mutating call
   const u32 *gf_valid = nullptr; // set by the last bucket order: device count of the words it holds (padded grouping), or null
   u32 *ucur_clean = nullptr;     // the un-permute's bin cursors at this address are all zero
   DBuf gf_cur;                    // cursors of the padded grouping (512 u32, kept at zero between uses)
@@ -260,9 +297,7 @@ struct humid_ctx {
   bool x_hist_done = false, x_peer_failed = false;   // humid_dedup_run_exchange: the pass's first gather is done; a peer's failure was seen
   bool route_checked = true;        // no humid_stage_route since the last humid_stage_route_check
   const u32 *route_bad = nullptr;   // device flag of the last humid_stage_route
-  bool last_unperm_tiled = false;   // kev[36]..kev[41] bracket k_unperm_window of the last map
   OrderedMemo ordered_memo;
-  bool stage_map_timed = false;                                                   // kev[37..38] bracket the last humid_stage_map_dense
   u32 g_wpr = 1;                                                                  // uint64 per word of g_word
   bool slots_done = false;   // slot_out already written by k_finalize_nodes (one-GPU fusion)
   int count_mode = 0;        // 0: hash-partitioned LDS tables (default), 1: one global HBM table
@@ -377,11 +412,9 @@ struct humid_ctx {
   DBuf uniq_word, s_word, s_slot, s_cnt, s_first;            // unique words (walk order)
   DBuf deg, nbr_off, nbr_idx, seg_k0, seg_v0, seg_ks, seg_vs, seg_ws, csize, cur;
   DBuf parent, mk0, mk1, cl_of, maxleaf, cl_size, flag, pos, cid, ismax, stk, tmp, scratch;
-  hipEvent_t ev[6] = {};
-  bool lean_events = false;  // set by run_device while the per-kernel timing is off: only ev[0], ev[4] and the count kernel's pair are recorded
-                             // (an event record between two kernels is a marker the second one waits behind: ~4 us of idle GPU each, 8 per pass)
-  bool kev_on = false;       // option "kernel_timing": events around the single kernels beyond the count kernel's kev[0..1] (13 more records per pass: 20-45 us)
-  hipEvent_t kev[44] = {};   // per-kernel timing: [0,1] insert, [2,3] cluster, [4..19] pairs fill, [20..35] pairs count
+  hipEvent_t ev[EV_N] = {};    // by StageEvent
+  bool kev_on = false;         // option "kernel_timing": events around the single kernels beyond the count kernel's pair (13 more records per pass: 20-45 us)
+  hipEvent_t kev[KEV_N] = {};  // by KernelEvent
   const void *g_word = nullptr;  // arrays stage B ran on (u64 or W2 per word)
   const u32 *g_cnt = nullptr;
   u32 gU = 0;
@@ -411,9 +444,6 @@ static int fail(humid_ctx *c, int code, const char *fmt, ...) {
                   #expr, hipGetErrorString(_e), __FILE__, __LINE__);                        \
   } while (0)
 
-// every event record of the library's passes goes through here: counted for humid_stamp_info
-#define EVREC(ev, st) do { c->ev_records++; HIPCHK(hipEventRecord((ev), (st))); } while (0)
-#define STAMP_N 4
 #define STAMP_AT (CTR_N + 2)   // h_ctr: CTR_N counters, the sequence word, the grouped runs' check word, the stamps
 // what the stages behind a count ask of its record
 static inline bool count_in_partition_order(const humid_ctx *c) { return c->count_left.road != COUNT_GLOBAL; }   // stage C walks pk_vals / pslot (or the records), not slot_of_read
@@ -593,7 +623,7 @@ static int scan_total(humid_ctx *c, const u32 *in, u32 *out, u64 n, u64 *total) 
 // ---- the record of CtxState: one reset, one publish, the predicates ----------------------------------------------
 static inline void state_reset(humid_ctx *c) {
   c->state = CtxState{}; c->roads = humid_run_roads{}; c->wo_waits = c->wo_overlapped = 0;
-  c->ev_records = 0; c->last_stamp_timed = c->last_stamp_live = false; memset(c->last_stamps, 0, sizeof c->last_stamps);
+  c->timing_left = TimingLeft{};
 }
 // one retry of the call now running (HUMID_ROAD_*): behind the host wait that showed it, a store on the host
 static inline void road_taken(humid_ctx *c, u8 road) {
@@ -731,6 +761,8 @@ static ComboPlan make_plan(u32 n, u32 d, u64 U, u32 force_segments, bool short_l
   return p;
 }
 
+#include "pass_timing.hip.h"
+
 // ---- cluster stage shared by the full pipeline and the explicit-graph entry point ------
 // The arrays a graph lives in: per unique word (legacy view: deg / nbr_off / ... of the context) or per
 // COMPACT node (cg_* buffers, kernels_cgraph.hip.h).  n nodes, cnt[n] their counts.
@@ -752,7 +784,7 @@ static GraphArrays legacy_arrays(humid_ctx *c) {
 static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt, u32 U, u64 M, u64 Mbig, u32 method,
                            bool trivial_done = false, const u32 *late_m = nullptr, u64 *late_m_out = nullptr) {
   hipStream_t st = c->stream;
-  if (!trivial_done && c->kev_on) EVREC(c->kev[2], st);
+  if (!trivial_done) TRY(mark_kernel(c, c->kev[KEV_CLUSTER_BEGIN]));
   if (trivial_done) {
   } else if (method == HUMID_METHOD_MAXIMUM)
     hipLaunchKernelGGL(k_cluster_trivial<true>, dim3(blocks_for(U)), dim3(256), 0, st, g.deg, g.parent, g.csize, U, g_cnt, g.off,
@@ -802,7 +834,7 @@ static int cluster_kernels(humid_ctx *c, const GraphArrays &g, const u32 *g_cnt,
       }
     }
   }
-  if (c->kev_on) EVREC(c->kev[3], st);
+  TRY(mark_kernel(c, c->kev[KEV_CLUSTER_END]));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -827,7 +859,7 @@ static int cluster_stage(humid_ctx *c, const u32 *g_cnt, u32 U, u64 M, u64 Mbig,
 
 static int n_clusters_from_scan(humid_ctx *c, u32 U, u64 *out) {
   // (the pass's last host wait: both values through the counters' mapped store)
-  TRY(read_counters(c, c->pos.as<u32>() + (U - 1), c->flag.as<u32>() + (U - 1), nullptr, c->stamp_live ? c->d_stamp : nullptr));
+  TRY(read_counters(c, c->pos.as<u32>() + (U - 1), c->flag.as<u32>() + (U - 1), nullptr, c->timing.stamp_live ? c->d_stamp : nullptr));
   *out = (c->h_ctr[CTR_N - 1] & 0xffffffffull) + (c->h_ctr[CTR_N - 2] & 0xffffffffull);
   return HUMID_OK;
 }
@@ -881,7 +913,7 @@ static ComboFields plan_fields(const ComboPlan &plan, u32 cb) {
 // A neighbour search that may ride in a grouping (stage_graph_compact): `group` is the search of the combination
 // being grouped, walked inside k_group_fine.  Taken only where every coarse bin is certain to be a small one (padded
 // bins of at most GF_SMALL words) -- did_group says whether; if not the caller launches k_pairs_append.
-// ev_group: events around the launch the search rode in (null: none).
+// ev_group: events around the launch the search rode in, as kernel marks (null: none).
 struct GroupRide {
   PairSearchDev group;
   bool did_group = false;
@@ -938,9 +970,9 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
       const FieldsRecs rsrc{W, sq, wb - d1};
       hipLaunchKernelGGL((k_p8_scatter1<FieldsRecs, 1024, CTR_GOVER>), dim3(tiles1), dim3(1024), 0, st, rsrc, n, wb, d1, ibits, cap1, cursor1,
                          c->seg_k0.as<u64>(), c->d_ctr);
-      if (ride->ev_group[0]) EVREC(ride->ev_group[0], st);
+      if (ride->ev_group[0]) TRY(mark_kernel(c, ride->ev_group[0]));
       group_fine_recs_with_search(c, src, sq, c->seg_k0.as<u64>(), cursor1, d1, d2, ibits, cap1, ride->group);
-      if (ride->ev_group[1]) EVREC(ride->ev_group[1], st);
+      if (ride->ev_group[1]) TRY(mark_kernel(c, ride->ev_group[1]));
       ride->did_group = ride->no_order = true;
       HIPCHK(hipGetLastError());
       return HUMID_OK;
@@ -974,9 +1006,9 @@ static int group_words_by_stretch(humid_ctx *c, const ComboPlan &plan, u32 cb, c
   const u32 largest = padded ? cap1 : n;
   if (ride_ok) {
     if constexpr (std::is_same<SRC, FieldsSrc>::value) {
-      if (ride->ev_group[0]) EVREC(ride->ev_group[0], st);
+      if (ride->ev_group[0]) TRY(mark_kernel(c, ride->ev_group[0]));
       group_fine_with_search(c, src, c->seg_k0.as<u64>(), c->seg_v0.as<u32>(), cbase, d1, d2, ws, vs, cap1, ride->group);
-      if (ride->ev_group[1]) EVREC(ride->ev_group[1], st);
+      if (ride->ev_group[1]) TRY(mark_kernel(c, ride->ev_group[1]));
       ride->did_group = true;
     }
   } else
@@ -1264,14 +1296,14 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
   // one pass over the combinations: PM_COUNT makes the bucket orders and leaves degrees and the component forest,
   // PM_FILL walks the same orders again and writes the CSR rows, the tiles of the large buckets behind each
   auto search_pass = [&](int mode) -> int {
-    const u32 ev0 = mode == PM_COUNT ? 20 : 4;
+    const PairPhase phase = mode == PM_COUNT ? PAIRS_COUNT : PAIRS_FILL;
     for (u32 seg = 0; seg < plan.ncombo; seg++) {
       if (seg && mode == PM_COUNT) TRY(bucket_order<WT>(c, plan, seg, g_word, U, seg_ws<WT>(c, seg, U), seg_vs(c, seg, U)));
       const Walked<WT> w = walked_seg<WT>(c, plan, seg, g_word, U);
-      if (seg < 8 && c->kev_on) EVREC(c->kev[ev0 + 2 * seg], st);
+      TRY(mark_pairs(c, phase, seg, 0));
       pairs_csr<WT>(c, ps, w, mode, 0u, U, sink(seg), &c->d_ctr[CTR_BIGMASK]);
       if (mode == PM_FILL && (big_mask >> seg & 1)) tiles_csr<WT>(c, ps, w, d_runs[seg], h_runs[seg], PM_FILL, sink(seg));
-      if (seg < 8 && c->kev_on) EVREC(c->kev[ev0 + 1 + 2 * seg], st);
+      TRY(mark_pairs(c, phase, seg, 1));
     }
     HIPCHK(hipGetLastError());
     return HUMID_OK;
@@ -1329,7 +1361,7 @@ static int stage_graph(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, 
     hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(U)), dim3(256), 0, st, c->nbr_off.as<u32>(), U,
                        c->nbr_idx.as<u32>());
   }
-  if (!c->lean_events) EVREC(c->ev[2], st);
+  TRY(mark_stage(c, c->ev[EV_GRAPH_BUILT]));
 
   // clusters
   TRY(cluster_stage(c, g_cnt, U, M, Mbig, method));
@@ -1445,7 +1477,7 @@ static int cg_build_back(humid_ctx *c, CgSource &src, u32 method, CgStatus &out)
                        c->cg_curs.as<u32>(), g.idx, src.no_wait ? (u32 *)nullptr : c->small.as<u32>(), gx, (const u32 *)g.deg, g.parent, Mb, g.csize, m_dev, r_first);
   }
   hipLaunchKernelGGL(k_sort_lists, dim3(blocks_for(Mb)), dim3(256), 0, st, (const u32 *)g.off, Mb, g.idx);
-  if (c->kev_on) EVREC(c->kev[2], st);
+  TRY(mark_kernel(c, c->kev[KEV_CLUSTER_BEGIN]));
   const u32 tg = (u32)std::min<u64>(std::max<u64>(blocks_for(Mb), 1), 512);
   if (method == HUMID_METHOD_MAXIMUM)
     hipLaunchKernelGGL(k_cg_trivial<true>, dim3(tg), dim3(256), 0, st, (const u32 *)g.parent, (const u32 *)g.csize, m_dev,
@@ -1483,7 +1515,7 @@ static int cg_cluster_rest(humid_ctx *c, u32 n_ids, u64 M, u64 Mbig, u32 method,
   const GraphArrays g = cg_arrays(c);
   ENSURE(c->cg_nblk, ((size_t)n_blk + 1) * 4);
   if (M > 0) TRY(cluster_kernels(c, g, c->cg_ncnt.as<u32>(), (u32)M, M, Mbig, method, true, fetch ? late_m : (const u32 *)nullptr, late_m_out));
-  else if (c->kev_on) EVREC(c->kev[3], st);
+  else TRY(mark_kernel(c, c->kev[KEV_CLUSTER_END]));
   if (M > 0)
     hipLaunchKernelGGL(k_noncreator_bits, dim3(blocks_for(M)), dim3(256), 0, st, (const u32 *)g.cl_of, c->cg_nodes.as<u32>(), (u32)M,
                        c->cg_nbits.as<u32>(), late_m);
@@ -1582,10 +1614,10 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
     }
     // a launch of k_pairs_append over the order of combination seg, between its two events
     auto search_alone = [&](u32 seg) -> int {
-      if (seg < 8 && c->kev_on) EVREC(c->kev[20 + 2 * seg], st);
+      TRY(mark_pairs(c, PAIRS_COUNT, seg, 0));
       pairs_append<WT>(c, ps, walked_seg<WT>(c, plan, seg, g_word, U), er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK],
                        (u32 *)&c->d_ctr[CTR_EOVER], seg_valid[seg]);
-      if (seg < 8 && c->kev_on) EVREC(c->kev[21 + 2 * seg], st);
+      TRY(mark_pairs(c, PAIRS_COUNT, seg, 1));
       return HUMID_OK;
     };
     // fused_search: while an order is MADE its search rides in the grouping (GroupRide; the events then bracket the
@@ -1610,7 +1642,8 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
           if constexpr (std::is_same<WT, u64>::value) {
             if (ride_now) {
               ride.group = pairs_append_dev(ps, w_from<u64>(plan.mask[seg]), seg, er, c->cg_bits.as<u32>(), multi, &c->d_ctr[CTR_BIGMASK], (u32 *)&c->d_ctr[CTR_EOVER]);
-              if (seg < 8 && c->kev_on) { ride.ev_group[0] = c->kev[20 + 2 * seg]; ride.ev_group[1] = c->kev[21 + 2 * seg]; }
+              if (seg < KEV_PAIR_COMBOS)                  // (kernel marks: recorded with the option only)
+                for (u32 end = 0; end < 2; end++) ride.ev_group[end] = c->kev[kev_pairs(PAIRS_COUNT, seg, end)];
               ride.word_bits = word_nt <= 32 ? 2 * word_nt : 0u;
             }
           }
@@ -1762,10 +1795,10 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
       c->cg_m_late = !fetch;
       M = std::min<u64>(U, 2 * R);                       // (a bound)
       Mbig = 0;
-    } else if (c->kev_on) EVREC(c->kev[2], st);   // (no rest pair, no cg_build: the cluster kernels' first event is its)
+    } else TRY(mark_kernel(c, c->kev[KEV_CLUSTER_BEGIN]));   // (no rest pair, no cg_build: the cluster kernels' first event is its)
   }
   s.edges = c->E = E;
-  if (!c->lean_events) EVREC(c->ev[2], st);
+  TRY(mark_stage(c, c->ev[EV_GRAPH_BUILT]));
   u64 M_rest = 0;
   TRY(cg_cluster_rest(c, U, M, Mbig, method, late_m, fetch, &M_rest));
   if (split) M = 2 * n_iso + (fetch ? M_rest : 0);       // (cg_m_late: n_clusters_compact adds the rest graph's nodes)
@@ -1792,7 +1825,7 @@ static int stage_graph_compact(humid_ctx *c, const WT *g_word, const u32 *g_cnt,
 // clusters = unique words - graph nodes that created no cluster (the pass's last host wait)
 static int n_clusters_compact(humid_ctx *c, u32 U, u64 *out) {
   TRY(read_counters(c, c->cg_nblk.as<u32>() + c->cg_nblocks, c->cg_m_late ? c->cg_blk.as<u32>() + c->cg_nblocks : (const u32 *)nullptr,
-                    nullptr, c->stamp_live ? c->d_stamp : nullptr));
+                    nullptr, c->timing.stamp_live ? c->d_stamp : nullptr));
   *out = (u64)U - (c->h_ctr[CTR_N - 1] & 0xffffffffull);
   if (c->cg_m_late) { c->M += c->h_ctr[CTR_N - 2] & 0xffffffffull; c->cg_m_late = false; }   // (the rest graph's nodes)
   return HUMID_OK;
@@ -1805,13 +1838,13 @@ static int n_clusters_compact(humid_ctx *c, u32 U, u64 *out) {
 // (k_pairs_split only reads), so the unsplit build and the cluster kernels run over them once, with cg_bits as the node
 // bitmap.  Nothing the run delivered is touched: not slot_out, not cid / keep, not the summary (cg_nbits / cg_nblk, which
 // the ids came from, stay as they are too).
-// It runs after the pass: the pass's per-kernel events (kev[2], kev[3]) are not recorded again, and d_ctr / h_ctr /
+// It runs after the pass: the pass's kernel marks (the cluster kernels' pair) are not recorded again, and d_ctr / h_ctr /
 // c->small, which it overwrites, are read by nothing once a pass has returned.  The build relabels the pair list in
 // place, so a failure halfway leaves nothing to build from: cg_broken, and the accessors fail from then on.
 static int cg_build_full(humid_ctx *c) {
   hipStream_t st = c->stream;
-  struct NoKernelEvents { humid_ctx *c; bool on; ~NoKernelEvents() { c->kev_on = on; } } quiet{c, c->kev_on};
-  c->kev_on = false;
+  struct Quiet { PassTiming &t; ~Quiet() { t.kernels_quiet = false; } } quiet{c->timing};
+  c->timing.kernels_quiet = true;
   // (nor does its wait count among the run's: humid_wait_overlap_info)
   struct RunsWaits { humid_ctx *c; u32 w, o; ~RunsWaits() { c->wo_waits = w; c->wo_overlapped = o; } } waits{c, c->wo_waits, c->wo_overlapped};
   {
@@ -2130,8 +2163,8 @@ static int paired_edges(humid_ctx *c, const WT *g_word, u32 U, u32 word_nt, u32 
 // (pk_vals = read, pslot = padded slot of its word) -> cluster_id / keep in read order, or, packed,
 // cluster id | keep << 31 per read.  *done = false: the read set is too large for the bin table
 // (more than 2048 windows of 32 K reads) or the option is off; the caller takes the one-kernel form.
-// ev_mid is recorded between the two kernels.
-static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_keep, hipEvent_t ev_mid, bool *done) {
+// The stage mark ev_mid is recorded between the two kernels.
+static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_keep, KernelEvent ev_mid, bool *done) {
   hipStream_t st = c->stream;
   *done = false;
   if (!c->use_tile_partition || N == 0) return HUMID_OK;
@@ -2168,7 +2201,7 @@ static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_k
   else
   hipLaunchKernelGGL(k_unperm_bins, dim3((N + PT_TILE - 1) / PT_TILE), dim3(1024), 0, st, c->pk_vals.as<u32>(),
                      c->pslot.as<u32>(), c->slot_out.as<u64>(), n_pos_dev, N, N, wshift, n_bins, ucur, rec);
-  if (!c->lean_events) EVREC(ev_mid, st);
+  TRY(mark_stage(c, c->kev[ev_mid]));
   if (packed) {
     if (wshift == 14) hipLaunchKernelGGL((k_unperm_window<true, 14>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
     else hipLaunchKernelGGL((k_unperm_window<true, 15>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
@@ -2176,7 +2209,7 @@ static int unpermute_tiled(humid_ctx *c, u32 N, bool packed, u32 *d_cid, u8 *d_k
     if (wshift == 14) hipLaunchKernelGGL((k_unperm_window<false, 14>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
     else hipLaunchKernelGGL((k_unperm_window<false, 15>), dim3(n_bins), dim3(UW_THREADS), 0, st, rec, ucur, N, d_cid, d_keep);
   }
-  if (c->kev_on) EVREC(c->kev[41], st);
+  TRY(mark_kernel(c, c->kev[KEV_UNPERM_END]));
   HIPCHK(hipGetLastError());
   c->ucur_clean = ucur;
   *done = true;
@@ -2194,11 +2227,14 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
   if (U > 0 && !fused)
     hipLaunchKernelGGL(k_slot_results, dim3(blocks_for(U)), dim3(256), 0, st, l_cid, l_ismax,
                        c->s_first.as<u32>(), c->s_slot.as<u32>(), U, c->slot_out.as<u64>());
-  if (!c->lean_events) EVREC(c->ev[3], st);
+  TRY(mark_stage(c, c->ev[EV_CLUSTERS_DONE]));
   if (count_in_partition_order(c)) {
     bool tiled = false;
-    TRY(unpermute_tiled(c, N, false, d_cid, d_keep, c->kev[36], &tiled));
-    c->last_unperm_tiled = tiled;
+    // KEV_MAP_MID is a STAGE mark in the tiled form (unpermute_tiled: recorded unless the pass is lean) and a KERNEL mark
+    // in the one-kernel form below (recorded with kernel_timing).  They differ with HUMID_ALL_EVENTS set and
+    // kernel_timing off: the tiled form records it then, the one-kernel form does not; nobody reads it there.
+    TRY(unpermute_tiled(c, N, false, d_cid, d_keep, KEV_MAP_MID, &tiled));
+    c->timing.unperm_tiled = tiled;
     if (!tiled) {
       // round-1 form: one scattered 4-byte store per read, then a coalesced split.  pk_keys (the
       // partitioned keys) is dead by now: reuse it for the packed per-read results; reads that were
@@ -2211,13 +2247,13 @@ static int stage_map(humid_ctx *c, const u32 *l_cid, const u8 *l_ismax, u32 N, u
       else
         hipLaunchKernelGGL(k_read_map_part, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->pk_vals.as<u32>(),
                            c->pslot.as<u32>(), c->slot_out.as<u64>(), N, packed);
-      if (c->kev_on) EVREC(c->kev[36], st);
+      TRY(mark_kernel(c, c->kev[KEV_MAP_MID]));
       hipLaunchKernelGGL(k_split_out, dim3(grid_stride_blocks(N)), dim3(256), 0, st, packed, N, d_cid, d_keep);
     }
   } else
     hipLaunchKernelGGL(k_read_map, dim3(grid_stride_blocks(N)), dim3(256), 0, st, c->slot_of_read.as<u32>(),
                        c->slot_out.as<u64>(), N, d_cid, d_keep);
-  if (!c->stamp_timed) EVREC(c->ev[4], st);
+  TRY(mark_frame(c, c->ev[EV_PASS_END]));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -2260,6 +2296,22 @@ static int check_run_args(humid_ctx *c, u64 n_reads, u32 word_nt, u32 method, u3
 template <class F>
 static int with_word_type(u32 word_nt, F f) { return word_nt > 32 ? f((const W2 *)nullptr) : f((const u64 *)nullptr); }
 
+// The pair list of a graph stage whose pairs are GIVEN: a null list means "search", so no pair is an empty list
+static inline const u64 *edges_or_empty(const u64 *edges, u64 n_edges) {
+  static const u64 no_edges = 0;
+  return n_edges ? edges : &no_edges;
+}
+// The graph stage of a run: the compact one or the per-unique-word one (option compact_graph).  given: the n_edges
+// pairs of `edges` are the neighbour pairs (duplicate-free, ascending); else the stage searches them.
+template <class WT>
+static int graph_stage(humid_ctx *c, const WT *g_word, const u32 *g_cnt, u32 U, u32 word_nt, u32 distance, u32 method, humid_summary &s,
+                       u32 &n_pair_segs, bool given = false, const u64 *edges = nullptr, u64 n_edges = 0) {
+  const u64 *ext = given ? edges_or_empty(edges, n_edges) : nullptr;
+  if (!given) n_edges = 0;
+  return c->use_compact ? stage_graph_compact<WT>(c, g_word, g_cnt, U, word_nt, distance, method, s, n_pair_segs, ext, n_edges)
+                        : stage_graph<WT>(c, g_word, g_cnt, U, word_nt, distance, method, s, n_pair_segs, ext, n_edges);
+}
+
 // ---- the full pipeline on device buffers (one GPU) -------------------------------------------
 // WT = u64: word_nt <= 32, one uint64 per read.  WT = W2: 33 <= word_nt <= 64, two per read.
 template <class WT>
@@ -2278,21 +2330,12 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
   humid_summary s;
   memset(&s, 0, sizeof s);
   s.total = n_reads;
-  c->last_unperm_tiled = false;
-  c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
-  c->word_nt = word_nt; c->distance = distance; c->method = method;
-  c->gU = 0;
+  pass_begin(c, n_reads, word_nt, distance, method);
   if (N == 0) { if (sum) *sum = s; return state_publish(c, CtxState::RUN); }
-  // the stages' own events only with the per-kernel timing (ms_count .. ms_map are 0 without it; ms_total and the
-  // count kernel's time are always measured: by device stamps where the pass takes the record road, by events elsewhere)
-  struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = c->stamp_ok = c->stamp_live = c->stamp_timed = false; } } lean_guard{c};
-  c->lean_events = !c->kev_on && getenv("HUMID_ALL_EVENTS") == nullptr;
-  // decided once, before the first launch: a plain run of one-word words whose counters reach the host through the
-  // mapped mirror may take its four times from device stamps.  stage_count_rec takes the offer up (no other count road
-  // does) and withdraws it when its count is discarded; the graph stage and the pass's end are the same on every road.
-  c->stamp_live = c->stamp_timed = false;
-  c->stamp_ok = !WIDE && c->device_stamps && c->d_stamp && c->pass_kind == RUN_PLAIN && !c->pd_run && !(c->edit && distance >= 2) &&
-                c->h_ctr_dev && !c->no_poll;
+  // a plain run of one-word words whose counters reach the host through the mapped mirror may take its four times from
+  // device stamps
+  PassTimingGuard timing(c, !WIDE && c->device_stamps && c->d_stamp && c->pass_kind == RUN_PLAIN && !c->pd_run && !(c->edit && distance >= 2) &&
+                            c->h_ctr_dev && !c->no_poll);
   if constexpr (WIDE) TRY(stage_count_wide(c, d_words, d_filt, N, word_nt, s));
   else TRY(stage_count(c, d_words, d_filt, N, word_nt, 0ull, ~0ull, 0, s));
   TRY(gkey_check(c));                                        // (the count stage's host wait has seen k_gkey_words)
@@ -2305,81 +2348,21 @@ static int run_device(humid_ctx *c, const WT *d_words, const u8 *d_filt, u64 n_r
     return state_publish(c, CtxState::RUN);
   }
   u32 n_pair_segs = 0;
-  if (c->pd_run && distance >= 1) {
-    // strand-symmetric run: the pairs of the plain and of the mirror join (paired_edges), given to the graph stage
-    u64 E = 0;
-    TRY(paired_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &E));
-    static const u64 no_edges = 0;
-    if (c->use_compact)
-      TRY(stage_graph_compact<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
-                                  E ? c->e_edges.as<u64>() : &no_edges, E));
-    else
-      TRY(stage_graph<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
-                          E ? c->e_edges.as<u64>() : &no_edges, E));
-  } else if (c->edit && distance >= 2) {
-    // -e: Levenshtein neighbours (src/humid.cc:140-158); distance <= 1 IS the Hamming search
-    u64 E = 0;
-    TRY(edit_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &E));
-    static const u64 no_edges = 0;
-    if (c->use_compact)
-      TRY(stage_graph_compact<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
-                                  E ? c->e_edges.as<u64>() : &no_edges, E));
-    else
-      TRY(stage_graph<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs,
-                          E ? c->e_edges.as<u64>() : &no_edges, E));
-  } else if (c->use_compact)
-    TRY(stage_graph_compact<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs));
-  else
-    TRY(stage_graph<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs));
+  u64 n_given = 0;
+  const bool paired = c->pd_run && distance >= 1, edit = !paired && c->edit && distance >= 2;
+  // strand-symmetric run: the pairs of the plain and of the mirror join (paired_edges), given to the graph stage
+  if (paired) TRY(paired_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &n_given));
+  // -e: Levenshtein neighbours (src/humid.cc:140-158); distance <= 1 IS the Hamming search
+  if (edit) TRY(edit_edges<WT>(c, c->s_word.as<WT>(), U, word_nt, distance, &n_given));
+  TRY(graph_stage<WT>(c, c->s_word.as<WT>(), c->s_cnt.as<u32>(), U, word_nt, distance, method, s, n_pair_segs, paired || edit,
+                      c->e_edges.as<u64>(), n_given));
   TRY(stage_map(c, c->cid.as<u32>(), c->ismax.as<u8>(), N, d_cid, d_keep));
   if (c->cg_valid) TRY(n_clusters_compact(c, U, &c->C));
   else TRY(n_clusters_from_scan(c, U, &c->C));
   s.clusters = c->C;
   s.nonsingle = c->M;
-  const u64 E = c->E, M = c->M;
-  // (the last host wait watches a mapped flag, not the stream: the runtime may not have seen the last
-  // event's signal yet -- "device not ready" from hipEventElapsedTime once in ~10^3 runs)
-  const bool timed = c->stamp_timed;
-  // the last host wait delivered the stamps with the counters.  (Not so in the one pass of a context whose first wait
-  // finds the mapped stores invisible, no_poll: no publishing kernel ran at its end.  That pass reports no times; the
-  // passes behind it record their events.)
-  const bool delivered = c->stamp_live && !c->no_poll;
-  if (delivered) {
-    for (u32 k = 0; k < STAMP_N; k++) c->last_stamps[k] = c->h_ctr[STAMP_AT + k];
-    c->last_stamp_live = true;
-    c->last_stamp_timed = timed;
-  }
-  if (!timed) HIPCHK(hipEventSynchronize(c->ev[4]));
-  const bool lean = c->lean_events;
-  c->lean_events = false;
-  if (!lean) {                                               // the stages' shares: option kernel_timing
-    HIPCHK(hipEventElapsedTime(&s.ms_count, c->ev[0], c->ev[1]));
-    HIPCHK(hipEventElapsedTime(&s.ms_neighbours, c->ev[1], c->ev[2]));
-    HIPCHK(hipEventElapsedTime(&s.ms_cluster, c->ev[2], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&s.ms_map, c->ev[3], c->ev[4]));
-  }
-  if (timed && delivered) {                                  // ticks of 10 ns
-    s.ms_total = (float)((double)(c->last_stamps[STAMP_END] - c->last_stamps[STAMP_START]) / 1e5);
-    s.ms_k_insert = (float)((double)(c->last_stamps[STAMP_K1] - c->last_stamps[STAMP_K0]) / 1e5);
-  } else if (!timed) HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
-  TRY(gkey_check(c));
-  if (!timed) HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));
-  if (!c->kev_on) s.ms_k_map = s.ms_map;
-  else if (count_in_partition_order(c)) HIPCHK(hipEventElapsedTime(&s.ms_k_map, c->ev[3], c->kev[36]));   // first map kernel alone
-  else s.ms_k_map = s.ms_map;   // ev[3]..ev[4] bracket exactly the k_read_map launch
-  if (c->kev_on && count_in_partition_order(c) && c->last_unperm_tiled) HIPCHK(hipEventElapsedTime(&s.ms_k_unperm, c->kev[36], c->kev[41]));
-  if (c->kev_on && count_part_timed(c)) HIPCHK(hipEventElapsedTime(&s.ms_k_part, c->kev[39], c->kev[40]));
   s.count_mode_used = count_mode_used(c);
-  if (c->kev_on) HIPCHK(hipEventElapsedTime(&s.ms_k_cluster, c->kev[2], c->kev[3]));
-  for (u32 g = 0; c->kev_on && g < n_pair_segs; g++) {
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, c->kev[20 + 2 * g], c->kev[21 + 2 * g]));   // count phase
-    s.ms_k_pairs += t;
-    if (E > 0 && !c->cg_valid) {
-      HIPCHK(hipEventElapsedTime(&t, c->kev[4 + 2 * g], c->kev[5 + 2 * g]));   // fill phase
-      s.ms_k_pairs += t;
-    }
-  }
+  TRY(timing_tail(c, s, n_pair_segs));
   if (sum) *sum = s;
   return state_publish(c, CtxState::RUN);
 }
@@ -2471,17 +2454,13 @@ static int run_device_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   humid_summary s;
   memset(&s, 0, sizeof s);
   s.total = n_reads;
-  c->last_unperm_tiled = false;
-  c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
-  c->word_nt = word_nt; c->distance = distance; c->method = method;
-  c->gU = 0;
+  pass_begin(c, n_reads, word_nt, distance, method);
   c->lg_info = humid_long_info_t{};
   c->lg_info.words_per_read = k;
   auto publish = [&]() { if (sum) *sum = s; state_publish(c, CtxState::RUN); c->state.long_words = true; return HUMID_OK; };
   s.count_mode_used = 3u;
   if (N == 0) return publish();
-  struct LeanEvents { humid_ctx *c; ~LeanEvents() { c->lean_events = false; } } lean_guard{c};
-  c->lean_events = !c->kev_on && getenv("HUMID_ALL_EVENTS") == nullptr;
+  PassTimingGuard timing(c, false);                          // (no device stamps: the sorting count stores none)
   TRY(stage_count_long(c, d_words, d_filt, N, word_nt, s));
   const u32 U = (u32)c->U;
   if (U == 0) {   // everything filtered
@@ -2493,34 +2472,17 @@ static int run_device_long(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   const u64 *leaf = c->s_word.as<u64>();
   u64 E = 0;
   TRY(long_edges(c, leaf, U, k, word_nt, distance, &E));
-  static const u64 no_edges = 0;
   u32 n_pair_segs = 0;
   // (the graph stage reads no word when its pairs are given: it runs as over one-uint64 leaves and the record is set right behind it)
-  const u32 plan_nt = std::min<u32>(word_nt, 32u);
-  if (c->use_compact)
-    TRY(stage_graph_compact<u64>(c, leaf, c->s_cnt.as<u32>(), U, plan_nt, distance, method, s, n_pair_segs,
-                                 E ? c->e_edges.as<u64>() : &no_edges, E));
-  else
-    TRY(stage_graph<u64>(c, leaf, c->s_cnt.as<u32>(), U, plan_nt, distance, method, s, n_pair_segs,
-                         E ? c->e_edges.as<u64>() : &no_edges, E));
+  TRY(graph_stage<u64>(c, leaf, c->s_cnt.as<u32>(), U, std::min<u32>(word_nt, 32u), distance, method, s, n_pair_segs, true,
+                       c->e_edges.as<u64>(), E));
   c->g_wpr = k;
   TRY(stage_map(c, c->cid.as<u32>(), c->ismax.as<u8>(), N, d_cid, d_keep));
   if (c->cg_valid) TRY(n_clusters_compact(c, U, &c->C));
   else TRY(n_clusters_from_scan(c, U, &c->C));
   s.clusters = c->C;
   s.nonsingle = c->M;
-  HIPCHK(hipEventSynchronize(c->ev[4]));
-  const bool lean = c->lean_events;
-  c->lean_events = false;
-  if (!lean) {                                               // the stages' shares: option kernel_timing
-    HIPCHK(hipEventElapsedTime(&s.ms_count, c->ev[0], c->ev[1]));
-    HIPCHK(hipEventElapsedTime(&s.ms_neighbours, c->ev[1], c->ev[2]));
-    HIPCHK(hipEventElapsedTime(&s.ms_cluster, c->ev[2], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&s.ms_map, c->ev[3], c->ev[4]));
-  }
-  HIPCHK(hipEventElapsedTime(&s.ms_total, c->ev[0], c->ev[4]));
-  HIPCHK(hipEventElapsedTime(&s.ms_k_insert, c->kev[0], c->kev[1]));   // the k sorts
-  s.ms_k_map = s.ms_map;
+  TRY(timing_tail(c, s, n_pair_segs, false));                // (ms_k_insert: the k sorts)
   return publish();
 }
 
@@ -2534,10 +2496,7 @@ static int accum_count_chunk(humid_ctx *c, const WT *d_words, const u8 *d_filt, 
   humid_summary s;
   memset(&s, 0, sizeof s);
   const u32 nt = c->ac_keyed ? c->ac_ent_nt : c->ac_nt;       // (a keyed accumulator counts entries)
-  c->last_unperm_tiled = false;
-  c->N = n_reads; c->U = c->E = c->M = c->C = c->usable = 0;
-  c->word_nt = nt;
-  c->gU = 0;
+  pass_begin(c, n_reads, nt);
   if (n_reads == 0) return HUMID_OK;
   if constexpr (sizeof(WT) == 16) return stage_count_wide(c, d_words, d_filt, (u32)n_reads, nt, s);
   else return stage_count(c, d_words, d_filt, (u32)n_reads, nt, 0ull, ~0ull, 0, s);
@@ -2601,8 +2560,7 @@ static int accum_finish(humid_ctx *c, u32 distance, u32 method, humid_summary &s
   if (c->edit && distance >= 2) {
     u64 E = 0;
     TRY(edit_edges<WT>(c, g_word, U, c->ac_nt, distance, &E));
-    static const u64 no_edges = 0;
-    TRY(stage_graph<WT>(c, g_word, g_cnt, U, c->ac_nt, distance, method, s, nps, E ? c->e_edges.as<u64>() : &no_edges, E));
+    TRY(stage_graph<WT>(c, g_word, g_cnt, U, c->ac_nt, distance, method, s, nps, edges_or_empty(c->e_edges.as<u64>(), E), E));
   } else
     TRY(stage_graph<WT>(c, g_word, g_cnt, U, c->ac_nt, distance, method, s, nps));
   TRY(n_clusters_from_scan(c, U, &c->C));
@@ -2837,8 +2795,7 @@ static int accum_finish_keyed(humid_ctx *c, u32 G, u32 distance, u32 method, hum
   if (c->edit && distance >= 2) {
     u64 E = 0;
     TRY(edit_edges<IT>(c, g_word, U, n_int, distance, &E));
-    static const u64 no_edges = 0;
-    TRY(stage_graph<IT>(c, g_word, g_cnt, U, n_int, distance, method, s, nps, E ? c->e_edges.as<u64>() : &no_edges, E));
+    TRY(stage_graph<IT>(c, g_word, g_cnt, U, n_int, distance, method, s, nps, edges_or_empty(c->e_edges.as<u64>(), E), E));
   } else
     TRY(stage_graph<IT>(c, g_word, g_cnt, U, n_int, distance, method, s, nps));
   TRY(n_clusters_from_scan(c, U, &c->C));

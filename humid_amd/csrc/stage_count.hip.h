@@ -34,14 +34,14 @@ static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt
   ENSURE(c->slot_of_read, (size_t)N * 4);
   ENSURE(c->uniq_slot, (size_t)expected_reads * 4 + 4);
   ENSURE(c->uniq_word, (size_t)expected_reads * 8 + 8);
-  EVREC(c->ev[0], st);
+  TRY(mark_frame(c, c->ev[EV_PASS_START]));
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
   HIPCHK(hipMemsetAsync(c->table.p, 0xff, (cap + 1) * sizeof(Slot), st));
-  EVREC(c->kev[0], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_BEGIN]));
   hipLaunchKernelGGL(k_hash_insert, dim3(grid_stride_blocks(N)), dim3(256), 0, st, d_words, d_filt, N,
                      c->table.as<Slot>(), cap_log2, c->slot_of_read.as<u32>(), range_lo, range_hi,
                      (u32)(cap - cap / 8), c->d_ctr);
-  EVREC(c->kev[1], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_END]));
   hipLaunchKernelGGL(k_compact_table, dim3(COMPACT_BLOCKS), dim3(256), 0, st,
                      c->table.as<Slot>(), (u32)(cap + 1), c->uniq_word.as<u64>(), c->uniq_slot.as<u32>(),
                      (u32)expected_reads, c->d_ctr);
@@ -53,13 +53,13 @@ static int stage_count_global(humid_ctx *c, const u64 *d_words, const u8 *d_filt
   const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
   s.usable = c->usable = c->h_ctr[CTR_USABLE];
   s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
+  if (U == 0) return mark_stage(c, c->ev[EV_COUNT_END]);
   TRY(ensure_walk_order(c, U, 8));
   TRY(sort_pairs<u64, u32>(c, c->uniq_word.as<u64>(), c->s_word.as<u64>(), c->uniq_slot.as<u32>(),
                            c->s_slot.as<u32>(), U, 0, 2 * word_nt));
   hipLaunchKernelGGL(k_post_sort, dim3(blocks_for(U)), dim3(256), 0, st, c->s_slot.as<u32>(),
                      c->table.as<Slot>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
+  TRY(mark_stage(c, c->ev[EV_COUNT_END]));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -156,13 +156,13 @@ static int count_partition(humid_ctx *c, const SRC &src, u32 N, u32 pb, bool *us
   if (padded)
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)cursor1, d1, d2, cbase, tprefix, c->pbeg.as<u32>(),
                        c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) EVREC(c->kev[39], st);
+  TRY(mark_kernel(c, c->kev[KEV_PART_BEGIN]));
   if (d2) {
     hipLaunchKernelGGL(k_pt_hist2<SRC>, dim3(tiles2), dim3(1024), 0, st, src, k1, tprefix, cbase, d1, d2, hist_fine, cap1);
     hipLaunchKernelGGL((k_pt_scatter<2, SRC>), dim3(tiles2), dim3(1024), 0, st, src, N, k1, v1, tprefix, cbase, d1, d2,
                        hist_fine, cursor2, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(), c->pbeg.as<u32>(), cap1, &c->d_ctr[CTR_SPECIAL]);
   }
-  if (c->kev_on) EVREC(c->kev[40], st);
+  TRY(mark_kernel(c, c->kev[KEV_PART_END]));
   return HUMID_OK;
 }
 
@@ -193,7 +193,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   ENSURE(c->slot_out, ((size_t)N + 1) * 8);
   ENSURE(c->uniq_slot, (size_t)N * 4 + 4);
   ENSURE(c->uniq_word, (size_t)N * 8 + 8);
-  EVREC(c->ev[0], st);
+  TRY(mark_frame(c, c->ev[EV_PASS_START]));
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
   const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
   const bool tiled = c->use_tile_partition && pb <= 2 * 9;
@@ -213,7 +213,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
     hipLaunchKernelGGL(k_part_bounds, dim3(blocks_for(n_parts + 1)), dim3(256), 0, st, c->pk_keys.as<u64>(), N,
                        pb, n_parts, c->pbeg.as<u32>(), c->ucount.as<u32>());
   }
-  EVREC(c->kev[0], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_BEGIN]));
   if (wide) {
     auto count = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(n_parts), dim3(256), 0, st, c->pk_keys.as<u64>(), c->pk_vals.as<u32>(), c->pbeg.as<u32>(), wide,
@@ -231,7 +231,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
     if (ordered) count(k_dedup_lds<true>);
     else count(k_dedup_lds<false>);
   }
-  EVREC(c->kev[1], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_END]));
   hipLaunchKernelGGL(k_part_totals, dim3(n_parts >= 16384 ? 64 : 4), dim3(256), 0, st, c->ucount.as<u32>(),
                      c->pusable.as<u32>(), n_parts, c->d_ctr);
   TRY(exscan_u32(c, c->ucount.as<u32>(), c->ubase.as<u32>(), (u64)n_parts + 1));
@@ -247,7 +247,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   const u32 U = (u32)c->h_ctr[CTR_UNIQUE];
   s.usable = c->usable = c->h_ctr[CTR_USABLE];
   s.unique = c->U = U;
-  if (U == 0) { if (!c->lean_events) EVREC(c->ev[1], st); return HUMID_OK; }
+  if (U == 0) return mark_stage(c, c->ev[EV_COUNT_END]);
   TRY(ensure_walk_order(c, (size_t)U + 1, wsize));
   if (wide) {
     hipLaunchKernelGGL(k_compact_padded_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st,
@@ -269,7 +269,7 @@ static int stage_count_lds(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
                          c->pad_cf.as<uint2>(), U, c->s_cnt.as<u32>(), c->s_first.as<u32>());
     }
   }
-  if (!c->lean_events) EVREC(c->ev[1], st);
+  TRY(mark_stage(c, c->ev[EV_COUNT_END]));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
@@ -329,9 +329,9 @@ struct RecWork {
 };
 // Sizes what both roads have behind their own record buffers -- level 2's positions (p8_b), the padded words of wsize
 // bytes and their (count, first read), the slots' results, the buckets' bounds -- carves the work area and launches the
-// kernel that zeroes the cursors, the counters and the scan's sentinel; ev0: ev[0] is recorded in front of that launch;
-// stamp: null, or where it stores the pass's start.
-static int rec_work(humid_ctx *c, const RecShape &sh, size_t wsize, bool ev0, u64 *stamp, RecWork *out) {
+// kernel that zeroes the cursors, the counters and the scan's sentinel, the pass-start frame mark in front of that
+// launch; stamp: null, or where it stores the pass's start.
+static int rec_work(humid_ctx *c, const RecShape &sh, size_t wsize, u64 *stamp, RecWork *out) {
   hipStream_t st = c->stream;
   ENSURE(c->p8_b, sh.room2 * 8);
   ENSURE(c->pad_word, sh.room2 * wsize);
@@ -345,7 +345,7 @@ static int rec_work(humid_ctx *c, const RecShape &sh, size_t wsize, bool ev0, u6
   w.agg = c->p8_status.as<u64>(); w.abase = w.agg + sh.n_parts + 1;
   w.cursor1 = c->p8_cur.as<u32>(); w.cursor2 = w.cursor1 + PT_MAXBINS1;
   w.cbase = w.cursor2 + sh.n_parts; w.tprefix = w.cbase + PT_MAXBINS1 + 1;
-  if (ev0) EVREC(c->ev[0], st);
+  TRY(mark_frame(c, c->ev[EV_PASS_START]));
   ZeroList z;
   memset(&z, 0, sizeof z);
   z.p[0] = w.cursor1; z.n[0] = PT_MAXBINS1 + sh.n_parts;
@@ -378,7 +378,7 @@ static int rec_tail(humid_ctx *c, const RecShape &sh, const RecWork &w, u32 N, s
   const bool early = c->overlap_waits;
   if (early) TRY(read_counters_begin(c, totals, totals + 1));
   squeeze();
-  if (!c->lean_events) EVREC(c->ev[1], st);
+  TRY(mark_stage(c, c->ev[EV_COUNT_END]));
   HIPCHK(hipGetLastError());
   if (early) TRY(read_counters_end(c, true));
   else TRY(read_counters(c, totals, totals + 1));
@@ -390,7 +390,7 @@ static int rec_tail(humid_ctx *c, const RecShape &sh, const RecWork &w, u32 N, s
             wsize == 8 ? "" : ", wide", N, sh.pb, sh.rk.kbits, sh.ibits, sh.cap1, (ull)special, (ull)overfull, U, (ull)usable);
   if (special || overfull) {
     if (own_redo) {
-      c->stamp_ok = c->stamp_live = c->stamp_timed = false;
+      c->timing.stamp_ok = c->timing.stamp_live = c->timing.stamp_timed = false;
       if (special) { c->pt_padded = false; road_taken(c, HUMID_ROAD_PART_PADDED_REDO); }     // the exact kernels from now on
     }
     return HUMID_OK;
@@ -414,13 +414,14 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   const RecKey &rk = sh.rk;
   ENSURE(c->p8_a, sh.room1 * 8);
   // the pass's four times from device stamps (humid_ctx::d_stamp)
-  const bool stamp = c->stamp_ok, timed = stamp && c->lean_events;
+  const bool stamp = c->timing.stamp_ok;
   u64 *const sp = stamp ? c->d_stamp : nullptr;
-  const bool events = !timed;                                 // ev[0], kev[0], kev[1] here and ev[4] in stage_map
+  // taken up in front of the first frame mark, which asks stamp_timed (a call that fails in the sizing behind it goes
+  // out through the pass's guard, which clears them)
+  c->timing.stamp_live = stamp;
+  c->timing.stamp_timed = stamp && c->timing.lean;           // no frame mark here, none at the pass's end in stage_map
   RecWork w;
-  TRY(rec_work(c, sh, 8, events, sp ? sp + STAMP_START : (u64 *)nullptr, &w));
-  c->stamp_live = stamp;                                      // (behind the sizing: a call that fails there leaves them alone)
-  c->stamp_timed = timed;
+  TRY(rec_work(c, sh, 8, sp ? sp + STAMP_START : (u64 *)nullptr, &w));
   const bool check_range = !(range_lo == 0 && range_hi == ~0ull);
   const Reads8 src{d_words, d_filt, range_lo, range_hi, check_range ? 1u : 0u, rk};
   const u32 tiles1 = (N + PT_TILE - 1) / PT_TILE, tiles2 = tiles1 + nb1;
@@ -430,21 +431,21 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
   // pbeg[n_parts] / ucount[n_parts], which no kernel of the record road reads: its un-permute, k_unperm_bins8, takes
   // the buckets' fills from cursor2).  One workgroup per tile of every bin's ROOM: those beyond the fill leave at once.
   if (c->static_tiles) {
-    if (c->kev_on) EVREC(c->kev[39], st);
+    TRY(mark_kernel(c, c->kev[KEV_PART_BEGIN]));
     hipLaunchKernelGGL(k_p8_scatter2<true>, dim3(nb1 * ((cap1 + PT_TILE - 1) / PT_TILE)), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(),
                        (const u32 *)w.cursor1, (const u32 *)nullptr, rk.kbits, d1, d2, ibits, cap1, w.cursor2, c->p8_b.as<u64>(), c->d_ctr);
   } else {
     hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)w.cursor1, d1, d2, w.cbase, w.tprefix, c->pbeg.as<u32>(),
                        c->ucount.as<u32>() + n_parts, cap1);
-    if (c->kev_on) EVREC(c->kev[39], st);
+    TRY(mark_kernel(c, c->kev[KEV_PART_BEGIN]));
     hipLaunchKernelGGL(k_p8_scatter2<false>, dim3(tiles2), dim3(1024), 0, st, (const u64 *)c->p8_a.as<u64>(), (const u32 *)w.tprefix,
                        (const u32 *)w.cbase, rk.kbits, d1, d2, ibits, cap1, w.cursor2, c->p8_b.as<u64>(), c->d_ctr);
   }
-  if (c->kev_on) EVREC(c->kev[40], st);
-  if (events) EVREC(c->kev[0], st);
+  TRY(mark_kernel(c, c->kev[KEV_PART_END]));
+  TRY(mark_frame(c, c->kev[KEV_INSERT_BEGIN]));
   hipLaunchKernelGGL(k_dedup_rec, dim3(n_parts), dim3(256), 0, st, c->p8_b.as<u64>(), (const u32 *)w.cursor2, N, pb, d1, ibits, rk,
                      c->pad_word.as<u64>(), c->pad_cf.as<uint2>(), w.agg, c->d_ctr, sp ? sp + STAMP_K0 : (u64 *)nullptr);
-  if (events) EVREC(c->kev[1], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_END]));
   auto squeeze = [&] {
     hipLaunchKernelGGL(k_compact_padded8, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, c->pad_word.as<u64>(),
                        c->pad_cf.as<uint2>(), (const u64 *)w.agg, (const u64 *)w.abase, n_parts, c->s_word.as<u64>(),
@@ -455,7 +456,7 @@ static int stage_count_rec(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u
 
 // Stage A for two-word words on records (kernels_part8.hip.h, second half): the 16-byte word + its read index travel
 // through both padded partition levels, k_dedup_wide_rec reads its bucket as two contiguous streams.  No device stamps
-// here: ev[0], kev[0] and kev[1] are always recorded.  *done = false: not this shape, or the count was discarded -- the
+// here: the frame marks are always recorded.  *done = false: not this shape, or the count was discarded -- the
 // caller takes stage_count_lds (keys + gather) or the sort.
 static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_filt, u32 N, u32 word_nt, const KeyMap &km,
                                 humid_summary &s, bool *done) {
@@ -471,18 +472,18 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
   ENSURE(c->pw_b, sh.room2 * 16);
   ENSURE(c->pw_bi, sh.room2 * 4);
   RecWork w;
-  TRY(rec_work(c, sh, sizeof(W2), true, nullptr, &w));
+  TRY(rec_work(c, sh, sizeof(W2), nullptr, &w));
   const u32 tiles1 = (N + PT_TILE - 1) / PT_TILE, tiles2 = tiles1 + nb1;
   hipLaunchKernelGGL(k_pw_scatter<1>, dim3(tiles1), dim3(1024), 0, st, d_words, d_filt, (const u32 *)nullptr, N, hbits, rk,
                      (const u32 *)nullptr, (const u32 *)nullptr, d1, d2, cap1, w.cursor1, c->pw_a.as<W2>(), c->pw_ai.as<u32>(), c->d_ctr);
   hipLaunchKernelGGL(k_pt_scan1, dim3(1), dim3(1024), 0, st, (const u32 *)w.cursor1, d1, d2, w.cbase, w.tprefix, c->pbeg.as<u32>(),
                      c->ucount.as<u32>() + n_parts, cap1);
-  if (c->kev_on) EVREC(c->kev[39], st);
+  TRY(mark_kernel(c, c->kev[KEV_PART_BEGIN]));
   hipLaunchKernelGGL(k_pw_scatter<2>, dim3(tiles2), dim3(1024), 0, st, (const W2 *)c->pw_a.as<W2>(), (const u8 *)nullptr,
                      (const u32 *)c->pw_ai.as<u32>(), N, hbits, rk, (const u32 *)w.tprefix, (const u32 *)w.cbase, d1, d2, cap1, w.cursor2,
                      c->pw_b.as<W2>(), c->pw_bi.as<u32>(), c->d_ctr);
-  if (c->kev_on) EVREC(c->kev[40], st);
-  EVREC(c->kev[0], st);
+  TRY(mark_kernel(c, c->kev[KEV_PART_END]));
+  TRY(mark_frame(c, c->kev[KEV_INSERT_BEGIN]));
   auto count = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(n_parts), dim3(256), 0, st, (const W2 *)c->pw_b.as<W2>(), (const u32 *)c->pw_bi.as<u32>(),
                        (const u32 *)w.cursor2, hbits, rk, N, pb, c->pad_word.as<W2>(), c->pad_cf.as<uint2>(), w.agg, c->p8_b.as<u64>(),
@@ -490,7 +491,7 @@ static int stage_count_rec_wide(humid_ctx *c, const W2 *d_words, const u8 *d_fil
   };
   count(k_dedup_wide_rec<9, 512, 0, WL_SMALL_LEN>);
   if (N > WL_SMALL_LEN) count(k_dedup_wide_rec<10, 1024, WL_SMALL_LEN, WL_STAGE>);
-  EVREC(c->kev[1], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_END]));
   auto squeeze = [&] {
     hipLaunchKernelGGL(k_compact_padded8_wide, dim3(blocks_for((u64)n_parts * 64)), dim3(256), 0, st, (const W2 *)c->pad_word.as<W2>(),
                        (const uint2 *)c->pad_cf.as<uint2>(), (const u64 *)w.agg, (const u64 *)w.abase, n_parts, c->s_word.as<W2>(),
@@ -582,7 +583,7 @@ static int stage_count(humid_ctx *c, const u64 *d_words, const u8 *d_filt, u32 N
 
 // ---- the sorting counts (two-word words: kernels_wide.hip.h; long words: kernels_long.hip.h) ----
 // Their frame around the key / sort passes, which stay with each road.  Front: the buffers of the sort and of the
-// sorted words (word_bytes each), the counters cleared, ev[0] and kev[0].
+// sorted words (word_bytes each), the counters cleared, the frame marks of the pass's start and the sorts' begin.
 static int sorted_count_front(humid_ctx *c, u32 N, size_t word_bytes) {
   hipStream_t st = c->stream;
   ENSURE(c->pk_keys, (size_t)N * 8);
@@ -593,18 +594,18 @@ static int sorted_count_front(humid_ctx *c, u32 N, size_t word_bytes) {
   ENSURE(c->w_sorted, (size_t)N * word_bytes);
   ENSURE(c->w_head, ((size_t)N + 1) * 4);
   ENSURE(c->w_hpos, ((size_t)N + 1) * 4);
-  EVREC(c->ev[0], st);
+  TRY(mark_frame(c, c->ev[EV_PASS_START]));
   HIPCHK(hipMemsetAsync(c->d_ctr, 0, CTR_N * sizeof(ull), st));
-  EVREC(c->kev[0], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_BEGIN]));
   return HUMID_OK;
 }
-// Back, behind the last sort: kev[1]; `heads` gathers the words in sorted order and flags the first of every run of
+// Back, behind the last sort: the frame mark of the sorts' end; `heads` gathers the words in sorted order and flags the first of every run of
 // equal words; their scan gives U (one host wait); `unique` writes a leaf per run and the partition-order arrays
-// pk_vals / pslot that stage C walks (k_read_map_part); the counts; ev[1].
+// pk_vals / pslot that stage C walks (k_read_map_part); the counts; the stage mark of the count's end.
 template <class Heads, class Unique>
 static int sorted_count_back(humid_ctx *c, u32 N, size_t word_bytes, Heads heads, Unique unique, humid_summary &s) {
   hipStream_t st = c->stream;
-  EVREC(c->kev[1], st);
+  TRY(mark_frame(c, c->kev[KEV_INSERT_END]));
   heads();
   u64 n_unique = 0;
   TRY(scan_total(c, c->w_head.as<u32>(), c->w_hpos.as<u32>(), N, &n_unique));
@@ -619,7 +620,7 @@ static int sorted_count_back(humid_ctx *c, u32 N, size_t word_bytes, Heads heads
   if (U)
     hipLaunchKernelGGL(k_wide_counts, dim3(blocks_for(U)), dim3(256), 0, st, c->w_start.as<u32>(), U,
                        c->s_cnt.as<u32>(), c->s_slot.as<u32>());
-  if (!c->lean_events) EVREC(c->ev[1], st);
+  TRY(mark_stage(c, c->ev[EV_COUNT_END]));
   HIPCHK(hipGetLastError());
   return HUMID_OK;
 }
